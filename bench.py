@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N = 1 runs in this process.  N > 1 with no WORLD_SIZE in the environment: this process stays CPU-only, SPAWNS N rank processes
 (one per GPU, torch.distributed backend nccl = RCCL over xGMI, rendezvous on 127.0.0.1) and relays rank 0's JSON line; when the
@@ -24,6 +24,13 @@ One JSON line on stdout (rank 0).  Besides the contract keys it carries
   cpu_baseline  -- the CPU oracle (oracle/reid_oracle.py, kind "port") timed on this host on a bounded sample, plus the two
                    CPU retrieval baselines of SURVEY 8(d)
   retrieval     -- eval queries/s of the fused cosine top-10 on 10k x 200k x 512 (BASELINE.json configs[3])
+
+--dump-outputs DIR (rank 0; bench_outputs/ is ignored by git) writes what the last timed step returned to its caller, for an
+output-by-output comparison of two builds: DIR/loss.<name>.npy (float64 scalars: total_loss, ce_loss, sdm_loss) and
+DIR/param.<name>.npy (float32: every trainable tensor after that step's optimizer update).  At most 64 MB in all: a tensor that
+does not fit is replaced by a fixed, seeded sample of its elements (DIR/param.<name>.sample_index.npy holds the flat indices).
+Inputs and weights are seeded: the same arguments give the same inputs on every run.  The backward reduces with fp32 atomics,
+so two runs of one build agree to rounding, not bit for bit (AdamW's early, sign-like updates make that up to ~lr per element).
 """
 import argparse
 import json
@@ -70,7 +77,51 @@ def parse():
     ap.add_argument('--compute-dtype', default=None, choices=[None, 'bf16', 'f16'], help='headline flavor (default bf16)')
     ap.add_argument('--no-second-flavor', action='store_true', help='skip the step-time leg of the other 16-bit flavor')
     ap.add_argument('--no-parity', action='store_true', help='skip the in-run full-size parity check against the CPU oracle')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the losses and the updated trainable tensors of the last timed step to DIR/*.npy (see the module docstring)')
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    return args
+
+
+DUMP_BUDGET_BYTES = 63 * 10**6        # array payload; the npy headers stay within the 64 MB of the dump
+
+
+def snapshot_outputs(model, L):
+    """Host copies of what the caller of the timed step receives: the loss scalars (float64) and the trainable tensors after the
+    step's optimizer update (float32).  Taken right after the timed region, before anything else runs on the model."""
+    out = {}
+    for k in ('total_loss', 'ce_loss', 'sdm_loss'):
+        out[f'loss.{k}'] = L[k].detach().to('cpu', torch.float64).numpy()
+    for name, p in model.named_parameters():
+        if p.requires_grad:
+            out['param.' + name.replace('/', '.')] = p.detach().to('cpu', torch.float32).numpy()
+    return out
+
+
+def dump_outputs(arrays, path):
+    """Write `arrays` as path/<name>.npy within DUMP_BUDGET_BYTES: the largest tensors are sampled (fixed seed, sorted flat
+    indices stored beside them) until everything fits."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = sorted(arrays, key=lambda n: arrays[n].nbytes)
+    left = DUMP_BUDGET_BYTES
+    written = {}
+    for i, n in enumerate(names):
+        a = arrays[n]
+        share = left // (len(names) - i)                 # even share of what is left; small tensors leave theirs to the large ones
+        if a.nbytes > share:
+            keep = max(1, share // (a.itemsize + 8))     # (+ 8: the int64 index of every kept element)
+            idx = np.sort(np.random.default_rng(20251015).choice(a.size, size=keep, replace=False)).astype(np.int64)
+            np.save(os.path.join(path, n + '.sample_index.npy'), idx)
+            left -= idx.nbytes
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, n + '.npy'), a)
+        left -= a.nbytes
+        written[n] = list(a.shape)
+    log(f'dump: {len(written)} arrays, {(DUMP_BUDGET_BYTES - left) / 1e6:.1f} MB -> {path}')
+    return written
 
 
 PMC_FILE = 'r04_pmc_traffic.json'
@@ -535,6 +586,7 @@ def main():
 
     log(f'[{head}] model built, {args.warmup} warm-up + {args.steps} timed steps (P={P},K={K} per GPU, world {world})')
     elapsed, L = timed(step, args.steps, args.warmup, world, dev)
+    dumped = snapshot_outputs(model, L) if (args.dump_outputs and rank == 0) else None
     # Kernel-duration pass for the roofline: the SAME K steps again, now with a HIP event pair around every launch of the
     # dominant kernels on the launch stream.  It is a second pass because timing events are not free here: each record is a
     # system-scope fence (L2 write-back), which slowed the step by 15-25 % when taken inside the throughput region.
@@ -579,6 +631,8 @@ def main():
         'rccl_world': (world if (world > 1 and args.backend == 'nccl') else 0), 'backend': args.backend if world > 1 else None,
         'hip_graph': graphed,
     }
+    if dumped is not None:
+        res['dump_outputs'] = {'dir': os.path.abspath(args.dump_outputs), 'arrays': dump_outputs(dumped, args.dump_outputs)}
     if prof:
         fl = sum(p[0] for p in prof); ms = sum(p[2].elapsed_time(p[3]) for p in prof)
         ach = fl / (ms * 1e-3) / 1e12

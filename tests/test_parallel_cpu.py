@@ -89,6 +89,13 @@ def test_global_head_on_gathered_features_equals_single_process(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+def _ranklist(sim, a, b, k):
+    """The oracle's ranking rule (O.topk_ranklist: score desc, index asc) on gallery columns [a, b) of one score matrix."""
+    s = sim[:, a:b]
+    idx = torch.argsort(s, dim=1, descending=True, stable=True)[:, :k]
+    return idx, s.gather(1, idx)
+
+
 def test_merge_topk_equals_global_ranking():
     """Per-shard top-k lists (made here with the oracle's ranking rule) merge into the global top-k, ties included."""
     from oracle import reid_oracle as O
@@ -98,18 +105,23 @@ def test_merge_topk_equals_global_ranking():
     Q = O.l2n(torch.randn(Nq, D, generator=g)); G = O.l2n(torch.randn(Ng, D, generator=g))
     G[100] = G[7]; G[301] = G[7]; G[302] = G[7]                       # exact ties across shards
     want_idx, want_sc = O.topk_ranklist(Q, G, k)
+    # the shards rank columns of the SAME score matrix: a (query, gallery) pair has one score wherever it is ranked, as on the
+    # GPU path (every gallery row scored on its own); a separate CPU GEMM per shard may round differently from the full one
+    sim = O.cosine_sim(Q, G)
+    gi, gs = _ranklist(sim, 0, Ng, k)
+    assert torch.equal(gi, want_idx) and torch.equal(gs, want_sc)
     bounds = [0, 101, 202, 303, Ng]
     parts_i, parts_s = [], []
     for w in range(W):
         a, b = bounds[w], bounds[w + 1]
-        li, ls = O.topk_ranklist(Q, G[a:b], k)
+        li, ls = _ranklist(sim, a, b, k)
         parts_i.append(li + a); parts_s.append(ls)
     gi, gs = merge_topk(torch.stack(parts_i), torch.stack(parts_s), k)
     assert torch.equal(gi, want_idx) and torch.allclose(gs, want_sc, atol=0, rtol=0)
     # shards shorter than k are padded with -1 / -inf
-    li, ls = O.topk_ranklist(Q, G[:4], 4)
+    li, ls = _ranklist(sim, 0, 4, 4)
     pad_i = torch.cat([li, torch.full((Nq, k - 4), -1)], 1); pad_s = torch.cat([ls, torch.full((Nq, k - 4), float('-inf'))], 1)
-    li2, ls2 = O.topk_ranklist(Q, G[4:], k)
+    li2, ls2 = _ranklist(sim, 4, Ng, k)
     gi, gs = merge_topk(torch.stack([pad_i, li2 + 4]), torch.stack([pad_s, ls2]), k)
     assert torch.equal(gi, want_idx)
 
