@@ -51,6 +51,9 @@ typedef enum {
 } reid_act;
 
 const char* reid_last_error(void);
+/* ABI version of this header: REID_ABI_VERSION.  201: reid_layernorm_bwd gained `overflow`; r04's positional y_dtype of
+ * reid_add_layernorm_fwd, dx_dtype of reid_layernorm_bwd and REID_F16 came without a bump of 200.  Bindings refuse any other value. */
+#define REID_ABI_VERSION 201
 int reid_version(void);
 /* 16-bit operand format of this build: 0 = bf16 (libreid_hip.so), 1 = IEEE f16 (libreid_hip_f16.so, same sources
  * compiled with -DREID_FLAVOR_F16).  Every `bf16` / REID_BF16 in this header means "the 16-bit format of the flavor". */
@@ -134,6 +137,9 @@ int reid_gemm_tn(const void* X, const void* Y, float* C, int32_t M, int32_t P, i
  *        DropPath-scaled residual branch); the f32 dx is unscaled.
  *        dx_dtype: REID_F32, or REID_F16 = the residual-stream gradient (dres read AND dx written) in IEEE half, saturating:
  *        12 instead of 16 bytes per element; the caller keeps the stream inside half's range by scaling the loss.
+ *        overflow (nullable, int32 on the device): with dx_dtype = REID_F16 the call ORs 1 into *overflow when it stored any
+ *        element clamped to +-65504, i.e. a finite value with |v| >= 65520 (in the f16 flavor: dx or its 16-bit copy); inf and
+ *        NaN are stored as they are and do not set it.  The caller zeroes the flag; REID_F32 forms leave it untouched.
  * ------------------------------------------------------------------------------------------ */
 int reid_layernorm_fwd(const float* x, int32_t ldx, const int32_t* row_index, const float* gamma,
                        const float* beta, void* y_bf16, float* y_f32, int32_t ldy, float* mean, float* rstd,
@@ -150,7 +156,7 @@ int reid_layernorm_bwd(const void* dy, int32_t dy_dtype, int32_t lddy, const flo
                        const int32_t* row_index, const float* gamma, const float* mean, const float* rstd,
                        const void* dres, void* dx, int32_t dx_dtype, void* dx_bf16, int32_t lddx,
                        float* dgamma, float* dbeta, int32_t rows, int32_t cols,
-                       const float* bf16_row_scale, int32_t rows_per_img, void* stream);
+                       const float* bf16_row_scale, int32_t rows_per_img, int32_t* overflow, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Patch extraction (im2col of the k=s=16 conv, models/patch_embeds.py:45-76):

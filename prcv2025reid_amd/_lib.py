@@ -30,6 +30,7 @@ def t16() -> torch.dtype:
     return T16_DTYPES[_flavor]
 
 
+ABI_VERSION = 201                 # REID_ABI_VERSION of include/reid_hip.h: a library that reports anything else is a stale build
 BF16, F32, F16 = 0, 1, 2          # reid_dtype: BF16 = the flavor's 16-bit format, F16 = IEEE half whatever the flavor
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU, ACT_DGELU, ACT_DQUICK_GELU, ACT_DRELU, ACT_MUL_AUX, ACT_GELU_DSAVE = range(9)
 
@@ -79,17 +80,26 @@ def lib():
         if not os.path.exists(path):
             raise ReidHipError(f'{path} not found: build it with `python -m prcv2025reid_amd.build` '
                                '(there is no CPU or PyTorch fallback for the hot path)')
-        h = C.CDLL(path)
-        h.reid_last_error.restype = C.c_char_p
-        missing = [n for n in EXPORTS if not hasattr(h, n)]
-        if missing:
-            raise ReidHipError(f'{path} lacks symbols {missing}: stale build, run `python -m prcv2025reid_amd.build --force`')
-        h.reid_sdm_ws_floats.restype = C.c_int64
-        h.reid_topk_ws_bytes.restype = C.c_int64
-        h.reid_topk_stream_ws_bytes.restype = C.c_int64
-        if h.reid_flavor() != (1 if _flavor == 'f16' else 0):
-            raise ReidHipError(f'{path} was built for the other 16-bit flavor')
+        h = _checked(C.CDLL(path), path)
         _libs[_flavor] = h
+    return h
+
+
+def _checked(h, path):
+    """Refuses a library whose exports, ABI version or flavor differ from what this module binds; sets the return types."""
+    missing = [n for n in EXPORTS if not hasattr(h, n)]
+    if missing:
+        raise ReidHipError(f'{path} lacks symbols {missing}: stale build, run `python -m prcv2025reid_amd.build --force`')
+    v = h.reid_version()
+    if v != ABI_VERSION:
+        raise ReidHipError(f'{path} has ABI version {v}, this package binds {ABI_VERSION}: stale build, '
+                           'run `python -m prcv2025reid_amd.build --force`')
+    h.reid_last_error.restype = C.c_char_p
+    h.reid_sdm_ws_floats.restype = C.c_int64
+    h.reid_topk_ws_bytes.restype = C.c_int64
+    h.reid_topk_stream_ws_bytes.restype = C.c_int64
+    if h.reid_flavor() != (1 if _flavor == 'f16' else 0):
+        raise ReidHipError(f'{path} was built for the other 16-bit flavor')
     return h
 
 

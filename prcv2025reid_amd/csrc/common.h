@@ -136,6 +136,8 @@ __device__ __forceinline__ uint32_t pack_f16x2(float lo, float hi) {
 __device__ __forceinline__ float f16_to_f32(unsigned short v) { return (float)__builtin_bit_cast(_Float16, v); }
 // MODE.FP16_OVFL for the calling wave: conversions to half clamp finite overflow to +-65504 (what REID_T16_ENTER does in the f16 flavor)
 #define REID_F16_SATURATE() __builtin_amdgcn_s_setreg(1 | (23 << 6) | (0 << 11), 1)
+// true for a finite value that such a conversion clamps: |v| >= 65520 rounds past 65504, the largest finite half (inf, NaN: false)
+__device__ __forceinline__ bool f16_clamps(float v) { const float a = fabsf(v); return a >= 65520.f && a <= 3.402823466e38f; }
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -15,7 +15,7 @@ void reid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* reid_last_error(void) { return g_err; }
-extern "C" int reid_version(void) { return 200; }
+extern "C" int reid_version(void) { return REID_ABI_VERSION; }
 
 // ---------------------------------------------------------------- experiment knobs (common.h)
 static const char* const g_knob_names[] = {
@@ -206,7 +206,8 @@ __global__ __launch_bounds__(256) void add_ln_fwd_kernel(const float* __restrict
 // element: 50k rows x 768 columns would otherwise serialise on 768 addresses).  Without dgamma/dbeta the launch has one
 // wave per row and the loop body runs once.
 // DX_HALF: the residual-stream gradient (dres read, dx written) in IEEE half instead of fp32: 12 instead of 16 bytes per element of
-// this HBM-bound kernel.  The caller scales the loss so that the stream sits in half's range (engine.py: loss_scaling).
+// this HBM-bound kernel.  The caller scales the loss so that the stream sits in half's range (engine.py: loss_scaling).  Storage saturates
+// (MODE.FP16_OVFL); a clamped element ORs 1 into *overflow (one ballot per row, one atomic per row that clamped) so the caller can tell.
 // VN: float4 vectors per lane (3 covers the towers' 768 columns: 78 -> 66 VGPRs = 7 waves per SIMD.  Measured r04, 50432 x 768, half dx:
 // 88.8 us at 7 waves, 90-92 us at 8 (forced: 2 spills) and at 6 -- occupancy is not what holds this kernel at 5.2 TB/s)
 template <bool DY_BF16, bool AFFINE, bool DX_HALF, int VN = MAXV>
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
                                                      const void* __restrict__ dres_, void* __restrict__ dx_,
                                                      bf16_t* __restrict__ dxb, int lddx, float* __restrict__ dgamma,
                                                      float* __restrict__ dbeta, int rows, int cols,
-                                                     const float* __restrict__ bscale, int rows_per_img) {
+                                                     const float* __restrict__ bscale, int rows_per_img, int* __restrict__ overflow) {
     REID_T16_ENTER();
     if (DX_HALF) REID_F16_SATURATE();
     const int lane = threadIdx.x & 63;
@@ -258,6 +259,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
         }
         const float m1 = wave_sum(s1) / cols, m2 = wave_sum(s2) / cols;
         const float bs = bscale ? bscale[xrow / rows_per_img] : 1.f;
+        bool clamped = false;
 #pragma unroll
         for (int i = 0; i < VN; ++i) {
             const int c = lane + i * 64;
@@ -271,6 +273,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
                         o[0] += f16_to_f32((unsigned short)(r.x & 0xffffu)); o[1] += f16_to_f32((unsigned short)(r.x >> 16));
                         o[2] += f16_to_f32((unsigned short)(r.y & 0xffffu)); o[3] += f16_to_f32((unsigned short)(r.y >> 16));
                     }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) clamped |= f16_clamps(o[e]) || (REID_FLAVOR_ID == 1 && dxb && f16_clamps(o[e] * bs));
                     *(uint2*)((unsigned short*)dx_ + xrow * lddx + c * 4) = uint2{pack_f16x2(o[0], o[1]), pack_f16x2(o[2], o[3])};
                 } else {
                     if (dres_) {
@@ -282,6 +286,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const void* __restrict__ dy
                 if (dxb) *(uint2*)(dxb + xrow * lddx + c * 4) = uint2{pack_bf16x2(o[0] * bs, o[1] * bs), pack_bf16x2(o[2] * bs, o[3] * bs)};
             }
         }
+        if (DX_HALF && overflow && __ballot(clamped) && lane == 0) atomicOr(overflow, 1);
     }
     if (affine) {
 #pragma unroll
@@ -408,7 +413,7 @@ __global__ __launch_bounds__(256) void ln_bwd8_kernel(const bf16_t* __restrict__
                                                       const float* __restrict__ mean, const float* __restrict__ rstd,
                                                       const unsigned short* __restrict__ dres, unsigned short* __restrict__ dx,
                                                       bf16_t* __restrict__ dxb, int lddx, int rows, int cols,
-                                                      const float* __restrict__ bscale, int rows_per_img) {
+                                                      const float* __restrict__ bscale, int rows_per_img, int* __restrict__ overflow) {
     REID_T16_ENTER();
     REID_F16_SATURATE();
     const int lane = threadIdx.x & 63;
@@ -443,6 +448,7 @@ __global__ __launch_bounds__(256) void ln_bwd8_kernel(const bf16_t* __restrict__
     }
     const float m1 = wave_sum(s1) / cols, m2 = wave_sum(s2) / cols;
     const float bs = bscale ? bscale[xrow / rows_per_img] : 1.f;
+    bool clamped = false;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int c = lane + i * 64;
@@ -456,12 +462,15 @@ __global__ __launch_bounds__(256) void ln_bwd8_kernel(const bf16_t* __restrict__
 #pragma unroll
                 for (int e = 0; e < 8; ++e) o[e] += f16_to_f32((unsigned short)((rw[e >> 1] >> (16 * (e & 1))) & 0xffffu));
             }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) clamped |= f16_clamps(o[e]) || (REID_FLAVOR_ID == 1 && dxb && f16_clamps(o[e] * bs));
             *(uint4*)(dx + xrow * lddx + c * 8) = uint4{pack_f16x2(o[0], o[1]), pack_f16x2(o[2], o[3]), pack_f16x2(o[4], o[5]), pack_f16x2(o[6], o[7])};
             if (dxb)
                 *(uint4*)(dxb + xrow * lddx + c * 8) = uint4{pack_bf16x2(o[0] * bs, o[1] * bs), pack_bf16x2(o[2] * bs, o[3] * bs),
                                                             pack_bf16x2(o[4] * bs, o[5] * bs), pack_bf16x2(o[6] * bs, o[7] * bs)};
         }
     }
+    if (overflow && __ballot(clamped) && lane == 0) atomicOr(overflow, 1);
 }
 }  // namespace
 
@@ -501,7 +510,8 @@ extern "C" int reid_add_layernorm_fwd(const float* x, int32_t ldx, const void* y
 extern "C" int reid_layernorm_bwd(const void* dy, int32_t dy_dtype, int32_t lddy, const float* x, int32_t ldx,
                                   const int32_t* row_index, const float* gamma, const float* mean, const float* rstd,
                                   const void* dres, void* dx, int32_t dx_dtype, void* dx_bf16, int32_t lddx, float* dgamma, float* dbeta,
-                                  int32_t rows, int32_t cols, const float* bf16_row_scale, int32_t rows_per_img, void* stream) {
+                                  int32_t rows, int32_t cols, const float* bf16_row_scale, int32_t rows_per_img, int32_t* overflow,
+                                  void* stream) {
     REID_CHECK_ARG(dy && x && gamma && mean && rstd && dx, "reid_layernorm_bwd: null pointer");
     REID_CHECK_ARG(dx_dtype == REID_F32 || dx_dtype == REID_F16, "reid_layernorm_bwd: dx_dtype must be REID_F32 or REID_F16");
     REID_CHECK_ARG(!bf16_row_scale || rows_per_img > 0, "reid_layernorm_bwd: bf16_row_scale needs rows_per_img");
@@ -515,13 +525,14 @@ extern "C" int reid_layernorm_bwd(const void* dy, int32_t dy_dtype, int32_t lddy
     const bool hx = dx_dtype == REID_F16;
     if (hx && dy_dtype == REID_BF16 && !aff && cols % 8 == 0 && cols <= 1024 && lddy % 8 == 0 && lddx % 8 == 0 && reid_knob(KNOB_LN_IMPL) != 1) {     // REID_LN_IMPL=1: the four-column form
         hipLaunchKernelGGL(ln_bwd8_kernel, dim3((rows + 3) / 4), b, 0, s, (const bf16_t*)dy, lddy, x, ldx, row_index, gamma, mean, rstd,
-                           (const unsigned short*)dres, (unsigned short*)dx, (bf16_t*)dx_bf16, lddx, rows, cols, bf16_row_scale, rows_per_img);
+                           (const unsigned short*)dres, (unsigned short*)dx, (bf16_t*)dx_bf16, lddx, rows, cols, bf16_row_scale, rows_per_img,
+                           overflow);
         REID_CHECK_LAUNCH("reid_layernorm_bwd");
         return REID_OK;
     }
 #define REID_LN_BWD3(B16, AFF, HX, VN)                                                                                         \
     hipLaunchKernelGGL((ln_bwd_kernel<B16, AFF, HX, VN>), g, b, 0, s, dy, lddy, x, ldx, row_index, gamma, mean, rstd, dres, dx, \
-                       (bf16_t*)dx_bf16, lddx, dgamma, dbeta, rows, cols, bf16_row_scale, rows_per_img)
+                       (bf16_t*)dx_bf16, lddx, dgamma, dbeta, rows, cols, bf16_row_scale, rows_per_img, overflow)
 #define REID_LN_BWD(B16, AFF)                                                                                                  \
     do { if (hx) { if (cols <= 768) REID_LN_BWD3(B16, AFF, true, 3); else REID_LN_BWD3(B16, AFF, true, MAXV); }                 \
          else { if (cols <= 768) REID_LN_BWD3(B16, AFF, false, 3); else REID_LN_BWD3(B16, AFF, false, MAXV); } } while (0)

@@ -140,6 +140,10 @@ class Engine:
         # The residual-stream gradient of the vision tower (dx between the LayerNorm backward kernels) in IEEE half: those kernels
         # are HBM-bound and move 12 instead of 16 bytes per element.  Needs the same scaling in either flavor.
         self.dx_half = os.environ.get('REID_DX_HALF', '1') != '0'
+        # Set by a half-dx LayerNorm backward that stored a clamped element (+-65504 for a finite |v| >= 65520): the scaled stream
+        # left half's range.  vision_backward zeroes it at entry and turns the gradients it returns into NaN when it is set, so the
+        # optimizer's non-finite check (trainer.py) sees the overflow instead of taking a step with finite, wrong gradients.
+        self.dx_overflow = torch.zeros(1, dtype=torch.int32, device=device)
         self._dense_ver = None
         self._lora_ver = None
         self._lora_pack = None
@@ -501,6 +505,10 @@ class Engine:
             dfeat = dfeat * scale_t
         dfb = ops.to_bf16(dfeat)
         gx = dict(dtype=torch.float16 if self.dx_half else torch.float32, device=dev)      # the residual-stream gradient
+        ovf = None
+        if self.dx_half:
+            ovf = self.dx_overflow
+            ovf.zero_()
         dcls = torch.empty(n_img, d, **b16)
         ops.gemm(dfb, W['vprojT'], dcls)
         prune = bool(st.get('cls_prune'))
@@ -535,10 +543,11 @@ class Engine:
         # dxb always holds the gradient ENTERING the next residual branch: dx times that branch's DropPath factor
         if prune:
             ops.layernorm_bwd(dcls, st['x_final'], P[ce + 'vision_ln_final.weight'], st['mf'], st['rf'], dx_c, dx_bf16=dxb_c,
-                              bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=1, dgamma=dgf, dbeta=dbf)
+                              bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=1, dgamma=dgf, dbeta=dbf, overflow=ovf)
         else:
             ops.layernorm_bwd(dcls, st['x_final'], P[ce + 'vision_ln_final.weight'], st['mf'], st['rf'], dx, dx_bf16=dxb,
-                              row_index=st['idx'], bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=S, dgamma=dgf, dbeta=dbf)
+                              row_index=st['idx'], bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=S, dgamma=dgf, dbeta=dbf,
+                              overflow=ovf)
         # Scratch.  Everything the SIDE stream reads (the dY of the four linears: dxb, du, dxmb, dqkv) exists twice, used by alternate
         # layers: the main stream may then run a whole layer ahead of the adapter-gradient kernels without overwriting their inputs.
         # U* (= dY . Bcat, the rank-r cotangents) are written and read on the side stream only.
@@ -647,7 +656,7 @@ class Engine:
             # ---- LN2
             dg2, db2 = ln_grads(lp + 'ln2')
             ops.layernorm_bwd(dhr, s['xm'], P[lp + 'ln2.weight'], s['mean2'], s['rstd2'], dxmr, dx_bf16=dxmbr, dres=gy,
-                              bf16_row_scale=s['sa'], rows_per_img=rpi, dgamma=dg2, dbeta=db2)
+                              bf16_row_scale=s['sa'], rows_per_img=rpi, dgamma=dg2, dbeta=db2, overflow=ovf)
             # ---- out proj:  xm = x + o Wo_eff^T + bo
             lora_grads(l, [(dxmbr, pk(l, 'out', 'BT'), Uor, mkr, [(dxmbr, s['To'], gB(l, 'out')), (Uor, s['o_rows'], gA(l, 'out'))])])
             ops.gemm(dxmbr, weT(l, 'out'), dor, row_groups=rg)
@@ -681,7 +690,8 @@ class Engine:
             wait_side(l + 1)
             dg1, db1 = ln_grads(lp + 'ln1')
             ops.layernorm_bwd(dh, s['x'], P[lp + 'ln1.weight'], s['mean1'], s['rstd1'], dx, dx_bf16=dxb2[(l - 1) & 1], dres=dxm,
-                              bf16_row_scale=st['layers'][l - 1]['sm'] if l > 0 else None, rows_per_img=S, dgamma=dg1, dbeta=db1)
+                              bf16_row_scale=st['layers'][l - 1]['sm'] if l > 0 else None, rows_per_img=S, dgamma=dg1, dbeta=db1,
+                              overflow=ovf)
         if side is not None:                                # the gradient arena is complete only when the side stream is
             ev = torch.cuda.Event(); ev.record(side); main.wait_event(ev)
         if want_dense:
@@ -712,10 +722,13 @@ class Engine:
                 dense[k] = v.view(P[k].shape)
             dense.update(acc_b)
         if scale_t is not None:
-            grad.mul_(1.0 / scale_t)
+            unscale = 1.0 / scale_t
+            if ovf is not None:                             # a clamped residual-stream gradient: NaN out everything (no host sync)
+                unscale = torch.where(ovf[0] != 0, torch.full_like(unscale, float('nan')), unscale)
+            grad.mul_(unscale)
             if want_dense:
                 for k in dense:
-                    dense[k] = dense[k] * (1.0 / scale_t)
+                    dense[k] = dense[k] * unscale
         return (grad, dense) if want_dense else grad
 
     # ------------------------------------------------------------------------------- text forward

@@ -28,12 +28,45 @@ def test_header_declares_what_python_binds():
 
 
 @pytest.mark.parametrize('flavor', ['bf16', 'f16'])
-def test_library_exports_every_declared_symbol(libs, flavor):
+def test_library_exports_every_declared_symbol_abi_201(libs, flavor):
     h = libs[flavor]
     missing = [n for n in header_functions() if not hasattr(h, n)]
     assert not missing, missing
-    assert h.reid_version() == 200              # round 2 ABI (reid_set_knob, fused SDM)
+    # ABI 201: reid_layernorm_bwd's overflow flag (200 was the round 2 ABI: reid_set_knob, fused SDM); the header says the same
+    src = open(os.path.join(ROOT, 'include', 'reid_hip.h')).read()
+    assert h.reid_version() == int(re.search(r'#define\s+REID_ABI_VERSION\s+(\d+)', src).group(1)) == 201
     assert h.reid_flavor() == (1 if flavor == 'f16' else 0)
+
+
+def test_header_abi_version_is_the_bound_one():
+    from prcv2025reid_amd import _lib
+    src = open(os.path.join(ROOT, 'include', 'reid_hip.h')).read()
+    assert int(re.search(r'#define\s+REID_ABI_VERSION\s+(\d+)', src).group(1)) == _lib.ABI_VERSION == 201
+
+
+def _stub_library(version, flavor):
+    # a stand-in for a loaded CDLL: every export present, reid_version / reid_flavor answering as given, no device code
+    import types
+    from prcv2025reid_amd import _lib
+    h = types.SimpleNamespace(**{n: (lambda *a: 0) for n in _lib.EXPORTS})
+    h.reid_version = lambda: version
+    h.reid_flavor = lambda: flavor
+    return h
+
+
+@pytest.mark.parametrize('version', [200, 202])
+def test_binding_refuses_other_abi_version(version):
+    from prcv2025reid_amd import _lib
+    with pytest.raises(_lib.ReidHipError, match=rf'ABI version {version}, this package binds 201: stale build, run `python -m prcv2025reid_amd.build --force`'):
+        _lib._checked(_stub_library(version, 1 if _lib.flavor() == 'f16' else 0), 'stub.so')
+
+
+def test_binding_accepts_current_abi_version():
+    from prcv2025reid_amd import _lib
+    h = _stub_library(201, 1 if _lib.flavor() == 'f16' else 0)
+    assert _lib._checked(h, 'stub.so') is h
+    with pytest.raises(_lib.ReidHipError, match='other 16-bit flavor'):
+        _lib._checked(_stub_library(201, 0 if _lib.flavor() == 'f16' else 1), 'stub.so')
 
 
 def test_argument_validation_needs_no_gpu(libs):

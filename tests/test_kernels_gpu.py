@@ -277,6 +277,233 @@ def test_layernorm(ops, rows, cols):
     assert rel_err(dxs, xr.grad) < 2e-5
 
 
+# ---------------------------------------------------------------- LayerNorm backward, residual-stream gradient in IEEE half
+# Every element is held to its own bound (never a global max, which would hide the small rows): the fp64 LayerNorm backward built
+# from the kernel's own fp32 mean / rstd, plus an fp32-evaluation allowance derived from the row below, then one 16-bit rounding.
+HALF_MAX = 65504.0
+_U32 = 2.0 ** -24
+_SENT16, _SENT32 = 0x7E5A, 0x12345678      # bit patterns of the sentinels around what a call may write
+
+
+def _rounding(v, mant, emin):
+    """Largest error of one round-to-nearest of |v| (fp64) into a format with ``mant`` stored mantissa bits and least normal
+    exponent ``emin`` (f16: 10, -14; bf16: 7, -126)."""
+    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** emin)))
+    return torch.exp2(e - mant - 1)
+
+
+def _fmt16(flavor):
+    return (10, -14) if flavor == 'f16' else (7, -126)
+
+
+def _ln_bwd_ref(dy, x, xrows, gamma, mean, rstd, dres):
+    """fp64 dx = dres + rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma, and the error an fp32 evaluation of it may make:
+    each of the two row sums is a chain of at most k = cols/64 + 16 roundings (a lane's columns, then six shuffle levels), so
+    |d mean(g)| <= (k+2) u mean|g|, |d mean(g xhat)| <= (k+4) u mean|g xhat|; xhat and g carry 2u and u; the last multiply and
+    the add of dres one u each."""
+    cols = x.shape[1]
+    k = cols / 64 + 16
+    xh = (x.double()[xrows] - mean.double()[:, None]) * rstd.double()[:, None]
+    g = dy.double() * gamma.double()
+    rs = rstd.double()[:, None]
+    m1 = g.sum(1, keepdim=True) / cols
+    m2 = (g * xh).sum(1, keepdim=True) / cols
+    ln = rs * (g - m1 - xh * m2)
+    a1 = g.abs().sum(1, keepdim=True) / cols
+    a2 = (g * xh).abs().sum(1, keepdim=True) / cols
+    allow = (k + 8) * _U32 * rs * (g.abs() + a1 + xh.abs() * a2) + 2 * _U32 * ln.abs()
+    o = ln if dres is None else ln + dres.double()[xrows]
+    allow = allow + 2 * _U32 * o.abs()
+    return o, allow.nan_to_num(0.0, 0.0, 0.0), xh
+
+
+def _check_elements(got, ref, allow, bound, what):
+    """Finite references: |got - ref| <= bound + allow per element.  Non-finite ones pass through: same NaN-ness, same inf."""
+    got = got.double()
+    fin = torch.isfinite(ref)
+    err = (got - ref).abs()
+    lim = bound + allow
+    bad = fin & ~(err <= lim)
+    if bad.any():
+        i = bad.nonzero()[0].tolist()
+        raise AssertionError(f'{what}: {int(bad.sum())} elements out of bound, first at {i}: got {float(got[tuple(i)])!r} '
+                             f'ref {float(ref[tuple(i)])!r} bound {float(lim[tuple(i)]):.3e}')
+    nf = ~fin
+    assert torch.equal(torch.isnan(got[nf]), torch.isnan(ref[nf])), f'{what}: NaN not passed through'
+    inf = torch.isinf(ref)
+    assert torch.equal(got[inf], ref[inf]), f'{what}: inf clamped or lost'
+
+
+def _saturate(v):
+    """What a saturating conversion to half keeps of a finite value (inf and NaN pass)."""
+    return torch.where(torch.isfinite(v), v.clamp(-HALF_MAX, HALF_MAX), v)
+
+
+def _sentinel_buf(rows, ld, dtype):
+    t = torch.empty(rows, ld, device='cuda', dtype=dtype)
+    if dtype == torch.float32:
+        t.view(torch.int32).fill_(_SENT32)
+    else:
+        t.view(torch.int16).fill_(_SENT16)
+    return t
+
+
+def _untouched(buf, written, what):
+    bits = buf.view(torch.int32 if buf.dtype == torch.float32 else torch.int16)
+    want = _SENT32 if buf.dtype == torch.float32 else _SENT16
+    assert bool((bits[~written] == want).all()), f'{what}: a write outside the rows / columns the call owns'
+
+
+# (name, cols, rows, lddy, lddx, options).  gather = image length of a row_index gather of every image's class row; rpi = rows_per_img
+# of bf16_row_scale (None: no scale); special: near = pre-rounding values in (65504, 65520), both signs (round to 65504, no flag);
+# over = also values >= 65520 (clamp, flag); copy = only the 16-bit copy leaves half's range (bs = 2); nonfinite = +-inf / NaN in dy
+# and dres.
+LN_BWD_HALF_CASES = [
+    ('step', 768, 50432, 768, 768, dict(rpi=197)),                # 256 images x 197 tokens: the training step's LN backward
+    ('rows1', 768, 1, 768, 768, dict(rpi=1)),
+    ('c512_ld', 512, 3, 528, 536, dict(rpi=2)),
+    ('c1024_4k1', 1024, 257, 1032, 1040, dict(rpi=7, dres=False)),
+    ('c520', 520, 33, 520, 528, dict(rpi=5)),                       # 65 eight-column groups: one lane in the second block
+    ('c64', 64, 5, 72, 64, dict(rpi=None)),
+    ('c8', 8, 3, 16, 8, dict(rpi=1)),
+    ('c772', 772, 9, 776, 784, dict(rpi=4)),                        # cols % 8 == 4: the four-column form
+    ('lddy_4', 768, 13, 772, 776, dict(rpi=3)),                     # lddy % 8 == 4: the four-column form
+    ('cls_rpi197', 768, 6, 776, 784, dict(gather=197, rpi=197)),
+    ('cls_rpi1', 768, 6, 768, 768, dict(gather=197, rpi=1, dres=False)),
+    ('nodres_nocopy', 768, 21, 768, 768, dict(rpi=None, dres=False, copy=False)),
+    ('near', 768, 9, 768, 768, dict(rpi=None, special='near')),
+    ('over', 768, 9, 768, 768, dict(rpi=None, special='over')),
+    ('copy', 768, 6, 768, 768, dict(rpi=1, special='copy')),
+    ('nonfinite', 768, 7, 768, 768, dict(rpi=1, special='nonfinite')),
+]
+
+
+@pytest.mark.parametrize('form', ['bwd8', 'four', 'affine', 'f32'])
+@pytest.mark.parametrize('case', LN_BWD_HALF_CASES, ids=[c[0] for c in LN_BWD_HALF_CASES])
+def test_layernorm_bwd_half_dx(ops, case, form):
+    """The towers' LayerNorm backward: 16-bit dy, residual-stream gradient dres / dx in IEEE half, 16-bit copy bs * dx.  Forms:
+    bwd8 = ln_bwd8_kernel (the default), four = ln_bwd_kernel<.., DX_HALF> (LN_IMPL=1), affine = the same with dgamma / dbeta
+    (freeze_backbone=False), f32 = dres / dx in fp32 (REID_DX_HALF=0).  dx within one half rounding of fp64 (saturating at 65504),
+    the copy within one 16-bit rounding of bs * o, the overflow flag set exactly when a finite stored value clamped, and nothing
+    written outside the named rows' first ``cols`` columns."""
+    from prcv2025reid_amd import _lib
+    name, cols, rows, lddy, lddx, opt = case
+    flavor = _lib.flavor()
+    half = form != 'f32'
+    special = opt.get('special')
+    g = torch.Generator(device='cuda').manual_seed(cols * 7919 + rows)
+    gather = opt.get('gather')
+    X = rows * gather if gather else rows                           # rows of x / dres / dx
+    xrows = torch.arange(rows, device='cuda') * (gather or 1)
+    ldx = cols + 4
+    xbuf = torch.randn(X, ldx, device='cuda', generator=g) * 2 + 0.5
+    flat = xrows[torch.arange(rows, device='cuda') % 3 == 1]        # low-variance rows (flat crops): rstd ~ 300 at eps 1e-5
+    xbuf[flat] = 0.25 + 1e-3 * torch.randn(flat.shape[0], ldx, device='cuda', generator=g)
+    x = xbuf[:, :cols]
+    xd = x.double()[xrows]
+    var = ((xd - xd.mean(1, keepdim=True)) ** 2).mean(1)
+    mean = xd.mean(1).float(); rstd = torch.rsqrt(var + 1e-5).float()
+    gamma = torch.exp(0.7 * torch.randn(cols, device='cuda', generator=g))         # spread like pretrained gains
+    gamma[torch.rand(cols, device='cuda', generator=g) < 0.05] *= -1
+    dybuf = torch.randn(rows, lddy, device='cuda', generator=g).to(T16())
+    dy = dybuf[:, :cols]
+    dres = None
+    if opt.get('dres', True):
+        dres = _sentinel_buf(X, lddx, torch.float16)
+        dres[:, :cols] = (torch.randn(X, cols, device='cuda', generator=g) * 3).half()
+    if special in ('near', 'over', 'copy'):
+        # rows 2 and 5: dy scaled so that |LN part| peaks at `top`, dres = sign(LN part) * s, so dres + LN part straddles 65504
+        top, s = {'near': (12.0, HALF_MAX), 'over': (40.0, HALF_MAX), 'copy': (12.0, 40000.0)}[special]
+        for r in (2, 5):
+            ln, _, _ = _ln_bwd_ref(dy[r:r + 1], x, xrows[r:r + 1], gamma, mean[r:r + 1], rstd[r:r + 1], None)
+            dy[r] = (dy[r].double() * (top / ln.abs().max())).to(T16())
+            ln, _, _ = _ln_bwd_ref(dy[r:r + 1], x, xrows[r:r + 1], gamma, mean[r:r + 1], rstd[r:r + 1], None)
+            mag = torch.where((ln[0].abs() - (65520.0 - s)).abs() < 0.5, s - 32.0, s)     # nothing within 0.5 of 65520
+            dres[xrows[r], :cols] = (torch.sign(ln[0]) * mag).half()
+    if special == 'nonfinite':
+        dy[1, 5] = float('inf'); dy[3, 17] = float('-inf'); dy[4, 3] = float('nan')
+        dres[xrows[0], 9] = float('inf'); dres[xrows[0], 10] = float('-inf'); dres[xrows[6], 2] = float('nan')
+    bscale = None
+    rpi = opt.get('rpi')
+    if rpi:
+        n_bs = (X + rpi - 1) // rpi
+        bscale = torch.tensor([0.0, 1 / 0.7, 1.0, 0.75], device='cuda')[torch.arange(n_bs, device='cuda') % 4]   # zero factors included
+        if special == 'copy':
+            bscale = torch.full((n_bs,), 2.0, device='cuda')
+    row_index = xrows.to(torch.int32) if gather else None
+
+    dx_dtype = torch.float16 if half else torch.float32
+    dxbuf = _sentinel_buf(X + 2, lddx, dx_dtype)                    # two rows past the last one the call may touch
+    dres_k = None if dres is None else (dres if half else dres.float())
+    want_copy = opt.get('copy', True)
+    dxbbuf = _sentinel_buf(X + 2, lddx, T16()) if want_copy else None
+    dgb = dbb = None
+    if form == 'affine':
+        dgb = torch.zeros(cols + 8, device='cuda'); dbb = torch.zeros(cols + 8, device='cuda')
+        dgb[cols:] = 12345.0; dbb[cols:] = 12345.0
+    flag = torch.zeros(3, dtype=torch.int32, device='cuda')        # [1] is the flag, [0] / [2] must stay zero
+    lib = _lib.lib()
+    if form == 'four':
+        _lib.check(lib.reid_set_knob(b'LN_IMPL', 1))
+    try:
+        ops.layernorm_bwd(dy, x, gamma, mean, rstd, dxbuf[:X, :cols], dx_bf16=None if dxbbuf is None else dxbbuf[:X, :cols],
+                          dres=None if dres_k is None else dres_k[:, :cols], row_index=row_index,
+                          dgamma=None if dgb is None else dgb[:cols], dbeta=None if dbb is None else dbb[:cols],
+                          bf16_row_scale=bscale, rows_per_img=rpi or 0, overflow=flag[1:2])
+        torch.cuda.synchronize()
+    finally:
+        if form == 'four':
+            _lib.check(lib.reid_set_knob(b'LN_IMPL', -1))
+
+    o, allow, xh = _ln_bwd_ref(dy, x, xrows, gamma, mean, rstd, None if dres is None else dres[:, :cols])
+    written = torch.zeros(X + 2, lddx, dtype=torch.bool, device='cuda')
+    written[xrows, :cols] = True
+    got = dxbuf[xrows, :cols]
+    if half:
+        _check_elements(got, _saturate(o), allow, _rounding(o.abs() + allow, 10, -14), f'{name}/{form} dx')
+    else:
+        _check_elements(got, o, allow, torch.zeros_like(o), f'{name}/{form} dx')
+    _untouched(dxbuf, written, f'{name}/{form} dx')
+    bs = torch.ones(rows, 1, device='cuda', dtype=torch.float64) if bscale is None else bscale.double()[xrows // rpi][:, None]
+    ob = bs * o
+    allow_b = bs.abs() * allow + _U32 * ob.abs()
+    if dxbbuf is not None:
+        mant, emin = _fmt16(flavor)
+        ref_b = _saturate(ob) if flavor == 'f16' else ob
+        _check_elements(dxbbuf[xrows, :cols], ref_b, allow_b, _rounding(ob.abs() + allow_b, mant, emin), f'{name}/{form} 16-bit copy')
+        _untouched(dxbbuf, written, f'{name}/{form} 16-bit copy')
+    if form == 'affine':
+        # per column a chain of (rows per wave + waves) fp32 roundings: the kernel sums its rows per wave, then one atomic per wave
+        waves = 4 * min((rows + 3) // 4, 1024)
+        n = (rows + waves - 1) // waves + waves + 4
+        dyd = dy.double()
+        for got_c, ref_c, mag, nm in ((dgb, (dyd * xh).sum(0), (dyd * xh).abs().sum(0), 'dgamma'),
+                                      (dbb, dyd.sum(0), dyd.abs().sum(0), 'dbeta')):
+            _check_elements(got_c[:cols], ref_c, n * _U32 * mag.nan_to_num(0.0, 0.0, 0.0), torch.zeros_like(ref_c), f'{name} {nm}')
+            assert bool((got_c[cols:] == 12345.0).all()), f'{name} {nm}: written past cols'
+
+    # the overflow flag: set iff a finite value stored in half clamped (|v| >= 65520); the fp32 forms leave it alone
+    fin = torch.isfinite(o)
+    mags = [o.abs()[fin]]
+    if flavor == 'f16' and dxbbuf is not None:
+        mags.append(ob.abs()[torch.isfinite(ob)])
+    over = any(bool((m >= 65520.0).any()) for m in mags)
+    margin = float(allow_b.max() + allow.max()) + 1e-3
+    assert not any(bool(((m - 65520.0).abs() < margin).any()) for m in mags), 'test input sits on the clamping threshold'
+    assert int(flag[0]) == 0 and int(flag[2]) == 0
+    assert int(flag[1]) == (1 if half and over else 0), (name, form, int(flag[1]))
+    if special == 'near':
+        assert bool(((o.abs() > HALF_MAX) & (o > 0)).any()) and bool(((o.abs() > HALF_MAX) & (o < 0)).any()) and not over
+    if special == 'over':
+        assert bool((o >= 65520).any()) and bool((o <= -65520).any()) and bool(((o.abs() > HALF_MAX) & (o.abs() < 65520)).any())
+        if half:
+            assert bool((got.double()[o.abs() >= 65520].abs() == HALF_MAX).all())
+    if special == 'copy':
+        assert over == (flavor == 'f16') and float(o.abs()[fin].max()) < HALF_MAX
+    if special == 'nonfinite':
+        assert bool(torch.isinf(got).any()) and bool(torch.isnan(got).any())
+
+
 @pytest.mark.parametrize('rows,rpi,cols,scaled', [(197 * 3, 197, 768, True), (64, 1, 768, False), (50 * 5 + 3, 50, 512, True), (8, 4, 64, True)])
 def test_add_layernorm(ops, rows, rpi, cols, scaled):
     """x_out = x + scale[image] * y (fp32 add of the 16-bit branch output), h = LN(x_out): clip_backbone.py:76/:83 fused into the
