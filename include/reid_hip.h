@@ -60,9 +60,12 @@ int reid_version(void);
 int reid_flavor(void);
 /* Checks that device `dev` is gfx950 (MI355X).  */
 int reid_check_device(int dev);
-/* Experiment knobs (tools/ and the A/B harnesses only; the product path never calls this): sets the cached value of
- * knob `name` ("GEMM_TILE", "GEMM_DBG", "GEMM_PERSIST", "GEMM_STAGGER", ... = the REID_<name> environment variables,
- * which are read ONCE per process); value -1 restores "not set" (the built-in default). */
+/* Knobs that force a kernel form (tests, tools/ and the A/B harnesses only; the product path never calls this): sets the
+ * cached value of knob `name` = the REID_<name> environment variable, which is read ONCE per process; value -1 restores
+ * "not set" (the built-in default).  The knobs: "GEMM_TILE" (3 = the 128 x 128 tile, 12 / 14 = the 256 / 224-row ping-pong
+ * tile), "ATTN_BWD" (1 = the two-kernel backward), "LORA_IMPL" (1 = the slab kernel), "LN_IMPL" (1 = the four-column
+ * LayerNorm backward), "TOPK_TILE" (9 = select_kernel for phase C), "TOPK_SCAN" (0 = the tiled filter instead of the
+ * query-resident scan).  Any other name: REID_ERR_ARG. */
 int reid_set_knob(const char* name, int value);
 
 /* ------------------------------------------------------------------------------------------

@@ -127,7 +127,6 @@ struct AttnParams {
     const bf16_t* dout; bf16_t* dqkv; int lddqkv; float* delta;
     int n_seq, S, heads, causal;
     int q_tiles;  // > 0: only the first q_tiles 32-row QUERY tiles of every sequence are computed (all keys still take part)
-    int dbg;     // timing experiments (REID_ATTN_DBG): 1 = no output stores, 2 = also no softmax / P.V, 3 = staging only
 };
 
 // A 32x32 MFMA result tile holds, for the row on lanes l and l+32, the two 4-element halves of every 8-element column
@@ -174,7 +173,6 @@ __global__ __launch_bounds__(NT * 64, TWO_PASS ? 4 : 1) void attn_fwd_kernel(con
     __syncthreads();
     if (q0 >= p.S || (p.q_tiles > 0 && wave >= p.q_tiles)) return;   // wave-uniform; no barrier follows
 
-    if (REID_DBG(p) == 3) return;
     const FragOff fo = make_frag_off(lane);
     const uint8_t* km = p.key_mask ? p.key_mask + (size_t)seq * p.S : nullptr;
     const int h4 = 4 * (lane >> 5);
@@ -222,7 +220,7 @@ __global__ __launch_bounds__(NT * 64, TWO_PASS ? 4 : 1) void attn_fwd_kernel(con
         if (mx == -INFINITY) mx = 0.f;
         const float nmc = -mx * c;
 #pragma unroll 1
-        for (int kt = 0; kt < (REID_DBG(p) == 2 ? 0 : NT); ++kt) {
+        for (int kt = 0; kt < NT; ++kt) {
             f32x16 t = score_tile(kt);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
@@ -266,7 +264,6 @@ __global__ __launch_bounds__(NT * 64, TWO_PASS ? 4 : 1) void attn_fwd_kernel(con
             }
     }
     l += __shfl_xor(l, 32, 64);
-    if (REID_DBG(p) >= 1 && l != 12345.678f) return;
     {
         const float inv = 1.0f / l;
         bf16_t* orow = p.out + ((size_t)seq * p.S + qrow) * p.ldo + head * 64;
@@ -684,310 +681,6 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const AttnParam
     }
 }
 
-// ------------------------------------------------------------------------------------------ backward: one pass, PERSISTENT (r04)
-// The kernel above is bound by what happens BETWEEN items: 112 KiB of LDS images = one workgroup per CU, so the ~4 us it takes the four
-// images to land is exposed once per (sequence, head) -- about as long as the item's arithmetic.  Here one workgroup per CU walks the items
-// (blockIdx.x, + gridDim.x, ...) and the images of an item land under arithmetic that does not need them:
-//   top of item n:  [wait: Q / dO / O images of item n landed]  stage K / V (n)  -- they land under delta + phase 1, which take K and V of the
-//                   wave's own key tile from REGISTERS (fetched one item ahead) and read only the Q / dO images
-//   after phase 1:  the wave's own Q / dO fragments go to registers; barrier; stage Q / dO / O (n + 1) into the freed regions -- they land
-//                   under phase 2, which reads only the K / V images; [counted wait: K / V (n) landed]
-// Waits are COUNTED: the wait in the middle sits right after exactly 12 LDS-DMA instructions of this wave (three images x 4), so
-// `vmcnt(12)` means "everything issued before those twelve has landed" whatever else is in flight; outputs are stored after a wait,
-// never in front of one.  Barriers are raw s_barrier (a __syncthreads would drain the prefetch).
-// hipcc places `s_waitcnt vmcnt(0)` in front of every ds_read_b64_tr_b16 BUILTIN while any LDS-DMA is outstanding (it does not for plain
-// ds_read_b128), which would serialise exactly the overlap this kernel is built for: the transposed reads here are inline assembly
-// (eight reads and one lgkmcnt wait per statement).
-typedef __attribute__((address_space(3))) char* lds_cptr;
-__device__ __forceinline__ uint32_t lds_addr(const char* ptr) { return (uint32_t)(uintptr_t)(lds_cptr)(char*)ptr; }
-
-// four col_frag operands (eight transposed 8-byte reads) issued back to back, one wait; a[2 i], a[2 i + 1] = LDS byte addresses of operand i
-__device__ __forceinline__ void tr_read4(const uint32_t (&a)[8], bf16x8 (&f)[4]) {
-    unsigned long long r0, r1, r2, r3, r4, r5, r6, r7;
-    asm volatile("ds_read_b64_tr_b16 %0, %8\n\t"
-                 "ds_read_b64_tr_b16 %1, %9\n\t"
-                 "ds_read_b64_tr_b16 %2, %10\n\t"
-                 "ds_read_b64_tr_b16 %3, %11\n\t"
-                 "ds_read_b64_tr_b16 %4, %12\n\t"
-                 "ds_read_b64_tr_b16 %5, %13\n\t"
-                 "ds_read_b64_tr_b16 %6, %14\n\t"
-                 "ds_read_b64_tr_b16 %7, %15\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3), "=&v"(r4), "=&v"(r5), "=&v"(r6), "=&v"(r7)
-                 : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(a[5]), "v"(a[6]), "v"(a[7])
-                 : "memory");
-    const unsigned long long r[8] = {r0, r1, r2, r3, r4, r5, r6, r7};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const s4 lo = __builtin_bit_cast(s4, r[2 * i]), hi = __builtin_bit_cast(s4, r[2 * i + 1]);
-        f[i] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
-}
-__device__ __forceinline__ void tr_read2(const uint32_t (&a)[4], bf16x8 (&f)[2]) {
-    unsigned long long r0, r1, r2, r3;
-    asm volatile("ds_read_b64_tr_b16 %0, %4\n\t"
-                 "ds_read_b64_tr_b16 %1, %5\n\t"
-                 "ds_read_b64_tr_b16 %2, %6\n\t"
-                 "ds_read_b64_tr_b16 %3, %7\n\t"
-                 "s_waitcnt lgkmcnt(0)"
-                 : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)
-                 : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3])
-                 : "memory");
-    const unsigned long long r[4] = {r0, r1, r2, r3};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const s4 lo = __builtin_bit_cast(s4, r[2 * i]), hi = __builtin_bit_cast(s4, r[2 * i + 1]);
-        f[i] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
-}
-
-// stage_head with the LDS-DMA issued from inline assembly: hipcc then has NO vector-memory operation of this kernel's prefetch in its
-// scoreboard and leaves the LDS reads of the phases alone (with the builtin it puts `s_waitcnt vmcnt(0)` in front of every transposed
-// read while a DMA is outstanding).  M0 = LDS base of the wave-instruction; nothing else in the persistent kernel uses M0 (no builtin DMA).
-template <int NT>
-__device__ __forceinline__ void stage_head_asm(const bf16_t* __restrict__ base, int ld, int S, uint32_t lds_base, int wave, int lane) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int rblk = (i * NT + wave) * 8;
-        const int row = rblk + (lane >> 3);
-        const int c = swz(row, lane & 7);
-        const int grow = row < S ? row : S - 1;
-        const bf16_t* src = base + (size_t)grow * ld + c * 8;
-        const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds_base + (uint32_t)rblk * 128u);
-        asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0v) : "memory");
-    }
-}
-
-template <int NT>
-__global__ __launch_bounds__(NT * 64) void attn_bwd_pers_kernel(const AttnParams p, int n_items) {
-    REID_T16_ENTER();
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int IMG = NT * 32 * 128;
-    char* Qs = smem;
-    char* Gs = smem + IMG;                           // dO
-    char* Os = smem + 2 * IMG;                       // O (delta only)
-    char* Ks = smem + 3 * IMG;
-    char* Vs = smem + 4 * IMG;
-    float* rowc = (float*)(smem + 5 * IMG);          // [2][NT*32]: -lse * log2(e), -delta / 8
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int d = p.heads * 64;
-    const int t0 = wave * 32;
-    const int ti = t0 + (lane & 31);
-    const int trow = ti < p.S ? ti : p.S - 1;
-    const bool tile_ok = ti < p.S;
-    const float c = 0.125f * LOG2E;
-    const int h4 = 4 * (lane >> 5);
-    const FragOff fo = make_frag_off(lane);
-    const int nt = (p.S + 31) / 32;                  // == NT (launch_bwd picks NT = ceil(S / 32)): every wave owns a real tile
-    const uint32_t aQ = lds_addr(Qs), aG = lds_addr(Gs), aO = lds_addr(Os), aK = lds_addr(Ks), aV = lds_addr(Vs);
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto item_ptrs = [&](int item, const bf16_t*& qb, const bf16_t*& gb, const bf16_t*& ob, size_t& so0) {
-        const int seq = item / p.heads, head = item % p.heads;
-        qb = p.qkv + (size_t)seq * p.S * p.ld + head * 64;
-        gb = p.dout + (size_t)seq * p.S * p.ldo + head * 64;
-        ob = p.out + (size_t)seq * p.S * p.ldo + head * 64;
-        so0 = ((size_t)seq * p.heads + head) * p.S;
-    };
-
-    int item = blockIdx.x;
-    const bf16_t *qb, *gb, *ob;
-    size_t so0;
-    item_ptrs(item, qb, gb, ob, so0);
-    // prologue: Q / dO / O images and the register operands of the first item
-    stage_head_asm<NT>(qb, p.ld, p.S, aQ, wave, lane);
-    stage_head_asm<NT>(gb, p.ldo, p.S, aG, wave, lane);
-    stage_head_asm<NT>(ob, p.ldo, p.S, aO, wave, lane);
-    bf16x8 kf[4], vf[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-        kf[ks] = gfrag(qb + d, p.ld, trow, 2 * ks, lane);
-        vf[ks] = gfrag(qb + 2 * d, p.ld, trow, 2 * ks, lane);
-    }
-    float lse_v = p.lse[so0 + trow];
-#ifdef REID_ATTN_TRACE
-#define PSTAMP(slot) do { if (g_attn_bwd_trace && threadIdx.x == 0) g_attn_bwd_trace[(size_t)item * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define PSTAMP(slot) do { } while (0)
-#endif
-    for (;;) {
-        PSTAMP(0);
-        // everything in flight has landed: this item's Q / dO / O images (staged under the previous item's phase 2) and register operands
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        // (the compiler tracks the register operands itself and does not see the wait above: a use of each of them HERE makes it place its
-        //  own wait here, where nothing else is in flight, rather than behind the K / V staging below)
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) asm volatile("" :: "v"(kf[ks]), "v"(vf[ks]));
-        asm volatile("" :: "v"(lse_v));
-        bar();                                       // ... for every wave; and nobody reads the previous item's K / V images any more
-        PSTAMP(1);
-        stage_head_asm<NT>(qb + d, p.ld, p.S, aK, wave, lane);          // this item's K / V images: they land under delta + phase 1
-        stage_head_asm<NT>(qb + 2 * d, p.ld, p.S, aV, wave, lane);
-        // ---- delta of this wave's query rows -> LDS, with the saved log-sum-exp
-        {
-            float dsum = 0.f;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const bf16x8 gfk = row_frag_o(Gs, t0, ks, fo), ofk = row_frag_o(Os, t0, ks, fo);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) dsum = fmaf(bf16_to_f32((bf16_t)gfk[j]), bf16_to_f32((bf16_t)ofk[j]), dsum);
-            }
-            dsum += __shfl_xor(dsum, 32, 64);
-            if (lane < 32) {
-                rowc[ti] = tile_ok ? -lse_v * LOG2E : -INFINITY;
-                rowc[NT * 32 + ti] = tile_ok ? -dsum * 0.125f : 0.f;
-            }
-        }
-        bar();                                       // rowc complete
-        PSTAMP(2);
-        // ---- phase 1: this wave's key tile (K, V of the tile in registers; Q / dO images)
-        f32x16 dkt[2], dvt[2];
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { dkt[dt][e] = 0.f; dvt[dt][e] = 0.f; }
-        {
-            auto scores = [&](int qt, f32x16& s, f32x16& dp) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { s[e] = 0.f; dp[e] = 0.f; }
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    s = mfma32(row_frag_o(Qs, qt * 32, ks, fo), kf[ks], s);
-                    dp = mfma32(row_frag_o(Gs, qt * 32, ks, fo), vf[ks], dp);
-                }
-            };
-            f32x16 s, dp, s_n, dp_n;
-            scores(0, s, dp);
-            for (int qt = 0; qt < nt; ++qt) {
-                if (qt + 1 < nt) scores(qt + 1, s_n, dp_n);          // next tile's matrix work first: it runs under this tile's exponentials
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    bf16x8 pf, df;
-#pragma unroll
-                    for (int g2 = 0; g2 < 2; ++g2) {
-                        const int g = 2 * s2 + g2;
-                        const f32x4 nl = *(const f32x4*)(rowc + qt * 32 + 8 * g + h4);
-                        const f32x4 nd = *(const f32x4*)(rowc + NT * 32 + qt * 32 + 8 * g + h4);
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const int e = 4 * g + j;
-                            const float pe = fast_exp2(fmaf(s[e], c, nl[j]));
-                            pf[4 * g2 + j] = (short)f32_to_bf16(pe);
-                            df[4 * g2 + j] = (short)f32_to_bf16(pe * fmaf(dp[e], 0.125f, nd[j]));
-                        }
-                    }
-#pragma unroll
-                    for (int dt = 0; dt < 2; ++dt) {
-                        dvt[dt] = mfma32(col_frag_o(Gs, qt * 32 + 16 * s2, dt, fo), pf, dvt[dt]);
-                        dkt[dt] = mfma32(col_frag_o(Qs, qt * 32 + 16 * s2, dt, fo), df, dkt[dt]);
-                    }
-                }
-                s = s_n; dp = dp_n;
-            }
-        }
-        PSTAMP(3);
-        // this wave's own query-tile fragments and row constants for phase 2: the last reads of the Q / dO images and of rowc
-        bf16x8 qf[4], gf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { qf[ks] = row_frag_o(Qs, t0, ks, fo); gf[ks] = row_frag_o(Gs, t0, ks, fo); }
-        const float nl = rowc[ti], nd = rowc[NT * 32 + ti];
-        bf16_t* drow = p.dqkv + ((size_t)(item / p.heads) * p.S + trow) * p.lddqkv + (item % p.heads) * 64;
-        bar();                                       // nobody reads the Q / dO / O images (or rowc) of this item any more
-        const int nxt = item + (int)gridDim.x;
-        const bool has_next = nxt < n_items;         // (workgroup-uniform)
-        const bf16_t *qb_n = qb, *gb_n = gb, *ob_n = ob;
-        size_t so_n = so0;
-        if (has_next) item_ptrs(nxt, qb_n, gb_n, ob_n, so_n);
-        if (has_next) {
-            // the next item's Q / dO / O images into the freed regions: twelve DMA instructions per wave, then the counted wait
-            stage_head_asm<NT>(qb_n, p.ld, p.S, aQ, wave, lane);
-            stage_head_asm<NT>(gb_n, p.ldo, p.S, aG, wave, lane);
-            stage_head_asm<NT>(ob_n, p.ldo, p.S, aO, wave, lane);
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(12)" ::: "memory");       // everything older has landed: in particular this item's K / V images
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        bar();                                       // ... for every wave
-        PSTAMP(4);
-        // (outputs of phase 1 are stored only now: a store in front of the wait would have to be acknowledged before it passes)
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) {
-            store_tile_row16(drow + d + dt * 32, tile_ok, dkt[dt], 1.0f, lane);
-            store_tile_row16(drow + 2 * d + dt * 32, tile_ok, dvt[dt], 1.0f, lane);
-        }
-        PSTAMP(5);
-        // ---- phase 2: this wave's query tile (Q, dO of the tile in registers; K / V images)
-        f32x16 dqt[2];
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) dqt[dt][e] = 0.f;
-        {
-            auto scores_t = [&](int kt, f32x16& s, f32x16& dp) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) { s[e] = 0.f; dp[e] = 0.f; }
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    s = mfma32(row_frag_o(Ks, kt * 32, ks, fo), qf[ks], s);
-                    dp = mfma32(row_frag_o(Vs, kt * 32, ks, fo), gf[ks], dp);
-                }
-            };
-            f32x16 s, dp;
-            scores_t(0, s, dp);
-            for (int kt = 0; kt < nt; ++kt) {
-                if (kt > 0) scores_t(kt, s, dp);     // (not pipelined like phase 1: with the next item's operands in registers a second accumulator pair spills, and a scratch reload is a VMEM operation in the middle of the counted waits)
-                const bool edge = (kt + 1) * 32 > p.S;
-                bf16x8 df[2];
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int e = 8 * s2 + j;
-                        float pe = fast_exp2(fmaf(s[e], c, nl));
-                        if (edge) {
-                            const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + h4;
-                            pe = key < p.S ? pe : 0.f;
-                        }
-                        df[s2][j] = (short)f32_to_bf16(pe * fmaf(dp[e], 0.125f, nd));
-                    }
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-                    for (int dt = 0; dt < 2; ++dt) dqt[dt] = mfma32(col_frag_o(Ks, kt * 32 + 16 * s2, dt, fo), df[s2], dqt[dt]);
-            }
-        }
-        PSTAMP(6);
-#pragma unroll
-        for (int dt = 0; dt < 2; ++dt) store_tile_row16(drow + dt * 32, tile_ok, dqt[dt], 1.0f, lane);
-        PSTAMP(7);
-        if (!has_next) break;
-        // register operands of the next item: K and V rows of this wave's key tile and the saved log-sum-exp.  Fetched HERE, after the
-        // phases (the compiler tracks these loads and would make every transposed LDS read of a phase wait for them); they are waited for
-        // at the top of the loop together with the dQ stores above (~1 us, the only exposed memory latency of an item)
-        bf16x8 kf_n[4], vf_n[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            kf_n[ks] = gfrag(qb_n + d, p.ld, trow, 2 * ks, lane);
-            vf_n[ks] = gfrag(qb_n + 2 * d, p.ld, trow, 2 * ks, lane);
-        }
-        const float lse_n = p.lse[so_n + trow];                        // (nothing of this wave is in flight towards LDS: the last DMA was waited for above)
-        item = nxt; qb = qb_n; gb = gb_n; ob = ob_n; so0 = so_n;
-        lse_v = lse_n;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { kf[ks] = kf_n[ks]; vf[ks] = vf_n[ks]; }
-    }
-}
-
 template <int NT>
 int launch_fwd(const AttnParams& p, hipStream_t s) {
     constexpr int LDS = 2 * NT * 32 * 128;
@@ -1004,26 +697,15 @@ int launch_bwd(const AttnParams& p, hipStream_t s) {
     constexpr int LDS2 = 2 * NT * 32 * 128;
     REID_MAX_LDS((attn_bwd_dkv_kernel<NT>), LDS1);
     REID_MAX_LDS((attn_bwd_dq_kernel<NT>), LDS2);
-    // REID_ATTN_BWD: 1 = the two-kernel form, 2 = one pass, one item per workgroup (default), 3 = one pass, persistent.  Masked / causal
-    // attention: two kernels.  Measured (r04, 256 images x 12 heads, profiles/r04_attn_bwd.log): 292 / 257 / 257 us alone; inside the training
-    // step 31.93 / 31.42 / 31.54 ms per step on one box -- the persistent form hides the image staging (top-of-item wait 1.0 us instead of
-    // 5.5 us) but pays it back in barriers and DMA issue (3.1 us between the phases), and like every persistent kernel it keeps its CUs
-    // from the side stream; the one-item form is the default.
-    const int impl = reid_knob(KNOB_ATTN_BWD);
-    if (!p.key_mask && !p.causal && impl != 1) {
+    // one pass, one item per workgroup; masked / causal attention, and REID_ATTN_BWD=1, take the two-kernel form.  Measured (r04,
+    // 256 images x 12 heads, profiles/r04_attn_bwd.log), two kernels / one pass / one pass persistent: 292 / 257 / 257 us alone; inside the
+    // training step 31.93 / 31.42 / 31.54 ms per step on one box -- the persistent form (at 13e2fd7) hides the image staging (top-of-item
+    // wait 1.0 us instead of 5.5 us) but pays it back in barriers and DMA issue (3.1 us between the phases), and like every persistent
+    // kernel it keeps its CUs from the side stream.
+    if (!p.key_mask && !p.causal && reid_knob(KNOB_ATTN_BWD) != 1) {
         constexpr int LDSF = 4 * NT * 32 * 128 + 2 * NT * 32 * 4;
-        constexpr int LDSP = 5 * NT * 32 * 128 + 2 * NT * 32 * 4;          // + the O image
-        const int n_items = p.n_seq * p.heads;
-        const int cus = reid_num_cus();
-        const bool pers_ok = p.q_tiles <= 0 && (p.S + 31) / 32 == NT;
-        if (pers_ok && impl == 3) {
-            REID_MAX_LDS((attn_bwd_pers_kernel<NT>), LDSP);
-            hipLaunchKernelGGL(attn_bwd_pers_kernel<NT>, dim3(n_items < cus ? n_items : cus), dim3(NT * 64), LDSP, s, p, n_items);
-            REID_CHECK_LAUNCH("reid_attn_bwd(persistent)");
-            return REID_OK;
-        }
         REID_MAX_LDS((attn_bwd_fused_kernel<NT>), LDSF);
-        hipLaunchKernelGGL(attn_bwd_fused_kernel<NT>, dim3(n_items), dim3(NT * 64), LDSF, s, p);
+        hipLaunchKernelGGL(attn_bwd_fused_kernel<NT>, dim3(p.n_seq * p.heads), dim3(NT * 64), LDSF, s, p);
         REID_CHECK_LAUNCH("reid_attn_bwd(fused)");
         return REID_OK;
     }
@@ -1067,8 +749,7 @@ extern "C" int reid_attn_fwd(const void* qkv, int32_t ld, const uint8_t* key_mas
     int rc = check_common("reid_attn_fwd", qkv, ld, n_seq, S, heads);
     if (rc) return rc;
     REID_CHECK_ARG(out && ldo >= heads * 64 && ldo % 4 == 0, "reid_attn_fwd: out/ldo");
-    AttnParams p{(const bf16_t*)qkv, ld, key_mask, (bf16_t*)out, ldo, lse, nullptr, nullptr, 0, nullptr, n_seq, S, heads, causal, q_tiles, 0};
-    if (reid_knob(KNOB_ATTN_DBG) > 0) p.dbg = reid_knob(KNOB_ATTN_DBG);
+    AttnParams p{(const bf16_t*)qkv, ld, key_mask, (bf16_t*)out, ldo, lse, nullptr, nullptr, 0, nullptr, n_seq, S, heads, causal, q_tiles};
     DISPATCH_NT((S + 31) / 32, launch_fwd, p, (hipStream_t)stream)
 }
 
@@ -1080,6 +761,6 @@ extern "C" int reid_attn_bwd(const void* qkv, int32_t ld, const uint8_t* key_mas
     REID_CHECK_ARG(out && dout && lse && dqkv && delta_ws, "reid_attn_bwd: null pointer");
     REID_CHECK_ARG(ldo >= heads * 64 && ldo % 8 == 0 && lddqkv >= 3 * heads * 64 && lddqkv % 4 == 0, "reid_attn_bwd: ldo/lddqkv");
     AttnParams p{(const bf16_t*)qkv, ld, key_mask, (bf16_t*)out, ldo, (float*)lse, (const bf16_t*)dout, (bf16_t*)dqkv, lddqkv,
-                 delta_ws, n_seq, S, heads, causal, q_tiles, 0};
+                 delta_ws, n_seq, S, heads, causal, q_tiles};
     DISPATCH_NT((S + 31) / 32, launch_bwd, p, (hipStream_t)stream)
 }

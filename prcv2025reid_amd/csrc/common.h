@@ -13,24 +13,13 @@ typedef unsigned short bf16_t;   // 16-bit storage (bf16 or f16 by flavor)
 
 __attribute__((visibility("hidden"))) void reid_set_error(const char* fmt, ...);
 
-// Experiment knobs (tile choice, early-exit builds, pipeline parameters): ONE cached table per process, filled from the
-// environment (REID_<NAME>) on first use and changed afterwards only through reid_set_knob() -- no getenv() on the launch path.
-enum reid_knob_id {
-    KNOB_GEMM_TILE, KNOB_GEMM_DBG, KNOB_GEMM_GROUPM, KNOB_GEMM_EPI, KNOB_GEMM_STAGGER,
-    KNOB_ATTN_DBG, KNOB_TN_BLOCKS, KNOB_TOPK_DBG, KNOB_TOPK_TILE, KNOB_STREAM_ROWS, KNOB_STREAM_GROUPS, KNOB_SDM_IMPL, KNOB_SKINNY_TILE, KNOB_GEMM_PERSIST,
-    KNOB_ATTN_BWD, KNOB_LORA_IMPL, KNOB_GELU_IMPL, KNOB_HEAD_IMPL, KNOB_STREAM_FUSE, KNOB_TOPK_SCAN, KNOB_LN_IMPL, KNOB_COUNT
-};
+// Knobs that force one kernel form over the one the dispatch would pick -- the reference forms the tests compare against, and the tile
+// A/B of the benchmarks: ONE cached table per process, filled from the environment (REID_<NAME>) on first use and changed afterwards only
+// through reid_set_knob() -- no getenv() on the launch path.
+enum reid_knob_id { KNOB_GEMM_TILE, KNOB_ATTN_BWD, KNOB_LORA_IMPL, KNOB_LN_IMPL, KNOB_TOPK_TILE, KNOB_TOPK_SCAN, KNOB_COUNT };
 // (internal C++ symbols of the library: hidden, only the extern "C" entry points of include/reid_hip.h are exported)
 __attribute__((visibility("hidden"))) int reid_knob(int id);
 __attribute__((visibility("hidden"))) int reid_num_cus();   // compute units of the current device (cached)
-// The *_DBG knobs switch kernels into timing-experiment modes that skip work (WRONG results).  They exist only in builds made with
-// -DREID_EXPERIMENTS (tools/): in the shipped library REID_DBG(p) is the constant 0 -- the early exits are compiled out -- the
-// REID_*_DBG environment variables are ignored and reid_set_knob() refuses those names.
-#ifdef REID_EXPERIMENTS
-#define REID_DBG(p) ((p).dbg)
-#else
-#define REID_DBG(p) 0
-#endif
 
 #define REID_CHECK_ARG(cond, ...)                     \
     do {                                              \

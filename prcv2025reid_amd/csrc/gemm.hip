@@ -33,10 +33,7 @@ struct GemmParams {
     float alpha;
     int tiles_m, tiles_n;
     int group_m;  // row tiles per L2 group of the tile order (gemm_core.h tile_coords)
-    int stagger;  // ping-pong kernel: spread (in 0.25 us units) of the start times of the first round of workgroups
-    int aux_pre;  // multiply-by-derivative epilogue on the 256-row tile: aux tile staged inside the K loop (REID_GELU_IMPL=1: after it, the r03 form)
     int perm_b;   // weight rows staged through perm32() (16-bit C with 16-byte pieces)
-    int dbg;      // timing experiments only (REID_GEMM_DBG): 1 = skip the epilogue, 4 = skip the K loop (epilogue only)
     int epi;      // EPI_*: which epilogue the kernel instance was built with (host side choice)
     // Row groups (n_groups > 0): activation rows [grp_row0[g], grp_row_end[g]) multiply weight matrix number grp_b[g] of a stack of
     // [N, K] matrices b_group_stride elements apart (the per-modality merged weights W + s B_mu A_mu: images are packed modality by
@@ -49,12 +46,12 @@ struct GemmParams {
 
 // Epilogue kinds.  The GENERIC epilogue evaluates every option of reid_mer_gemm at run time (~100-600 instructions per 16-byte
 // piece, ~1 000 scalar branches in the kernel): it is instruction-issue bound and held the C / residual traffic of the big GEMMs at
-// 3-4 TB/s where plain 16-byte stores of the same shape reach 7 TB/s (r02: tools/store_patterns.hip, REID_GEMM_DBG=4).  The four
+// 3-4 TB/s where plain 16-byte stores of the same shape reach 7 TB/s (r02: tools/store_patterns.hip and an epilogue-only timing mode, at 13e2fd7).  The four
 // kinds below cover the seven ViT GEMM variants of a training step with straight-line code (32-bit offsets, one predicate per
 // row, no option tests); everything else (patch embed row remap, routing masks, alpha, quick-GELU, ...) stays on GENERIC.
 // GELU2D / MULAUX (r02): the training path saves gelu'(u) in the forward epilogue -- it shares the erfc and exp of the value -- so
 // the backward epilogue is one multiply per element instead of ~23 VALU operations (epilogues of this family are VALU-bound at
-// two waves per SIMD: ~12 us per 256 x 256 tile, tools/exp_epilogue_scale.py).
+// two waves per SIMD: ~12 us per 256 x 256 tile, tools/exp_epilogue_scale.py at 13e2fd7).
 // PLAIN16H (r04, bf16 flavor only): the plain 16-bit store in IEEE half (REID_F16 output) -- the residual-branch outputs (out-projection,
 // fc2) are consumed by the add + LayerNorm kernel, never by an MFMA, so they can carry half's 11 significant bits instead of bf16's 8.
 enum { EPI_GENERIC = 0, EPI_PLAIN16 = 1, EPI_RES32 = 2, EPI_GELU2 = 3, EPI_DGELU = 4, EPI_GELU2D = 5, EPI_MULAUX = 6, EPI_PLAIN16H = 7 };
@@ -245,19 +242,6 @@ __device__ __forceinline__ void store_tile_m(const GemmParams& p, f32x4 (&acc)[T
     }
 }
 
-// Output stores of the lean epilogues.  -DREID_NT_STORES: non-temporal (the tile is written once and never re-read by this kernel, so it
-// need not displace the operand panels the XCD's other workgroups are re-reading from L2).
-template <typename T>
-__device__ __forceinline__ void st_out(T* ptr, const T& v) {
-#ifdef REID_NT_STORES
-    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
-    static_assert(sizeof(T) == 16, "16-byte pieces");
-    __builtin_nontemporal_store(__builtin_bit_cast(u32x4_t, v), (u32x4_t*)ptr);
-#else
-    *ptr = v;
-#endif
-}
-
 // Lean epilogues (host side guarantees: N a multiple of the tile, every stride a multiple of 8 elements, every operand below
 // 4 GiB, alpha == 1, no mask / row remap / periodic residual).  Layout as in store_tile_m: the 16-bit kinds use the perm32
 // weight-row staging (a lane owns 8 consecutive columns per pair of MFMA sub-tiles), EPI_RES32 the natural one (4 columns).
@@ -299,7 +283,7 @@ __device__ __forceinline__ void store_tile_fast(const GemmParams& p, f32x4 (&acc
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const f32x4 v = acc[j][i] * rs[ii] + r[ii][j];
-                    if (ok) st_out((f32x4*)(C + co + 64u * j), v);
+                    if (ok) *(f32x4*)(C + co + 64u * j) = v;
                 }
             }
         }
@@ -339,7 +323,7 @@ __device__ __forceinline__ void store_tile_fast(const GemmParams& p, f32x4 (&acc
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] = acc[2 * pc + (e >> 2)][i][e & 3];
                 if constexpr (EPI == EPI_GELU2) {
-                    if (ok) st_out((uint4*)((char*)p.C2 + c2o + 64u * pc), uint4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])});
+                    if (ok) *(uint4*)((char*)p.C2 + c2o + 64u * pc) = uint4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
 #pragma unroll
                     for (int e = 0; e < 8; e += 2) {
                         f32x2_t gg, dd;
@@ -354,7 +338,7 @@ __device__ __forceinline__ void store_tile_fast(const GemmParams& p, f32x4 (&acc
                         gelu_both_x2(f32x2_t{v[e], v[e + 1]}, gg, dd);
                         v[e] = gg.x; v[e + 1] = gg.y; dv[e] = dd.x; dv[e + 1] = dd.y;
                     }
-                    if (ok) st_out((uint4*)((char*)p.C2 + c2o + 64u * pc), uint4{pack_bf16x2(dv[0], dv[1]), pack_bf16x2(dv[2], dv[3]), pack_bf16x2(dv[4], dv[5]), pack_bf16x2(dv[6], dv[7])});
+                    if (ok) *(uint4*)((char*)p.C2 + c2o + 64u * pc) = uint4{pack_bf16x2(dv[0], dv[1]), pack_bf16x2(dv[2], dv[3]), pack_bf16x2(dv[4], dv[5]), pack_bf16x2(dv[6], dv[7])};
                 } else if constexpr (EPI == EPI_DGELU) {
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= dgelu_erf_f(bf16_to_f32((bf16_t)av[i][pc][e]));
@@ -363,9 +347,9 @@ __device__ __forceinline__ void store_tile_fast(const GemmParams& p, f32x4 (&acc
                     for (int e = 0; e < 8; ++e) v[e] *= bf16_to_f32((bf16_t)av[i][pc][e]);
                 }
                 if constexpr (EPI == EPI_PLAIN16H) {
-                    if (ok) st_out((uint4*)(C + co + 64u * pc), uint4{pack_f16x2(v[0], v[1]), pack_f16x2(v[2], v[3]), pack_f16x2(v[4], v[5]), pack_f16x2(v[6], v[7])});
+                    if (ok) *(uint4*)(C + co + 64u * pc) = uint4{pack_f16x2(v[0], v[1]), pack_f16x2(v[2], v[3]), pack_f16x2(v[4], v[5]), pack_f16x2(v[6], v[7])};
                 } else {
-                    if (ok) st_out((uint4*)(C + co + 64u * pc), uint4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])});
+                    if (ok) *(uint4*)(C + co + 64u * pc) = uint4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
                 }
             }
         }
@@ -440,13 +424,11 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void mer_gemm_kernel(const GemmPara
     if constexpr (EPI == EPI_GENERIC) init_acc<C::TM, C::TN>(p, acc, n0 + wn * (BN / WN), lane);
     else if constexpr (EPI == EPI_RES32) init_acc_m<C::TM, C::TN, 0>(p, acc, n0 + wn * (BN / WN), lane);
     else init_acc_m<C::TM, C::TN, 1>(p, acc, n0 + wn * (BN / WN), lane);
-    if (REID_DBG(p) != 4)
-        mainloop<BM, BN, WM, WN>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc,
-                                 p.perm_b != 0);
+    mainloop<BM, BN, WM, WN>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc,
+                             p.perm_b != 0);
 
     // ------------------------------------------------------------------ epilogue (registers -> global, no LDS)
     constexpr int WTM = BM / WM, WTN = BN / WN;
-    if (REID_DBG(p) == 1) return;
     if constexpr (EPI == EPI_GENERIC) store_tile<C::TM, C::TN>(p, acc, m0 + wm * WTM, n0 + wn * WTN, lane, m_end);
     else store_tile_fast<C::TM, C::TN, EPI>(p, acc, m0 + wm * WTM, n0 + wn * WTN, lane, m_end);
 }
@@ -470,12 +452,6 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pp_kernel(const GemmParams p)
 #define GEMM_TRACE(slot) do { } while (0)
 #endif
     GEMM_TRACE(0);
-    if (p.stagger > 0 && blockIdx.x < 256) {
-        // first round only: CU c of every XCD starts c/32 of the spread late, so the epilogues of the chip's 256 tiles in flight
-        // do not all hit HBM in the same few microseconds (see launch_pp)
-        const int n = ((blockIdx.x >> 3) & 31) * p.stagger >> 5;
-        for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(8);            // 8 x 64 cycles ~ 0.25 us
-    }
     const int lin = xcd_linear_block(blockIdx.x, gridDim.x);
     int tm, tn;
     tile_coords(lin, p.tiles_m, p.tiles_n, tm, tn, p.group_m);
@@ -489,29 +465,12 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pp_kernel(const GemmParams p)
     if constexpr (EPI == EPI_GENERIC) init_acc<TM, 4>(p, acc, n0 + wn * 64, lane);
     else if constexpr (EPI == EPI_RES32) init_acc_m<TM, 4, 0>(p, acc, n0 + wn * 64, lane);
     else init_acc_m<TM, 4, 1>(p, acc, n0 + wn * 64, lane);
-#ifdef REID_GEMM_ABLATIONS                                  // K-loop anatomy builds (profiles/r02_gemm_variants10*.log); not in the shipped library
-    if (EPI == EPI_PLAIN16 && BM == 256 && REID_DBG(p) >= 16) {
-        switch (REID_DBG(p) - 16) {
-            case 1: mainloop_pp<BM, 256, 1>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc, p.perm_b != 0); break;
-            case 2: mainloop_pp<BM, 256, 2>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc, p.perm_b != 0); break;
-            case 3: mainloop_pp<BM, 256, 3>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc, p.perm_b != 0); break;
-            case 4: mainloop_pp<BM, 256, 4>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc, p.perm_b != 0); break;
-            case 6: mainloop_pp<BM, 256, 6>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc, p.perm_b != 0); break;
-            case 11: mainloop_pp<BM, 256, 11>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc, p.perm_b != 0); break;
-            default: break;
-        }
-        if (acc[0][0][0] != 1234.5f) return;
-    }
-#endif
     // multiply-by-derivative epilogue on the 256-row tile: the aux tile is staged by the K loop's last two steps (gemm_core.h AUXPRE)
     constexpr bool AUX_IN_LOOP = EPI == EPI_MULAUX && BM == 256;
-    const bool aux_staged = AUX_IN_LOOP && p.aux_pre != 0 && p.K2 == 0 && (p.K >> 6) >= 2 && REID_DBG(p) != 4;
-    if (REID_DBG(p) != 4) {
-        mainloop_pp<BM, 256, 0, AUX_IN_LOOP>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc, p.perm_b != 0,
-                                             aux_staged ? (const bf16_t*)p.aux : nullptr, p.ldaux);
-    }
+    const bool aux_staged = AUX_IN_LOOP && p.K2 == 0 && (p.K >> 6) >= 2;
+    mainloop_pp<BM, 256, AUX_IN_LOOP>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc, p.perm_b != 0,
+                                      aux_staged ? (const bf16_t*)p.aux : nullptr, p.ldaux);
     GEMM_TRACE(1);
-    if (REID_DBG(p) == 1) return;
     if constexpr (EPI == EPI_MULAUX) {
         if (aux_staged) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -651,41 +610,30 @@ static int pick_pp_bm(const GemmParams& p, int tile_knob) {
     return (t224 + cus - 1) / cus <= (t256 + cus - 1) / cus ? 224 : 256;
 }
 int launch_pp(GemmParams& p, hipStream_t s, int tile_knob) {
-    p.epi = reid_knob(KNOB_GEMM_EPI) == 0 ? EPI_GENERIC : pick_epilogue(p, 256);
+    p.epi = pick_epilogue(p, 256);
     const int bm = p.epi == EPI_GENERIC ? 256 : pick_pp_bm(p, tile_knob);     // (the generic epilogue is only built for the 256-row tile)
     p.tiles_m = row_tiles(p, bm, true);
     p.tiles_n = (p.N + 255) / 256;
-    p.stagger = reid_knob(KNOB_GEMM_STAGGER) > 0 ? reid_knob(KNOB_GEMM_STAGGER) : 0;
-    p.aux_pre = reid_knob(KNOB_GELU_IMPL) != 1;
 #ifdef REID_GEMM_TRACE
     p.trace = g_gemm_trace;
 #endif
-    // persistent stream form (default where it applies; REID_GEMM_PERSIST=0 keeps one tile per workgroup)
-    // REID_GEMM_PERSIST bits: 1 = persistent form on; 2 = GELU epilogues too; 4 = multiply-by-derivative epilogue too (register-direct
-    // aux operand); 8 = the short-K narrow-N out-projection shapes on this tile as well.  Default 9.  In-step A/B (r03, bench.py, one box):
-    // 1: 33.15-33.25 ms/step, 9: 33.02, 13: 32.98-33.00, 5: 33.40 -- inside the step a persistent GEMM keeps its CUs for its whole duration,
-    // so the HBM-bound side-stream kernels cannot take compute units from it (q|k|v backward 263 -> 194 us in-step)
-    const int pk = reid_knob(KNOB_GEMM_PERSIST) < 0 ? 9 : reid_knob(KNOB_GEMM_PERSIST);
-    const bool persist = pk != 0 && p.K2 == 0 && p.K >= 192 && (reid_num_cus() & ~7) >= 8 &&
-                         (p.epi == EPI_PLAIN16 || p.epi == EPI_PLAIN16H || p.epi == EPI_RES32 || ((pk & 2) && (p.epi == EPI_GELU2 || p.epi == EPI_GELU2D)) ||
-                          ((pk & 4) && p.epi == EPI_MULAUX));
+    // persistent stream form for the plain and residual epilogues, the out-projection shapes included.  In-step A/B (r03, bench.py,
+    // one box; the persistent set as a bit mask, 1 = plain / residual, 2 = GELU too, 4 = multiply-by-derivative too, 8 = out-projection
+    // shapes too; the switch is at 13e2fd7): 1: 33.15-33.25 ms/step, 9: 33.02, 13: 32.98-33.00, 5: 33.40 -- inside the step a persistent
+    // GEMM keeps its CUs for its whole duration, so the HBM-bound side-stream kernels cannot take compute units from it (q|k|v backward
+    // 263 -> 194 us in-step)
     // (r03, tools/bench_gemm_shapes.py, profiles/r03_gemm_pps2.log: q|k|v 195 -> 183 us, q|k|v backward 157 -> 151, fc1 backward 207 -> 202,
     //  residual shapes unchanged; the GELU shapes are 2 % SLOWER persistent (327 -> 334 us: their 6 + 3.5 us VALU-bound epilogue dominates the
-    //  tile boundary and a static tile sequence cannot rebalance it), so they stay one tile per workgroup unless REID_GEMM_PERSIST=2)
-    if (persist) {
-#define REID_PPS_CASE(E) case E: return bm == 224 ? launch_pps_e<E, 224>(p, s) : launch_pps_e<E, 256>(p, s);
+    //  tile boundary and a static tile sequence cannot rebalance it), so they stay one tile per workgroup)
+    if (p.K2 == 0 && p.K >= 192 && (reid_num_cus() & ~7) >= 8) {
         switch (p.epi) {
-            REID_PPS_CASE(EPI_PLAIN16)
+            case EPI_PLAIN16: return bm == 224 ? launch_pps_e<EPI_PLAIN16, 224>(p, s) : launch_pps_e<EPI_PLAIN16, 256>(p, s);
 #ifndef REID_FLAVOR_F16
-            REID_PPS_CASE(EPI_PLAIN16H)
+            case EPI_PLAIN16H: return bm == 224 ? launch_pps_e<EPI_PLAIN16H, 224>(p, s) : launch_pps_e<EPI_PLAIN16H, 256>(p, s);
 #endif
-            REID_PPS_CASE(EPI_RES32)
-            REID_PPS_CASE(EPI_GELU2)
-            REID_PPS_CASE(EPI_GELU2D)
-            REID_PPS_CASE(EPI_MULAUX)
+            case EPI_RES32: return bm == 224 ? launch_pps_e<EPI_RES32, 224>(p, s) : launch_pps_e<EPI_RES32, 256>(p, s);
             default: break;
         }
-#undef REID_PPS_CASE
     }
 #define REID_PP_CASE(E) case E: return bm == 224 ? launch_pp_e<E, 224>(p, s) : launch_pp_e<E, 256>(p, s);
     switch (p.epi) {
@@ -715,7 +663,7 @@ int launch_e(GemmParams& p, hipStream_t s) {
 int launch_main(GemmParams& p, hipStream_t s) {
     p.tiles_m = row_tiles(p, 128, true);
     p.tiles_n = (p.N + 127) / 128;
-    p.epi = reid_knob(KNOB_GEMM_EPI) == 0 ? EPI_GENERIC : pick_epilogue(p, 128);
+    p.epi = pick_epilogue(p, 128);
     switch (p.epi) {
         case EPI_PLAIN16: return launch_e<128, 128, 2, 2, EPI_PLAIN16>(p, s);
 #ifndef REID_FLAVOR_F16
@@ -786,7 +734,6 @@ extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
         REID_CHECK_ARG(a->c_group == 0 && a->r_period == 0, "reid_mer_gemm: row groups do not combine with c_group / r_period");
     }
     GemmParams p;
-    p.stagger = 0;
     p.trace = nullptr;
     p.A = (const bf16_t*)a->A; p.B = (const bf16_t*)a->B; p.A2 = (const bf16_t*)a->A2; p.B2 = (const bf16_t*)a->B2;
     p.bias = a->bias; p.R = a->R; p.aux = (const bf16_t*)a->aux; p.C = a->C; p.C2 = a->C2; p.img_mod = a->img_mod; p.row_scale = a->row_scale;
@@ -807,21 +754,19 @@ extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
     p.r_period = a->r_period; p.mask_r = a->mask_r; p.mask_period = a->mask_period; p.rows_per_img = a->rows_per_img;
     p.c_group = a->c_group; p.c_group_stride = a->c_group_stride; p.c_row_off = a->c_row_off;
     p.alpha = a->alpha == 0.f ? 1.f : a->alpha;
-    p.dbg = 0;
     if (p.c_dtype == REID_F16 && REID_FLAVOR_ID == 1) p.c_dtype = REID_BF16;          // the f16 flavor's own format (saturating there too)
     REID_CHECK_ARG(!(a->C2 && a->c2_dtype == REID_F16 && REID_FLAVOR_ID == 0) && !(a->R && a->r_dtype == REID_F16 && REID_FLAVOR_ID == 0),
                    "reid_mer_gemm: REID_F16 is supported for C only");
     // L2 group height of the tile order: 16 row tiles when the weight panel set is wide and K short (q|k|v, fc1: the whole
     // [N, K] weight no longer fits one XCD's L2 next to 8 activation tiles and was re-streamed per group; r01 sweep 4..64)
-    // r04, 256-row tiles, in-step A/B on one box (tools/exp_r04_ab.sh): 8 for every shape 30.73-30.79 ms per step, 16 for the wide short-K
+    // r04, 256-row tiles, in-step A/B on one box (tools/exp_ab.sh): 8 for every shape 30.73-30.79 ms per step, 16 for the wide short-K
     // shapes (the r01 choice, made with 128-row tiles) 30.87-30.89, 4: 30.72-30.84, 16 everywhere 31.3, 32: 32.2
     p.group_m = 8;
-    if (reid_knob(KNOB_GEMM_GROUPM) > 0) p.group_m = reid_knob(KNOB_GEMM_GROUPM);
     p.perm_b = epilogue_wide16(p) ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
     if (p.c_dtype == REID_F16) {
         // only the plain lean epilogue stores IEEE half in the bf16 flavor (what the residual-branch GEMMs of the vision blocks use)
-        REID_CHECK_ARG(a->N > 96 && a->N % 128 == 0 && reid_knob(KNOB_GEMM_EPI) != 0 && reid_knob(KNOB_GEMM_TILE) <= 0 &&
+        REID_CHECK_ARG(a->N > 96 && a->N % 128 == 0 && reid_knob(KNOB_GEMM_TILE) <= 0 &&
                        pick_epilogue(p, 128) == EPI_PLAIN16H,
                        "reid_mer_gemm: a REID_F16 output needs the plain 16-bit epilogue (N a multiple of 128, no activation / residual / second output / mask / row remap)");
     }
@@ -834,20 +779,12 @@ extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
     //  loads (16 rows x 64 bytes per instruction) cost the vector-memory path more than the LDS round trip saves; stand-alone
     //  the tiled form already streams at 4.9-5.4 TB/s -- the 31 us seen in the train step is interference from the dA/dB
     //  reductions on the side stream, not this kernel.)
-    if (a->N <= 32) {
-        const int sk = reid_knob(KNOB_SKINNY_TILE);
-        if (sk == 1) return launch<256, 32, 4, 1>(p, s);
-        if (sk == 2) return launch<128, 32, 4, 1>(p, s);
-        return a->M >= 65536 ? launch<256, 32, 4, 1>(p, s) : launch<64, 32, 4, 1>(p, s);
-    }
+    if (a->N <= 32) return a->M >= 65536 ? launch<256, 32, 4, 1>(p, s) : launch<64, 32, 4, 1>(p, s);
     if (a->N <= 64) return a->M >= 65536 ? launch<256, 64, 4, 1>(p, s) : launch<64, 64, 4, 1>(p, s);
     if (a->N <= 96) return launch<128, 32, 4, 1>(p, s);
-    // experiment knobs (cached table, common.h; a benchmark A/Bs tiles inside one process through reid_set_knob)
+    // REID_GEMM_TILE (cached knob table, common.h): 3 forces the 128 x 128 tile, 12 / 14 the 256 / 224-row ping-pong tile
     const int tile = reid_knob(KNOB_GEMM_TILE) > 0 ? reid_knob(KNOB_GEMM_TILE) : 0;
-    p.dbg = reid_knob(KNOB_GEMM_DBG) > 0 ? reid_knob(KNOB_GEMM_DBG) : 0;
-    if (tile == 2) return launch<256, 256, 2, 4>(p, s);
     if (tile == 3) return launch_main(p, s);
-    if (tile == 8) return launch<128, 256, 2, 4>(p, s);
     {
         // 256 x 256 ping-pong tile (gemm_core.h mainloop_pp) where it wins (r02, same harness, sum of the seven ViT shapes: 1.74 ms vs
         // 1.89 ms for the 128 x 128 tile, both with the lean epilogues; with the GENERIC epilogue it loses, 2.16 ms): every shape
@@ -865,9 +802,8 @@ extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
         // drains the prefetch at every tile start, and the loop carries ~40 spilled registers across tile boundaries.)
         const bool pp_ok = (p.k2_group_n == 0 || p.k2_group_n % 256 == 0) && p.N % 256 == 0;
         const long tiles256 = (long)row_tiles(p, 256, false) * (p.N / 256);
-        const bool small_too = reid_knob(KNOB_GEMM_PERSIST) < 0 || (reid_knob(KNOB_GEMM_PERSIST) & 8);     // out-projection shapes as well (see launch_pp)
-        const bool pp_shape = (p.K + p.K2 >= 1536 || p.N >= 1536 || small_too) && tiles256 >= reid_num_cus();
-        if (pp_ok && (tile == 12 || tile == 14 || (tile == 0 && pp_shape && reid_knob(KNOB_GEMM_EPI) != 0 && pick_epilogue(p, 256) != EPI_GENERIC)))
+        const bool pp_shape = tiles256 >= reid_num_cus();         // the out-projection shapes as well (persistent, see launch_pp)
+        if (pp_ok && (tile == 12 || tile == 14 || (tile == 0 && pp_shape && pick_epilogue(p, 256) != EPI_GENERIC)))
             return launch_pp(p, s, tile);
     }
     // Default from same-process A/B runs of the seven ViT GEMM variants (tools/bench_gemm_variants.py, r01): 128x128x64
@@ -876,7 +812,7 @@ extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
     // overlap the other's MFMAs (sum over the seven shapes: 1.90 ms vs 2.04-2.17 ms for 256x256 / 128x256 tiles).
     // (k2_group_n is a multiple of 128, so a column tile never straddles two LoRA groups of the fused q|k|v projection.)
     // r02 anatomy of this kernel on the seven ViT shapes (profiles/r02_gemm_variants*.log, sum per layer, 1 MI355X):
-    //   whole kernel 1.93 ms = K loop alone 1.40-1.43 ms (REID_GEMM_DBG=1) + epilogue alone 0.59-0.60 ms (REID_GEMM_DBG=4): they do
+    //   whole kernel 1.93 ms = K loop alone 1.40-1.43 ms + epilogue alone 0.59-0.60 ms (timing modes, at 13e2fd7): they do
     //   NOT overlap although two workgroups share a CU.  K loop with the MFMAs removed (LDS-DMA + fragment reads only): 1.22 ms =
     //   22 GB of L2->LDS operand traffic at 71 GB/s per CU, the per-CU LDS-DMA rate of MI355X_MICROARCH.md ("Indexed rows:
     //   gather into LDS", 66-73 GB/s): the 128x128 K loop is bound by the CU's vector-memory path, not by the matrix pipe

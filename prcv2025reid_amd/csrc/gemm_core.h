@@ -218,13 +218,12 @@ __device__ __forceinline__ void pp_wait_vm4() { asm volatile("s_waitcnt vmcnt(4)
 __device__ __forceinline__ void pp_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ void pp_wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// ABL (timing experiments only, results are wrong): bit 0 = no LDS-DMA in the loop, 1 = no fragment reads, 2 = no MFMAs, 3 = no barriers
 // AUXPRE (256-row tile, aux != null): the epilogue's [256 rows x 512 B] tile of a second operand (the saved GELU derivative of the
 // multiply-by-derivative epilogue) rides in on the LAST TWO K-tiles' staging slots -- where K-tiles nk and nk + 1 would be staged -- so it
 // lands under the last MFMAs instead of after the loop: rows 128 b + .. of the tile go to buffer b as the image the epilogue reads
 // (row r at r * 512, chunk c at position c ^ (r & 15)), the weight halves' slots taking rows 64..127 and each wave row's own activation
 // slot rows 32 wm .. + 31, with the instruction counts of the steady state (the counted waits stay as they are).  Needs nk >= 2.
-template <int BM, int BN, int ABL = 0, bool AUXPRE = false>
+template <int BM, int BN, bool AUXPRE = false>
 __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int lda, const bf16_t* __restrict__ B, int ldb,
                                             const bf16_t* __restrict__ A2, int lda2, const bf16_t* __restrict__ B2, int ldb2,
                                             int M, int N, int K, int K2, int m0, int n0, char* smem, f32x4 (&acc)[4][PPCfg<BM, BN>::TM], bool perm_b,
@@ -264,7 +263,6 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
         }
     // steady state (a full 64-wide K-tile): no conditions, the K offset is the only run-time term
     auto stage_a = [&](int t, int buf) {
-        if constexpr (ABL & 1) return;
         char* dst = smem + buf * C::BUF_BYTES + wm * C::HALF_BYTES;
         const char* src = (const char*)A + (size_t)t * 128;
 #pragma unroll
@@ -274,7 +272,6 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
             __builtin_amdgcn_global_load_lds((gptr_t)(src + offA[3]), (lptr_t)(dst + (12 + wn) * 8 * 128), 16, 0, 0);
     };
     auto stage_b = [&](int t, int buf) {
-        if constexpr (ABL & 1) return;
         const char* src = (const char*)B + (size_t)t * 128;
 #pragma unroll
         for (int h = 0; h < 2; ++h)
@@ -343,16 +340,9 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
     const int a_base = wm * C::HALF_BYTES;                                   // SA[wm]
     const int b_base = (2 + (wn >> 1)) * C::HALF_BYTES + (wn & 1) * 64 * 128; // SB[wn >> 1], this wave's 64 weight rows
     bf16x8 af[4][2], bfr[2][2][2];
-    if constexpr (ABL & 2) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) { af[i][ks] = bf16x8{1, 2, 3, 4, 5, 6, 7, (short)lane}; bfr[i >> 1][i & 1][ks] = af[i][ks]; }
-    }
     // (NKS is a compile-time constant: with a run-time k-half count hipcc turns the fragment arrays into scratch memory)
     auto read_a = [&](int buf, int a, auto nks_c) {
         constexpr int NKS = decltype(nks_c)::value;
-        if constexpr (ABL & 2) return;
         const char* base = smem + buf * C::BUF_BYTES + a_base + a * 64 * 128;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -363,7 +353,6 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
     };
     auto read_b = [&](int buf, auto nks_c) {
         constexpr int NKS = decltype(nks_c)::value;
-        if constexpr (ABL & 2) return;
         const char* base = smem + buf * C::BUF_BYTES + b_base;
 #pragma unroll
         for (int b = 0; b < 2; ++b)
@@ -374,7 +363,6 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
     };
     auto half = [&](auto a_c, auto nks_c) {                                   // 32 MFMAs: output rows a*64 .. a*64+63 of the wave
         constexpr int NKS = decltype(nks_c)::value, a = decltype(a_c)::value;
-        if constexpr (ABL & 4) return;
         __builtin_amdgcn_s_setprio(1);
 #pragma unroll
         for (int ks = 0; ks < NKS; ++ks)
@@ -389,7 +377,7 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
     };
     auto bar = [&]() {
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(ABL & 8)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
     };
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;

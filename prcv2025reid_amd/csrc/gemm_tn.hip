@@ -159,9 +159,7 @@ int launch_tn(TnParams& p, hipStream_t s) {
     const int tiles = p.tiles_p * p.tiles_q;
     // workgroups per launch: few, long-lived slabs (each pays its load latency once) -- 384 instead of 1536 took the small
     // products from 30 to 22 us stand-alone and 0.6 ms off the train step (less interference with the dX GEMMs; r01 sweep 128..6144)
-    int target = 384;
-    if (reid_knob(KNOB_TN_BLOCKS) > 0) target = reid_knob(KNOB_TN_BLOCKS);
-    int slabs = target / tiles;
+    int slabs = 384 / tiles;
     if (slabs < 1) slabs = 1;
     const int max_slabs = (p.M + 255) / 256;
     if (slabs > max_slabs) slabs = max_slabs;

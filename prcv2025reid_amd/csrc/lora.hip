@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void merge_lora_kernel(const int64_t* __restri
 
 // ---------------------------------------------------------------- adapter gradients of one linear: U = dY.B and dB = dY^T.T in ONE pass over dY
 // r03's side stream read every dY twice: the skinny GEMM U = mask(dY . B) * (alpha/r) (the rank-r cotangent dA = U^T x needs) and the
-// row-reduction dB += dY^T . T.  Leaving the first out takes 1.1 ms off the 32.9 ms step (tools/exp_skip_u.sh: an upper bound), so
+// row-reduction dB += dY^T . T.  Leaving the first out takes 1.1 ms off the 32.9 ms step (tools/exp_skip_u.sh at 13e2fd7: an upper bound), so
 // both products are formed from one staged tile here.  Splitting dY by COLUMN panels (as gemm_tn does) would leave U as N/128 partial
 // sums per row (fp32 atomics: more bytes than the re-read saves); so a workgroup owns a ROW slab and all N = 768 columns: its eight
 // waves own 96 columns each, keep their [96, 32] slice of dB in registers for the whole slab (48 VGPRs) and flush it once, and the
@@ -186,41 +186,34 @@ __global__ __launch_bounds__(NW * 64, 2) void lora_bwd_fused_kernel(const Params
     f32x4 acc[MT][2];
 #pragma unroll
     for (int i = 0; i < MT; ++i) { acc[i][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[i][1] = acc[i][0]; }
-#ifndef REID_FUSED_DEPTH
-#define REID_FUSED_DEPTH 1
-#endif
-    // DEPTH steps of operands in flight in registers (1 or 2).  The slot of a step is a compile-time constant (the loop is unrolled by
-    // DEPTH): indexing the register arrays with (t & 1) put them into scratch memory (80 bytes per lane: 35.0 ms per step).  Two steps
-    // in flight (226 VGPRs) change nothing: 32.61 / 32.73 against 32.88 / 32.71 ms per step on one box (profiles/r03_lora_fused_depth.log)
-    // -- the step is not what waits for HBM; one step in flight (194 VGPRs) stays.
-    constexpr int DEPTH = REID_FUSED_DEPTH;
-    uint4 xr[DEPTH][XL], tr[DEPTH][2];
-    auto gload = [&](int t, auto slot_c) {
-        constexpr int slot = decltype(slot_c)::value;
+    // One step of operands in flight in registers (194 VGPRs).  Two steps in flight (226 VGPRs, the loop unrolled by two so that a step's
+    // register slot is a compile-time constant; at 13e2fd7) change nothing: 32.61 / 32.73 against 32.88 / 32.71 ms per step on one box
+    // (profiles/r03_lora_fused_depth.log) -- the step is not what waits for HBM.
+    uint4 xr[XL], tr[2];
+    auto gload = [&](int t) {
         const int mb = mbeg + t * R;
 #pragma unroll
         for (int i = 0; i < XL; ++i) {                    // 32 rows x CH chunks of 16 bytes
             const int c = lane + 64 * i, row = c / CH, ch = c % CH;
             const int m = mb + row;
-            xr[slot][i] = m < mend ? *(const uint4*)(p.dY + (size_t)m * p.lddy + col0 + ch * 8) : uint4{0u, 0u, 0u, 0u};
+            xr[i] = m < mend ? *(const uint4*)(p.dY + (size_t)m * p.lddy + col0 + ch * 8) : uint4{0u, 0u, 0u, 0u};
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i) {                     // 32 rows x 4 chunks
             const int c = lane + 64 * i, row = c >> 2, ch = c & 3;
             const int m = mb + row;
-            tr[slot][i] = m < mend ? *(const uint4*)(p.T + (size_t)m * p.ldt + ch * 8) : uint4{0u, 0u, 0u, 0u};
+            tr[i] = m < mend ? *(const uint4*)(p.T + (size_t)m * p.ldt + ch * 8) : uint4{0u, 0u, 0u, 0u};
         }
     };
-    auto step = [&](int t, auto slot_c) {
-        constexpr int slot = decltype(slot_c)::value;
+    auto step = [&](int t) {
 #pragma unroll
-        for (int i = 0; i < XL; ++i) { const int c = lane + 64 * i; *(uint4*)(xs + (c / CH) * XP + (c % CH) * 16) = xr[slot][i]; }
+        for (int i = 0; i < XL; ++i) { const int c = lane + 64 * i; *(uint4*)(xs + (c / CH) * XP + (c % CH) * 16) = xr[i]; }
 #pragma unroll
-        for (int i = 0; i < 2; ++i) { const int c = lane + 64 * i; *(uint4*)(ts + (c >> 2) * TP + (c & 3) * 16) = tr[slot][i]; }
+        for (int i = 0; i < 2; ++i) { const int c = lane + 64 * i; *(uint4*)(ts + (c >> 2) * TP + (c & 3) * 16) = tr[i]; }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (t + DEPTH < steps) gload(t + DEPTH, slot_c);
+        if (t + 1 < steps) gload(t + 1);
         // dB[CPW columns of dY, 32] += dY^T . T over the 32 rows of this step
         const bf16x8 tf0 = tr_frag(ts, TP, 0, 0, lane), tf1 = tr_frag(ts, TP, 0, 16, lane);
 #pragma unroll
@@ -271,13 +264,8 @@ __global__ __launch_bounds__(NW * 64, 2) void lora_bwd_fused_kernel(const Params
         }
         __syncthreads();
     };
-    using S0 = std::integral_constant<int, 0>; using S1 = std::integral_constant<int, DEPTH - 1>;
-    gload(0, S0{});
-    if (DEPTH == 2 && steps > 1) gload(1, S1{});
-    for (int t = 0; t < steps; t += DEPTH) {
-        step(t, S0{});
-        if (DEPTH == 2 && t + 1 < steps) step(t + 1, S1{});
-    }
+    gload(0);
+    for (int t = 0; t < steps; ++t) step(t);
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -351,11 +339,6 @@ __global__ __launch_bounds__(256) void u_finish_kernel(const float* __restrict__
     *(uint32_t*)(U + (size_t)m * ldu + c) = pack_bf16x2(c / mask_r == mu ? a * scale : 0.f, (c + 1) / mask_r == mu ? b * scale : 0.f);
 }
 
-#ifdef REID_EXPERIMENTS
-#define LORA_ABL(bit) ((p.slab_rows >> (bit)) & 1)            // timing experiments (wrong results): REID_LORA_IMPL = 16 + bits, tools/exp_lora_ablate.py
-#else
-#define LORA_ABL(bit) 0
-#endif
 __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) {
     REID_T16_ENTER();
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -384,7 +367,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
             dma16(p.dY + (size_t)gr * p.lddy + ((c ^ (row & 15)) << 3), base + qd * 1024);
         }
-        if (w < 2 && !LORA_ABL(4)) {
+        if (w < 2) {
             const int g = w * 64 + lane;                      // T tile: 32 rows x 4 chunks, lane-linear
             const int row = g >> 2, c = g & 3;
             int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
@@ -395,7 +378,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
     if (steps > 1) issue(1, 1);
     // B^T fragments of the window (waves 0, 1: B operand of U = dY . B: n = adapter column w0 + l16, k = dY column)
     bf16x8 bfr[24];
-    if (w < 2 && !LORA_ABL(5)) {
+    if (w < 2) {
 #pragma unroll
         for (int ks = 0; ks < 24; ++ks) bfr[ks] = *(const bf16x8*)(p.BT + (size_t)(w0 + l16) * p.ldbt + ks * 32 + 8 * fq);
         // a use of every fragment HERE: the compiler tracks these loads and would otherwise wait for them with `vmcnt(0)` at their first use
@@ -412,7 +395,6 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
     void* pend_ptr = nullptr;
     int pend_n = 0;                                            // rows (u_mode != 0) / "this lane has a row" (u_mode == 0) still to go out
     auto flush_pending = [&]() {
-        if (LORA_ABL(1)) { pend_n = 0; return; }
         if (p.u_mode == 0) {
             if (pend_n) asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(pend_ptr), "v"(pend_val) : "memory");
         } else {
@@ -456,7 +438,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             const char* xrow = xs + row * ROW_BYTES;
             const int rsw = row & 15;
 #pragma unroll
-            for (int k0 = 0; k0 < (LORA_ABL(0) ? 0 : 24); k0 += 4) {
+            for (int k0 = 0; k0 < 24; k0 += 4) {
                 bf16x8 af[4];
 #pragma unroll
                 for (int a = 0; a < 4; ++a) af[a] = *(const bf16x8*)(xrow + (((4 * (k0 + a) + fq) ^ rsw) << 4));
@@ -505,7 +487,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             }
             const int cbase = (w - 2) * 128;
 #pragma unroll
-            for (int i = 0; i < (LORA_ABL(2) ? 0 : 8); ++i) acc[i] = mfma16(tr_frag_swz(xs, cbase + i * 16, lane), tf, acc[i]);
+            for (int i = 0; i < 8; ++i) acc[i] = mfma16(tr_frag_swz(xs, cbase + i * 16, lane), tf, acc[i]);
         }
         // step t + 2 into the buffer step t - 1 was read from (every wave is past this step's barrier, hence done with it); issued AFTER
         // this step's U stores so that the counted wait above has exactly one step's DMA instructions behind everything it waits for
@@ -528,7 +510,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
     __syncthreads();
     {
         const int rr = p.mask_r, total = N * rr;
-        for (int idx = tid; idx < (LORA_ABL(3) ? 0 : total); idx += 512) {
+        for (int idx = tid; idx < total; idx += 512) {
             const int col = idx / rr, j = idx - col * rr;
             atomicAdd(p.dB + (size_t)col * p.lddb + mu * rr + j, fl[col * 16 + c_lo + j]);
         }
@@ -657,9 +639,6 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
     if (reid_knob(KNOB_LORA_IMPL) != 1 && rows_per_img >= image::R && mask_r <= 16 && 16 % mask_r == 0) {
         REID_MAX_LDS((image::lora_bwd_image_kernel), image::LDS_BYTES);
         const int n_img = (M + rows_per_img - 1) / rows_per_img;
-#ifdef REID_EXPERIMENTS
-        p.slab_rows = reid_knob(KNOB_LORA_IMPL) >= 16 ? reid_knob(KNOB_LORA_IMPL) - 16 : 0;
-#endif
         hipLaunchKernelGGL(image::lora_bwd_image_kernel, dim3(n_img), dim3(512), image::LDS_BYTES, (hipStream_t)stream, p);
         REID_CHECK_LAUNCH("reid_lora_bwd_fused(image)");
         if (u_mode == 1) {                                    // last column block of a wide cotangent: every partial sum is in Up now
@@ -670,8 +649,7 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
         return REID_OK;
     }
     // few, long slabs: each workgroup flushes its [768, 32] slice of dB with atomics once (64 slabs = the flush traffic of gemm_tn's grid)
-    int slabs = reid_knob(KNOB_TN_BLOCKS) > 0 ? reid_knob(KNOB_TN_BLOCKS) / 6 : 64;
-    if (slabs < 1) slabs = 1;
+    int slabs = 64;
     p.slab_rows = ((M + slabs - 1) / slabs + fused::R - 1) / fused::R * fused::R;
     slabs = (M + p.slab_rows - 1) / p.slab_rows;
     REID_MAX_LDS((fused::lora_bwd_fused_kernel<8>), fused::Geo<8>::LDS_BYTES);

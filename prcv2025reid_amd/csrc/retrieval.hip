@@ -31,7 +31,6 @@ struct TopkParams {
     float* dense; int ld_dense;    // phase A: dense scores [Nq, g_end-g_begin]
     int32_t* cand_idx; float* cand_score; int32_t* cand_cnt; int cap;   // phase B
     int tiles_m, tiles_n;
-    int dbg;                       // timing experiments (REID_TOPK_DBG): 1 = skip the compare epilogue
 };
 
 // Compare epilogue shared by the filter kernels.  A lane owns, per 16-row group i, ONE query row and 16 of its scores
@@ -126,12 +125,11 @@ __global__ __launch_bounds__(WM* WN * 64) void score_kernel(const TopkParams p) 
 #pragma unroll
         for (int i = 0; i < C::TM; ++i) {
             const int m = m0 + wm * (BM / WM) + i * 16 + mrow;
-            th[i] = REID_DBG(p) == 2 ? INFINITY : p.thr[m < p.Nq ? m : 0];
+            th[i] = p.thr[m < p.Nq ? m : 0];
         }
     }
     // no low-rank pair: K2 = 0 (non-null dummies keep the staging code free of constant-null pointers)
     mainloop<BM, BN, WM, WN>(p.Q, p.D, p.G, p.D, p.Q, p.D, p.G, p.D, p.Nq, p.g_end, p.D, 0, m0, n0, smem, acc);
-    if (REID_DBG(p) == 1 && acc[0][0][0] != 12345.678f) return;
     if (!DENSE) {
         __syncthreads();                                    // every wave is done reading the operand buffers: reuse them
         filter_epilogue<C::TM, C::TN>(p, acc, th, m0 + wm * (BM / WM), n0 + wn * (BN / WN), lane, (int*)(smem + wave * 1024));
@@ -471,7 +469,6 @@ struct ScanParams {
     uint32_t* gmax;               // [4 query groups][KG][32] keys of the group maxima; zero (= nothing yet) when the kernel starts
     int32_t* cand_idx; float* cand_score; int32_t* cand_cnt;
     unsigned long long* trace;    // -DREID_SCAN_TRACE builds: 8 stamps per workgroup (tools/exp_scan_trace.py)
-    int dbg;                      // -DREID_SCAN_TRACE builds: ablations (wrong results): 1 = no scoring, 2 = no publish / bar requests, 4 = no enqueue
 };
 #ifdef REID_SCAN_TRACE
 #define SCAN_TRACE(slot, v) do { if (p.trace && threadIdx.x == 0) p.trace[(size_t)blockIdx.x * 8 + (slot)] = (v); } while (0)
@@ -479,11 +476,6 @@ struct ScanParams {
 #define SCAN_TRACE(slot, v) do { } while (0)
 #endif
 #define SCAN_STAMP(slot) SCAN_TRACE(slot, __builtin_amdgcn_s_memrealtime())
-#ifdef REID_SCAN_TRACE
-#define SCAN_DBG(bit) ((p.dbg & (bit)) != 0)
-#else
-#define SCAN_DBG(bit) false
-#endif
 
 // order-preserving unsigned key of a float; 0 is below every float
 __device__ __forceinline__ uint32_t key_of(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
@@ -760,11 +752,9 @@ __global__ __launch_bounds__(512) void scan_filter_kernel(const ScanParams p) {
                 read_bars();
                 if (valid && first_valid == NO_BAR) first_valid = i;
             }
-            if (!SCAN_DBG(1)) {
-                score_tile(t, true, valid && !SCAN_DBG(4));
-                fold_local();
-            }
-            if ((t & 1) == 1 && rh == 0 && !SCAN_DBG(2)) {       // end of step i
+            score_tile(t, true, valid);
+            fold_local();
+            if ((t & 1) == 1 && rh == 0) {                       // end of step i
                 if (first_valid == NO_BAR || refresh_after(i)) { request_bars(); r0 = BAR_INSTR; }
                 if (first_valid == NO_BAR || publish_after(i)) p0 = publish();
             }
@@ -910,7 +900,6 @@ extern "C" int reid_cosine_topk(const void* Q_bf16, const void* G_bf16, const fl
             sp.k = k; sp.cap = cap; sp.gmax = gmax; sp.cand_idx = cidx; sp.cand_score = cscore; sp.cand_cnt = cnt2;
 #ifdef REID_SCAN_TRACE
             sp.trace = scan::g_scan_trace;
-            sp.dbg = getenv("REID_SCAN_DBG") ? atoi(getenv("REID_SCAN_DBG")) : 0;
 #endif
 #define REID_SCAN_LAUNCH(KS, EX) do {                                                                                           \
             constexpr size_t lds = 4 * 32 * (KS * 64) + 512 * scan::QCAP * 8 + 4 * scan::KG * 32 * 4 + 1024 + 64 + 1024;                \
@@ -926,7 +915,6 @@ extern "C" int reid_cosine_topk(const void* Q_bf16, const void* G_bf16, const fl
     TopkParams p{};
     p.Q = (const bf16_t*)Q_bf16; p.G = (const bf16_t*)G_bf16; p.Nq = Nq; p.Ng = Ng; p.D = D;
     p.exq = exclude_q; p.exg = exclude_g; p.cap = cap;
-    p.dbg = reid_knob(KNOB_TOPK_DBG) > 0 ? reid_knob(KNOB_TOPK_DBG) : 0;
     p.tiles_m = (Nq + BM - 1) / BM;
     // phase A: sample = first ns gallery rows, dense scores, k-th best -> thr
     p.g_begin = 0; p.g_end = ns; p.thr = nullptr; p.dense = dense; p.ld_dense = ns;
@@ -943,26 +931,20 @@ extern "C" int reid_cosine_topk(const void* Q_bf16, const void* G_bf16, const fl
     p.g_begin = 0; p.g_end = Ng; p.thr = thr; p.dense = nullptr;
     p.cand_idx = cidx; p.cand_score = cscore; p.cand_cnt = cnt;
     {
-        // Filter-pass anatomy at 10k x 200k x 512 (REID_TOPK_DBG=1/2, r01): K loops 1.1-1.7 ms depending on the tile, compare of
+        // Filter-pass anatomy at 10k x 200k x 512 (r01, timing modes at 13e2fd7): K loops 1.1-1.7 ms depending on the tile, compare of
         // every score against its row threshold 0.7 ms, candidate appends 0.6 ms; 128x128 / 128x256 / 256x128 tiles all end
         // at 4.0-4.1 ms per top-10 call.  Tried and dropped: a persistent variant with a 3-stage ring across tiles (4.02 ms: the
         // per-tile latency it removes is not the bottleneck), the 256x256 tile (fastest K loop, but its epilogue spills).
         // r02: the MER GEMM's wave-row ping-pong K loop (gemm_core.h mainloop_pp) under this epilogue, 256x256: 4.68 ms against 4.10 ms
         // for the default on the same box (profiles/r02_retrieval_tiles_pingpong.log, patch next to it): the loop leaves the compare
         // epilogue no registers (176-228 B/lane of scratch in it), and the epilogue, not the K loop, is what this pass waits on.
-        const int tile = reid_knob(KNOB_TOPK_TILE) >= 0 ? reid_knob(KNOB_TOPK_TILE) : 2;
         int rc;
-        if (tile == 1) rc = launch_filter<256, 128, 4, 2>(p, s);
-        else if (tile == 3) rc = launch_filter<256, 256, 2, 4>(p, s);
-        else if (tile == 4) rc = launch_filter<128, 256, 2, 4>(p, s);
-        else if (tile == 5) rc = launch_filter<64, 256, 1, 4>(p, s);
-        else if (tile == 6) rc = launch_filter<64, 128, 1, 4>(p, s);
-        else if (tile == 2 && Nq <= 64 && Ng >= 1024) rc = launch_filter<64, 256, 1, 4>(p, s);   // few queries: half the query panel staged per gallery row (r03: 123 -> 105 us at 5-32 queries x 200k)
-        else if (tile == 0 || Nq < 256 || Ng < 1024) rc = launch_filter<128, 128, 2, 2>(p, s);
+        if (Nq <= 64 && Ng >= 1024) rc = launch_filter<64, 256, 1, 4>(p, s);   // few queries: half the query panel staged per gallery row (r03: 123 -> 105 us at 5-32 queries x 200k)
+        else if (Nq < 256 || Ng < 1024) rc = launch_filter<128, 128, 2, 2>(p, s);
         else rc = launch_filter<128, 256, 2, 4>(p, s);
         if (rc) return rc;
     }
-    // phase C
+    // phase C (REID_TOPK_TILE=9, the knob's only value, forces select_kernel: the reference form of the retrieval test)
     if (k <= SELECT_FAST_K_MAX && reid_knob(KNOB_TOPK_TILE) != 9)
         return launch_select_fast(Qf, Gf, D, exclude_q, exclude_g, cidx, cscore, cnt, cap, k, out_idx, out_score, Nq, s);
     const size_t lds = (size_t)cap * 8 + (size_t)D * 4;
@@ -1035,20 +1017,11 @@ __device__ __forceinline__ int wave_select_lds(const float* sc, const int32_t* i
 }
 
 __host__ __device__ inline int merge_survivor_cap(int n, int k) { const int c = 16 * k * k + 64; return c < n ? c : n; }
-__device__ __forceinline__ void merge_lists_in_lds(const float* sc, const int32_t* ix, float* ssc, int32_t* six, int* lcnt, int groups, int k,
-                                                   int32_t* __restrict__ out_idx, float* __restrict__ out_score, int tid, int lane);
 
-// FUSE (one query per pass): the workgroup whose lists arrive LAST merges them and writes the final top-k -- no second launch (r03: the
-// merge kernel was 10.8 us of a 77 us call).  Hand-off per MI355X_MICROARCH "Valid forms", first row of the sc1 table: every list entry is
-// stored and loaded with agent-scope relaxed atomics (global_store / global_load ... sc1: write-through, L1-bypassing), every storing wave
-// drains its stores (vmcnt(0)) before the workgroup barrier, ONE lane then adds to the arrival counter, and the workgroup that sees the
-// last ticket loads the lists behind a barrier that follows the returned add.  The counter is left at zero for the next call.
-template <int DJ, int STREAM_ROWS, int NQP, bool FUSE = false>      // D = 256 * DJ; NQP = queries of the pass rounded up to 1, 2 or 4
+template <int DJ, int STREAM_ROWS, int NQP>      // D = 256 * DJ; NQP = queries of the pass rounded up to 1, 2 or 4
 __global__ __launch_bounds__(256) void stream_topk_kernel(const float* __restrict__ Qf, const float* __restrict__ Gf, int Ng,
                                                           const int32_t* __restrict__ exq, const int32_t* __restrict__ exg, int nq,
-                                                          int k, float* __restrict__ part_score, int32_t* __restrict__ part_idx,
-                                                          int32_t* __restrict__ counter = nullptr, int32_t* __restrict__ out_idx = nullptr,
-                                                          float* __restrict__ out_score = nullptr) {
+                                                          int k, float* __restrict__ part_score, int32_t* __restrict__ part_idx) {
     constexpr int D = 256 * DJ;
     __shared__ float lsc[SQ][4][STREAM_K_MAX];
     __shared__ int32_t lix[SQ][4][STREAM_K_MAX];
@@ -1152,48 +1125,9 @@ __global__ __launch_bounds__(256) void stream_topk_kernel(const float* __restric
         const int real = wave_select_lds(&lsc[w][0][0], &lix[w][0][0], 4 * STREAM_K_MAX, k, lane, e);
         if (lane < k) {
             const size_t o = ((size_t)w * gridDim.x + blockIdx.x) * k + lane;
-            if constexpr (FUSE) {
-                __hip_atomic_store(part_score + o, lane < real ? e.s : -INFINITY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(part_idx + o, lane < real ? e.i : -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-                part_score[o] = lane < real ? e.s : -INFINITY;
-                part_idx[o] = lane < real ? e.i : -1;
-            }
+            part_score[o] = lane < real ? e.s : -INFINITY;
+            part_idx[o] = lane < real ? e.i : -1;
         }
-    }
-    if constexpr (FUSE) {
-        extern __shared__ __attribute__((aligned(16))) char smm[];
-        __shared__ int last_flag, lcnt;
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // this wave's list entries have left for memory
-        __syncthreads();
-        if (tid == 0) {
-            const int ticket = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            last_flag = ticket == (int)gridDim.x - 1;
-            lcnt = 0;
-        }
-        __syncthreads();                                              // (every wave loads behind the barrier that follows the returned add)
-        if (!last_flag) return;
-        const int groups = gridDim.x, n = groups * k, n4 = (n + 3) & ~3;
-        float* sc = (float*)smm;
-        int32_t* ix = (int32_t*)(sc + n4);
-        float* ssc = (float*)(ix + n4);
-        int32_t* six = (int32_t*)(ssc + merge_survivor_cap(n, k));
-        // all lists -> LDS by LDS-DMA with the sc1 policy (16 bytes per lane, L1 bypassed: the table row's `buffer_load_dwordx4` form); every
-        // load is in flight before the one wait (a loop of 4-byte atomic loads was issued one round trip at a time: 86 vs 77 us per call)
-        {
-            const int nchunks = n4 >> 2;                              // 16-byte chunks per array (the workspace extends beyond both arrays)
-            const int w4 = tid >> 6;
-            for (int c0 = w4 * 64; c0 < nchunks; c0 += 256) {
-                if (c0 + lane < nchunks) {
-                    __builtin_amdgcn_global_load_lds((gptr_t)(part_score + 4 * (size_t)(c0 + lane)), (lptr_t)((char*)sc + (size_t)c0 * 16), 16, 0, 16);
-                    __builtin_amdgcn_global_load_lds((gptr_t)(part_idx + 4 * (size_t)(c0 + lane)), (lptr_t)((char*)ix + (size_t)c0 * 16), 16, 0, 16);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        if (tid == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // ready for the next call (stream-ordered)
-        __syncthreads();
-        merge_lists_in_lds(sc, ix, ssc, six, &lcnt, groups, k, out_idx, out_score, tid, lane);
     }
 }
 
@@ -1435,7 +1369,7 @@ int launch_select_fast(const float* Qf, const float* Gf, int D, const int32_t* e
 extern "C" int32_t reid_topk_stream_ok(int32_t Nq, int32_t Ng, int32_t D, int32_t k) {
     return Nq >= 1 && Nq <= SQ && k >= 1 && k <= STREAM_K_MAX && k <= Ng && D % 256 == 0 && D >= 256 && D <= 1024 && Ng >= 1;
 }
-// lists of SQ queries + 256 bytes for the arrival counter of the one-query form (zero before the first call; every call leaves it zero)
+// lists of SQ queries + 256 bytes that no kernel uses (they held the arrival counter of a fused-merge form, at 13e2fd7; the size is ABI)
 extern "C" int64_t reid_topk_stream_ws_bytes(int32_t k) { return (int64_t)SQ * stream_groups(k) * k * 8 + 256; }
 
 /* Top-k of a few queries in ONE pass over the fp32 gallery (the reference's one-query-at-a-time form).  Same results as
@@ -1450,9 +1384,8 @@ extern "C" int reid_cosine_topk_stream(const float* Qf, const float* Gf, int32_t
     hipStream_t s = (hipStream_t)stream;
     int groups = stream_groups(k);
     // one query: 512 workgroups scan as fast as 1024 and leave the merge half as many lists (77.6 vs 81.8 us per call); with 2-4 queries
-    // per pass the larger grid wins (91.9 vs 102.6 us, 111 vs 135 us).  REID_STREAM_GROUPS overrides.
+    // per pass the larger grid wins (91.9 vs 102.6 us, 111 vs 135 us)
     if (Nq == 1 && groups > 512) groups = 512;
-    if (reid_knob(KNOB_STREAM_GROUPS) > 0 && reid_knob(KNOB_STREAM_GROUPS) < stream_groups(k)) groups = reid_knob(KNOB_STREAM_GROUPS);
     const int need = (Ng + 15) / 16;        // no more workgroups than there is work
     if (groups > need) groups = need;
     float* ps = (float*)ws;
@@ -1464,31 +1397,23 @@ extern "C" int reid_cosine_topk_stream(const float* Qf, const float* Gf, int32_t
         const float* Q = Qf + (size_t)q0 * D;
         const int32_t* eq = exclude_q ? exclude_q + q0 : nullptr;
         // gallery rows per wave and iteration (the loads of all rows are issued before the first dot): 4 rows = 8 KiB in flight per wave at D = 512
-        const int rows_env = reid_knob(KNOB_STREAM_ROWS);
         const int n_ent = groups * k;
         const size_t lds_fast = (size_t)((n_ent + 3) & ~3) * 8 + (size_t)merge_survivor_cap(n_ent, k) * 8;
-        // REID_STREAM_FUSE=1 (one query, lists that fit the LDS next to a second resident workgroup): the last-arriving workgroup merges inside
-        // the scan launch.  Built for the r03 verdict's ">= 70 % of HBM end to end"; measured (r04, profiles/r04_stream_fused_merge.log):
-        // 78.1-78.5 us per call against 77.0-78 us with the separate merge launch -- the launch boundary it removes (~1.5 us) is what the
-        // hand-off costs (drain + barrier + ticket + 40 KiB of sc1 loads behind the slowest scan workgroup), so it is OFF by default.
-        const bool fuse = nq == 1 && lds_fast <= 72 * 1024 && reid_knob(KNOB_STREAM_FUSE) == 1;
-        int32_t* counter = (int32_t*)((char*)ws + (size_t)SQ * stream_groups(k) * k * 8);
+        // A fused form in which the last-arriving workgroup merged the lists inside the scan launch (one query; at 13e2fd7) was built for the
+        // r03 verdict's ">= 70 % of HBM end to end"; measured (r04, profiles/r04_stream_fused_merge.log): 78.1-78.5 us per call against
+        // 77.0-78 us with the separate merge launch -- the launch boundary it removes (~1.5 us) is what the hand-off costs (drain + barrier +
+        // ticket + 40 KiB of sc1 loads behind the slowest scan workgroup).
 #define REID_STREAM_LAUNCH1(DJ, R, P) hipLaunchKernelGGL((stream_topk_kernel<DJ, R, P>), dim3(groups), dim3(256), 0, s, Q, Gf, Ng, eq, exclude_g, nq, k, ps, pi)
-#define REID_STREAM_LAUNCHF(DJ, R) do { REID_MAX_LDS((stream_topk_kernel<DJ, R, 1, true>), 72 * 1024); \
-        hipLaunchKernelGGL((stream_topk_kernel<DJ, R, 1, true>), dim3(groups), dim3(256), lds_fast, s, Q, Gf, Ng, eq, exclude_g, nq, k, ps, pi, counter, \
-                           out_idx + (size_t)q0 * k, out_score + (size_t)q0 * k); } while (0)
-#define REID_STREAM_LAUNCH(DJ, R) do { if (fuse) REID_STREAM_LAUNCHF(DJ, R); else if (nq == 1) REID_STREAM_LAUNCH1(DJ, R, 1); else if (nq == 2) REID_STREAM_LAUNCH1(DJ, R, 2); else REID_STREAM_LAUNCH1(DJ, R, 4); } while (0)
+#define REID_STREAM_LAUNCH(DJ, R) do { if (nq == 1) REID_STREAM_LAUNCH1(DJ, R, 1); else if (nq == 2) REID_STREAM_LAUNCH1(DJ, R, 2); else REID_STREAM_LAUNCH1(DJ, R, 4); } while (0)
         switch (D / 256) {
             case 1: REID_STREAM_LAUNCH(1, 4); break;
-            case 2: if (rows_env == 2) REID_STREAM_LAUNCH(2, 2); else if (rows_env == 8) REID_STREAM_LAUNCH(2, 8); else REID_STREAM_LAUNCH(2, 4); break;
+            case 2: REID_STREAM_LAUNCH(2, 4); break;
             case 3: REID_STREAM_LAUNCH(3, 2); break;
             default: REID_STREAM_LAUNCH(4, 2); break;
         }
 #undef REID_STREAM_LAUNCH
-#undef REID_STREAM_LAUNCHF
 #undef REID_STREAM_LAUNCH1
         REID_CHECK_LAUNCH("reid_cosine_topk_stream(scan)");
-        if (fuse) continue;
         if (lds_fast <= 160 * 1024 - 64)
             hipLaunchKernelGGL(stream_merge_lds_kernel, dim3(nq), dim3(256), lds_fast, s, ps, pi, groups, k, out_idx + (size_t)q0 * k,
                                out_score + (size_t)q0 * k);

@@ -17,14 +17,10 @@ void reid_set_error(const char* fmt, ...) {
 extern "C" const char* reid_last_error(void) { return g_err; }
 extern "C" int reid_version(void) { return REID_ABI_VERSION; }
 
-// ---------------------------------------------------------------- experiment knobs (common.h)
-static const char* const g_knob_names[] = {
-    "GEMM_TILE", "GEMM_DBG", "GEMM_GROUPM", "GEMM_EPI", "GEMM_STAGGER",
-    "ATTN_DBG", "TN_BLOCKS", "TOPK_DBG", "TOPK_TILE", "STREAM_ROWS", "STREAM_GROUPS", "SDM_IMPL", "SKINNY_TILE", "GEMM_PERSIST",
-    "ATTN_BWD", "LORA_IMPL", "GELU_IMPL", "HEAD_IMPL", "STREAM_FUSE", "TOPK_SCAN", "LN_IMPL"};
+// ---------------------------------------------------------------- knobs (common.h)
+static const char* const g_knob_names[] = {"GEMM_TILE", "ATTN_BWD", "LORA_IMPL", "LN_IMPL", "TOPK_TILE", "TOPK_SCAN"};
 static_assert(sizeof(g_knob_names) / sizeof(g_knob_names[0]) == KNOB_COUNT, "one name per reid_knob_id");
 static int g_knobs[KNOB_COUNT];
-static bool knob_is_debug(int i) { return i == KNOB_GEMM_DBG || i == KNOB_ATTN_DBG || i == KNOB_TOPK_DBG; }
 static int* knob_table() {
     static const bool init = [] {
         for (int i = 0; i < KNOB_COUNT; ++i) {
@@ -32,7 +28,6 @@ static int* knob_table() {
             snprintf(name, sizeof(name), "REID_%s", g_knob_names[i]);
             const char* e = getenv(name);
             g_knobs[i] = e ? atoi(e) : -1;          // -1 = "not set": every reader has its own default
-            if (knob_is_debug(i)) g_knobs[i] = -1;  // wrong-result modes: experiment builds only, and only through reid_set_knob()
         }
         return true;
     }();
@@ -44,12 +39,6 @@ extern "C" int reid_set_knob(const char* name, int value) {
     int* t = knob_table();
     for (int i = 0; i < KNOB_COUNT; ++i)
         if (strcmp(name, g_knob_names[i]) == 0) {
-#ifndef REID_EXPERIMENTS
-            if (knob_is_debug(i) && value > 0) {
-                reid_set_error("reid_set_knob: %s is a wrong-result timing mode, available only in -DREID_EXPERIMENTS builds", name);
-                return REID_ERR_ARG;
-            }
-#endif
             t[i] = value; return REID_OK;
         }
     reid_set_error("reid_set_knob: unknown knob %s", name);

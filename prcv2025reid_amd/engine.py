@@ -38,10 +38,6 @@ def round_up(a, b):
     return (a + b - 1) // b * b
 
 
-_EXP_SKIP_U = os.environ.get('REID_EXP_SKIP_U', '0') == '1'
-_EXP_SKIP_DA = os.environ.get('REID_EXP_SKIP_DA', '0') == '1'
-
-
 class LoraLayout:
     """Where each (layer, linear) adapter set lives in the flat fp32 arena and in the bf16 pack arena."""
 
@@ -159,13 +155,6 @@ class Engine:
         self.text_backward_ready = True
         self._text_packed = None
         self.overlap_tn = os.environ.get('REID_TN_STREAM', '1') != '0'
-        self.cls_prune = os.environ.get('REID_CLS_PRUNE', '1') != '0'
-        # experiment switches, read once (the per-layer code paths test attributes, not the environment)
-        self.add_ln = os.environ.get('REID_ADD_LN', '1') != '0'
-        self.lora_down_defer = os.environ.get('REID_LORA_DOWN_DEFER', '1') != '0'
-        self.lora_fused = os.environ.get('REID_LORA_FUSED', '1') != '0'
-        self.lora_da_fused = os.environ.get('REID_LORA_DA_FUSED', '1') != '0'
-        self.lora_fused_max_n = 768 if os.environ.get('REID_LORA_FUSED') == '768' else 1 << 30      # (A/B: only the 768-column linears)
         self.W = {}
         self.W32 = {}
 
@@ -189,14 +178,11 @@ class Engine:
         """Stream of the adapter-gradient kernels: LOWEST priority, so its workgroups are dispatched only where the main stream has
         none pending (the partly filled last round of a GEMM, gaps between kernels) instead of taking compute units from it."""
         if self._side is None:
-            prio = os.environ.get('REID_SIDE_PRIORITY')
-            if prio is None:
-                try:
-                    least, _greatest = torch.cuda.Stream.priority_range()
-                except Exception:
-                    least = 0
-                prio = least
-            self._side = torch.cuda.Stream(self.dev, priority=int(prio))
+            try:
+                least, _greatest = torch.cuda.Stream.priority_range()
+            except Exception:
+                least = 0
+            self._side = torch.cuda.Stream(self.dev, priority=int(least))
         return self._side
 
     # ------------------------------------------------------------------------------- packing
@@ -351,7 +337,6 @@ class Engine:
         rg_cls = (ends[1:], mus)
         saved = []
         buf = {}
-        idx = self._const(('cls_idx', n_img, S), lambda: torch.arange(n_img, dtype=torch.int32) * S)
         idxl = self._const(('cls_idx64', n_img, S), lambda: torch.arange(n_img, dtype=torch.int64) * S)
         main = torch.cuda.current_stream(dev)
         side = self._side_stream() if (save and self.overlap_tn) else None
@@ -392,7 +377,7 @@ class Engine:
 
         # Residual adds live in the LayerNorm that follows them (reid_add_layernorm_fwd): the out-projection and fc2 GEMMs store their
         # 16-bit branch output, the add + LN kernel streams x once.  LN1 of block l+1 is therefore produced at the end of block l.
-        add_ln = self.add_ln
+        # (The pruned last block keeps the unfused residual GEMM + LayerNorm.)
         L = a['vision_layers']
         nxt = None
         for l in range(L):
@@ -405,10 +390,10 @@ class Engine:
                 nxt = None
             qkv = new('qkv', (M, 3 * d), b16)
             ops.gemm(h, we(l, 'qkv'), qkv, bias=W[('v', l, 'bqkv')], row_groups=rg_full)
+            last = l == L - 1
             o = new('o', (M, d), b16); lse = new('lse', (n_img, heads, S), f32)
-            ops.attn_fwd(qkv, o, lse, n_img, S, heads, q_tiles=1 if (self.cls_prune and l == a['vision_layers'] - 1) else 0)
+            ops.attn_fwd(qkv, o, lse, n_img, S, heads, q_tiles=1 if last else 0)
             sa, sm_ = (None, None) if drop_scales is None else drop_scales[l]
-            last = self.cls_prune and l == a['vision_layers'] - 1
             if last:
                 # Only the class-token row of the last block's output is ever used (clip_backbone.py:281: x[:, 0]), and rows do
                 # not mix after the attention core: out-projection, LN2 and the MLP of the LAST block run on the n_img class rows
@@ -421,7 +406,7 @@ class Engine:
             mkr = dict(img_mod=img_mod, mask_r=r, mask_period=Rp, rows_per_img=rpi, alpha=self.scaling)
             xm = new('xm', (Mr, d), f32)
             h2 = new('h2', (Mr, d), b16); mean2 = new('m2', (Mr,), f32); rstd2 = new('r2', (Mr,), f32)
-            if add_ln and not last:
+            if not last:
                 yb = buf.get('yb')
                 if yb is None:
                     # branch output of the out-projection / fc2 GEMM: consumed by the add + LayerNorm kernel, never by an MFMA, so it
@@ -444,10 +429,8 @@ class Engine:
                 T1 = torch.empty(Mr, Rp, **b16); T2 = torch.empty(Mr, Rp, **b16)
                 lora_down([(h, pk(l, 'qkv', 'A'), T, mk), (oin, pk(l, 'out', 'A'), To, mkr), (h2, pk(l, 'fc1', 'A'), T1, mkr),
                            (g, pk(l, 'fc2', 'A'), T2, mkr)])
-                if side is not None and not self.lora_down_defer:
-                    flush_lora_down()
             xn = torch.empty(Mr, d, **f32) if save else new('xn' + str(l & 1) + ('c' if last else ''), (Mr, d), f32)
-            if add_ln and not last and l + 1 < L:
+            if not last:
                 np_ = f'{ce}vision_layers.{l + 1}.'
                 ops.gemm(g, we(l, 'fc2'), yb, bias=P[lp + 'mlp.fc2.shared_linear.bias'], row_groups=rg)
                 # (eval keeps two h buffers: the next block's h is written while nothing reads this block's any more, but a fresh
@@ -463,14 +446,12 @@ class Engine:
                                   mean2=mean2, rstd2=rstd2, T1=T1, u=u, g=g, T2=T2, sa=sa, sm=sm_, cls=last, o_rows=oin))
             x = xn
         cls_h = torch.empty(n_img, d, **b16); mf = torch.empty(n_img, **f32); rf = torch.empty(n_img, **f32)
-        ops.layernorm_fwd(x, P[ce + 'vision_ln_final.weight'], P[ce + 'vision_ln_final.bias'], y_bf16=cls_h, mean=mf, rstd=rf,
-                          row_index=None if self.cls_prune else idx)
+        ops.layernorm_fwd(x, P[ce + 'vision_ln_final.weight'], P[ce + 'vision_ln_final.bias'], y_bf16=cls_h, mean=mf, rstd=rf)
         feats = torch.empty(n_img, a['fusion_dim'], **f32)
         ops.gemm(cls_h, W['vproj'], feats)
-        if self.lora_down_defer:
-            flush_lora_down()
-        state = dict(layers=saved, x_final=x, idx=idx, idxl=idxl, mf=mf, rf=rf, img_mod=img_mod, n_img=n_img, cls_h=cls_h,
-                     groups=groups, cls_prune=self.cls_prune, rg_full=rg_full, rg_cls=rg_cls) if save else None
+        flush_lora_down()
+        state = dict(layers=saved, x_final=x, idxl=idxl, mf=mf, rf=rf, img_mod=img_mod, n_img=n_img, cls_h=cls_h,
+                     groups=groups, rg_full=rg_full, rg_cls=rg_cls) if save else None
         return feats, state
 
     # ------------------------------------------------------------------------------- vision backward
@@ -511,13 +492,10 @@ class Engine:
             ovf.zero_()
         dcls = torch.empty(n_img, d, **b16)
         ops.gemm(dfb, W['vprojT'], dcls)
-        prune = bool(st.get('cls_prune'))
         idxl = st['idxl']
-        if prune:                                           # class rows only until the last block's attention (see vision_forward)
-            dx = torch.empty(M, d, **gx); dxb = torch.empty(M, d, **b16)        # first written (all rows) by the last block's LN1 backward
-            dx_c = torch.empty(n_img, d, **gx); dxb_c = torch.empty(n_img, d, **b16)
-        else:
-            dx = torch.zeros(M, d, **gx); dxb = torch.zeros(M, d, **b16)
+        # class rows only until the last block's attention (see vision_forward)
+        dx = torch.empty(M, d, **gx); dxb = torch.empty(M, d, **b16)            # first written (all rows) by the last block's LN1 backward
+        dx_c = torch.empty(n_img, d, **gx); dxb_c = torch.empty(n_img, d, **b16)
         dense = {} if want_dense else None
         ones8 = torch.ones(M, 8, **b16) if want_dense else None
 
@@ -541,13 +519,8 @@ class Engine:
             dense[ce + 'vision_proj.weight'] = wgrad(dfb, st['cls_h'])
         dgf, dbf = ln_grads(ce + 'vision_ln_final')
         # dxb always holds the gradient ENTERING the next residual branch: dx times that branch's DropPath factor
-        if prune:
-            ops.layernorm_bwd(dcls, st['x_final'], P[ce + 'vision_ln_final.weight'], st['mf'], st['rf'], dx_c, dx_bf16=dxb_c,
-                              bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=1, dgamma=dgf, dbeta=dbf, overflow=ovf)
-        else:
-            ops.layernorm_bwd(dcls, st['x_final'], P[ce + 'vision_ln_final.weight'], st['mf'], st['rf'], dx, dx_bf16=dxb,
-                              row_index=st['idx'], bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=S, dgamma=dgf, dbeta=dbf,
-                              overflow=ovf)
+        ops.layernorm_bwd(dcls, st['x_final'], P[ce + 'vision_ln_final.weight'], st['mf'], st['rf'], dx_c, dx_bf16=dxb_c,
+                          bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=1, dgamma=dgf, dbeta=dbf, overflow=ovf)
         # Scratch.  Everything the SIDE stream reads (the dY of the four linears: dxb, du, dxmb, dqkv) exists twice, used by alternate
         # layers: the main stream may then run a whole layer ahead of the adapter-gradient kernels without overwriting their inputs.
         # U* (= dY . Bcat, the rank-r cotangents) are written and read on the side stream only.
@@ -567,23 +540,15 @@ class Engine:
         side_done = {}
         L = a['vision_layers']
         # the gradient ENTERING layer l (dx times that layer's MLP DropPath factor, 16-bit) lives in dxb2[l & 1]
-        if not prune:
-            cur_dxb = dxb2[(L - 1) & 1]
-            if cur_dxb is not dxb:
-                cur_dxb.copy_(dxb)
-
-        fuse_u_db, fuse_max_n = self.lora_fused, self.lora_fused_max_n
-        u_part = torch.empty(M, Rp, **f32) if fuse_u_db else None      # fp32 partial U of fc1's four column blocks (side stream only)
+        u_part = torch.empty(M, Rp, **f32)                  # fp32 partial U of fc1's four column blocks (side stream only)
         # Class-row scratch of the pruned last block.  Read and written by the SIDE stream (lora_grads) long after the main stream has
         # moved on, so it must not be released inside the loop: a block freed by the main stream is handed to the main stream's next
         # allocation at once (wgrad / colsum / ln_grads with want_dense), whatever other streams still have pending on it (r03 found
         # this hazard for forward-only calls).  Allocated here, these tensors die when this function returns -- after the join of the
         # side stream into the main stream below has been enqueued, which orders every later main-stream use behind the side kernels.
-        cls_tmp = None
-        if prune:
-            cls_tmp = dict(U2=torch.empty(n_img, Rp, **b16), U1=torch.empty(n_img, Rp, **b16), Uo=torch.empty(n_img, Rp, **b16),
-                           du=torch.empty(n_img, ff, **b16), dh=torch.empty(n_img, d, **b16), do=torch.empty(n_img, d, **b16),
-                           dxm=torch.empty(n_img, d, **gx), dxmb=torch.empty(n_img, d, **b16))
+        cls_tmp = dict(U2=torch.empty(n_img, Rp, **b16), U1=torch.empty(n_img, Rp, **b16), Uo=torch.empty(n_img, Rp, **b16),
+                       du=torch.empty(n_img, ff, **b16), dh=torch.empty(n_img, d, **b16), do=torch.empty(n_img, d, **b16),
+                       dxm=torch.empty(n_img, d, **gx), dxmb=torch.empty(n_img, d, **b16))
 
         def lora_grads(l, calls):
             """Adapter gradients of one linear on the side stream: U = mask(dY . Bcat) * (alpha/r), dB += dY^T T, dA += U^T X.
@@ -592,20 +557,17 @@ class Engine:
                 for dY, BT, U, kw, tns in calls:
                     # tns[0] = (dY, T, dB): with N = 768 output columns (every linear but fc1) U and dB come out of ONE pass over dY
                     same = tns[0][0].data_ptr() == dY.data_ptr() and tns[0][0].shape == dY.shape and tns[0][0].stride() == dY.stride()
-                    if fuse_u_db and same and ops.lora_bwd_fused_ok(dY.shape[1], tns[0][1].shape[1]) and dY.shape[1] <= fuse_max_n:
+                    if same and ops.lora_bwd_fused_ok(dY.shape[1], tns[0][1].shape[1]):
                         ops.lora_bwd_fused(dY, tns[0][1], BT, U, tns[0][2], kw['img_mod'], kw['rows_per_img'], kw['mask_r'], kw['alpha'],
                                            u_partial=u_part[:dY.shape[0]] if dY.shape[1] > 768 else None)
                         rest = tns[1:]
                     else:
-                        if not _EXP_SKIP_U:                  # (timing experiment only: REID_EXP_SKIP_U=1 leaves U unwritten -> wrong dA)
-                            ops.gemm(dY, BT, U, **kw)
+                        ops.gemm(dY, BT, U, **kw)
                         rest = tns
                     for xx, yy, out in rest:
-                        if _EXP_SKIP_DA:                     # (timing experiment only: REID_EXP_SKIP_DA=1 leaves dA unwritten)
-                            continue
                         # (xx, yy, out) = (U [M, G Rp], the linear's input X [M, K], dA [G Rp, K]): one pass over X, one image per workgroup
                         ng = xx.shape[1] // Rp
-                        if self.lora_da_fused and xx.shape[1] == ng * Rp and out.shape[0] == ng * Rp and \
+                        if xx.shape[1] == ng * Rp and out.shape[0] == ng * Rp and \
                                 ops.lora_da_fused_ok(yy.shape[1], Rp, kw['rows_per_img'], kw['mask_r'], ng):
                             ops.lora_da_fused(yy, xx, out, kw['img_mod'], kw['rows_per_img'], kw['mask_r'], n_groups=ng)
                         else:

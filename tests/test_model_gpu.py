@@ -594,8 +594,8 @@ def test_vision_backbone_gradients_random_cotangent(flavor, tol):
     print(f'  [{flavor}] {n} backbone tensors, worst grad rel-L2 = {worst:.3e}')
 
 
-def test_dense_gradients_independent_of_side_stream_timing():
-    """freeze_backbone=False with the class-row pruning of the last block on: the class-row scratch of that block is read by the
+def test_pruned_dense_gradients_independent_of_side_stream_timing():
+    """freeze_backbone=False with the class-row pruning of the last block (always on): the class-row scratch of that block is read by the
     adapter-gradient SIDE stream while the main stream goes on allocating (weight gradients, column sums, LayerNorm pairs).  The side
     stream is held back by ~20 ms of sleep so that every one of its kernels is still pending when the main stream has finished
     allocating; gradients must equal those of the same backward run on ONE stream (r03 hazard: blocks released inside the loop)."""
@@ -607,12 +607,15 @@ def test_dense_gradients_independent_of_side_stream_timing():
     grads = {}
     for mode in ('one_stream', 'side_delayed'):
         model = build_model(meta, state, True, 'bf16')
-        assert model.engine.cls_prune
+        saved = []                                       # the forward's saved state: shows that the last block ran on the class rows
+        fwd = model.engine.vision_forward
+        model.engine.vision_forward = lambda *a_, **k_: saved.append(fwd(*a_, **k_)) or saved[-1]
         for k, p in model.named_parameters():
             p.requires_grad_(not k.startswith('clip_encoder.clip_model.') and k != 'clip_encoder.text_proj.weight')
         model.engine.overlap_tn = mode == 'side_delayed'
         model.engine.refresh()
         feats = model._vision_apply(tuple(model.vision_modalities.index(m) for m in imgs), [imgs[m].cuda() for m in imgs])
+        assert len(saved) == 1 and saved[0][1]['layers'][-1]['cls'] and saved[0][1]['layers'][-1]['o_rows'].shape[0] == 12
         if mode == 'side_delayed':
             with torch.cuda.stream(model.engine._side_stream()):
                 torch.cuda._sleep(40_000_000)

@@ -18,7 +18,7 @@ def timeit(fn, reps=20):
     for _ in range(reps): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps * 1e3
-variants = [v.split(':') for v in os.environ.get('VARIANTS', 'base:GEMM_PERSIST=1').split(';')]
+variants = [v.split(':') for v in os.environ.get('VARIANTS', 'default:;two_kernel:ATTN_BWD=1').split(';')]
 res = {}
 for rnd in range(3):
     for vn, spec in variants:

@@ -44,7 +44,7 @@ def set_knobs(spec):
         if kv:
             k, v = kv.split('=')
             _lib.check(_lib.lib().reid_set_knob(k.encode(), int(v)))
-variants = [v.split(':') for v in os.environ.get('VARIANTS', 'pp:GEMM_PERSIST=0;pps:GEMM_PERSIST=1').split(';')]
+variants = [v.split(':') for v in os.environ.get('VARIANTS', 'default:;t12:GEMM_TILE=12;t14:GEMM_TILE=14').split(';')]
 knobs = sorted({kv.split('=')[0] for _, spec in variants for kv in spec.split(',') if kv})
 tot = {n: 0.0 for n, _ in variants}; flt = 0.0
 for name, fl, fn in cases:

@@ -35,14 +35,14 @@ cases = [
  ('fc1b bf16 K=3072      ', 2.0*M*d*(ff+Rp), lambda: ops.gemm(gact, W2, dh, A2=T[:, :Rp], B2=Bo, K2=Rp)),
  ('qkvb bf16 K=2304+96   ', 2.0*M*d*(3*d+3*Rp), lambda: ops.gemm(qkv, rnd(d, 3*d, scale=0.03), dh, A2=T, B2=rnd(d, 3*Rp, scale=0.1), K2=3*Rp)),
 ]
-# variants = knob settings, e.g. VARIANTS="base:GEMM_PERSIST=0;pers:GEMM_PERSIST=1,GEMM_STAGGER=0;stag:GEMM_PERSIST=1,GEMM_STAGGER=100"
+# variants = knob settings, e.g. VARIANTS="default:;t3:GEMM_TILE=3;t12:GEMM_TILE=12;t14:GEMM_TILE=14" (the tiles REID_GEMM_TILE can force)
 import ctypes
 def set_knobs(spec):
     for kv in spec.split(','):
         if kv:
             k, v = kv.split('=')
             _lib.check(_lib.lib().reid_set_knob(k.encode(), int(v)))
-variants = [v.split(':') for v in os.environ.get('VARIANTS', 'base:GEMM_PERSIST=0;stag:GEMM_PERSIST=1').split(';')]
+variants = [v.split(':') for v in os.environ.get('VARIANTS', 'default:;t3:GEMM_TILE=3;t12:GEMM_TILE=12;t14:GEMM_TILE=14').split(';')]
 knobs = sorted({kv.split('=')[0] for _, spec in variants for kv in spec.split(',') if kv})
 tot = {n: 0.0 for n, _ in variants}
 for name, fl, fn in cases:

@@ -29,12 +29,8 @@ def timeit(fn, reps=50):
 t = timeit(lambda: ops.lora_bwd_fused(dY, T, BT, U, dB, mods, 197, r, 2.0))
 print(f'one image per workgroup (r04 default, 256 workgroups): {t:7.1f} us = {M * N * 2 / t / 1e6:7.2f} TB/s of dY = {M * N * 2 / t / 1e3 / 256:6.1f} GB/s per workgroup')
 _lib.check(_lib.lib().reid_set_knob(b'LORA_IMPL', 1))
-for knob in (-1, 192, 768, 1536):
-    _lib.check(_lib.lib().reid_set_knob(b'TN_BLOCKS', knob))
-    t = timeit(lambda: ops.lora_bwd_fused(dY, T, BT, U, dB, mods, 197, r, 2.0))
-    slabs = 64 if knob < 0 else knob // 6
-    print(f'fused, {slabs:4d} slabs: {t:7.1f} us = {M * N * 2 / t / 1e6:7.2f} TB/s of dY = {M * N * 2 / t / 1e3 / slabs:6.1f} GB/s per workgroup')
-_lib.check(_lib.lib().reid_set_knob(b'TN_BLOCKS', -1))
+t = timeit(lambda: ops.lora_bwd_fused(dY, T, BT, U, dB, mods, 197, r, 2.0))
+print(f'fused, 64 slabs: {t:7.1f} us = {M * N * 2 / t / 1e6:7.2f} TB/s of dY = {M * N * 2 / t / 1e3 / 64:6.1f} GB/s per workgroup')
 _lib.check(_lib.lib().reid_set_knob(b'LORA_IMPL', -1))
 t1 = timeit(lambda: ops.gemm(dY, BT, U, img_mod=mods, mask_r=r, mask_period=Rp, rows_per_img=197, alpha=2.0))
 t2 = timeit(lambda: ops.gemm_tn(dY, T, dB, beta=1.0))

@@ -31,23 +31,3 @@ for i, n in enumerate(names):
     print(f'{n:36s}: mean {dd[:, i].mean():6.2f}  p10 {np.percentile(dd[:, i], 10):6.2f}  p50 {np.percentile(dd[:, i], 50):6.2f}  p90 {np.percentile(dd[:, i], 90):6.2f} us')
 life = ts[:, 6] - ts[:, 0]
 print('workgroup lifetime (wave 0): mean %.2f  p10 %.2f  p90 %.2f us' % (life.mean(), np.percentile(life, 10), np.percentile(life, 90)))
-
-# ---- the persistent form: stamps per ITEM (wave 0 of the workgroup that owns it)
-_lib.check(lib.reid_set_knob(b'ATTN_BWD', 3))
-trace.zero_()
-for _ in range(3): ops.attn_bwd(qkv, o, do, lse, dqkv, delta, n_img, S, heads)
-torch.cuda.synchronize()
-lib.reid_debug_attn_bwd_trace(ctypes.c_void_p(trace.data_ptr()))
-ops.attn_bwd(qkv, o, do, lse, dqkv, delta, n_img, S, heads)
-torch.cuda.synchronize()
-lib.reid_debug_attn_bwd_trace(ctypes.c_void_p(0))
-t = trace.cpu().numpy().astype(np.int64)
-ts = (t - t[:, 0].min()) / 100.0
-names = ['top: wait (this item landed) + barrier', 'K/V staging issue + delta + barrier', 'phase 1', 'own frags, barrier, stage next Q/dO/O, wait K/V, barrier',
-         'dK/dV stores issued', 'phase 2', 'dQ stores issued']
-dd = np.diff(ts, axis=1)
-print('persistent: kernel span %.1f us, %d items' % (ts[:, 7].max(), nwg))
-for i, n in enumerate(names):
-    print(f'{n:60s}: mean {dd[:, i].mean():6.2f}  p10 {np.percentile(dd[:, i], 10):6.2f}  p50 {np.percentile(dd[:, i], 50):6.2f}  p90 {np.percentile(dd[:, i], 90):6.2f} us')
-life = ts[:, 7] - ts[:, 0]
-print('item time (wave 0): mean %.2f  p10 %.2f  p90 %.2f us' % (life.mean(), np.percentile(life, 10), np.percentile(life, 90)))

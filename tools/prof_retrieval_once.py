@@ -1,4 +1,4 @@
-"""One retrieval call under rocprofv3 (kernel stats), optionally with REID_TOPK_TILE / REID_TOPK_DBG."""
+"""One retrieval call under rocprofv3 (kernel stats), optionally with REID_TOPK_TILE / REID_TOPK_SCAN."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -15,4 +15,4 @@ e0.record()
 for _ in range(5):
     ix.topk(Q, k=10, normalized=True)
 e1.record(); torch.cuda.synchronize()
-print(f'tile={os.environ.get("REID_TOPK_TILE")} dbg={os.environ.get("REID_TOPK_DBG")}: {e0.elapsed_time(e1) / 5:.3f} ms per call')
+print(f'tile={os.environ.get("REID_TOPK_TILE")} scan={os.environ.get("REID_TOPK_SCAN")}: {e0.elapsed_time(e1) / 5:.3f} ms per call')
