@@ -658,6 +658,265 @@ def test_attention_backward_forms(ops, n_seq, S, heads, q_tiles):
         assert rel_err(res[2][:, i * d:(i + 1) * d], want[:, i * d:(i + 1) * d]) < 3e-2, nm
 
 
+# ---------------------------------------------------------------- attention, element by element against fp64
+# The reference takes the exact 16-bit q, k, v, dO the kernels read.  Each output element gets its own bound, counted from the
+# roundings on its path; fp32 operations count one ulp (2^-23) each, which covers any rounding of the MFMA adders, and a sum of
+# n terms n ulps of the sum of the terms' magnitudes (products of two 16-bit values are exact in fp32).  u = one 16-bit rounding
+# (`_rounding`, floored at the least normal exponent: subnormal P / dS in f16).
+#   P~ (forward, before packing), relative: score dot product 64 ulp * A_ij / 8, A = |q|.|k|^T, over the row's largest A; the exp2
+#     argument (c's rounding, the fma, |t| < 126 before exp2 leaves fp32's normal range) and exp2 itself: (200 + |m|) ulp, m the row
+#     maximum of the scaled scores.  2^-126 absolute for what falls below fp32's normal range.
+#   O: one 16-bit rounding of each unnormalised P~ (<= 1) before the PV product, divided by l, weighted by |v|; P~'s relative error
+#     twice (numerator and l); l summed over 16 NT + 1 terms, the PV MFMA over 32 NT, 1/l and the scale 3 -> (48 NT + 4) ulp of
+#     sum_j P_ij |v_jd|; then the store: one rounding of |O| + bound.
+#   lse = m + log l: the score and exp2 terms above, l's sum, logf (2 ulp of log l <= 5.5) and the add: (16 NT + 20) ulp + 1 ulp |lse|.
+#   P (backward, recomputed from the saved lse), relative: the score term, the kernel lse's own bound, the argument and exp2:
+#     (200 + |lse|) ulp.
+#   delta = dO . O: the kernel forms it from its own 16-bit O, so its error against fp64 dO . O_ref is sum_d |dO| bound(O) plus a
+#     64-term fp32 sum.  (The delta it publishes is held to the 64-term sum bound against dO . O_kernel.)
+#   dS = P (dP - delta) / 8 before packing: P's relative error times |dP - delta|; dP a 64-term MFMA, 64 ulp * sum_d |dO||v|; delta's
+#     error; the fma and the product, 2 ulp |dS|.  Then one 16-bit rounding of dS (and of P for dV).
+#   dQ / dK / dV: those per-element errors of dS (P) weighted by |k| (|q|, |dO|), a 32 NT-term MFMA, one rounding at the store.
+_ULP32 = 2.0 ** -23
+_TINY32 = 2.0 ** -126
+
+
+def _attn_ref64(q, k, v, do, allowed, q_rows, mant, emin):
+    """fp64 attention forward and backward of [c, heads, S, 64] q, k, v, dO (scale 1/8) with ``allowed`` [c or 1, 1, S, S] key
+    predicates; only query rows < q_rows take part in the backward.  Returns the references and their bounds (see above)."""
+    S = q.shape[2]
+    nt = (S + 31) // 32
+    ulp = _ULP32
+    al = allowed.double()
+    s = q @ k.transpose(-1, -2)
+    maxA = ((q.abs() @ k.abs().transpose(-1, -2)) * al).amax(-1, keepdim=True)
+    ss = (0.125 * s).masked_fill(~allowed, float('-inf'))
+    m = ss.amax(-1, keepdim=True)
+    ph = torch.exp(ss - m)                                          # the kernel's unnormalised P (max 1)
+    l = ph.sum(-1, keepdim=True)
+    P = ph / l
+    lse = m + torch.log(l)
+    O = P @ v
+    va, ka, qa, da = v.abs(), k.abs(), q.abs(), do.abs()
+    e_score = 8 * ulp * maxA
+    ef = e_score + (200 + m.abs()) * ulp
+    rp = (_rounding(ph * (1 + ef) + _TINY32, mant, emin) + _TINY32) * al / l
+    bO = rp @ va + (2 * ef + (48 * nt + 4) * ulp) * (P @ va)
+    bO_all = bO + _rounding(O.abs() + bO, mant, emin)
+    b_lse = e_score + (200 + m.abs()) * ulp + (16 * nt + 20) * ulp + ulp * lse.abs()
+
+    live = (torch.arange(S, device=q.device) < q_rows).double().view(S, 1)
+    alq = al * live
+    Pb = P * live
+    dP = do @ v.transpose(-1, -2)
+    D = da @ va.transpose(-1, -2)
+    delta = (do * O).sum(-1, keepdim=True)
+    e_delta = (da * bO_all).sum(-1, keepdim=True) + 64 * ulp * (da * (O.abs() + bO_all)).sum(-1, keepdim=True)
+    eb = e_score + b_lse + (200 + lse.abs()) * ulp
+    dS = 0.125 * Pb * (dP - delta)
+    pe = eb * Pb + _TINY32 * alq                                    # P's error before packing
+    E = 0.125 * pe * (dP - delta).abs() + 0.125 * Pb * (64 * ulp * D + e_delta) + 2 * ulp * dS.abs()
+    F = E + _rounding(dS.abs() + E, mant, emin) * alq               # dS's error after packing
+    G = pe + _rounding(Pb + pe, mant, emin) * alq                   # P's error after packing
+    acc = 32 * nt * ulp
+    dSa, FT, GT = dS.abs() + F, F.transpose(-1, -2), G.transpose(-1, -2)
+    r = dict(O=O, lse=lse[..., 0], delta=delta[..., 0], dQ=dS @ k, dK=dS.transpose(-1, -2) @ q, dV=Pb.transpose(-1, -2) @ do)
+    b = dict(O=bO, lse=b_lse[..., 0], dQ=F @ ka + acc * (dSa @ ka), dK=FT @ qa + acc * (dSa.transpose(-1, -2) @ qa),
+             dV=GT @ da + acc * ((Pb + G).transpose(-1, -2) @ da))
+    return r, b
+
+
+def _attn_ref64_chunked(q, k, v, do, allowed, q_rows, mant, emin):
+    n, h, S = q.shape[:3]
+    step = max(1, (6 << 20) // (h * S * S))                         # <= ~50 MB per [c, heads, S, S] fp64 temporary
+    parts = [_attn_ref64(q[i:i + step], k[i:i + step], v[i:i + step], do[i:i + step],
+                         allowed[i:i + step] if allowed.shape[0] > 1 else allowed, q_rows, mant, emin) for i in range(0, n, step)]
+    return tuple({key: torch.cat([p[j][key] for p in parts]) for key in parts[0][j]} for j in (0, 1))
+
+
+def _attn_inputs(n_seq, S, heads, opt, g):
+    """q, k, v, dO as [n, heads, S, 64] fp32 before the 16-bit rounding, and the key mask [n, S] (uint8) or None."""
+    q, k, v, do = (torch.randn(n_seq, heads, S, 64, device='cuda', generator=g) for _ in range(4))
+    inputs = opt.get('inputs')
+    if inputs == 'peaked':
+        # scaled scores of about +-30 (std 10) and a sink key per head: +40 * 10 / 8 = +50 on dim 0, in the first tile for even
+        # heads and the last tile for odd ones -- pretrained-like rows, P's maximum well above what the other keys reach
+        q = q * 10 ** 0.5; k = k * 10 ** 0.5
+        q[..., 0] = 10.0; k[..., 0] = 0.0
+        for h in range(heads):
+            k[:, h, 3 if h % 2 == 0 else S - 2, 0] = 40.0
+    elif inputs == 'extreme':
+        # selector dims 0..7: key j_a holds 40 in dim a, query i holds 40 in dim (i + head) % 8 -> its key scores 1600 / 8 = 200
+        # above a rest of about N(0, 1); j_0 = 0 and j_7 = S - 1 (first and last tile)
+        q[..., :8] = 0.0; k[..., :8] = 0.0
+        for a in range(8):
+            k[:, :, round(a * (S - 1) / 7), a] = 40.0
+        for h in range(heads):
+            i = torch.arange(S, device='cuda')
+            q[:, h, i, (i + h) % 8] = 40.0
+    km = None
+    mask = opt.get('mask')
+    if mask == 'prefix':                                            # the text tower: valid lengths 2..S, BOS always valid
+        lens = torch.randint(2, S + 1, (n_seq,), device='cuda', generator=g)
+        lens[0], lens[-1] = 2, S
+        km = (torch.arange(S, device='cuda')[None] < lens[:, None]).to(torch.uint8)
+    elif mask == 'edges':
+        km = (torch.rand(n_seq, S, device='cuda', generator=g) > 0.3).to(torch.uint8)
+        nt = (S + 31) // 32
+        for i in range(n_seq):
+            if i % 4 == 1:
+                km[i, 32:64] = 0                                    # a whole key tile (the second)
+            elif i % 4 == 2:
+                km[i, [j for j in (31, 32, S - 1) if j < S]] = 0    # both sides of a tile boundary and the last key
+            elif i % 4 == 3 and nt > 1:
+                km[i, 32 * (nt - 1):] = 0                           # the whole last tile
+        km[:, 0] = 1
+    return q, k, v, do, km
+
+
+# (name, n_seq, S, heads, options): causal; mask = 'edges' (random, whole tiles, bits at 31 / 32 / S-1) or 'prefix' (text tower);
+# q_tiles; inputs = 'peaked' or 'extreme'; strided = padded row strides with NaN in qkv's / dO's padding
+ATTN_CASES = ([(f'S{S}', 3, S, 1 + i % 4, {}) for i, S in enumerate((1, 2, 31, 32, 33, 64, 96, 97, 128, 129, 160, 170, 192, 193, 224))] + [
+    ('mask_nt3', 4, 77, 3, dict(mask='edges')),
+    ('mask_nt5', 4, 150, 2, dict(mask='edges')),
+    ('mask_nt7', 4, 224, 2, dict(mask='edges')),
+    ('text', 64, 77, 8, dict(causal=True, mask='prefix')),          # engine.py text tower call
+    ('causal_nt1', 4, 20, 2, dict(causal=True)),
+    ('causal_nt4', 3, 110, 2, dict(causal=True)),
+    ('causal_nt7', 2, 200, 3, dict(causal=True)),
+    ('vision_step', 256, 197, 12, {}),                              # the benchmark's call
+    ('vision_cls', 256, 197, 12, dict(q_tiles=1)),                  # the last vision block: class rows only
+    ] + [(f'qt{qt}_S{S}', 3, S, 2, dict(q_tiles=qt)) for S in (129, 197) for qt in (1, 2, (S + 31) // 32 - 1)] + [
+    ('peaked_nt3', 4, 96, 4, dict(inputs='peaked')),
+    ('peaked_nt7', 4, 197, 4, dict(inputs='peaked')),
+    ('extreme_nt3', 3, 80, 2, dict(inputs='extreme')),
+    ('extreme_nt7', 3, 200, 2, dict(inputs='extreme')),
+    ('strided', 3, 197, 2, dict(strided=True, q_tiles=2)),
+    ('strided_nt5', 2, 150, 4, dict(strided=True)),
+    ('strided_text', 4, 77, 3, dict(strided=True, causal=True, mask='prefix')),
+])
+
+
+def _ratio(got, ref, bound):
+    err = (got.double() - ref).abs() / bound
+    return float(err.max()) if err.numel() else 0.0
+
+
+@pytest.mark.parametrize('case', ATTN_CASES, ids=[c[0] for c in ATTN_CASES])
+def test_attention_elementwise_fp64(ops, case):
+    """Forward (both forms: single pass NT <= 3, TWO_PASS NT >= 4) and every backward form that applies (fused one-pass, and
+    ATTN_BWD=1 two-kernel; masked / causal calls have only the latter) against an fp64 reference, each element within its own
+    bound (_attn_ref64).  Also: lse and the published delta; dK / dV of masked keys and dQ of rows left out by q_tiles exactly 0;
+    nothing written outside what the call owns (sentinels, guard rows, stride padding); the same bits from a repeated call."""
+    from prcv2025reid_amd import _lib
+    name, n_seq, S, heads, opt = case
+    flavor = _lib.flavor()
+    mant, emin = _fmt16(flavor)
+    g = torch.Generator(device='cuda').manual_seed(S * 1009 + heads * 31 + n_seq)
+    d = heads * 64
+    nS, nhS = n_seq * S, n_seq * heads * S
+    causal = bool(opt.get('causal'))
+    q_tiles = opt.get('q_tiles', 0)
+    q_rows = min(S, 32 * q_tiles) if q_tiles else S
+    strided = bool(opt.get('strided'))
+    ld, ldo, ldd = (3 * d + 64, d + 8, 3 * d + 4) if strided else (3 * d, d, 3 * d)
+    GUARD = 32                                                      # rows (elements for lse / delta) after every buffer
+
+    q32, k32, v32, do32, km = _attn_inputs(n_seq, S, heads, opt, g)
+    qkv_buf = torch.full((nS + GUARD, ld), float('nan'), device='cuda', dtype=T16())     # NaN padding / guard: a read poisons
+    qkv = qkv_buf[:nS, :3 * d]
+    qkv.view(n_seq, S, 3, heads, 64).copy_(torch.stack([q32, k32, v32], 2).permute(0, 3, 2, 1, 4))
+    do_buf = torch.full((nS + GUARD, ldo), float('nan'), device='cuda', dtype=T16())
+    dout = do_buf[:nS, :d]
+    dout.view(n_seq, S, heads, 64).copy_(do32.transpose(1, 2))
+    q, k, v = (qkv.double().view(n_seq, S, 3, heads, 64)[:, :, i].transpose(1, 2) for i in range(3))
+    do = dout.double().view(n_seq, S, heads, 64).transpose(1, 2)
+
+    allowed = torch.ones(1, 1, S, S, dtype=torch.bool, device='cuda')
+    if causal:
+        allowed = allowed.tril()
+    if km is not None:
+        allowed = allowed & km.bool().view(n_seq, 1, 1, S)
+    ref, bnd = _attn_ref64_chunked(q, k, v, do, allowed, q_rows, mant, emin)
+
+    def fwd():
+        out_buf = _sentinel_buf(nS + GUARD, ldo, T16())
+        lse_buf = _sentinel_buf(1, nhS + GUARD, torch.float32)[0]
+        ops.attn_fwd(qkv, out_buf[:nS, :d], lse_buf[:nhS].view(n_seq, heads, S), n_seq, S, heads, causal=causal, key_mask=km,
+                     q_tiles=q_tiles)
+        return out_buf, lse_buf
+
+    out_buf, lse_buf = fwd()
+    out_buf2, lse_buf2 = fwd()
+    torch.cuda.synchronize()
+    assert torch.equal(out_buf.view(torch.int16), out_buf2.view(torch.int16)) and torch.equal(lse_buf.view(torch.int32), lse_buf2.view(torch.int32)), \
+        f'{name}: forward not deterministic'
+    out = out_buf[:nS, :d]
+    # forward: query rows < q_rows are the call's; everything else keeps its sentinel
+    rows_o = torch.zeros(n_seq, S, dtype=torch.bool, device='cuda'); rows_o[:, :q_rows] = True
+    written = torch.zeros(nS + GUARD, ldo, dtype=torch.bool, device='cuda'); written[:nS, :d] = rows_o.view(nS, 1)
+    _untouched(out_buf, written, f'{name} out')
+    written = torch.zeros(nhS + GUARD, dtype=torch.bool, device='cuda')
+    written[:nhS] = rows_o.view(n_seq, 1, S).expand(n_seq, heads, S).reshape(-1)
+    _untouched(lse_buf, written, f'{name} lse')
+    got_o = out.view(n_seq, S, heads, 64).transpose(1, 2)[:, :, :q_rows]
+    ref_o, b_o = ref['O'][:, :, :q_rows], bnd['O'][:, :, :q_rows]
+    _check_elements(got_o, ref_o, b_o, _rounding(ref_o.abs() + b_o, mant, emin), f'{name} O')
+    got_lse = lse_buf[:nhS].view(n_seq, heads, S)[:, :, :q_rows]
+    _check_elements(got_lse, ref['lse'][:, :, :q_rows], bnd['lse'][:, :, :q_rows], 0.0, f'{name} lse')
+    ratios = dict(O=_ratio(got_o, ref_o, b_o + _rounding(ref_o.abs() + b_o, mant, emin)),
+                  lse=_ratio(got_lse, ref['lse'][:, :, :q_rows], bnd['lse'][:, :, :q_rows]))
+    print(f'\nattention[{flavor}] {name} fwd: ' + ' '.join(f'{kk} {vv:.3f}' for kk, vv in ratios.items()))
+
+    lse = lse_buf[:nhS].view(n_seq, heads, S)
+    # delta from the kernel's own O (rows < q_rows): a 64-term fp32 sum
+    o_k = out.double().view(n_seq, S, heads, 64).transpose(1, 2)[:, :, :q_rows]
+    ref_delta = (do[:, :, :q_rows] * o_k).sum(-1)
+    b_delta = 64 * _ULP32 * (do[:, :, :q_rows] * o_k).abs().sum(-1) + _TINY32
+    lib = _lib.lib()
+    forms = [('fused', -1), ('two', 1)] if km is None and not causal else [('two', -1)]
+    for form, knob in forms:
+        if knob != -1:
+            _lib.check(lib.reid_set_knob(b'ATTN_BWD', knob))
+        try:
+            runs = []
+            for _ in range(2):
+                dq_buf = _sentinel_buf(nS + GUARD, ldd, T16())
+                dl_buf = _sentinel_buf(1, nhS + GUARD, torch.float32)[0]
+                ops.attn_bwd(qkv, out, dout, lse, dq_buf[:nS, :3 * d], dl_buf[:nhS].view(n_seq, heads, S), n_seq, S, heads,
+                             causal=causal, key_mask=km, q_tiles=q_tiles)
+                runs.append((dq_buf, dl_buf))
+            torch.cuda.synchronize()
+        finally:
+            if knob != -1:
+                _lib.check(lib.reid_set_knob(b'ATTN_BWD', -1))
+        (dq_buf, dl_buf), (dq_buf2, dl_buf2) = runs
+        what = f'{name}/{form}'
+        assert torch.equal(dq_buf.view(torch.int16), dq_buf2.view(torch.int16)) and torch.equal(dl_buf.view(torch.int32), dl_buf2.view(torch.int32)), \
+            f'{what}: backward not deterministic'
+        written = torch.zeros(nS + GUARD, ldd, dtype=torch.bool, device='cuda'); written[:nS, :3 * d] = True
+        _untouched(dq_buf, written, f'{what} dqkv')
+        written = torch.zeros(nhS + GUARD, dtype=torch.bool, device='cuda'); written[:nhS] = True   # rows >= q_rows: either form
+        _untouched(dl_buf, written, f'{what} delta_ws')
+        got_delta = dl_buf[:nhS].view(n_seq, heads, S)[:, :, :q_rows]
+        _check_elements(got_delta, ref_delta, b_delta, 0.0, f'{what} delta')
+        ratios = dict(delta=_ratio(got_delta, ref_delta, b_delta))
+        dqkv = dq_buf[:nS, :3 * d].view(n_seq, S, 3, heads, 64)
+        for i, nm in enumerate(('dQ', 'dK', 'dV')):
+            got = dqkv[:, :, i].transpose(1, 2)
+            rr, bb = ref[nm], bnd[nm]
+            if nm == 'dQ':
+                assert bool((got[:, :, q_rows:] == 0).all()), f'{what} dQ: rows left out by q_tiles not exactly 0'
+                got, rr, bb = got[:, :, :q_rows], rr[:, :, :q_rows], bb[:, :, :q_rows]
+            elif km is not None:
+                dead = (km == 0).view(n_seq, 1, S).expand(n_seq, heads, S)
+                assert bool((got[dead] == 0).all()), f'{what} {nm}: masked keys not exactly 0'
+            tol = _rounding(rr.abs() + bb, mant, emin)
+            _check_elements(got, rr, bb, tol, f'{what} {nm}')
+            ratios[nm] = _ratio(got, rr, bb + tol)
+        print(f'attention[{flavor}] {what} bwd: ' + ' '.join(f'{kk} {vv:.3f}' for kk, vv in ratios.items()))
+
+
 def test_patch_and_cls(ops):
     g = torch.Generator(device='cuda').manual_seed(3)
     img = torch.randn(5, 3, 224, 224, device='cuda', generator=g)
