@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N = 1 runs in this process.  N > 1 with no WORLD_SIZE in the environment: this process stays CPU-only, SPAWNS N rank processes
 (one per GPU, torch.distributed backend nccl = RCCL over xGMI, rendezvous on 127.0.0.1) and relays rank 0's JSON line; when the
@@ -12,12 +12,20 @@ zero_grad -> forward (4 vision modalities + text through the HIP executor) -> CE
 backward (hand-written HIP backward, LoRA/bn_neck/null-token gradients = the reference's default
 trainable set, train.py:1418-1425) -> gradient all-reduce (N > 1) -> AdamW step.
 Workload: N = 1: BASELINE.json configs[1] (P=16, K=4, LoRA r=8, masks all-on, ViT-B/16 + CLIP text random-init, 400
-identities).  N > 1: configs[2] (P=32, K=4 PER GPU, same model; weak scaling), and the line also carries the single-GPU
-value of that same per-GPU workload measured on rank 0 alone (`n1_same_workload`).  Inputs are resident in HBM.
+identities).  N > 1: configs[2] (P=32, K=4 PER GPU, same model; weak scaling).  Inputs are resident in HBM.
 
-One JSON line on stdout (rank 0).  Besides the contract keys it carries
+One JSON line on stdout (rank 0).  A plain run does only what its headline needs: it sets up, runs the W warm-up and the K
+timed steps, writes --dump-outputs if given and prints the line (the contract keys, the workload's `config`, `final_loss`).
+--full adds every other measurement and check; each runs after the timed steps, and the --no-* options leave single ones out:
+  loss_spread_over_ranks, params_spread_over_ranks
+                -- N > 1: how far the ranks' global losses and parameter replicas disagree after the timed steps
+  n1_same_workload, scaling_vs_n1_same_workload
+                -- N > 1: the single-GPU value of the same per-GPU workload measured on rank 0 alone, and the ratio
   roofline      -- dominant kernel (the MER GEMM: mer_gemm_pps_kernel / mer_gemm_pp_kernel / mer_gemm_kernel<128,128,2,2>, bf16 MFMA): algorithmic FLOPs of every launch in
                    the timed region / its duration measured with HIP events on the launch stream
+  roofline_hbm  -- the same event-pair figure for the LayerNorm backward (ln_bwd8_kernel), against the HBM peak
+  head_section_ms -- the loss head alone (forward + loss + backward) at this rank's batch, the global batch and 1024
+                   (configs[2] on 8 GPUs): the work every rank repeats under data parallelism
   flavors       -- step time of BOTH 16-bit operand flavors (bf16 = headline, f16) on the same workload
   parity        -- per flavor, HIP vs the CPU oracle on the full-size batch of this workload (regularisers off): per-modality
                    features, bn_features / 8, the three losses -- so the record shows which flavor meets 1e-3 and its speed
@@ -79,9 +87,14 @@ def parse():
     ap.add_argument('--no-parity', action='store_true', help='skip the in-run full-size parity check against the CPU oracle')
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='write the losses and the updated trainable tensors of the last timed step to DIR/*.npy (see the module docstring)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps, also run every other measurement and check (see the module docstring); '
+                         'without it the run times the headline alone')
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:                  # a plain run: every leg that only --full adds is left out
+        args.no_cpu_baseline = args.no_retrieval = args.no_kernel_events = args.no_second_flavor = args.no_parity = True
     return args
 
 
@@ -601,14 +614,17 @@ def main():
         ms_with_events = (time.perf_counter() - te) / args.steps * 1e3
         prof = ops.gemm_profile_end(); ln_prof = ops.ln_profile_end()
     loss = float(L['total_loss'].detach())
-    loss_spread = params_spread = 0.0
-    if world > 1:                                  # every rank evaluates the same global loss (parallel.py): check it
-        lt = torch.tensor([loss, -loss], device=dev, dtype=torch.float64)
-        dist.all_reduce(lt, op=dist.ReduceOp.MAX)
-        loss_spread = abs(float(lt[0]) + float(lt[1]))   # max over ranks - min over ranks; reported, and loud when it is not rounding
-        if loss_spread > 1e-5 * max(1.0, abs(loss)):
-            log(f'WARNING: ranks disagree on the global loss by {loss_spread:.3e} (loss {loss:.6f})')
-        params_spread = dp.params_in_sync()              # replicas must stay bit-identical (head gradients are averaged too)
+    spreads = {}
+    if args.full:
+        loss_spread = params_spread = 0.0
+        if world > 1:                              # every rank evaluates the same global loss (parallel.py): check it
+            lt = torch.tensor([loss, -loss], device=dev, dtype=torch.float64)
+            dist.all_reduce(lt, op=dist.ReduceOp.MAX)
+            loss_spread = abs(float(lt[0]) + float(lt[1]))   # max over ranks - min over ranks; reported, and loud when it is not rounding
+            if loss_spread > 1e-5 * max(1.0, abs(loss)):
+                log(f'WARNING: ranks disagree on the global loss by {loss_spread:.3e} (loss {loss:.6f})')
+            params_spread = dp.params_in_sync()              # replicas must stay bit-identical (head gradients are averaged too)
+        spreads = {'loss_spread_over_ranks': loss_spread, 'params_spread_over_ranks': params_spread}
     value = world * B * args.steps / elapsed
     res = {
         'metric': 'multimodal instances/sec (PxK, 5-modality) at 1/2/4/8 GPU; eval queries/sec',
@@ -627,7 +643,7 @@ def main():
                    'parallelism': f'dp{world}'},
         'model_tflops_per_gpu': value / world * FLOP_PER_INSTANCE / 1e12,
         'mfma_frac_whole_step': value / world * FLOP_PER_INSTANCE / 1e12 / PEAK_BF16_TFLOPS,
-        'final_loss': loss, 'loss_spread_over_ranks': loss_spread, 'params_spread_over_ranks': params_spread,
+        'final_loss': loss, **spreads,
         'rccl_world': (world if (world > 1 and args.backend == 'nccl') else 0), 'backend': args.backend if world > 1 else None,
         'hip_graph': graphed,
     }
@@ -673,7 +689,8 @@ def main():
                                'note': 'event pairs around the launches inside the running step (the side stream shares the chip); since r04 the kernel '
                                        'moves 12 B per element (residual-stream gradient in IEEE half) instead of 16: 81-84 us per launch alone against 106 '
                                        'for the r03 form, i.e. a shorter kernel at a lower fraction of the HBM peak'}
-    res['flavors'] = {head: {'ms_per_step': elapsed / args.steps * 1e3, 'value': value, 'role': 'headline'}}
+    if args.full:
+        res['flavors'] = {head: {'ms_per_step': elapsed / args.steps * 1e3, 'value': value, 'role': 'headline'}}
     if rank == 0 and not args.no_kernel_events:             # (profiled runs pass --no-kernel-events: their kernel trace is of the step only)
         # the head section alone at this rank's batch and at the global batches of configs 3 / 5: under DP every rank runs it on the GLOBAL
         # batch, so (head at world * B) - (head at B) is per-rank work that data parallelism adds
@@ -683,7 +700,7 @@ def main():
                                       'what': 'head_section + compute_loss + backward to the encoder features, wall time per call, this GPU alone'}
         except Exception as e:                              # (attribution only: never fail the bench line on it)
             res['head_section_ms'] = {'error': repr(e)}
-    if world > 1:
+    if world > 1 and args.full:
         # single-GPU value of the SAME per-GPU workload, rank 0 alone (the others wait): what the N-GPU value is to be divided by
         dist.barrier()
         if rank == 0:

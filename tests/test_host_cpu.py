@@ -175,3 +175,23 @@ def test_cmc_from_topk_equals_bruteforce_definition():
             hit[i] = bool((g_pids[idx] == q_pids[i]).any())
         want = float(hit[has_pos].float().mean())
         assert abs(got[f'R@{kk}'] - want) < 1e-7, (kk, got, want)
+
+
+def test_bench_plain_run_leaves_every_other_leg_to_full(monkeypatch):
+    """bench.py without --full times the headline alone: every leg a --no-* option can leave out is off.  --full turns them all
+    on, and the --no-* options still leave single legs out of it."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location('bench_under_test', os.path.join(os.path.dirname(os.path.dirname(__file__)), 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    legs = ('no_cpu_baseline', 'no_retrieval', 'no_kernel_events', 'no_second_flavor', 'no_parity')
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '2', '--warmup', '1'])
+    a = bench.parse()
+    assert not a.full and all(getattr(a, n) for n in legs)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '2', '--full'])
+    a = bench.parse()
+    assert a.full and not any(getattr(a, n) for n in legs)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--steps', '2', '--full', '--no-parity'])
+    a = bench.parse()
+    assert a.no_parity and not a.no_retrieval

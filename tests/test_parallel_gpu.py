@@ -145,12 +145,12 @@ def test_two_ranks_equal_one_process_on_the_global_batch(tmp_path):
 def test_bench_gpus2_spawn_and_relay_gloo():
     """``bench.py --gpus 2`` with no WORLD_SIZE: the CPU-only parent spawns the ranks, watches all of them and relays rank 0's line
     (gloo rehearsal: both ranks on the one GPU of the test box; RCCL needs one GPU per rank).  Checks the keys the driver's scaling
-    run relies on."""
+    run relies on and, with --full, the rank checks and the single-GPU leg."""
     import json
     import subprocess
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--P', '2', '--K', '2', '--steps', '2',
            '--warmup', '1', '--no-cpu-baseline', '--no-retrieval', '--no-parity', '--no-second-flavor', '--no-kernel-events',
-           '--spawn-timeout', '900']
+           '--spawn-timeout', '900', '--full']
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1000, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
