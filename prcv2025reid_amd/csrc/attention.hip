@@ -9,7 +9,8 @@
 // trip.  V is staged row-major like K and consumed through the hardware transpose read
 // ds_read_b64_tr_b16.  The backward pass is two kernels of the same shape (dK/dV with keys on the
 // lane, dQ with queries on the lane), each needing only products that sum over the accumulator's
-// row index; P is recomputed from the saved log-sum-exp.
+// row index; P is recomputed from the saved log-sum-exp.  Unmasked, non-causal calls take the one-pass backward instead
+// (attn_bwd_fused_kernel), which forms dS once, for dK, and keeps it in LDS for dQ.
 //
 // r02 experiments, measured and not kept (profiles/r02_attn_*.log, r02_attn_persistent_experiment.patch): starting the second
 // workgroup of every CU late, waiting for K only before the first sweep (V lands under it), and PERSISTENT workgroups walking the
@@ -480,17 +481,29 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_dq_kernel(const AttnParams p
     }
 }
 
-// ------------------------------------------------------------------------------------------ backward: one pass (r04)
-// dQ, dK and dV of one (sequence, head) from ONE staging of Q, K, V and dO (the two kernels above each stage half of them and
-// each read dO / Q / K / V again: 8 LDS-DMA head images and ~930 MB of HBM traffic per ViT layer where 4 images and ~620 MB do).
-// One workgroup holds the four swizzled images (4 x NT x 4 KiB = 112 KiB at S = 197) and runs, without any barrier between them,
-//   phase 1 -- wave w owns KEY tile w (keys on the lane):  S = Q K^T, dP = dO V^T per query tile -> dV^T += dO^T P, dK^T += Q^T dS
-//   phase 2 -- wave w owns QUERY tile w (queries on the lane):  S^T = K Q^T, dP^T = V dO^T per key tile -> dQ^T += K^T dS^T
-// i.e. the products of the two kernels above, fed from LDS.  delta = rowsum(dO . O) is formed first by the query-owning waves (O is
-// read once, from global memory) and shared through LDS with the saved log-sum-exp.
+// ------------------------------------------------------------------------------------------ backward: one pass
+// dQ, dK and dV of one (sequence, head) from ONE staging of Q and dO (the two kernels above each stage half of the four operands and
+// read the rest again: 8 LDS-DMA head images and ~930 MB of HBM traffic per ViT layer where ~620 MB do).  One workgroup, 7 waves:
+//   phase 1 -- wave w owns KEY tile w (keys on the lane; its K and V rows straight from global memory into registers):
+//              S = Q K^T, dP = dO V^T per query tile -> dV^T += dO^T P, dK^T += Q^T dS, and every 16-query half of the packed dS is
+//              also parked in an LDS image of the whole [keys][queries] dS
+//   phase 2 -- wave w owns QUERY tile w (queries on the lane):  dQ^T += K^T dS^T per key tile, both operands through the transposed
+//              read: no scores, no exponentials (the r04 form recomputed S^T and dP^T and their exponentials here: 8 of every 12 MFMAs
+//              and half the exp2 of the kernel, for the dS bits phase 1 had already formed)
+// delta = rowsum(dO . O) is formed first by the query-owning waves (O is read once, from global memory) and shared through LDS with
+// the saved log-sum-exp.  LDS at NT = 7: Q and dO images 56 KiB (K's image in phase 2 overwrites Q's), dS 98 KiB, rowc 1.75 KiB
+// = 159 488 of the CU's 163 840 bytes.  dS is the same bf16 / f16 value phase 1 feeds into dK, and phase 2 sums it over the key tiles
+// in a fixed order: deterministic, no atomics.
 // In-wave pipelining: the S / dP MFMAs of tile t + 1 are issued BEFORE the exponentials of tile t (two accumulator sets), so that
 // a wave's matrix work does not wait behind its own exp -> pack -> MFMA chain (r03: with one workgroup per CU that chain is exposed).
 // No key mask / causal form: the text tower's backward (rare: freeze_text_backbone=False) keeps the two-kernel path.
+//
+// dS image: key row r is 64 NT bytes (NT * 32 queries).  A 16-query group of a row is two 16-byte chunks, chunk h holding queries
+// 4h..4h+3 and 8+4h..8+4h+3 -- exactly the 8 values of lane half h of the accumulator-as-operand tile, so phase 1 writes one
+// ds_write_b128 per lane and 16-query half.  Chunk c of row r sits at chunk c ^ ((r >> 1) & 3): the 8 rows of an 8-lane write group
+// then cover the 128-byte bank window (448-byte rows alone put them on 2 chunk positions), and the swizzle stays inside a query
+// tile's 64 bytes, so the transposed reads of phase 2 (4 rows x one query tile per 32-lane half; 448 = 256 + 192) stay conflict-free.
+__device__ __forceinline__ int ds_chunk(int r, int c) { return c ^ ((r >> 1) & 3); }
 #ifdef REID_ATTN_TRACE
 // experiment builds (tools/exp_attn_bwd_trace.py): s_memrealtime stamps of wave 0 / lane 0 of every workgroup at the phase boundaries
 __device__ unsigned long long* g_attn_bwd_trace = nullptr;
@@ -504,11 +517,12 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const AttnParam
     ATTN_BWD_STAMP(0);
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int IMG = NT * 32 * 128;
+    constexpr int DS_ROW = NT * 64;                  // bytes per key row of the dS image
     char* Qs = smem;
     char* Gs = smem + IMG;                           // dO
-    char* Ks = smem + 2 * IMG;
-    char* Vs = smem + 3 * IMG;
-    float* rowc = (float*)(smem + 4 * IMG);          // [2][NT*32]: -lse * log2(e), -delta / 8
+    char* Ks = smem;                                 // phase 2: K, written over Q's image
+    char* Ds = smem + 2 * IMG;                       // dS [NT*32 keys][NT*32 queries]
+    float* rowc = (float*)(Ds + NT * 32 * DS_ROW);   // [2][NT*32]: -lse * log2(e), -delta / 8
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int seq = blockIdx.x / p.heads, head = blockIdx.x % p.heads;
@@ -518,16 +532,22 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const AttnParam
     const bf16_t* ob = p.out + (size_t)seq * p.S * p.ldo + head * 64;
     const int nq = p.q_tiles > 0 ? (p.q_tiles < NT ? p.q_tiles : NT) : NT;     // query tiles that take part (class-row pruning)
     const int q_rows = nq * 32;
-    // all four head images in flight at once (16 LDS-DMA instructions per wave)
-    stage_head<NT>(qb, p.ld, p.S, Qs, wave, lane, q_rows);
-    stage_head<NT>(gb, p.ldo, p.S, Gs, wave, lane, q_rows);
-    stage_head<NT>(qb + d, p.ld, p.S, Ks, wave, lane);
-    stage_head<NT>(qb + 2 * d, p.ld, p.S, Vs, wave, lane);
+    // The dispatch picks NT = ceil(S / 32): every wave's tile holds at least one real row, and every wave reaches both barriers
+    // between the phases.
     const int t0 = wave * 32;                        // first row of this wave's tile (key tile in phase 1, query tile in phase 2)
     const int ti = t0 + (lane & 31);
     const int trow = ti < p.S ? ti : p.S - 1;
-    const bool own_q = wave < nq && t0 < p.S;        // wave-uniform: this wave's QUERY tile takes part
-    // delta of this wave's query rows: O fragments straight from global memory (their latency hides behind the image staging)
+    const bool own_q = wave < nq;                    // wave-uniform: this wave's QUERY tile takes part
+    // this wave's K and V rows first (their latency hides behind the image DMA), then the Q and dO images (8 LDS-DMA per wave)
+    bf16x8 kf[4], vf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        kf[ks] = gfrag(qb + d, p.ld, trow, 2 * ks, lane);
+        vf[ks] = gfrag(qb + 2 * d, p.ld, trow, 2 * ks, lane);
+    }
+    stage_head<NT>(qb, p.ld, p.S, Qs, wave, lane, q_rows);
+    stage_head<NT>(gb, p.ldo, p.S, Gs, wave, lane, q_rows);
+    // delta of this wave's query rows: O fragments straight from global memory
     bf16x8 of[4];
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) of[ks] = gfrag(ob, p.ldo, trow, 2 * ks, lane);
@@ -556,21 +576,22 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const AttnParam
     }
     __syncthreads();
     ATTN_BWD_STAMP(2);
-    if (t0 >= p.S) return;                           // (wave-uniform; no barrier follows)
     const float c = 0.125f * LOG2E;
     const int h4 = 4 * (lane >> 5);
     const bool tile_ok = ti < p.S;
+    bf16_t* trow_out = p.dqkv + ((size_t)seq * p.S + trow) * p.lddqkv + head * 64;
 
     // ------------------------------------------------------------------ phase 1: this wave's key tile
     {
-        bf16x8 kf[4], vf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { kf[ks] = row_frag_o(Ks, t0, ks, fo); vf[ks] = row_frag_o(Vs, t0, ks, fo); }
         f32x16 dkt[2], dvt[2];
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int e = 0; e < 16; ++e) { dkt[dt][e] = 0.f; dvt[dt][e] = 0.f; }
+        // this lane's dS row (key ti), chunk h of each 16-query half; the query tile adds 64 bytes
+        const int hsw = (lane >> 5) ^ (((lane & 31) >> 1) & 3);
+        char* const ds_w0 = Ds + ti * DS_ROW + 16 * hsw;
+        char* const ds_w1 = Ds + ti * DS_ROW + 16 * (hsw ^ 2);
         const int nqt = nq < (p.S + 31) / 32 ? nq : (p.S + 31) / 32;      // query tiles with at least one real row
         auto scores = [&](int qt, f32x16& s, f32x16& dp) {
 #pragma unroll
@@ -607,76 +628,62 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const AttnParam
                     dvt[dt] = mfma32(col_frag_o(Gs, qt * 32 + 16 * s2, dt, fo), pf, dvt[dt]);
                     dkt[dt] = mfma32(col_frag_o(Qs, qt * 32 + 16 * s2, dt, fo), df, dkt[dt]);
                 }
+                // padded keys (rows of the last key tile >= S) park 0: phase 2 sums over every key row of the image
+                *(bf16x8*)((s2 ? ds_w1 : ds_w0) + qt * 64) = tile_ok ? df : bf16x8{};
             }
             s = s_n; dp = dp_n;
         }
         ATTN_BWD_STAMP(3);
-        bf16_t* drow = p.dqkv + ((size_t)seq * p.S + trow) * p.lddqkv + head * 64;
+        // (issued here, not after phase 2 with dQ: measured 204-207 vs 223-225 us alone, 30.0 vs 30.2 ms per step)
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt) {
-            store_tile_row16(drow + d + dt * 32, tile_ok, dkt[dt], 1.0f, lane);
-            store_tile_row16(drow + 2 * d + dt * 32, tile_ok, dvt[dt], 1.0f, lane);
+            store_tile_row16(trow_out + d + dt * 32, tile_ok, dkt[dt], 1.0f, lane);
+            store_tile_row16(trow_out + 2 * d + dt * 32, tile_ok, dvt[dt], 1.0f, lane);
         }
     }
 
-    // ------------------------------------------------------------------ phase 2: this wave's query tile
+    // ------------------------------------------------------------------ between the phases: K over Q's image
+    __syncthreads();                                 // every read of Q and dO is done, the dS image is complete
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) *(bf16x8*)(Ks + t0 * 128 + fo.row[ks]) = kf[ks];   // the layout stage_head gives
+    __syncthreads();
     ATTN_BWD_STAMP(4);
-    bf16_t* qrow_out = p.dqkv + ((size_t)seq * p.S + trow) * p.lddqkv + head * 64;
+
+    // ------------------------------------------------------------------ phase 2: this wave's query tile
     if (!own_q) {                                    // query tile left out by q_tiles: its dQ rows are exactly zero
         if (tile_ok) {
 #pragma unroll
             for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) *(uint2*)(qrow_out + dt * 32 + 8 * g + 4 * (lane >> 5)) = uint2{0u, 0u};
+                for (int g = 0; g < 4; ++g) *(uint2*)(trow_out + dt * 32 + 8 * g + 4 * (lane >> 5)) = uint2{0u, 0u};
         }
         return;
     }
     {
-        bf16x8 qf[4], gf[4];
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) { qf[ks] = row_frag_o(Qs, t0, ks, fo); gf[ks] = row_frag_o(Gs, t0, ks, fo); }
-        const float nl = rowc[ti], nd = rowc[NT * 32 + ti];
+        // B operand dS^T (16 keys x 32 queries) in the accumulator-as-operand key order, through the transposed read: lane 4q+pp of a
+        // 16-lane group addresses key row krow0 + 4h + q (+ 8 for elements 4..7), queries 4pp..4pp+3 of its 16-query half
+        const int h = lane >> 5, half16 = (lane >> 4) & 1, q = (lane & 15) >> 2, pp = lane & 3;
+        const int r = 4 * h + q;
+        const int ds_r = r * DS_ROW + 16 * ds_chunk(r, 4 * wave + 2 * half16 + (pp & 1)) + 8 * (pp >> 1);
         f32x16 dqt[2];
 #pragma unroll
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int e = 0; e < 16; ++e) dqt[dt][e] = 0.f;
-        const int nkt = (p.S + 31) / 32;
-        auto scores_t = [&](int kt, f32x16& s, f32x16& dp) {
 #pragma unroll
-            for (int e = 0; e < 16; ++e) { s[e] = 0.f; dp[e] = 0.f; }
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                s = mfma32(row_frag_o(Ks, kt * 32, ks, fo), qf[ks], s);
-                dp = mfma32(row_frag_o(Vs, kt * 32, ks, fo), gf[ks], dp);
-            }
-        };
-        f32x16 s, dp, s_n, dp_n;
-        scores_t(0, s, dp);
-        for (int kt = 0; kt < nkt; ++kt) {
-            if (kt + 1 < nkt) scores_t(kt + 1, s_n, dp_n);
-            const bool edge = (kt + 1) * 32 > p.S;    // only the last key tile holds padded keys
+        for (int kt = 0; kt < NT; ++kt)
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                bf16x8 df;
+                const int krow0 = kt * 32 + 16 * s2;
+                const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(Ds + krow0 * DS_ROW + ds_r));
+                const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(Ds + (krow0 + 8) * DS_ROW + ds_r));
+                const bf16x8 df = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int e = 8 * s2 + j;
-                    float pe = fast_exp2(fmaf(s[e], c, nl));
-                    if (edge) {
-                        const int key = kt * 32 + (e & 3) + 8 * (e >> 2) + h4;
-                        pe = key < p.S ? pe : 0.f;
-                    }
-                    df[j] = (short)f32_to_bf16(pe * fmaf(dp[e], 0.125f, nd));
-                }
-#pragma unroll
-                for (int dt = 0; dt < 2; ++dt) dqt[dt] = mfma32(col_frag_o(Ks, kt * 32 + 16 * s2, dt, fo), df, dqt[dt]);
+                for (int dt = 0; dt < 2; ++dt) dqt[dt] = mfma32(col_frag_o(Ks, krow0, dt, fo), df, dqt[dt]);
             }
-            s = s_n; dp = dp_n;
-        }
         ATTN_BWD_STAMP(5);
 #pragma unroll
-        for (int dt = 0; dt < 2; ++dt) store_tile_row16(qrow_out + dt * 32, tile_ok, dqt[dt], 1.0f, lane);
+        for (int dt = 0; dt < 2; ++dt) store_tile_row16(trow_out + dt * 32, tile_ok, dqt[dt], 1.0f, lane);
         ATTN_BWD_STAMP(6);
     }
 }
@@ -701,9 +708,10 @@ int launch_bwd(const AttnParams& p, hipStream_t s) {
     // 256 images x 12 heads, profiles/r04_attn_bwd.log), two kernels / one pass / one pass persistent: 292 / 257 / 257 us alone; inside the
     // training step 31.93 / 31.42 / 31.54 ms per step on one box -- the persistent form (at 13e2fd7) hides the image staging (top-of-item
     // wait 1.0 us instead of 5.5 us) but pays it back in barriers and DMA issue (3.1 us between the phases), and like every persistent
-    // kernel it keeps its CUs from the side stream.
+    // kernel it keeps its CUs from the side stream.  r05 (profiles/r05_attn_bwd.log): dS parked in LDS instead of recomputed for dQ,
+    // 252-256 -> 204-207 us alone, 30.56 -> 30.03 ms per step (4 alternating rounds on one box).
     if (!p.key_mask && !p.causal && reid_knob(KNOB_ATTN_BWD) != 1) {
-        constexpr int LDSF = 4 * NT * 32 * 128 + 2 * NT * 32 * 4;
+        constexpr int LDSF = 2 * NT * 32 * 128 + (NT * 32) * (NT * 64) + 2 * NT * 32 * 4;   // Q, dO; dS; rowc
         REID_MAX_LDS((attn_bwd_fused_kernel<NT>), LDSF);
         hipLaunchKernelGGL(attn_bwd_fused_kernel<NT>, dim3(p.n_seq * p.heads), dim3(NT * 64), LDSF, s, p);
         REID_CHECK_LAUNCH("reid_attn_bwd(fused)");

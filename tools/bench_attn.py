@@ -18,11 +18,11 @@ def timeit(fn, reps=20):
     for _ in range(reps): fn()
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps * 1e3
-variants = [v.split(':') for v in os.environ.get('VARIANTS', 'default:;two_kernel:ATTN_BWD=1').split(';')]
+variants = [v.split(':') for v in os.environ.get('VARIANTS', 'default:ATTN_BWD=-1;two_kernel:ATTN_BWD=1').split(';')]
 res = {}
 for rnd in range(3):
     for vn, spec in variants:
-        for kv in spec.split(','):
+        for kv in filter(None, spec.split(',')):
             k, v = kv.split('='); _lib.check(_lib.lib().reid_set_knob(k.encode(), int(v)))
         f = timeit(lambda: ops.attn_fwd(qkv, o, lse, n_seq, S, heads))
         b = timeit(lambda: ops.attn_bwd(qkv, o, do, lse, dqkv, delta, n_seq, S, heads))

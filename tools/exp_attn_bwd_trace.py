@@ -24,7 +24,8 @@ torch.cuda.synchronize()
 lib.reid_debug_attn_bwd_trace(ctypes.c_void_p(0))
 t = trace.cpu().numpy().astype(np.int64)
 ts = (t[:, :7] - t[:, 0].min()) / 100.0
-names = ['stage (start -> 4 images landed)', 'delta + barrier', 'phase 1 (7 query tiles)', 'dK/dV stores issued', 'phase 2 (7 key tiles)', 'dQ stores issued']
+names = ['stage (start -> Q, dO images landed)', 'delta + barrier', 'phase 1 (7 query tiles, dS parked)', 'dK/dV stores, K over Q, 2 barriers',
+         'phase 2 (dQ = dS K, 7 key tiles)', 'dQ stores issued']
 dd = np.diff(ts, axis=1)
 print('kernel span %.1f us, %d workgroups' % (ts[:, 6].max(), nwg))
 for i, n in enumerate(names):
