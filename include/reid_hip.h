@@ -86,8 +86,9 @@ int reid_set_knob(const char* name, int value);
  *   (c % K_mask_period)/mask_r == img_mod[m / rows_per_img], the LoRA routing of
  *   mer_lora.py:96 for a batch that mixes modalities); * alpha; store as c_dtype at row
  *   (m / c_group) * c_group_stride + m % c_group + c_row_off when c_group > 0 (patch rows ->
- *   token rows behind the CLS slot, models/clip_backbone.py:269-270), else row m.
- * Requirements: K % 64 == 0 or K % 32 == 0, K2 % 32 == 0, N % 4 == 0, 16-byte aligned rows.
+ *   token rows behind the CLS slot, models/clip_backbone.py:269-270), else row m.  alpha == 0 is taken as 1 (a zero-filled
+ *   argument struct multiplies by nothing).
+ * Requirements: K % 64 == 0 (other K are refused), K2 % 32 == 0, N % 4 == 0, 16-byte aligned rows.
  * ------------------------------------------------------------------------------------------ */
 #define REID_GEMM_MAX_GROUPS 8
 typedef struct {

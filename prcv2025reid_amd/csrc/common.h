@@ -140,8 +140,10 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // Exact-erf GELU (nn.GELU() default, mer_lora.py:257) without libm's erff (~100 instructions with branches: it made
-// the fc1 epilogue cost as much as the fc1 GEMM).  Normal CDF by Abramowitz-Stegun 7.1.26 on erfc (|abs error| <= 1.5e-7,
-// and RELATIVE accuracy kept in the negative tail because erfc is evaluated directly, no 1 - x cancellation):
+// the fc1 epilogue cost as much as the fc1 GEMM).  Normal CDF by Abramowitz-Stegun 7.1.26 on erfc: |erf error| <= 1.5e-7, so the
+// ABSOLUTE error of the CDF stays below 7.5e-8 and GELU's x * CDF is off by at most |x| * 7.5e-8 (2.1e-7 over the range where
+// it is not exactly 0 or x).  The formula's RELATIVE error in the negative tail grows: 0.5 erfc is off by 4.7e-4 at x = -4, 3.6e-3
+// at x = -6 and 2.0e-2 at x = -10 (the formula itself, evaluated in fp64) -- harmless next to the tail's tiny absolute values:
 //   erfc(z) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-z^2),  t = 1 / (1 + p z),  z = |x| / sqrt(2)
 // exp(-z^2) = exp(-x^2/2) is also the Gaussian density needed by the derivative.
 __device__ __forceinline__ void gauss_cdf_pdf(float x, float& cdf, float& pdf_unnorm) {

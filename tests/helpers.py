@@ -107,3 +107,65 @@ def reference_trainable_groups(tag='tiny_frozen'):
         if keys:
             out.append(dict(name=g['name'], lr=g['lr'], params=keys))
     return out
+
+
+# ---- exact-operand tests (test_gemm_exact_gpu.py) ------------------------------------------------------------------------------
+# Operands that are small integers times a power of two make every product and every partial sum of a GEMM a multiple of one
+# quantum; while the largest possible partial sum stays below 2^24 quanta, fp32 represents all of them exactly, so a kernel's
+# accumulator equals the fp64 reference whatever the order of the sum (tiling, split K, atomics).
+FMT16 = {'bf16': (8, -126), 'f16': (11, -14), 'f32': (24, -126)}   # significant bits, exponent of the smallest normal
+SENTINEL16 = {'bf16': 0x7F9D, 'f16': 0x7DAD}                         # signalling-NaN patterns: no arithmetic produces them
+SENTINEL32 = 0x7FBADBAD
+
+
+def exact_ints(shape, lo, hi, exp, gen, device='cuda'):
+    """float64 tensor of integers in [lo, hi] times 2**exp."""
+    return torch.randint(lo, hi + 1, tuple(shape), generator=gen, device=device, dtype=torch.int64).double() * 2.0 ** exp
+
+
+def assert_bit_budget(abs_sum, quantum):
+    """`abs_sum` bounds every partial sum (the sum of the absolute values of the terms), and every term is a multiple of `quantum`:
+    then every partial sum is exact in fp32 iff it needs at most 24 significant bits."""
+    worst = float(abs_sum.max()) / quantum
+    assert worst < 2.0 ** 24, f'operands exceed the fp32 bit budget: {worst:.4g} quanta >= 2^24'
+
+
+def quantum16(x, fmt):
+    """Spacing of the `fmt` grid (FMT16) at |x| (float64): 2^(e - p) for |x| in [2^(e-1), 2^e), the subnormal spacing below."""
+    p, emin = FMT16[fmt]
+    xc = x.cpu()                                      # (evaluated on the host: plain IEEE fp64 arithmetic, no device math library)
+    _, e = torch.frexp(xc)
+    e = torch.where(xc == 0, torch.full_like(e, emin + 1), e)
+    return torch.ldexp(torch.ones_like(xc), torch.clamp(e, min=emin + 1) - p).to(x.device)
+
+
+def round16(x, fmt):
+    """Round-to-nearest-even of float64 `x` into `fmt`, independent of any conversion routine; IEEE half saturates finite overflow
+    to +-65504 (what the kernels' MODE.FP16_OVFL conversions do)."""
+    xc = x.cpu()
+    q = quantum16(xc, fmt)
+    y = torch.round(xc / q) * q                      # torch.round: ties to even
+    if fmt == 'f16':
+        y = torch.where(y.abs() > 65504.0, torch.copysign(torch.full_like(y, 65504.0), y), y)
+    return y.to(x.device)
+
+
+def count_ties16(x, fmt):
+    """Elements of `x` that lie exactly half-way between two neighbours of the `fmt` grid (where only ties-to-even decides)."""
+    xc = x.cpu()
+    s = xc / quantum16(xc, fmt)
+    return int(((s - torch.floor(s)) == 0.5).sum())
+
+
+def sentinel_buffer(rows, cols, dtype, fmt=None, device='cuda'):
+    """[rows, cols] buffer whose every element holds the sentinel NaN pattern of its type."""
+    if dtype == torch.float32:
+        return torch.full((rows, cols), SENTINEL32, dtype=torch.int32, device=device).view(torch.float32)
+    return torch.full((rows, cols), SENTINEL16[fmt], dtype=torch.int16, device=device).view(dtype)
+
+
+def is_sentinel(t, fmt=None):
+    """Bool tensor: the element still holds the sentinel of sentinel_buffer."""
+    if t.dtype == torch.float32:
+        return t.view(torch.int32) == SENTINEL32
+    return t.view(torch.int16) == SENTINEL16[fmt]
