@@ -34,19 +34,6 @@ ABI_VERSION = 201                 # REID_ABI_VERSION of include/reid_hip.h: a li
 BF16, F32, F16 = 0, 1, 2          # reid_dtype: BF16 = the flavor's 16-bit format, F16 = IEEE half whatever the flavor
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU, ACT_DGELU, ACT_DQUICK_GELU, ACT_DRELU, ACT_MUL_AUX, ACT_GELU_DSAVE = range(9)
 
-EXPORTS = [
-    'reid_last_error', 'reid_version', 'reid_flavor', 'reid_check_device', 'reid_set_knob', 'reid_mer_gemm', 'reid_gemm_tn',
-    'reid_layernorm_fwd', 'reid_layernorm_bwd', 'reid_patch_im2col', 'reid_cls_rows',
-    'reid_attn_fwd', 'reid_attn_bwd', 'reid_cast_f32_bf16', 'reid_cast_bf16_f32', 'reid_gather_rows_f32',
-    'reid_bnneck_stats', 'reid_bnneck_fwd', 'reid_bnneck_bwd_p1', 'reid_bnneck_bwd_p2',
-    'reid_ce_ls_fwd', 'reid_ce_ls_bwd', 'reid_sdm_fwd', 'reid_sdm_bwd', 'reid_sdm_ws_floats',
-    'reid_topk_ws_bytes', 'reid_cosine_topk', 'reid_cosine_topk_exact', 'reid_cosine_topk_exact_slots', 'reid_l2norm_rows', 'reid_sgemm', 'reid_pack_bf16_table',
-    'reid_eltwise_f32', 'reid_small_attn_fwd', 'reid_small_attn_bwd', 'reid_masked_mean',
-    'reid_opt_entry_bytes', 'reid_opt_ws_floats', 'reid_opt_state_floats', 'reid_opt_sumsq', 'reid_opt_clip', 'reid_opt_adamw',
-    'reid_rank_metrics', 'reid_scatter_add_rows_f32', 'reid_embed_tokens',
-    'reid_topk_stream_ok', 'reid_topk_scan_ok', 'reid_topk_stream_ws_bytes', 'reid_cosine_topk_stream', 'reid_merge_lora_table', 'reid_add_layernorm_fwd', 'reid_lora_bwd_fused', 'reid_lora_da_fused',
-]
-
 
 class GemmArgs(C.Structure):
     _fields_ = [('A', C.c_void_p), ('B', C.c_void_p), ('A2', C.c_void_p), ('B2', C.c_void_p),
@@ -63,6 +50,68 @@ class GemmArgs(C.Structure):
                 ('alpha', C.c_float), ('row_scale', C.c_void_p),
                 ('n_row_groups', C.c_int32), ('row_group_end', C.c_int32 * 8), ('row_group_b', C.c_int32 * 8),
                 ('b_group_stride', C.c_int64)]
+
+
+# Every entry point of include/reid_hip.h in header order, name -> (restype, argtypes): ctypes then refuses a call with too few
+# arguments and converts each plain Python value (int or None for a pointer, int for an integer, float for a float) itself.
+_P, _I, _I64, _F, _S = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_char_p   # T*; int, int32_t, enum; int64_t; float; const char*
+_GEMM = C.POINTER(GemmArgs)
+SIGNATURES = {
+    'reid_last_error': (_S, []),
+    'reid_version': (_I, []),
+    'reid_flavor': (_I, []),
+    'reid_check_device': (_I, [_I]),
+    'reid_set_knob': (_I, [_S, _I]),
+    'reid_mer_gemm': (_I, [_GEMM, _P]),
+    'reid_gemm_tn': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
+    'reid_layernorm_fwd': (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _P]),
+    'reid_add_layernorm_fwd': (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _F, _P]),
+    'reid_layernorm_bwd': (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _I, _I, _P, _I, _P, _P]),
+    'reid_patch_im2col': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    'reid_cls_rows': (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    'reid_attn_fwd': (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    'reid_attn_bwd': (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    'reid_cast_f32_bf16': (_I, [_P, _P, _I64, _P]),
+    'reid_cast_bf16_f32': (_I, [_P, _P, _I64, _P]),
+    'reid_pack_bf16_table': (_I, [_P, _P, _P, _I, _P]),
+    'reid_lora_bwd_fused': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F, _P, _I, _P]),
+    'reid_lora_da_fused': (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'reid_merge_lora_table': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _F, _P]),
+    'reid_gather_rows_f32': (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
+    'reid_embed_tokens': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    'reid_scatter_add_rows_f32': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    'reid_bnneck_stats': (_I, [_P, _I, _I, _I, _P, _P, _P]),
+    'reid_bnneck_fwd': (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _F, _I, _P, _P, _I, _P, _P, _P, _I, _I, _F, _F, _F, _P]),
+    'reid_bnneck_bwd_p1': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
+    'reid_bnneck_bwd_p2': (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _F, _I, _P, _I, _I, _I, _P]),
+    'reid_ce_ls_fwd': (_I, [_P, _I, _P, _P, _I, _I, _F, _P, _P, _P]),
+    'reid_ce_ls_bwd': (_I, [_P, _I, _P, _P, _I, _I, _F, _P, _P, _I, _P]),
+    'reid_sdm_fwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    'reid_sdm_bwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P, _I, _P]),
+    'reid_sdm_ws_floats': (_I64, [_I, _I, _I, _I]),
+    'reid_topk_ws_bytes': (_I64, [_I, _I, _I]),
+    'reid_topk_scan_ok': (_I, [_I, _I, _I, _I]),
+    'reid_cosine_topk': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'reid_cosine_topk_exact': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'reid_cosine_topk_exact_slots': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P]),
+    'reid_topk_stream_ok': (_I, [_I, _I, _I, _I]),
+    'reid_topk_stream_ws_bytes': (_I64, [_I]),
+    'reid_cosine_topk_stream': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    'reid_sgemm': (_I, [_P, _P, _P, _I, _I, _I, _I64, _I64, _I64, _I64, _I, _F, _F, _P, _I, _P]),
+    'reid_eltwise_f32': (_I, [_I, _P, _P, _P, _I64, _F, _P]),
+    'reid_small_attn_fwd': (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _P]),
+    'reid_small_attn_bwd': (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'reid_masked_mean': (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
+    'reid_l2norm_rows': (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _F, _P]),
+    'reid_opt_entry_bytes': (_I, []),
+    'reid_opt_ws_floats': (_I, [_I]),
+    'reid_opt_state_floats': (_I, []),
+    'reid_opt_sumsq': (_I, [_P, _I, _P, _P]),
+    'reid_opt_clip': (_I, [_P, _I, _P, _I, _F, _I, _P]),
+    'reid_opt_adamw': (_I, [_P, _I, _P, _F, _F, _F, _I, _I, _P, _P]),
+    'reid_rank_metrics': (_I, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+}
+EXPORTS = list(SIGNATURES)
 
 
 _libs = {}
@@ -86,7 +135,7 @@ def lib():
 
 
 def _checked(h, path):
-    """Refuses a library whose exports, ABI version or flavor differ from what this module binds; sets the return types."""
+    """Refuses a library whose exports, ABI version or flavor differ from what this module binds; then binds SIGNATURES."""
     missing = [n for n in EXPORTS if not hasattr(h, n)]
     if missing:
         raise ReidHipError(f'{path} lacks symbols {missing}: stale build, run `python -m prcv2025reid_amd.build --force`')
@@ -94,12 +143,16 @@ def _checked(h, path):
     if v != ABI_VERSION:
         raise ReidHipError(f'{path} has ABI version {v}, this package binds {ABI_VERSION}: stale build, '
                            'run `python -m prcv2025reid_amd.build --force`')
-    h.reid_last_error.restype = C.c_char_p
-    h.reid_sdm_ws_floats.restype = C.c_int64
-    h.reid_topk_ws_bytes.restype = C.c_int64
-    h.reid_topk_stream_ws_bytes.restype = C.c_int64
     if h.reid_flavor() != (1 if _flavor == 'f16' else 0):
         raise ReidHipError(f'{path} was built for the other 16-bit flavor')
+    return bind(h)
+
+
+def bind(h):
+    """Sets restype and argtypes of every entry point of ``h`` (a loaded library) from SIGNATURES; returns ``h``."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        f = getattr(h, name)
+        f.restype, f.argtypes = restype, argtypes
     return h
 
 
@@ -108,12 +161,12 @@ def check(rc: int):
         raise ReidHipError(f'libreid_hip: rc={rc}: {lib().reid_last_error().decode()}')
 
 
-def stream_ptr() -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def stream_ptr() -> int:
+    return torch.cuda.current_stream().cuda_stream
 
 
 def ptr(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
+    return None if t is None else t.data_ptr()
 
 
 def dt(t, allow_half: bool = False) -> int:

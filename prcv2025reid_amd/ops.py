@@ -70,10 +70,12 @@ def gemm(A, B, C_out, *, A2=None, B2=None, K2=0, k2_group_n=0, bias=None, R=None
     a.alpha = alpha
     if row_scale is not None:
         a.row_scale = ptr(row_scale); a.rows_per_img = rows_per_img
-    if _gemm_profile is not None and a.N > 96:   # mer_gemm_kernel<128,128,2,2> (dominant); skinny LoRA projections use other tiles
+    profiled = _gemm_profile is not None and a.N > 96   # mer_gemm_kernel<128,128,2,2> (dominant); skinny LoRA projections use other tiles
+    if profiled:
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
         e0.record()
-        check(lib().reid_mer_gemm(C.byref(a), stream_ptr()))
+    check(lib().reid_mer_gemm(C.byref(a), stream_ptr()))
+    if profiled:
         e1.record()
         kk = a.K + a.K2
         flops = 2.0 * a.M * a.N * kk
@@ -87,8 +89,6 @@ def gemm(A, B, C_out, *, A2=None, B2=None, K2=0, k2_group_n=0, bias=None, R=None
         if C2 is not None:
             nbytes += a.M * a.N * (2 if a.c2_dtype == BF16 else 4)
         _gemm_profile.append((flops, nbytes, e0, e1))
-        return C_out
-    check(lib().reid_mer_gemm(C.byref(a), stream_ptr()))
     return C_out
 
 
@@ -96,7 +96,7 @@ def gemm_tn(X, Y, C_out, alpha=1.0, beta=0.0, M=None):
     """C_out[P,Q] = beta*C_out + alpha * X[:M].T @ Y[:M]  (fp32 out, bf16 in)."""
     M = X.shape[0] if M is None else M
     check(lib().reid_gemm_tn(ptr(X), ptr(Y), ptr(C_out), M, X.shape[1], Y.shape[1], X.stride(0), Y.stride(0),
-                             C_out.stride(0), C.c_float(alpha), C.c_float(beta), stream_ptr()))
+                             C_out.stride(0), alpha, beta, stream_ptr()))
     return C_out
 
 
@@ -105,14 +105,14 @@ def layernorm_fwd(x, gamma, beta, y_bf16=None, y_f32=None, mean=None, rstd=None,
     rows = (row_index.shape[0] if row_index is not None else x.shape[0]) if rows is None else rows
     y = y_bf16 if y_bf16 is not None else y_f32
     check(lib().reid_layernorm_fwd(ptr(x), x.stride(0), ptr(row_index), ptr(gamma), ptr(beta), ptr(y_bf16), ptr(y_f32),
-                                   y.stride(0), ptr(mean), ptr(rstd), rows, x.shape[1], C.c_float(eps), stream_ptr()))
+                                   y.stride(0), ptr(mean), ptr(rstd), rows, x.shape[1], eps, stream_ptr()))
 
 
 def add_layernorm_fwd(x, y, x_out, gamma, beta, h, mean=None, rstd=None, row_scale=None, rows_per_img=0, eps=1e-5):
     """x_out = x + row_scale[row // rows_per_img] * y;  h = LayerNorm(x_out) (16-bit);  see reid_add_layernorm_fwd."""
     check(lib().reid_add_layernorm_fwd(ptr(x), x.stride(0), ptr(y), L.dt(y, allow_half=True), y.stride(0), ptr(row_scale), rows_per_img, ptr(x_out), x_out.stride(0),
                                        ptr(gamma), ptr(beta), ptr(h), h.stride(0), ptr(mean), ptr(rstd), x.shape[0], x.shape[1],
-                                       C.c_float(eps), stream_ptr()))
+                                       eps, stream_ptr()))
 
 
 _ln_profile = None
@@ -138,22 +138,19 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dx, dx_bf16=None, dres=None, row_ind
         raise ValueError('layernorm_bwd: dres and dx must have one dtype (float32 or float16)')
     if overflow is not None:
         L._req(overflow, torch.int32, 'overflow')
-    if _ln_profile is not None and rows >= 4096 and row_index is None:
+    profiled = _ln_profile is not None and rows >= 4096 and row_index is None
+    if profiled:
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-        cols = x.shape[1]
-        # algorithmic bytes per row: dy (2 or 4) + x (4) + dres (4 or 2) + dx (4 or 2) + 16-bit copy (2)
-        nbytes = rows * cols * ((2 if dy.dtype != torch.float32 else 4) + 4 + (dx.element_size() if dres is not None else 0) +
-                                dx.element_size() + (2 if dx_bf16 is not None else 0))
         e0.record()
-        check(lib().reid_layernorm_bwd(ptr(dy), L.dt(dy), dy.stride(0), ptr(x), x.stride(0), ptr(row_index), ptr(gamma),
-                                       ptr(mean), ptr(rstd), ptr(dres), ptr(dx), L.F16 if dx.dtype == torch.float16 else L.F32, ptr(dx_bf16), dx.stride(0), ptr(dgamma),
-                                       ptr(dbeta), rows, x.shape[1], ptr(bf16_row_scale), rows_per_img, ptr(overflow), stream_ptr()))
-        e1.record()
-        _ln_profile.append((nbytes, e0, e1))
-        return
     check(lib().reid_layernorm_bwd(ptr(dy), L.dt(dy), dy.stride(0), ptr(x), x.stride(0), ptr(row_index), ptr(gamma),
                                    ptr(mean), ptr(rstd), ptr(dres), ptr(dx), L.F16 if dx.dtype == torch.float16 else L.F32, ptr(dx_bf16), dx.stride(0), ptr(dgamma),
                                    ptr(dbeta), rows, x.shape[1], ptr(bf16_row_scale), rows_per_img, ptr(overflow), stream_ptr()))
+    if profiled:
+        e1.record()
+        # algorithmic bytes per row: dy (2 or 4) + x (4) + dres (4 or 2) + dx (4 or 2) + 16-bit copy (2)
+        nbytes = rows * x.shape[1] * ((2 if dy.dtype != torch.float32 else 4) + 4 + (dx.element_size() if dres is not None else 0) +
+                                      dx.element_size() + (2 if dx_bf16 is not None else 0))
+        _ln_profile.append((nbytes, e0, e1))
 
 
 def patch_im2col(images, patches, patch, cin):
@@ -176,12 +173,7 @@ def attn_bwd(qkv, out, dout, lse, dqkv, delta_ws, n_seq, S, heads, causal=False,
 
 
 def cast_f32_bf16(src, dst):
-    check(lib().reid_cast_f32_bf16(ptr(src), ptr(dst), C.c_int64(src.numel()), stream_ptr()))
-    return dst
-
-
-def cast_bf16_f32(src, dst):
-    check(lib().reid_cast_bf16_f32(ptr(src), ptr(dst), C.c_int64(src.numel()), stream_ptr()))
+    check(lib().reid_cast_f32_bf16(ptr(src), ptr(dst), src.numel(), stream_ptr()))
     return dst
 
 
@@ -197,7 +189,7 @@ def lora_bwd_fused(dY, T, BT, U, dB, img_mod, rows_per_img, mask_r, scale, u_par
         dYq, BTq, dBq = dY[:, q * 768:(q + 1) * 768], BT[:, q * 768:(q + 1) * 768], dB[q * 768:(q + 1) * 768]
         check(lib().reid_lora_bwd_fused(ptr(dYq), dYq.stride(0), ptr(T), T.stride(0), ptr(BTq), BTq.stride(0), ptr(U), U.stride(0),
                                         ptr(dBq), dBq.stride(0), ptr(img_mod), rows_per_img, mask_r, dY.shape[0], 768, T.shape[1],
-                                        C.c_float(scale), ptr(u_partial), mode, stream_ptr()))
+                                        scale, ptr(u_partial), mode, stream_ptr()))
 
 
 def lora_da_fused(X, U, dA, img_mod, rows_per_img, mask_r, n_groups=1):
@@ -215,7 +207,7 @@ def lora_bwd_fused_ok(N, Rp):
 
 
 def merge_lora_table(table, n_entries, max_tiles, arena, weff, Rp, r, nmod, scaling):
-    check(lib().reid_merge_lora_table(ptr(table), n_entries, max_tiles, ptr(arena), ptr(weff), Rp, r, nmod, C.c_float(scaling), stream_ptr()))
+    check(lib().reid_merge_lora_table(ptr(table), n_entries, max_tiles, ptr(arena), ptr(weff), Rp, r, nmod, scaling, stream_ptr()))
 
 
 def to_bf16(src: torch.Tensor) -> torch.Tensor:
@@ -234,16 +226,10 @@ def pack_bf16_table(src_arena, dst_arena, table, n_entries):
 to_t16 = to_bf16
 
 
-def gather_rows(src, index, dst):
-    check(lib().reid_gather_rows_f32(ptr(src), src.stride(0), ptr(index), ptr(dst), dst.stride(0), index.shape[0],
-                                     src.shape[1], stream_ptr()))
-    return dst
-
-
 def l2norm_rows(x, y=None, y_bf16=None, eps=1e-12, scale=1.0):
     o = y if y is not None else y_bf16
     check(lib().reid_l2norm_rows(ptr(x), x.stride(0), ptr(y), ptr(y_bf16), o.stride(0), x.shape[0], x.shape[1],
-                                 C.c_float(eps), C.c_float(scale), stream_ptr()))
+                                 eps, scale, stream_ptr()))
 
 
 def sgemm(A, B, C_out, *, ta=False, tb=False, alpha=1.0, beta=0.0, bias=None, act='none'):
@@ -253,9 +239,8 @@ def sgemm(A, B, C_out, *, ta=False, tb=False, alpha=1.0, beta=0.0, bias=None, ac
     N = B.shape[0] if tb else B.shape[1]
     sam, sak = (1, A.stride(0)) if ta else (A.stride(0), 1)
     sbk, sbn = (1, B.stride(0)) if tb else (B.stride(0), 1)
-    check(lib().reid_sgemm(ptr(A), ptr(B), ptr(C_out), M, N, K, C.c_int64(sam), C.c_int64(sak), C.c_int64(sbk),
-                           C.c_int64(sbn), C_out.stride(0),
-                           C.c_float(alpha), C.c_float(beta), ptr(bias), ACT[act], stream_ptr()))
+    check(lib().reid_sgemm(ptr(A), ptr(B), ptr(C_out), M, N, K, sam, sak, sbk, sbn, C_out.stride(0), alpha, beta, ptr(bias),
+                           ACT[act], stream_ptr()))
     return C_out
 
 
@@ -267,31 +252,30 @@ def bnneck_stats(x, sum_, sqsum):
 def bnneck_fwd(x, gamma, beta, running_mean, running_var, sum_, sqsum, count, training, y, y_bf16, mean, invstd, rnorm,
                eps=1e-5, momentum=0.1, scale=8.0):
     check(lib().reid_bnneck_fwd(ptr(x), x.stride(0), ptr(gamma), ptr(beta), ptr(running_mean), ptr(running_var), ptr(sum_),
-                                ptr(sqsum), C.c_float(count), int(training), ptr(y), ptr(y_bf16), y.stride(0), ptr(mean),
-                                ptr(invstd), ptr(rnorm), x.shape[0], x.shape[1], C.c_float(eps), C.c_float(momentum),
-                                C.c_float(scale), stream_ptr()))
+                                ptr(sqsum), count, int(training), ptr(y), ptr(y_bf16), y.stride(0), ptr(mean),
+                                ptr(invstd), ptr(rnorm), x.shape[0], x.shape[1], eps, momentum, scale, stream_ptr()))
 
 
 def bnneck_bwd_p1(dy, x, gamma, beta, mean, invstd, rnorm, dz, sum_dz, sum_dz_xhat, scale=8.0):
     check(lib().reid_bnneck_bwd_p1(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(gamma), ptr(beta), ptr(mean), ptr(invstd),
                                    ptr(rnorm), ptr(dz), ptr(sum_dz), ptr(sum_dz_xhat), x.shape[0], x.shape[1],
-                                   C.c_float(scale), stream_ptr()))
+                                   scale, stream_ptr()))
 
 
 def bnneck_bwd_p2(dz, x, gamma, mean, invstd, sum_dz, sum_dz_xhat, count, training, dx):
     check(lib().reid_bnneck_bwd_p2(ptr(dz), ptr(x), x.stride(0), ptr(gamma), ptr(mean), ptr(invstd), ptr(sum_dz),
-                                   ptr(sum_dz_xhat), C.c_float(count), int(training), ptr(dx), dx.stride(0), x.shape[0],
+                                   ptr(sum_dz_xhat), count, int(training), ptr(dx), dx.stride(0), x.shape[0],
                                    x.shape[1], stream_ptr()))
 
 
 def ce_ls_fwd(logits, labels, valid, row_loss, loss_sum, smoothing=0.1):
     check(lib().reid_ce_ls_fwd(ptr(logits), logits.stride(0), ptr(labels), ptr(valid), logits.shape[0], logits.shape[1],
-                               C.c_float(smoothing), ptr(row_loss), ptr(loss_sum), stream_ptr()))
+                               smoothing, ptr(row_loss), ptr(loss_sum), stream_ptr()))
 
 
 def ce_ls_bwd(logits, labels, valid, grad_scale, dlogits, smoothing=0.1):
     check(lib().reid_ce_ls_bwd(ptr(logits), logits.stride(0), ptr(labels), ptr(valid), logits.shape[0], logits.shape[1],
-                               C.c_float(smoothing), ptr(grad_scale), ptr(dlogits), dlogits.stride(0), stream_ptr()))
+                               smoothing, ptr(grad_scale), ptr(dlogits), dlogits.stride(0), stream_ptr()))
 
 
 def sdm_ws_floats(P, N, Mg, D):
@@ -302,13 +286,13 @@ def sdm_fwd(q, g, q_label, g_label, q_valid, g_valid, tau, ws, result, P=1):
     """q [P*N, D] (P query sides stacked), g [Mg, D]; result f32 [2*P] = (loss, contributes) per pair."""
     N = q.shape[0] // P
     check(lib().reid_sdm_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_label), ptr(g_label), ptr(q_valid), ptr(g_valid),
-                             P, N, g.shape[0], q.shape[1], C.c_float(tau), ptr(ws), ptr(result), stream_ptr()))
+                             P, N, g.shape[0], q.shape[1], tau, ptr(ws), ptr(result), stream_ptr()))
 
 
 def sdm_bwd(q, g, q_label, g_label, q_valid, g_valid, tau, ws, gscale, dq, dg, P=1):
     N = q.shape[0] // P
     check(lib().reid_sdm_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_label), ptr(g_label), ptr(q_valid), ptr(g_valid),
-                             P, N, g.shape[0], q.shape[1], C.c_float(tau), ptr(ws), ptr(gscale), ptr(dq), dq.stride(0),
+                             P, N, g.shape[0], q.shape[1], tau, ptr(ws), ptr(gscale), ptr(dq), dq.stride(0),
                              ptr(dg), dg.stride(0), stream_ptr()))
 
 
@@ -355,7 +339,7 @@ ELT = {'add': 0, 'relu': 1, 'relu_bwd': 2, 'gelu': 3, 'gelu_bwd': 4, 'mul': 5, '
 
 def eltwise(op, x, y=None, out=None, alpha=1.0):
     out = torch.empty_like(x) if out is None else out
-    check(lib().reid_eltwise_f32(ELT[op], ptr(x), ptr(y), ptr(out), C.c_int64(x.numel()), C.c_float(alpha), stream_ptr()))
+    check(lib().reid_eltwise_f32(ELT[op], ptr(x), ptr(y), ptr(out), x.numel(), alpha, stream_ptr()))
     return out
 
 
@@ -376,7 +360,7 @@ def masked_mean(x, mask, out, B, M, D, backward=False):
 
 def rank_metrics(scores, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, Ng, max_pos, ap, rank1, npos):
     """Per-query AP / first-positive rank / #positives from fp32 score rows (reid_rank_metrics, include/reid_hip.h)."""
-    check(lib().reid_rank_metrics(ptr(scores), C.c_int64(scores.stride(0)), ptr(g_pid), ptr(g_img), ptr(q_pid), ptr(q_slot),
+    check(lib().reid_rank_metrics(ptr(scores), scores.stride(0), ptr(g_pid), ptr(g_img), ptr(q_pid), ptr(q_slot),
                                   ptr(q_excl), ptr(csr_off), ptr(csr_idx), scores.shape[0], Ng, max_pos, ptr(ap), ptr(rank1), ptr(npos),
                                   stream_ptr()))
 

@@ -134,11 +134,10 @@ class FusedAdamW:
         self.step_count += 1
         check(lib().reid_opt_sumsq(ptr(self._table), n, ptr(self.ws), stream_ptr()))
         rec = -int(record_norm) if device_counters else int(bool(record_norm))
-        check(lib().reid_opt_clip(ptr(self.ws), n, ptr(self.state), int(adaptive_clip), C.c_float(fixed_max_norm), rec, stream_ptr()))
-        coef = C.c_void_p(self.state.data_ptr() + 8)         # state[2]
-        check(lib().reid_opt_adamw(ptr(self._table), n, coef, C.c_float(self.betas[0]), C.c_float(self.betas[1]),
-                                   C.c_float(self.eps), 0 if device_counters else self.step_count, int(zero_grad), ptr(self.state),
-                                   stream_ptr()))
+        check(lib().reid_opt_clip(ptr(self.ws), n, ptr(self.state), int(adaptive_clip), fixed_max_norm, rec, stream_ptr()))
+        coef = self.state.data_ptr() + 8                     # state[2]
+        check(lib().reid_opt_adamw(ptr(self._table), n, coef, self.betas[0], self.betas[1], self.eps,
+                                   0 if device_counters else self.step_count, int(zero_grad), ptr(self.state), stream_ptr()))
         # the kernel wrote through raw pointers: tell autograd / the engine's pack cache (engine.refresh keys on _version)
         for p in self.params:
             torch.autograd.graph.increment_version(p)
