@@ -430,6 +430,26 @@ int reid_rank_metrics(const float* scores, int64_t ld, const int32_t* g_pid, con
                       const int32_t* csr_idx, int32_t nq, int32_t Ng, int32_t max_pos, double* ap, int32_t* rank1,
                       int32_t* npos, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Image transforms of the training input (datasets/dataset.py:284-307, train.py:1634-1641; eval: dataset.py:300-307,
+ * tools/eval_mm_protocol.py:171-173), bit-exact against PIL + torch for given parameters, per image in this order:
+ *   Image.crop(box).resize((S, S), BILINEAR) -> horizontal flip -> ImageEnhance.Brightness / .Contrast (Image.blend) in the
+ *   drawn order -> ToTensor + Normalize (lut f32 [3, 256] = (v / 255 - mean[c]) / std[c] computed by torch on fp32) ->
+ *   RandomErasing(value=0) over the erase box of the output; an empty slot (absent modality) is all zeros.
+ *   src   uint8 RGB HWC images packed into one buffer of src_bytes bytes
+ *   table / host_table  int32 [n, REID_AUG_FIELDS], the same entries on the device (read by the kernels) and on the host
+ *         (validated before any launch): off_lo, off_hi (byte offset of the image in src), H, W, crop x, crop y, crop w,
+ *         crop h, flags (reid_aug_flag), brightness factor, contrast factor (fp32 bit patterns; 1.0 = identity), erase x,
+ *         erase y, erase w, erase h (w = 0: no erase), 0
+ *   ws    scratch of reid_augment_ws_bytes(n, S) bytes, 16-byte aligned; out f32 [n, 3, S, S], 16-byte aligned
+ * Limits: 4 <= S <= 1024, S % 4 == 0; 1 <= H, W <= 8192; crop inside the image; erase box inside S x S.
+ * ------------------------------------------------------------------------------------------ */
+#define REID_AUG_FIELDS 16
+typedef enum { REID_AUG_FLIP = 1, REID_AUG_CONTRAST_FIRST = 2, REID_AUG_EMPTY = 4 } reid_aug_flag;
+int64_t reid_augment_ws_bytes(int32_t n, int32_t S);
+int reid_augment_images(const void* src, int64_t src_bytes, const int32_t* table, const int32_t* host_table, int32_t n,
+                        int32_t S, const float* lut, void* ws, int64_t ws_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

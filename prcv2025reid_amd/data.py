@@ -5,14 +5,16 @@ Reference: ``ModalAwarePKBatchSampler_Strict`` (datasets/dataset.py:1327-1464), 
 ``infer_modalities_of_sample`` (:188-255), ``canon_mod`` (:62-76).  The sampler reproduces the reference's draw sequence
 (same calls to ``random`` in the same order), so with the same seed it yields the SAME index lists -- pinned by
 tests/golden/pipeline_cases.json, which make_golden.py writes by executing the reference's own code.
-The dataset class itself (file layout of ORBench, PIL decoding, torchvision transforms) is out of scope: anything that
-yields the reference's sample dictionaries works.
+The dataset class itself (file layout of ORBench, JPEG decoding) is out of scope: anything that yields the reference's sample
+dictionaries works -- with transformed tensors, or with raw uint8 images for a feeder that runs the device transforms of
+transforms.py (``collate_raw``).
 """
 import random as _random
 import threading
 import queue
 from typing import Any, Dict, Iterable, Iterator, List, Optional, Sequence, Set
 
+import numpy as np
 import torch
 
 CANON_DS = {'vis': 'vis', 'rgb': 'vis', 'visible': 'vis', 'v': 'vis', 'nir': 'nir', 'ir': 'nir', 'infrared': 'nir',
@@ -282,35 +284,100 @@ def collate(batch: List[dict], image_size: int = 224) -> Dict[str, Any]:
     return out
 
 
+def _raw_image(value, modality: str):
+    """A sample's decoded image as a host array (from a uint8 array, CPU tensor or PIL image), None where it is absent (no entry
+    or no pixels); its dtype and layout are checked where the transform stages it.  Anything else (a path, ...) is refused."""
+    if value is None:
+        return None
+    if isinstance(value, torch.Tensor):
+        return value if value.numel() > 0 else None
+    if isinstance(value, np.ndarray) or hasattr(value, '__array_interface__'):
+        a = np.asarray(value)
+        return a if a.size > 0 else None
+    raise ValueError(f"images[{modality!r}]: expected a decoded image (uint8 HWC array, CPU tensor or PIL image), "
+                     f"got {type(value).__name__}")
+
+
+def collate_raw(batch: List[dict]) -> Dict[str, Any]:
+    """``collate`` for samples whose ``images`` hold raw uint8 RGB HWC images (before the device transform): the same fields, with
+    ``images`` = {m: list of B images, None where absent}.  An image counts iff it is present AND the sample's own mask agrees --
+    what ``collate`` finds on the transformed tensors, since no uint8 value normalises to exactly 0 and an erase box covers at most
+    a fifth of the image."""
+    if not batch:
+        return {}
+    first, B = batch[0], len(batch)
+    out: Dict[str, Any] = {}
+    if 'person_id' in first:
+        out['person_id'] = torch.stack([torch.as_tensor(s['person_id']) for s in batch])
+    caption_key = next((k for k in ('text_description', 'text_descriptions') if k in first), None)
+    out['text_description'] = [''] * B if caption_key is None else \
+        [_caption_of(s, caption_key, accept_plain=caption_key == 'text_description') for s in batch]
+    nested = [s['images'] if isinstance(s.get('images'), dict) else {} for s in batch]
+    out['images'] = {m: [_raw_image(box.get(m), m) for box in nested] for m in MODALITIES}
+    mask: Dict[str, torch.Tensor] = {}
+    for m in MODALITIES:
+        mask[m] = torch.tensor([img is not None and _own_flag(s, m) for img, s in zip(out['images'][m], batch)]).float()
+    mask['text'] = torch.tensor([_caption_present(s) for s in batch]).float()
+    out['modality_mask'] = mask
+    out['modality'] = [_primary_name(s) for s in batch]
+    return out
+
+
 class DeviceFeeder:
     """Background producer: sampler -> dataset[i] -> collate -> tokeniser -> pinned staging -> HBM on a copy stream.
 
     Yields batches whose ``images`` / ``tokens`` / ``person_id`` are device tensors ready for ``StepDriver.step`` (masks stay
     on the host: the model's routing plan reads them there).  ``depth`` batches are prepared ahead; a batch's H2D copies are
     ordered before its consumer by an event the consumer stream waits on, so the training stream never waits for the host.
+
+    With ``transform`` (a ``transforms.TrainTransform`` / ``EvalTransform``) the dataset yields raw uint8 RGB HWC images: the
+    worker collates them per modality (``collate_raw``), stages the bytes and runs the transform on the copy stream -- one launch
+    pair for all modalities of the batch -- and ``images`` holds its fp32 output; ``last_params`` is the batch's drawn table
+    (modalities in ``MODALITIES`` order, B images each).
     """
 
-    def __init__(self, dataset, batch_sampler: Iterable[List[int]], tokenizer, device, depth: int = 2, max_length: int = 77):
+    def __init__(self, dataset, batch_sampler: Iterable[List[int]], tokenizer, device, depth: int = 2, max_length: int = 77,
+                 transform=None):
         self.dataset, self.sampler, self.tok = dataset, batch_sampler, tokenizer
+        self.transform = transform
         self.dev = torch.device(device)
         self.max_length = max_length
         self.q: "queue.Queue" = queue.Queue(maxsize=max(1, depth))
         self.copy_stream = torch.cuda.Stream(self.dev) if self.dev.type == 'cuda' else None
         self._t = threading.Thread(target=self._work, daemon=True)
         self._started = False
+        self._error = None
 
     def _stage(self, t: torch.Tensor) -> torch.Tensor:
         if self.copy_stream is None:
             return t
         return t.pin_memory().to(self.dev, non_blocking=True)
 
+    def _transformed(self, raw: Dict[str, list]):
+        """{m: fp32 [B, 3, S, S] on the device} of one batch's raw images (one call of the transform) and the drawn table."""
+        from .transforms import Packed
+        B = len(raw[MODALITIES[0]])
+        packed = Packed([img for m in MODALITIES for img in raw[m]])
+        params = self.transform.draw_params(packed.sizes)
+        out = self.transform.apply(packed, params)
+        return {m: out[k * B:(k + 1) * B] for k, m in enumerate(MODALITIES)}, params
+
     def _work(self):
         try:
             for idxs in self.sampler:
-                b = collate([self.dataset[i] for i in idxs])
+                samples = [self.dataset[i] for i in idxs]
+                b = collate(samples) if self.transform is None else collate_raw(samples)
                 tok = self.tok(b['text_description'], return_tensors='pt', padding=True, truncation=True, max_length=self.max_length)
                 ev = None
-                if self.copy_stream is not None:
+                if self.transform is not None:
+                    if self.copy_stream is None:
+                        raise ValueError('the image transforms run on the GPU: give the feeder a CUDA device')
+                    with torch.cuda.stream(self.copy_stream):
+                        b['images'], b['transform_params'] = self._transformed(b['images'])
+                        b['tokens'] = {k: self._stage(v) for k, v in tok.items()}
+                        b['person_id'] = self._stage(b['person_id'])
+                        ev = torch.cuda.Event(); ev.record(self.copy_stream)
+                elif self.copy_stream is not None:
                     with torch.cuda.stream(self.copy_stream):
                         b['images'] = {m: self._stage(t.float()) for m, t in b['images'].items()}
                         b['tokens'] = {k: self._stage(v) for k, v in tok.items()}
@@ -319,6 +386,10 @@ class DeviceFeeder:
                 else:
                     b['tokens'] = dict(tok)
                 self.q.put((b, ev))
+        except BaseException as e:
+            if self.transform is None:
+                raise
+            self._error = e                                  # (raised by the consumer: a failing transform does not end the epoch silently)
         finally:
             self.q.put(None)
 
@@ -328,8 +399,13 @@ class DeviceFeeder:
         while True:
             item = self.q.get()
             if item is None:
+                if self._error is not None:
+                    raise self._error
                 return
             b, ev = item
             if ev is not None:
                 torch.cuda.current_stream(self.dev).wait_event(ev)
+                if self.transform is not None:                # the transform's output was allocated on the copy stream
+                    for t in b['images'].values():
+                        t.record_stream(torch.cuda.current_stream(self.dev))
             yield b

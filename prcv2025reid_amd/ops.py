@@ -376,3 +376,16 @@ def embed_tokens(tok, pos, ids, out):
     B, T = ids.shape
     check(lib().reid_embed_tokens(ptr(tok), ptr(pos), ptr(ids), ptr(out), B, T, tok.shape[1], tok.shape[0], stream_ptr()))
     return out
+
+
+# ----------------------------------------------------------------------------------------- image transforms of the input
+def augment_ws_bytes(n, S):
+    return int(lib().reid_augment_ws_bytes(n, S))
+
+
+def augment_images(src, src_bytes, table, host_table, n, S, lut, ws, out):
+    """uint8 RGB HWC images packed in ``src`` -> normalised fp32 ``out`` [n, 3, S, S] by the int32 entries of ``table`` (device) /
+    ``host_table`` (host, validated before the launch); see reid_augment_images in include/reid_hip.h."""
+    check(lib().reid_augment_images(ptr(src), src_bytes, ptr(table), ptr(host_table), n, S, ptr(lut), ptr(ws), ws.numel(), ptr(out),
+                                    stream_ptr()))
+    return out
