@@ -250,8 +250,15 @@ int reid_scatter_add_rows_f32(const float* src, int32_t lds, const int32_t* inde
  *   training != 0: batch statistics over `rows` (biased variance), running stats updated with
  *   momentum 0.1 / unbiased variance; else running statistics.  The classifier GEMM that
  *   follows is reid_mer_gemm on the bf16 copy.
- *   With ext_sum/ext_sqsum/ext_count non-NULL the statistics are taken from those buffers
- *   (data-parallel SyncBN: the caller all-reduces them between the two phases).
+ *   Statistics, training != 0: reid_bnneck_stats writes the column sums of x and x^2 (fp32, zeroed by the call) into sum / sqsum.
+ *     count == rows (the sums are this call's own rows; the only form the model uses): the mean is taken from `sum` and the
+ *       variance from a second pass over x, centred on that mean and accumulated in fp64 -- mean and invstd are the correctly
+ *       rounded batch statistics to a few fp32 ulps whatever |mean|/std of a column is (sqsum is not read).
+ *     count != rows (data-parallel SyncBN: the caller adds the sums of all ranks between the two phases and passes the global
+ *       count): the call cannot see the other ranks' rows, so var = sqsum/count - mean^2 in fp32, clamped at 0.  With d fp32
+ *       roundings on the way of a term through the sums, |d var| <= (3 d + 6) 2^-24 E[x^2]: the RELATIVE error of the variance
+ *       (half of it in invstd) grows as 1 + (mean/std)^2 -- about 1e-6 at |mean|/std = 1, 1e-4..1e-3 at 30, useless beyond
+ *       a few hundred.  A caller with such columns must reduce centred sums itself.
  *   fwd outputs: y f32 [rows, D] (norm 8 per row), y_bf16 optional, saved xhat-free state:
  *   mean[D], invstd[D], rnorm[rows].
  * ------------------------------------------------------------------------------------------ */

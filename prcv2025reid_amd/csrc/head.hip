@@ -150,6 +150,39 @@ __global__ void bn_finalize_kernel(const float* __restrict__ sum, const float* _
     invstd[c] = rsqrtf(var + eps);
 }
 
+// Batch statistics of rows this call itself holds (count == rows): the one-pass variance sqsum/count - mu^2 above loses
+// (|mean|/std)^2 of fp32's precision, and the fused feature that feeds the BN-neck has |mean|/std of 3..65 per column.  So the
+// local form makes a second pass over x (64 x 512 fp32 = 128 KB, L2-resident) with the data shifted by mu0 = sum/count:
+//   delta = mean(x - mu0),  mu = mu0 + delta,  var = mean((x - mu0)^2) - delta^2       (delta ~ fp32 rounding of mu0: nothing cancels)
+// accumulated in fp64, so mean and variance are the correctly rounded batch statistics up to the final conversions.
+// block = 64 columns x 16 row lanes; grid = D/64.
+__global__ __launch_bounds__(1024) void bn_finalize_local_kernel(const float* __restrict__ x, int ldx, int rows,
+                                                                 const float* __restrict__ sum, float* __restrict__ running_mean,
+                                                                 float* __restrict__ running_var, float* __restrict__ mean,
+                                                                 float* __restrict__ invstd, int D, float eps, float momentum) {
+    REID_T16_ENTER();
+    __shared__ double s1[16][64], s2[16][64];
+    const int cl = threadIdx.x & 63, rl = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    const float count = (float)rows;
+    const double mu0 = c < D ? (double)(sum[c] / count) : 0.0;
+    double a = 0.0, b = 0.0;
+    if (c < D)
+        for (int r = rl; r < rows; r += 16) { const double d = (double)x[(size_t)r * ldx + c] - mu0; a += d; b = fma(d, d, b); }
+    s1[rl][cl] = a; s2[rl][cl] = b;
+    __syncthreads();
+    if (rl != 0 || c >= D) return;
+#pragma unroll
+    for (int i = 1; i < 16; ++i) { a += s1[i][cl]; b += s2[i][cl]; }
+    const double delta = a / rows;
+    const float mu = (float)(mu0 + delta);
+    const float var = (float)fmax(b / rows - delta * delta, 0.0);
+    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
+    if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * var * (count / fmaxf(count - 1.f, 1.f));
+    mean[c] = mu;
+    invstd[c] = rsqrtf(var + eps);
+}
+
 constexpr int MAXV = 4;
 
 __global__ __launch_bounds__(256) void bnneck_fwd_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
@@ -276,26 +309,40 @@ __device__ __forceinline__ void row_softmax_stats(const float* __restrict__ z, i
     se = wave_sum(se);
 }
 
+// At most CE_FWD_BLOCKS workgroups walk the rows (one wave per row, grid stride); each adds ITS rows' losses in fp64 and makes one
+// fp32 atomic: loss_sum is rounded CE_FWD_BLOCKS times, not once per row (a chain of rows/4 fp32 atomics drifts by ~sqrt(rows) ulps).
+constexpr int CE_FWD_BLOCKS = 16;
 __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, int ld, const int64_t* __restrict__ labels,
                                                      const uint8_t* __restrict__ valid, int rows, int C, float eps,
                                                      float* __restrict__ row_loss, float* __restrict__ loss_sum) {
     REID_T16_ENTER();
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const long y = labels[row];
-    const bool ok = (!valid || valid[row]) && y >= 0 && y < C;
-    float loss = 0.f;
-    if (ok) {
-        const float* z = logits + (size_t)row * ld;
-        float mx, se, sz;
-        row_softmax_stats(z, C, lane, mx, se, sz);
-        const float lse = mx + logf(se);
-        loss = (1.f - eps) * (lse - z[y]) + eps * (lse - sz / C);
+    __shared__ double wsum[4];
+    __shared__ int wcnt[4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double acc = 0.0;
+    int cnt = 0;
+    for (int row = blockIdx.x * 4 + w; row < rows; row += gridDim.x * 4) {
+        const long y = labels[row];
+        const bool ok = (!valid || valid[row]) && y >= 0 && y < C;
+        float loss = 0.f;
+        if (ok) {
+            const float* z = logits + (size_t)row * ld;
+            float mx, se, sz;
+            row_softmax_stats(z, C, lane, mx, se, sz);
+            const float lse = mx + logf(se);
+            loss = (1.f - eps) * (lse - z[y]) + eps * (lse - sz / C);
+            acc += (double)loss; ++cnt;
+        }
+        if (lane == 0 && row_loss) row_loss[row] = loss;
     }
-    if (lane == 0) {
-        if (row_loss) row_loss[row] = loss;
-        if (ok) { atomicAdd(loss_sum, loss); atomicAdd(loss_sum + 1, 1.0f); }
+    if (lane == 0) { wsum[w] = acc; wcnt[w] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int n = (wcnt[0] + wcnt[1]) + (wcnt[2] + wcnt[3]);
+        if (n > 0) {
+            atomicAdd(loss_sum, (float)((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])));
+            atomicAdd(loss_sum + 1, (float)n);
+        }
     }
 }
 
@@ -541,8 +588,12 @@ extern "C" int reid_bnneck_fwd(const float* x, int32_t ldx, const float* gamma, 
     REID_CHECK_ARG(rows > 0 && D % 4 == 0 && D <= 64 * 4 * MAXV && ldx % 4 == 0 && ldy % 4 == 0, "reid_bnneck_fwd: shape");
     REID_CHECK_ARG(training ? (sum && sqsum && count > 0) : (running_mean && running_var), "reid_bnneck_fwd: statistics missing");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((D + 255) / 256), dim3(256), 0, s, sum, sqsum, count, training, running_mean,
-                       running_var, mean, invstd, D, eps, momentum);
+    if (training && count == (float)rows)                // the statistics are this call's own rows: cancellation-safe second pass over x
+        hipLaunchKernelGGL(bn_finalize_local_kernel, dim3((D + 63) / 64), dim3(1024), 0, s, x, ldx, rows, sum, running_mean, running_var,
+                           mean, invstd, D, eps, momentum);
+    else                                                 // externally reduced sums (count != rows) or running statistics
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3((D + 255) / 256), dim3(256), 0, s, sum, sqsum, count, training, running_mean,
+                           running_var, mean, invstd, D, eps, momentum);
     REID_CHECK_LAUNCH("reid_bnneck_fwd(finalize)");
     hipLaunchKernelGGL(bnneck_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, x, ldx, gamma, beta, mean, invstd, y, (bf16_t*)y_bf16,
                        ldy, rnorm, rows, D, scale);
@@ -578,7 +629,8 @@ extern "C" int reid_bnneck_bwd_p2(const float* dz, const float* x, int32_t ldx, 
 extern "C" int reid_ce_ls_fwd(const float* logits, int32_t ld, const int64_t* labels, const uint8_t* valid, int32_t rows, int32_t C,
                               float smoothing, float* row_loss, float* loss_sum, void* stream) {
     REID_CHECK_ARG(logits && labels && loss_sum && rows > 0 && C > 0 && ld >= C, "reid_ce_ls_fwd: bad args");
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, ld, labels, valid, rows, C, smoothing,
+    const int blocks = (rows + 3) / 4;
+    hipLaunchKernelGGL(ce_fwd_kernel, dim3(blocks < CE_FWD_BLOCKS ? blocks : CE_FWD_BLOCKS), dim3(256), 0, (hipStream_t)stream, logits, ld, labels, valid, rows, C, smoothing,
                        row_loss, loss_sum);
     REID_CHECK_LAUNCH("reid_ce_ls_fwd");
     return REID_OK;

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import loss_refs as R
 from helpers import GOLDEN
 from oracle import reid_oracle as O
 
@@ -62,6 +63,8 @@ def test_metrics_vs_oracle(flavor, Nq, Ng, npid):
     qp = torch.randint(0, npid + 3, (Nq,), generator=g)          # some query pids have no gallery row
     G = centers[gp] * 0.6 + torch.randn(Ng, 512, generator=g)
     Q = centers[qp] * 0.6 + torch.randn(Nq, 512, generator=g)
+    dup = torch.randint(0, Ng, (Ng // 10,), generator=g)           # duplicated gallery images: exact score ties end to end
+    G[dup] = G[(dup * 7 + 3) % Ng]
     g_img = [f'im{i}' for i in range(Ng)]
     q_img = []
     for i in range(Nq):
@@ -77,6 +80,20 @@ def test_metrics_vs_oracle(flavor, Nq, Ng, npid):
     assert abs(got['mAP'] - want['mAP']) < 2e-6, (got, want)
     for k in ('R@1', 'R@5', 'R@10'):
         assert abs(got[k] - want[k]) < 1e-12, (k, got, want)
+    # per query, not only the means: the kernel's (ap, rank1, npos) against the numpy walk of the stable descending argsort of
+    # the evaluator's OWN fp32 score rows (an exact contract: ties by gallery index), and the number of positives against the CPU
+    ap, rank1, npos = (t.cpu().numpy() for t in ev.per_query(Q.cuda(), qp, q_img))
+    S = ev.scores(Q.cuda())[:, :Ng].cpu().numpy()
+    ids = np.arange(Ng)
+    ties = 0
+    for i in range(Nq):
+        excl = [int(x[2:]) for x in q_img[i]]
+        w_ap, w_r1, w_np = R.rank_metrics_ref(S[i], gp.numpy(), int(qp[i]), ids, excl)
+        assert (int(rank1[i]), int(npos[i])) == (w_r1, w_np) and abs(float(ap[i]) - w_ap) <= 1e-12, (i, ap[i], rank1[i], npos[i], w_ap, w_r1, w_np)
+        keep = ~np.isin(ids, excl)
+        assert int(npos[i]) == int(((gp.numpy() == int(qp[i])) & keep).sum())
+        ties += Ng - len(np.unique(S[i]))
+    assert ties > 0                                                 # the duplicated rows did produce equal scores
 
 
 def test_competition_metrics_and_csv(tmp_path, flavor):
