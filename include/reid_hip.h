@@ -206,8 +206,10 @@ int reid_pack_bf16_table(const float* src, void* dst_bf16, const int64_t* table,
  *   U[m, :]  = mask_modality(dY[m, :] . B) * scale      (16-bit [M, Rp]; column c kept iff c / mask_r == img_mod[m / rows_per_img];
  *                                                        BT = B^T [Rp, N] 16-bit; the operand of dA = U^T x, reid_gemm_tn)
  *   dB      += dY^T . T                                  (fp32 [N, Rp], atomics; T = the forward's masked x . A^T, 16-bit [M, Rp])
- * Rp must be 32.  A wider cotangent (fc1: 3072 columns) is handled as column blocks of 768, one launch each on the same stream:
- * u_mode bit 0 = add the fp32 partial sums u_partial [M, 32] of the earlier blocks to this block's, bit 1 = store the sum to
+ * Rp must be 32, or 64 with rows_per_img >= 32 and mask_r a divisor of 16 (the one-image-per-workgroup kernel below; the class-row form
+ * rows_per_img < 32 and REID_LORA_IMPL = 1 have no kernel for 64 adapter columns: REID_ERR_ARG).  A wider cotangent (fc1: 3072
+ * columns) is handled as column blocks of 768, one launch each on the same stream:
+ * u_mode bit 0 = add the fp32 partial sums u_partial [M, Rp] of the earlier blocks to this block's, bit 1 = store the sum to
  * u_partial instead of finishing U (mask, scale, 16-bit); the last block has bit 1 clear.  u_mode = 0: a 768-column linear, u_partial unused.
  * Other shapes: reid_mer_gemm (U) + reid_gemm_tn (dB).
  * T must be modality-masked (T[m, c] = 0 unless c / mask_r == img_mod[m / rows_per_img]) -- it is how reid_mer_gemm's mask epilogue
@@ -218,7 +220,7 @@ int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, int32_t ldt
                         int32_t Rp, float scale, float* u_partial, int32_t u_mode, void* stream);
 /* The other adapter gradient of a MERLinear, dA += U^T . X (autograd of lora_A, mer_lora.py:40-49), as one pass over the linear's INPUT
  * X [M, K] (16-bit; K a multiple of 768): dA[g Rp + c, k] += sum_m U[m, g Rp + c] X[m, k] for the n_groups (1, or 3 for the fused q|k|v
- * projection) adapter groups of Rp = 32 columns of U [M, n_groups Rp] (16-bit, modality-masked as reid_lora_bwd_fused writes it).
+ * projection) adapter groups of Rp = 32 or 64 columns of U [M, n_groups Rp] (16-bit, modality-masked as reid_lora_bwd_fused writes it).
  * dA: fp32 [n_groups Rp, K] (row stride ldda), accumulated with atomics.  One workgroup per (image, 768-column block): rows_per_img >= 32,
  * mask_r a divisor of 16; other shapes: reid_gemm_tn(U, X). */
 int reid_lora_da_fused(const void* X, int32_t ldx, const void* U, int32_t ldu, float* dA, int32_t ldda, const int32_t* img_mod,

@@ -146,7 +146,7 @@ struct Params {
     const int32_t* img_mod;
     int lddy, ldt, ldbt, ldu, lddb, rows_per_img, mask_r, M, slab_rows;
     float scale;
-    float* Up;                                            // fp32 [M, 32] partial sums of U over column blocks of a wider dY (or null)
+    float* Up;                                            // fp32 [M, Rp] partial sums of U over column blocks of a wider dY (or null)
     int u_mode;                                           // bit 0: add Up to this block's sum; bit 1: store the sum to Up instead of U
 };
 
@@ -289,14 +289,19 @@ __global__ __launch_bounds__(NW * 64, 2) void lora_bwd_fused_kernel(const Params
 // Contract difference to the slab kernel: T must be modality-masked (zero outside the columns of the row's modality), which is how the
 // forward produces it -- columns outside the window are neither read nor accumulated.
 namespace image {
-constexpr int N = fused::N, RP = fused::RP, R = 32;
+constexpr int N = fused::N, R = 32;
 constexpr int ROW_BYTES = N * 2;                           // 1536: 96 chunks of 16 bytes
 constexpr int IMG_BYTES = R * ROW_BYTES;                   // 48 KiB
-constexpr int T_BYTES = R * RP * 2;                        // 2 KiB
-constexpr int BUF_BYTES = IMG_BYTES + T_BYTES;
 constexpr int NBUF = 3;                                      // ring of step buffers: two steps (96 KiB) in flight while one is read
-constexpr int USTAGE_BYTES = R * RP * 2;                    // U tile of a step, row-major, staged for whole-row stores
-constexpr int LDS_BYTES = NBUF * BUF_BYTES + USTAGE_BYTES;
+// lora_bwd_image_kernel<RP>, RP = adapter columns of T / U / dB (32 or 64).  RP = 32 stages the whole T tile (2 KiB: two DMA instructions); RP = 64
+// only the 16-column window of it, as lora_da_image_kernel stages its U windows (32 rows x 32 bytes = 1 KiB: one instruction) -- the window
+// is all the dB waves read, and the whole 4 KiB tile would fill the LDS to its last byte.  RP = 64: 3 x (49 152 + 1 024) + 4 096 = 154 624 bytes <= 163 840.
+template <int RP> struct BwdGeo {
+    static constexpr int T_BYTES = RP == 32 ? R * RP * 2 : R * 32;
+    static constexpr int BUF_BYTES = IMG_BYTES + T_BYTES;
+    static constexpr int USTAGE_BYTES = R * RP * 2;        // U tile of a step, row-major, staged for whole-row stores
+    static constexpr int LDS_BYTES = NBUF * BUF_BYTES + USTAGE_BYTES;
+};
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 using fused::s4; using fused::lds_s4_ptr; using fused::Params;
@@ -327,20 +332,24 @@ __device__ __forceinline__ bf16x8 tr_frag_swz(const char* img, int col0, int lan
     return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
-// U = mask(Up) * scale in 16 bits once the last column block of a wide cotangent has added its partial sums (fp32 [M, 32]) to Up
+// U = mask(Up) * scale in 16 bits once the last column block of a wide cotangent has added its partial sums (fp32 [M, Rp]) to Up
 __global__ __launch_bounds__(256) void u_finish_kernel(const float* __restrict__ Up, bf16_t* __restrict__ U, int ldu, const int32_t* __restrict__ img_mod,
-                                                       int rows_per_img, int mask_r, float scale, int M) {
+                                                       int rows_per_img, int mask_r, float scale, int M, int Rp) {
     REID_T16_ENTER();
-    const int i = blockIdx.x * 256 + threadIdx.x;             // one thread per (row, pair of columns)
-    const int m = i >> 4, c = (i & 15) * 2;
+    const int i = blockIdx.x * 256 + threadIdx.x;             // one thread per (row, pair of columns): Rp / 2 threads per row
+    const int h = Rp >> 1;
+    const int m = i / h, c = (i - m * h) * 2;
     if (m >= M) return;
     const int mu = img_mod[m / rows_per_img];
-    const float a = Up[(size_t)m * RP + c], b = Up[(size_t)m * RP + c + 1];
+    const float a = Up[(size_t)m * Rp + c], b = Up[(size_t)m * Rp + c + 1];
     *(uint32_t*)(U + (size_t)m * ldu + c) = pack_bf16x2(c / mask_r == mu ? a * scale : 0.f, (c + 1) / mask_r == mu ? b * scale : 0.f);
 }
 
+template <int RP>
 __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) {
     REID_T16_ENTER();
+    static_assert(RP == 32 || RP == 64, "adapter columns");
+    constexpr int BUF_BYTES = BwdGeo<RP>::BUF_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -354,7 +363,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
     const int c_lo = mu * p.mask_r - w0, c_hi = c_lo + p.mask_r;   // this modality's columns inside the window
     const int steps = (rend - rbeg + R - 1) / R;
 
-    // one step's operands -> LDS: 48 dY instructions (eight waves x six) + two T instructions (waves 0, 1)
+    // one step's operands -> LDS: 48 dY instructions (eight waves x six) + the T instructions (RP = 32: two, waves 0 and 1; RP = 64: one, wave 0)
     const uint32_t smem_a = lds_addr(smem);
     auto issue = [&](int t, int buf) {
         const uint32_t base = smem_a + buf * BUF_BYTES;
@@ -367,11 +376,19 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
             dma16(p.dY + (size_t)gr * p.lddy + ((c ^ (row & 15)) << 3), base + qd * 1024);
         }
-        if (w < 2) {
-            const int g = w * 64 + lane;                      // T tile: 32 rows x 4 chunks, lane-linear
-            const int row = g >> 2, c = g & 3;
-            int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
-            dma16(p.T + (size_t)gr * p.ldt + c * 8, base + IMG_BYTES + w * 1024);
+        if constexpr (RP == 32) {
+            if (w < 2) {
+                const int g = w * 64 + lane;                  // T tile: 32 rows x 4 chunks, lane-linear
+                const int row = g >> 2, c = g & 3;
+                int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
+                dma16(p.T + (size_t)gr * p.ldt + c * 8, base + IMG_BYTES + w * 1024);
+            }
+        } else {
+            if (w == 0) {                                     // the window of T: 32 rows x 2 chunks, lane-linear (row pitch 32 bytes)
+                const int row = lane >> 1, c = lane & 1;
+                int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
+                dma16(p.T + (size_t)gr * p.ldt + w0 + c * 8, base + IMG_BYTES);
+            }
         }
     };
     issue(0, 0);
@@ -392,11 +409,28 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
     for (int i = 0; i < 8; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
     u32x4_t pend_val = u32x4_t{0u, 0u, 0u, 0u};                // waves 0, 1: the previous step's output, not yet issued
+    u32x4_t pend_val2 = u32x4_t{0u, 0u, 0u, 0u};               // (RP = 64, u_mode == 0: the lane's second 16-byte piece, eight rows below the first)
     void* pend_ptr = nullptr;
-    int pend_n = 0;                                            // rows (u_mode != 0) / "this lane has a row" (u_mode == 0) still to go out
+    int pend_n = 0;                                            // rows (u_mode != 0) / "this lane has a row" (u_mode == 0; RP = 64: bit per piece) still to go out
+    if constexpr (RP == 64) {
+        // U staging rows of this wave: all 64 columns +0.0 once -- the steps rewrite the window columns only, the other 48 stay zero
+        if (w < 2 && p.u_mode == 0) {
+            char* ub = smem + NBUF * BUF_BYTES + w * (16 * RP * 2);
+            *(u32x4_t*)(ub + lane * 16) = u32x4_t{0u, 0u, 0u, 0u};
+            *(u32x4_t*)(ub + 1024 + lane * 16) = u32x4_t{0u, 0u, 0u, 0u};
+        }
+    }
     auto flush_pending = [&]() {
         if (p.u_mode == 0) {
-            if (pend_n) asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(pend_ptr), "v"(pend_val) : "memory");
+            if constexpr (RP == 32) {
+                if (pend_n) asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(pend_ptr), "v"(pend_val) : "memory");
+            } else {
+                if (pend_n & 1) asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(pend_ptr), "v"(pend_val) : "memory");
+                if (pend_n & 2) {
+                    void* pp2 = (void*)((bf16_t*)pend_ptr + (size_t)8 * p.ldu);
+                    asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(pp2), "v"(pend_val2) : "memory");
+                }
+            }
         } else {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -412,9 +446,10 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
     int buf = 0;
     for (int t = 0; t < steps; ++t) {
         // this wave's share of step t has landed: everything but the DMA instructions of step t + 1 (the newest this wave has issued: six,
-        // seven in waves 0 and 1 which also fetch T) -- the two-byte U stores of the previous step are older than those and drain here too
+        // seven in the waves that also fetch T: waves 0 and 1 with RP = 32, wave 0 alone with RP = 64 -- wave 1 forms U there too, but
+        // its U stores of the previous step are older than the newest DMA instructions and drain here like those of wave 0)
         if (t + 1 < steps) {
-            if (w < 2) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
+            if (w < (RP == 32 ? 2 : 1)) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -455,20 +490,29 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             // cotangent: partial sum stored to Up; 3 / 1 = later blocks: added to Up (the host entry finishes U after the last block)
             const bool mine = l16 >= c_lo && l16 < c_hi;
             if (p.u_mode == 0) {
-                // through LDS ([32 rows][32 adapter columns], 16-bit): the wave then writes its 16 rows as whole 64-byte rows (one 16-byte
-                // store per lane) -- two-byte stores straight from the accumulator layout were 112 wave-instructions of eight 32-byte pieces
+                // through LDS ([32 rows][RP adapter columns], 16-bit): the wave then writes its 16 rows as whole 64-byte rows (one 16-byte
+                // store per lane; RP = 64: 128-byte rows, two stores per lane, eight whole rows each) -- two-byte stores straight from the
+                // accumulator layout were 112 wave-instructions of eight 32-byte pieces
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     bf16_t* ul = (bf16_t*)(smem + NBUF * BUF_BYTES) + (16 * w + 4 * fq + e) * RP;
                     ul[w0 + l16] = f32_to_bf16(mine ? ua[e] * p.scale : 0.f);
-                    ul[(w0 ^ 16) + l16] = f32_to_bf16(0.f);                   // the other half of the 32 adapter columns: other modalities
+                    if constexpr (RP == 32) ul[(w0 ^ 16) + l16] = f32_to_bf16(0.f);   // the other half of the 32 adapter columns: other modalities
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's 16 rows are in LDS (written and read by this wave only)
                 __builtin_amdgcn_wave_barrier();
-                const int row = 16 * w + (lane >> 2), ch = lane & 3;
-                pend_val = *(const u32x4_t*)(smem + NBUF * BUF_BYTES + row * (RP * 2) + ch * 16);
-                pend_ptr = (void*)(p.U + (size_t)(r0 + row) * p.ldu + ch * 8);
-                pend_n = (r0 + row) < rend ? 1 : 0;
+                if constexpr (RP == 32) {
+                    const int row = 16 * w + (lane >> 2), ch = lane & 3;
+                    pend_val = *(const u32x4_t*)(smem + NBUF * BUF_BYTES + row * (RP * 2) + ch * 16);
+                    pend_ptr = (void*)(p.U + (size_t)(r0 + row) * p.ldu + ch * 8);
+                    pend_n = (r0 + row) < rend ? 1 : 0;
+                } else {
+                    const int row = 16 * w + (lane >> 3), ch = lane & 7;      // rows `row` and `row + 8`
+                    pend_val = *(const u32x4_t*)(smem + NBUF * BUF_BYTES + row * (RP * 2) + ch * 16);
+                    pend_val2 = *(const u32x4_t*)(smem + NBUF * BUF_BYTES + (row + 8) * (RP * 2) + ch * 16);
+                    pend_ptr = (void*)(p.U + (size_t)(r0 + row) * p.ldu + ch * 8);
+                    pend_n = ((r0 + row) < rend ? 1 : 0) | ((r0 + row + 8) < rend ? 2 : 0);
+                }
             } else {
                 pend_val = u32x4_t{__float_as_uint(ua[0]), __float_as_uint(ua[1]), __float_as_uint(ua[2]), __float_as_uint(ua[3])};
                 pend_ptr = (void*)(p.Up + (size_t)(r0 + 16 * w + 4 * fq) * RP + w0 + l16);
@@ -477,7 +521,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             }
         } else {
             // dB[128 columns of this wave, window] += dY^T . T over the rows of this step (rows beyond the image: T fragment zeroed)
-            bf16x8 tf = fused::tr_frag(ts, RP * 2, 0, w0, lane);
+            bf16x8 tf = RP == 32 ? fused::tr_frag(ts, RP * 2, 0, w0, lane) : fused::tr_frag(ts, 32, 0, 0, lane);   // (RP = 64: the window alone is staged)
             const int nvalid = rend - r0;                     // >= 32 except in the last step
             if (nvalid < R) {
 #pragma unroll
@@ -628,7 +672,7 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
                                    int32_t M, int32_t N, int32_t Rp, float scale, float* u_partial, int32_t u_mode, void* stream) {
     REID_CHECK_ARG(u_mode >= 0 && u_mode <= 3 && (u_mode == 0 || u_partial), "reid_lora_bwd_fused: u_mode=%d needs u_partial", u_mode);
     REID_CHECK_ARG(dY && T && BT && U && dB && img_mod, "reid_lora_bwd_fused: null pointer");
-    REID_CHECK_ARG(N == fused::N && Rp == fused::RP, "reid_lora_bwd_fused: N=%d Rp=%d (this kernel is built for N = 768, Rp = 32)", N, Rp);
+    REID_CHECK_ARG(N == fused::N && (Rp == 32 || Rp == 64), "reid_lora_bwd_fused: N=%d Rp=%d (this kernel is built for N = 768, Rp = 32 or 64)", N, Rp);
     REID_CHECK_ARG(M > 0 && rows_per_img > 0 && mask_r > 0 && mask_r <= Rp, "reid_lora_bwd_fused: M=%d rows_per_img=%d mask_r=%d", M, rows_per_img, mask_r);
     REID_CHECK_ARG(lddy % 8 == 0 && ldt % 8 == 0 && ldbt % 8 == 0 && ldu % 2 == 0 && lddy >= N && ldt >= Rp && ldbt >= N && ldu >= Rp && lddb >= Rp,
                    "reid_lora_bwd_fused: leading dimensions");
@@ -636,14 +680,23 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
     fused::Params p{(const bf16_t*)dY, (const bf16_t*)T, (const bf16_t*)BT, (bf16_t*)U, dB, img_mod, lddy, ldt, ldbt, ldu, lddb, rows_per_img,
                     mask_r, M, 0, scale, u_partial, u_mode};
     // REID_LORA_IMPL: 1 = the slab kernel always; default: one image per workgroup where an image spans at least one 32-row step
-    if (reid_knob(KNOB_LORA_IMPL) != 1 && rows_per_img >= image::R && mask_r <= 16 && 16 % mask_r == 0) {
-        REID_MAX_LDS((image::lora_bwd_image_kernel), image::LDS_BYTES);
+    const bool use_image = reid_knob(KNOB_LORA_IMPL) != 1 && rows_per_img >= image::R && mask_r <= 16 && 16 % mask_r == 0;
+    // the slab kernel exists for Rp = 32 only: the class-row form (rows_per_img < 32) of 64 adapter columns is reid_mer_gemm + reid_gemm_tn
+    REID_CHECK_ARG(Rp == 32 || use_image, "reid_lora_bwd_fused: Rp=64 runs one image per workgroup only: rows_per_img=%d must be >= 32, mask_r=%d a "
+                   "divisor of 16, and REID_LORA_IMPL not 1 (the slab kernel is built for Rp = 32)", rows_per_img, mask_r);
+    if (use_image) {
         const int n_img = (M + rows_per_img - 1) / rows_per_img;
-        hipLaunchKernelGGL(image::lora_bwd_image_kernel, dim3(n_img), dim3(512), image::LDS_BYTES, (hipStream_t)stream, p);
+        if (Rp == 32) {
+            REID_MAX_LDS((image::lora_bwd_image_kernel<32>), image::BwdGeo<32>::LDS_BYTES);
+            hipLaunchKernelGGL(image::lora_bwd_image_kernel<32>, dim3(n_img), dim3(512), image::BwdGeo<32>::LDS_BYTES, (hipStream_t)stream, p);
+        } else {
+            REID_MAX_LDS((image::lora_bwd_image_kernel<64>), image::BwdGeo<64>::LDS_BYTES);
+            hipLaunchKernelGGL(image::lora_bwd_image_kernel<64>, dim3(n_img), dim3(512), image::BwdGeo<64>::LDS_BYTES, (hipStream_t)stream, p);
+        }
         REID_CHECK_LAUNCH("reid_lora_bwd_fused(image)");
         if (u_mode == 1) {                                    // last column block of a wide cotangent: every partial sum is in Up now
-            hipLaunchKernelGGL(image::u_finish_kernel, dim3((M * 16 + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)u_partial, (bf16_t*)U,
-                               ldu, img_mod, rows_per_img, mask_r, scale, M);
+            hipLaunchKernelGGL(image::u_finish_kernel, dim3((M * (Rp / 2) + 255) / 256), dim3(256), 0, (hipStream_t)stream, (const float*)u_partial, (bf16_t*)U,
+                               ldu, img_mod, rows_per_img, mask_r, scale, M, Rp);
             REID_CHECK_LAUNCH("reid_lora_bwd_fused(finish)");
         }
         return REID_OK;
@@ -661,7 +714,7 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
 extern "C" int reid_lora_da_fused(const void* X, int32_t ldx, const void* U, int32_t ldu, float* dA, int32_t ldda, const int32_t* img_mod,
                                   int32_t rows_per_img, int32_t mask_r, int32_t M, int32_t K, int32_t Rp, int32_t n_groups, void* stream) {
     REID_CHECK_ARG(X && U && dA && img_mod, "reid_lora_da_fused: null pointer");
-    REID_CHECK_ARG(M > 0 && K > 0 && K % 768 == 0 && Rp == 32 && (n_groups == 1 || n_groups == 3), "reid_lora_da_fused: M=%d K=%d Rp=%d groups=%d (K a multiple of 768, Rp = 32, 1 or 3 groups)", M, K, Rp, n_groups);
+    REID_CHECK_ARG(M > 0 && K > 0 && K % 768 == 0 && (Rp == 32 || Rp == 64) && (n_groups == 1 || n_groups == 3), "reid_lora_da_fused: M=%d K=%d Rp=%d groups=%d (K a multiple of 768, Rp = 32 or 64, 1 or 3 groups)", M, K, Rp, n_groups);
     REID_CHECK_ARG(rows_per_img >= image::R && mask_r > 0 && mask_r <= 16 && 16 % mask_r == 0, "reid_lora_da_fused: rows_per_img=%d (>= 32) mask_r=%d (a divisor of 16)", rows_per_img, mask_r);
     REID_CHECK_ARG(ldx % 8 == 0 && ldu % 8 == 0 && ldx >= K && ldu >= n_groups * Rp && ldda >= K, "reid_lora_da_fused: leading dimensions");
     REID_CHECK_ARG(((uintptr_t)X | (uintptr_t)U) % 16 == 0, "reid_lora_da_fused: operand alignment");

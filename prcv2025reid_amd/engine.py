@@ -557,7 +557,7 @@ class Engine:
                 for dY, BT, U, kw, tns in calls:
                     # tns[0] = (dY, T, dB): with N = 768 output columns (every linear but fc1) U and dB come out of ONE pass over dY
                     same = tns[0][0].data_ptr() == dY.data_ptr() and tns[0][0].shape == dY.shape and tns[0][0].stride() == dY.stride()
-                    if same and ops.lora_bwd_fused_ok(dY.shape[1], tns[0][1].shape[1]):
+                    if same and ops.lora_bwd_fused_ok(dY.shape[1], tns[0][1].shape[1], kw['rows_per_img'], kw['mask_r']):
                         ops.lora_bwd_fused(dY, tns[0][1], BT, U, tns[0][2], kw['img_mod'], kw['rows_per_img'], kw['mask_r'], kw['alpha'],
                                            u_partial=u_part[:dY.shape[0]] if dY.shape[1] > 768 else None)
                         rest = tns[1:]

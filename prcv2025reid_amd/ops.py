@@ -178,8 +178,8 @@ def cast_f32_bf16(src, dst):
 
 
 def lora_bwd_fused(dY, T, BT, U, dB, img_mod, rows_per_img, mask_r, scale, u_partial=None):
-    """U = mask(dY . B) * scale and dB += dY^T . T from one pass over dY (Rp = 32; N = 768, or a multiple of 768 as column blocks with
-    the fp32 scratch ``u_partial`` [M, 32]); see reid_lora_bwd_fused."""
+    """U = mask(dY . B) * scale and dB += dY^T . T from one pass over dY (Rp = 32, or 64 with ``rows_per_img`` >= 32 and ``mask_r`` a
+    divisor of 16; N = 768, or a multiple of 768 as column blocks with the fp32 scratch ``u_partial`` [M, Rp]); see reid_lora_bwd_fused."""
     N = dY.shape[1]
     nb = N // 768
     if nb > 1 and u_partial is None:
@@ -199,11 +199,18 @@ def lora_da_fused(X, U, dA, img_mod, rows_per_img, mask_r, n_groups=1):
 
 
 def lora_da_fused_ok(K, Rp, rows_per_img, mask_r, n_groups):
-    return K % 768 == 0 and Rp == 32 and rows_per_img >= 32 and mask_r <= 16 and 16 % mask_r == 0 and n_groups in (1, 3)
+    """Whether reid_lora_da_fused takes this shape: Rp = 32 or 64 adapter columns per group, images of at least one 32-row step."""
+    return K % 768 == 0 and Rp in (32, 64) and rows_per_img >= 32 and mask_r <= 16 and 16 % mask_r == 0 and n_groups in (1, 3)
 
 
-def lora_bwd_fused_ok(N, Rp):
-    return N % 768 == 0 and N // 768 in (1, 2, 3, 4) and Rp == 32
+def lora_bwd_fused_ok(N, Rp, rows_per_img=None, mask_r=None):
+    """Whether reid_lora_bwd_fused takes this shape.  Rp = 32: any rows_per_img / mask_r (the slab kernel takes what the image kernel
+    does not).  Rp = 64: the image kernel only, which needs ``rows_per_img`` >= 32 and ``mask_r`` a divisor of 16."""
+    if N % 768 != 0 or N // 768 not in (1, 2, 3, 4):
+        return False
+    if Rp == 32:
+        return True
+    return Rp == 64 and rows_per_img is not None and mask_r is not None and rows_per_img >= 32 and 0 < mask_r <= 16 and 16 % mask_r == 0
 
 
 def merge_lora_table(table, n_entries, max_tiles, arena, weff, Rp, r, nmod, scaling):
