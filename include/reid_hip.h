@@ -459,6 +459,28 @@ int64_t reid_augment_ws_bytes(int32_t n, int32_t S);
 int reid_augment_images(const void* src, int64_t src_bytes, const int32_t* table, const int32_t* host_table, int32_t n,
                         int32_t S, const float* lut, void* ws, int64_t ws_bytes, float* out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * k-reciprocal re-ranking (Zhong et al., CVPR 2017) of pooled unit rows X = [Q; G], N = Nq + Ng <= 65 536, dense; the
+ * definition is DESIGN.md "k-reciprocal re-ranking" (the reference has none).  kh = round-half-to-even(k1 / 2).
+ *   nbr   i32 [N, ldn >= k1 + 1]: row i of the pooled ranking (score descending, index ascending; i itself is an entry)
+ *   reid_rerank_weights   R(i, k) = { j in nbr[i, :k+1] : i in nbr[j, :k+1] };  R*(i) = R(i, k1) plus every R(j, kh),
+ *         j in R(i, k1), with 3 |R(j, kh) & R(i, k1)| > 2 |R(j, kh)|;  V[i, c] = exp(x_i.x_c - 1) / sum over R*(i), else 0.
+ *         X f32 [N, ldx >= D]; V f32 [N, ldv >= N], columns < N of every row zero-filled by the call.  1 <= k1 <= 64, k1 + 1 <= N.
+ *   reid_rerank_expand    V2[i, :N] = (1 / k2) sum_{t < k2} V[nbr[i, t], :N]; 1 <= k2 <= k1 + 1 (k2 = 1 copies V bit for bit);
+ *         ldv, ldo multiples of 4, 16-byte aligned.
+ *   reid_rerank_jaccard   out[q, g] = (1 - lambda) m / (2 - m) + lambda cosr[q, g], m = sum_{j < N} min(A[q, j], B[g, j]), for
+ *         nq rows of A (a query chunk of V2) and Ng rows of B (V2[Nq:]), both non-negative, lda and ldb multiples of 4,
+ *         16-byte aligned; cosr f32 [nq, ldc >= Ng]; out f32 [nq, ldo >= Ng], ldo % 4 == 0 (what reid_rank_metrics accepts),
+ *         columns >= Ng are not written.
+ * All fp32, deterministic (no atomics), nothing allocated or synchronised.
+ * ------------------------------------------------------------------------------------------ */
+int reid_rerank_weights(const int32_t* nbr, int32_t ldn, const float* X, int32_t ldx, float* V, int64_t ldv, int32_t N,
+                        int32_t D, int32_t k1, void* stream);
+int reid_rerank_expand(const float* V, int64_t ldv, const int32_t* nbr, int32_t ldn, float* V2, int64_t ldo, int32_t N,
+                       int32_t k1, int32_t k2, void* stream);
+int reid_rerank_jaccard(const float* A, int64_t lda, const float* B, int64_t ldb, const float* cosr, int64_t ldc, float* out,
+                        int64_t ldo, int32_t nq, int32_t Ng, int32_t N, float lambda, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,12 +11,15 @@ The reference scores one query at a time, argsorts the whole gallery row and wal
   * AP / CMC come from ``reid_rank_metrics`` (csrc/metrics.hip): ranks of the positives only, no sort of the gallery.
 Nothing here falls back to the CPU; the pure-Python oracle lives in oracle/reid_oracle.py and is used by tests only.
 """
-from typing import Dict, List, Optional, Sequence
+from typing import TYPE_CHECKING, Dict, List, Optional, Sequence
 
 import torch
 
 from . import _lib, ops
 from .retrieval import GalleryIndex, l2_normalize
+
+if TYPE_CHECKING:          # (rerank.py imports this module: the class is only named in annotations here)
+    from .rerank import RerankParams
 
 _SCALE = 16.0        # features are scaled into the 16-bit formats' comfortable range before splitting (undone by alpha)
 
@@ -39,6 +42,21 @@ def _split_operands(Qf: torch.Tensor, Gf: torch.Tensor):
     return torch.cat([q[i] for i, _ in pairs], 1).contiguous(), torch.cat([g[j] for _, j in pairs], 1).contiguous()
 
 
+def split_gallery(Gf: torch.Tensor) -> torch.Tensor:
+    """The gallery half of the split operands (rows padded with zeros to a multiple of 4), built once per gallery."""
+    pad = (-Gf.shape[0]) % 4
+    Gp = torch.cat([Gf, torch.zeros(pad, Gf.shape[1], device=Gf.device)], 0) if pad else Gf
+    return _split_operands(Gp[:1], Gp)[1]
+
+
+def split_scores(Qf: torch.Tensor, Gcat: torch.Tensor) -> torch.Tensor:
+    """fp32-grade cosine rows [nq, Gcat rows] of normalised queries against ``split_gallery``'s operand."""
+    Qcat = _split_operands(Qf, Qf[:1])[0]
+    S = torch.empty(Qf.shape[0], Gcat.shape[0], device=Qf.device)
+    ops.gemm(Qcat, Gcat, S, alpha=1.0 / (_SCALE * _SCALE))
+    return S
+
+
 class ProtocolEvaluator:
     """Gallery-side state built once: normalised features, split 16-bit operand, pid CSR, image ids."""
 
@@ -50,9 +68,7 @@ class ProtocolEvaluator:
         self.dev = g.device
         self.Gf = g if normalized else l2_normalize(g)
         self.Ng, self.D = self.Gf.shape
-        pad = (-self.Ng) % 4
-        Gp = torch.cat([self.Gf, torch.zeros(pad, self.D, device=self.dev)], 0) if pad else self.Gf
-        self._Gcat = _split_operands(Gp[:1], Gp)[1]          # only the gallery half is kept
+        self._Gcat = split_gallery(self.Gf)                   # only the gallery half is kept
         pids = gallery_pids.to(self.dev).long()
         self.g_pid = pids.to(torch.int32).contiguous()
         uniq, inv = torch.unique(pids, return_inverse=True)
@@ -80,14 +96,18 @@ class ProtocolEvaluator:
         Qf = q_feats.contiguous().float().to(self.dev)
         if not normalized:
             Qf = l2_normalize(Qf)
-        Qcat = _split_operands(Qf, Qf[:1])[0]
-        S = torch.empty(Qf.shape[0], self._Gcat.shape[0], device=self.dev)
-        ops.gemm(Qcat, self._Gcat, S, alpha=1.0 / (_SCALE * _SCALE))
-        return S
+        return split_scores(Qf, self._Gcat)
+
+    def _reranker(self, q_feats: torch.Tensor, rerank: 'RerankParams', normalized: bool = False):
+        """Pooled state of one re-ranked evaluation (rerank.py): every query of the call at once."""
+        from .rerank import Reranker
+        Qf = q_feats.contiguous().float().to(self.dev)
+        return Reranker(Qf if normalized else l2_normalize(Qf), self.Gf, rerank, self._Gcat)
 
     def per_query(self, q_feats: torch.Tensor, q_pids: torch.Tensor, q_img_ids: Optional[Sequence] = None,
-                  ignore_same_img: bool = True, chunk: int = 1024, normalized: bool = False):
-        """(ap f64 [Nq], rank1 i32 [Nq], npos i32 [Nq]) on the device."""
+                  ignore_same_img: bool = True, chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None):
+        """(ap f64 [Nq], rank1 i32 [Nq], npos i32 [Nq]) on the device.  ``rerank``: a ``RerankParams`` ranks by the k-reciprocal
+        re-ranked similarity s* (rerank.py) instead of the cosine; the same-image exclusion is the same."""
         Nq = q_feats.shape[0]
         qp = q_pids.to(self.dev).long()
         pos = torch.searchsorted(self._uniq, qp).clamp(max=self._uniq.numel() - 1)
@@ -106,16 +126,18 @@ class ProtocolEvaluator:
         ap = torch.zeros(Nq, dtype=torch.float64, device=self.dev)
         rank1 = torch.zeros(Nq, dtype=torch.int32, device=self.dev)
         npos = torch.zeros(Nq, dtype=torch.int32, device=self.dev)
+        rr = None if rerank is None else self._reranker(q_feats, rerank, normalized)
         for a in range(0, Nq, chunk):
             b = min(Nq, a + chunk)
-            S = self.scores(q_feats[a:b], normalized)
+            S = self.scores(q_feats[a:b], normalized) if rr is None else rr.rows(a, b)
             ops.rank_metrics(S, self.g_pid, self.g_img, qp32[a:b], slot[a:b], None if excl is None else excl[a:b].contiguous(),
                              self.csr_off, self.csr_idx, self.Ng, self.max_pos, ap[a:b], rank1[a:b], npos[a:b])
         return ap, rank1, npos
 
-    def rank_and_metrics(self, q_feats, q_pids, q_img_ids=None, ignore_same_img: bool = True, chunk: int = 1024) -> Dict[str, float]:
+    def rank_and_metrics(self, q_feats, q_pids, q_img_ids=None, ignore_same_img: bool = True, chunk: int = 1024,
+                         rerank: Optional['RerankParams'] = None) -> Dict[str, float]:
         """Same dictionary as eval_mm_protocol.py:455-469: queries without an (unmasked) positive are skipped."""
-        ap, rank1, npos = self.per_query(q_feats, q_pids, q_img_ids, ignore_same_img, chunk)
+        ap, rank1, npos = self.per_query(q_feats, q_pids, q_img_ids, ignore_same_img, chunk, rerank=rerank)
         if bool((npos < 0).any()):
             raise _lib.ReidHipError('a query has more than 8192 positives in the gallery: not supported by reid_rank_metrics')
         valid = npos > 0
@@ -135,12 +157,18 @@ class ProtocolEvaluator:
 
     # ---------------------------------------------------------------------------------------------------------
     def export_submission_csv(self, q_feats, query_keys: Sequence[str], gallery_img_names: Sequence, output_path: str,
-                              top_k: int = 100):
-        """eval_mm_protocol.py:595-649: one row per query, the top_k gallery image ids of the unmasked ranking."""
+                              top_k: int = 100, rerank: Optional['RerankParams'] = None, chunk: int = 1024):
+        """eval_mm_protocol.py:595-649: one row per query, the top_k gallery image ids of the unmasked ranking.  ``rerank``: a
+        ``RerankParams`` lists by the re-ranked similarity s* (stable descending sort of the s* rows on the device)."""
         import csv
-        if self.index is None:
-            self.index = GalleryIndex(self.Gf, normalized=True)
-        idx, _ = self.index.topk(q_feats.to(self.dev), k=min(top_k, self.Ng))
+        if rerank is None:
+            if self.index is None:
+                self.index = GalleryIndex(self.Gf, normalized=True)
+            idx, _ = self.index.topk(q_feats.to(self.dev), k=min(top_k, self.Ng))
+        else:
+            rr = self._reranker(q_feats, rerank)
+            idx = torch.cat([torch.sort(rr.rows(a, min(rr.Nq, a + chunk))[:, :self.Ng], dim=1, descending=True, stable=True)[1][:, :top_k]
+                             for a in range(0, rr.Nq, chunk)], 0)
         idx = idx.cpu().tolist()
         with open(output_path, 'w', newline='') as f:
             w = csv.writer(f)

@@ -372,6 +372,23 @@ def rank_metrics(scores, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, 
                                   stream_ptr()))
 
 
+def rerank_weights(nbr, X, V, k1):
+    """V[i, :N] = k-reciprocal weights of pooled row i (reid_rerank_weights, include/reid_hip.h); zero-fills V[:, :N] first."""
+    check(lib().reid_rerank_weights(ptr(nbr), nbr.stride(0), ptr(X), X.stride(0), ptr(V), V.stride(0), X.shape[0], X.shape[1], k1,
+                                    stream_ptr()))
+
+
+def rerank_expand(V, nbr, V2, k1, k2):
+    """V2[i, :N] = mean of V[nbr[i, :k2], :N] (reid_rerank_expand)."""
+    check(lib().reid_rerank_expand(ptr(V), V.stride(0), ptr(nbr), nbr.stride(0), ptr(V2), V2.stride(0), V.shape[0], k1, k2, stream_ptr()))
+
+
+def rerank_jaccard(A, B, cos, out, Ng, N, lambda_value):
+    """out[q, :Ng] = (1 - lambda) J + lambda cos, J from sum_j min(A[q, j], B[g, j]) over N columns (reid_rerank_jaccard)."""
+    check(lib().reid_rerank_jaccard(ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(cos), cos.stride(0), ptr(out), out.stride(0),
+                                    A.shape[0], Ng, N, lambda_value, stream_ptr()))
+
+
 def scatter_add_rows(src, index, out):
     """out[index[r]] += src[r] (f32 rows; int32 index)."""
     check(lib().reid_scatter_add_rows_f32(ptr(src), src.stride(0), ptr(index), ptr(out), out.stride(0), src.shape[0], src.shape[1],

@@ -1,0 +1,134 @@
+"""k-reciprocal re-ranking (prcv2025reid_amd/rerank.py, csrc/rerank.hip) per stage at protocol scale.
+
+    python tools/bench_rerank.py [--shapes 4096x16384,2048x8192] [--D 512] [--k1 20] [--k2 6] [--runs 10] [--yard-runs 10]
+
+Seeded clustered rows (16 images per identity), warm-up, then ``--runs`` timed runs per stage with device events: median, min and
+max in ms.  Stages: pooled kNN lists, cosine rows (all query chunks), weights, expand, Jaccard (all query chunks).  The Jaccard
+stage does Nq * Ng * N min-add pairs; its rate is pairs over the median time.
+
+Yardstick of the Jaccard stage (there is no older implementation): the same definition in torch ops on the same GPU and the same
+V2, chunked ``torch.minimum(A[:, None, :], B[None, :, :]).sum(-1)``, then J and the blend.  Its result is compared with the
+kernel's before it is timed.  Last, the accuracy line: mAP of the small Gaussian test fixture before and after re-ranking, fp64
+reference against the evaluator.  One JSON line per shape and one for the accuracy line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch
+
+from prcv2025reid_amd import ops
+from prcv2025reid_amd.evaluate import ProtocolEvaluator, split_gallery, split_scores
+from prcv2025reid_amd.rerank import RerankParams, Reranker
+from prcv2025reid_amd.retrieval import GalleryIndex
+
+
+def timed(fn, runs, warmup=2):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(runs):
+        e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return {'median_ms': statistics.median(ms), 'min_ms': min(ms), 'max_ms': max(ms), 'runs': runs}
+
+
+def clustered(Nq, Ng, D, dev, seed=0, per_id=16, noise=1.0):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    N = Nq + Ng
+    cent = torch.randn((N + per_id - 1) // per_id, D, device=dev, generator=g)
+    pid = torch.randperm(N, device=dev, generator=g) % cent.shape[0]
+    X = cent[pid] + noise * torch.randn(N, D, device=dev, generator=g)
+    return torch.nn.functional.normalize(X, dim=1), pid
+
+
+def torch_jaccard(A, B, cos, lam, qc=64, gc=1024):
+    out = torch.empty(A.shape[0], B.shape[0], device=A.device)
+    for a in range(0, A.shape[0], qc):
+        for b in range(0, B.shape[0], gc):
+            m = torch.minimum(A[a:a + qc, None, :], B[None, b:b + gc, :]).sum(-1)
+            out[a:a + qc, b:b + gc] = (1 - lam) * (m / (2 - m)) + lam * cos[a:a + qc, b:b + gc]
+    return out
+
+
+def run_shape(Nq, Ng, D, params, runs, yard_runs, chunk):
+    dev = torch.device('cuda', 0)
+    X, _ = clustered(Nq, Ng, D, dev)
+    N = Nq + Ng
+    k1, k2, lam = params.k1, params.k2, params.lambda_value
+    res = {'Nq': Nq, 'Ng': Ng, 'N': N, 'D': D, 'k1': k1, 'k2': k2, 'lambda': lam, 'chunk': chunk}
+    index = GalleryIndex(X, normalized=True)
+    res['knn_lists'] = timed(lambda: index.topk(X, k=k1 + 1, normalized=True), runs)
+    nbr = index.topk(X, k=k1 + 1, normalized=True)[0]
+    Gcat = split_gallery(X[Nq:])
+    res['cosine_rows'] = timed(lambda: [split_scores(X[a:a + chunk], Gcat) for a in range(0, Nq, chunk)], runs)
+    ld = (N + 3) // 4 * 4
+    V = torch.empty(N, ld, device=dev); V2 = torch.empty(N, ld, device=dev)
+    res['weights'] = timed(lambda: ops.rerank_weights(nbr, X, V, k1), runs)
+    res['expand'] = timed(lambda: ops.rerank_expand(V, nbr, V2, k1, k2), runs)
+    res['v2_nonzero_fraction'] = float((V2[:, :N] != 0).float().mean())
+    cos = [split_scores(X[a:a + chunk], Gcat) for a in range(0, Nq, chunk)]
+    outs = [torch.empty_like(c) for c in cos]
+
+    def jaccard():
+        for i, a in enumerate(range(0, Nq, chunk)):
+            ops.rerank_jaccard(V2[a:a + chunk], V2[Nq:], cos[i], outs[i], Ng, N, lam)
+    res['jaccard'] = timed(jaccard, runs)
+    pairs = float(Nq) * Ng * N
+    res['jaccard_pairs'] = pairs
+    res['jaccard_pairs_per_s'] = pairs / (res['jaccard']['median_ms'] * 1e-3)
+    res['total_median_ms'] = sum(res[s]['median_ms'] for s in ('knn_lists', 'cosine_rows', 'weights', 'expand', 'jaccard'))
+    res['whole_call'] = timed(lambda: [Reranker(X[:Nq], X[Nq:], params, Gcat).rows(a, min(Nq, a + chunk)) for a in range(0, Nq, chunk)][-1],
+                              max(3, runs // 3), warmup=1)
+    # yardstick: the same V2 through torch ops; compared before it is timed
+    A, B = V2[:Nq, :N], V2[Nq:, :N]
+    cos_all = torch.cat([c[:, :Ng] for c in cos], 0)
+    want = torch_jaccard(A[:128], B, cos_all[:128], lam)
+    res['kernel_vs_torch_max_abs'] = float((outs[0][:128, :Ng] - want).abs().max())
+    res['torch_jaccard'] = timed(lambda: torch_jaccard(A, B, cos_all, lam), yard_runs, warmup=1)
+    res['torch_over_kernel'] = res['torch_jaccard']['median_ms'] / res['jaccard']['median_ms']
+    return res
+
+
+def accuracy_line():
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import numpy as np
+    import rerank_ref as R
+    X, qp, gp = R.gaussian_fixture(422, 32, 219, 64, 24, 2.2)
+    Nq, k1, k2, lam = 32, 8, 3, 0.3
+    ref = R.rerank_ref(X, Nq, k1, k2, lam)
+    keep = np.ones(len(gp), bool)
+
+    def mean_ap(s):
+        return float(np.mean([R.ap_cmc(s[i], gp, qp[i], keep)[0] for i in range(Nq)]))
+    ev = ProtocolEvaluator(torch.as_tensor(X[Nq:]).cuda(), torch.as_tensor(gp), normalized=True)
+    Q, qpt = torch.as_tensor(X[:Nq]).cuda(), torch.as_tensor(qp)
+    return {'fixture': 'gaussian seed 422, 32 x 219, D 64, k1 8, k2 3, lambda 0.3',
+            'ref_mAP_cosine': mean_ap(ref['cos'][:Nq, Nq:]), 'ref_mAP_reranked': mean_ap(ref['s']),
+            'gpu_mAP_cosine': ev.rank_and_metrics(Q, qpt)['mAP'],
+            'gpu_mAP_reranked': ev.rank_and_metrics(Q, qpt, rerank=RerankParams(k1, k2, lam))['mAP']}
+
+
+if __name__ == '__main__':
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--shapes', default='4096x16384,2048x8192')
+    ap.add_argument('--D', type=int, default=512)
+    ap.add_argument('--k1', type=int, default=20)
+    ap.add_argument('--k2', type=int, default=6)
+    ap.add_argument('--lambda-value', type=float, default=0.3)
+    ap.add_argument('--runs', type=int, default=10)
+    ap.add_argument('--yard-runs', type=int, default=10)
+    ap.add_argument('--chunk', type=int, default=1024)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit('bench_rerank.py needs the GPU: nothing is measured without one')
+    for shape in a.shapes.split(','):
+        Nq, Ng = (int(v) for v in shape.split('x'))
+        print(json.dumps(run_shape(Nq, Ng, a.D, RerankParams(a.k1, a.k2, a.lambda_value), a.runs, a.yard_runs, a.chunk)), flush=True)
+    print(json.dumps(accuracy_line()), flush=True)
