@@ -166,7 +166,8 @@ int reid_layernorm_bwd(const void* dy, int32_t dy_dtype, int32_t lddy, const flo
  * Patch extraction (im2col of the k=s=16 conv, models/patch_embeds.py:45-76):
  *   images f32 [n_img, 3, H, W] -> patches bf16 [n_img*(H/16)*(W/16), cin*256]; cin == 1 first
  *   averages the three channels (patch_embeds.py:63-65).  The conv itself is reid_mer_gemm.
- * cls rows: x[img*tokens + 0] = cls + pos[0]   (models/clip_backbone.py:269-273)
+ * cls rows: x[img*tokens + 0] = cls + pos[0]   (models/clip_backbone.py:269-273); cols % 4 == 0, ldx % 4 == 0, ldx >= cols (16-byte
+ *   stores); no other row and no padding column of x is written.
  * ------------------------------------------------------------------------------------------ */
 int reid_patch_im2col(const float* images, void* patches, int32_t n_img, int32_t H, int32_t W,
                       int32_t patch, int32_t cin, void* stream);
@@ -195,6 +196,8 @@ int reid_attn_bwd(const void* qkv, int32_t ld, const uint8_t* key_mask, const vo
 /* ------------------------------------------------------------------------------------------
  * Element-wise helpers.
  * ------------------------------------------------------------------------------------------ */
+/* fp32 -> the flavor's 16-bit format, round-to-nearest-even (IEEE half saturates finite overflow to +-65504; inf and NaN pass), 16-byte
+ * aligned pointers; and back, exactly.  Exactly n elements are written. */
 int reid_cast_f32_bf16(const float* src, void* dst, int64_t n, void* stream);
 int reid_cast_bf16_f32(const void* src, float* dst, int64_t n, void* stream);
 /* Batched fp32 -> bf16 repack of many small matrices that live in one fp32 arena (the LoRA parameters):
@@ -235,11 +238,12 @@ int reid_lora_da_fused(const void* X, int32_t ldx, const void* U, int32_t ldu, f
  * Ranks: r <= 64 per modality and nmod * r <= Rp (up to 64 adapter rows are staged at once, more one modality at a time: same results). */
 int reid_merge_lora_table(const int64_t* table, int32_t n_entries, int32_t max_tiles, const float* arena, void* weff,
                           int32_t Rp, int32_t r, int32_t nmod, float scaling, void* stream);
-/* dst[r, :] = src[index[r], :] (f32, cols % 4 == 0);  scatter_add is the adjoint. */
+/* dst[r, :] = src[index[r], :] (f32; cols, lds, ldd multiples of 4; every index inside src);  scatter_add is the adjoint. */
 int reid_gather_rows_f32(const float* src, int32_t lds, const int32_t* index, float* dst, int32_t ldd,
                          int32_t rows, int32_t cols, void* stream);
 /* Text-tower input (HF CLIPTextEmbeddings, models/clip_backbone.py:307): out[b*T + t, :] = tok[ids[b, t], :] + pos[t, :]
- * (f32 tables [vocab, D] / [>= T, D], ids int64 [B, T]; ids outside the vocabulary are clamped). */
+ * (f32 tables [vocab, D] / [>= T, D], ids int64 [B, T], D % 4 == 0; ids outside the vocabulary are clamped as 64-bit numbers: below 0
+ * to row 0, at or above vocab to row vocab - 1). */
 int reid_embed_tokens(const float* tok, const float* pos, const int64_t* ids, float* out, int32_t B, int32_t T, int32_t D,
                       int32_t vocab, void* stream);
 /* out[index[r], :] += src[r, :] (f32; rows with an index outside [0, out_rows) are skipped): gradient of an embedding
@@ -270,7 +274,8 @@ int reid_bnneck_fwd(const float* x, int32_t ldx, const float* gamma, const float
                     float* y, void* y_bf16, int32_t ldy, float* mean, float* invstd, float* rnorm,
                     int32_t rows, int32_t D, float eps, float momentum, float scale, void* stream);
 /* bwd phase 1: per-row L2-normalise backward -> dz (grad wrt BN output), and column sums
- *   sum_dz[D], sum_dz_xhat[D] (all-reduced by the caller under data parallelism);
+ *   sum_dz[D], sum_dz_xhat[D] (all-reduced by the caller under data parallelism); dy and x are read 16 bytes at a time: lddy and ldx
+ *   multiples of 4 and >= D; dz is [rows, D] contiguous;
  * bwd phase 2: dx = gamma*invstd*(dz - sum_dz/count - xhat*sum_dz_xhat/count); dgamma = sum_dz_xhat; dbeta = sum_dz */
 int reid_bnneck_bwd_p1(const float* dy, int32_t lddy, const float* x, int32_t ldx, const float* gamma,
                        const float* beta, const float* mean, const float* invstd, const float* rnorm,
@@ -363,7 +368,9 @@ int reid_cosine_topk_stream(const float* Qf, const float* Gf, int32_t Nq, int32_
                             float* out_score, void* stream);
 /* fp32 C[M,N] = act(alpha * op(A).op(B) + bias[n]) + beta*C on the vector ALU with arbitrary element strides
  * (A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn]); the small exact GEMMs of the head
- * (models/model.py:57-77,152-162) and of the SDM loss. */
+ * (models/model.py:57-77,152-162) and of the SDM loss.  act: REID_ACT_NONE, _GELU_ERF, _QUICK_GELU or _RELU; the RELU epilogue is
+ * torch.relu (a NaN stays NaN).  beta == 0: C is not read.  K > 0, ldc >= N.  The K range is split over the 8 (at most 256 tiles of
+ * 32 x 32) or 4 waves of a workgroup and reduced in a fixed order: bit-reproducible. */
 int reid_sgemm(const float* A, const float* B, float* C, int32_t M, int32_t N, int32_t K, int64_t sam, int64_t sak,
                int64_t sbk, int64_t sbn, int32_t ldc, float alpha, float beta, const float* bias, int32_t act,
                void* stream);
@@ -371,13 +378,19 @@ int reid_sgemm(const float* A, const float* B, float* C, int32_t M, int32_t N, i
  * Small fp32 pieces of the head: SemanticDisentanglementModule.forward (models/model.py:57-77) and
  * FeatureFusion.forward (:113-183) on [B,512] / [B,M<=8,512] tensors.
  *   reid_eltwise_f32: op 0 out=x+alpha*y, 1 relu(x), 2 relu' (x pre-activation, y = dy), 3 erf-GELU(x),
- *                     4 y*GELU'(x), 5 x*y, 6 nan_to_num(x, 0, 1e4, -1e4) (model.py:165)
+ *                     4 y*GELU'(x), 5 x*y, 6 nan_to_num(x, 0, 1e4, -1e4) (model.py:165), 7 dropout multiplier from a uniform draw x:
+ *                     1/(1-alpha) where x >= alpha, else 0 (out may be x).  relu and relu' are torch's on non-finite input: relu(NaN)
+ *                     = NaN, relu' is 0 where x <= 0 and dy elsewhere (NaN and +inf included) -- the SDM module's ReLU (model.py:42)
+ *                     is not followed by nan_to_num, so a diverged activation must stay visible to the loss's isfinite checks
  *   reid_small_attn_fwd/bwd: softmax(q k^T / 8 + key-padding mask) v over S <= 8 tokens, head_dim 64, fp32
  *                     (nn.MultiheadAttention, model.py:152-155); qkv [n_seq*S, ld] = q|k|v; probs [n_seq, heads, 8, 8] saved;
  *                     drop (optional, same layout as probs): attention-dropout multipliers 0 or 1/keep applied to the
- *                     probabilities after the softmax (nn.MultiheadAttention(dropout=0.1), model.py:35,95)
+ *                     probabilities after the softmax (nn.MultiheadAttention(dropout=0.1), model.py:35,95).
+ *                     ld >= 3*heads*64 (also lddqkv), ldo >= heads*64.  probs[item, i, j]: rows i < S are written, with +0 for masked
+ *                     keys and for j >= S; rows i >= S are not.  A sequence whose keys are ALL masked gives NaN in its rows of out and
+ *                     probs (what torch's softmax over nothing gives), and only there
  *   reid_masked_mean: out[b,:] = sum_m mask[b,m] x[b,m,:] / max(sum_m mask[b,m], 1) (model.py:168-178); backward != 0:
- *                     x = dout [B,D], out = dx [B,M,D]
+ *                     x = dout [B,D], out = dx [B,M,D] (all M rows written, +0 where mask == 0); B <= 65535
  * ------------------------------------------------------------------------------------------ */
 int reid_eltwise_f32(int32_t op, const float* x, const float* y, float* out, int64_t n, float alpha, void* stream);
 int reid_small_attn_fwd(const float* qkv, int32_t ld, const uint8_t* key_mask, const float* drop, float* out, int32_t ldo,
@@ -386,7 +399,8 @@ int reid_small_attn_bwd(const float* qkv, int32_t ld, const float* probs, const 
                         float* dqkv, int32_t lddqkv, int32_t n_seq, int32_t S, int32_t heads, void* stream);
 int reid_masked_mean(const float* x, const float* mask, float* out, int32_t B, int32_t M, int32_t D, int32_t backward,
                      void* stream);
-/* L2-normalise rows (F.normalize, train.py:442): x f32 [rows, D] -> y f32 and/or bf16. */
+/* L2-normalise rows (F.normalize, train.py:442): x f32 [rows, D] -> y = x * scale / max(||x||, eps) as f32 and/or bf16 (one ldy for both).
+ * D % 4 == 0, D <= 1024; ldx and ldy multiples of 4 and >= D (16-byte accesses). */
 int reid_l2norm_rows(const float* x, int32_t ldx, float* y, void* y_bf16, int32_t ldy, int32_t rows, int32_t D,
                      float eps, float scale, void* stream);
 

@@ -14,6 +14,9 @@ namespace {
 // no workgroup barrier inside the loop), the next K-step's operands prefetched into registers while the current one is
 // multiplied, and ONE deterministic in-LDS reduction of the partial tiles at the end (fixed order: bit-reproducible).
 // (The first version -- 64x64 tiles, K = 16 per barrier pair, no prefetch -- took 42 us per call, 4.9 ms per train step.)
+// torch.relu: max(x, 0) that PROPAGATES a NaN (fmaxf returns the other operand): the SDM module's ReLU (models/model.py:42) is not
+// followed by nan_to_num, so a diverged activation must reach the loss's isfinite checks instead of turning into 0.
+__device__ __forceinline__ float relu_f(float v) { return v > 0.f ? v : (v != v ? v : 0.f); }
 constexpr int SG_PITCH = 36;                            // floats per staged k-row: 32 + 4 (conflict-free transposed writes)
 template <int SG_WAVES>
 __global__ __launch_bounds__(SG_WAVES * 64) void sgemm_kernel(const float* __restrict__ A, const float* __restrict__ B,
@@ -104,7 +107,7 @@ __global__ __launch_bounds__(SG_WAVES * 64) void sgemm_kernel(const float* __res
         if (bias) v += bias[n];
         if (act == REID_ACT_GELU_ERF) v = gelu_erf_f(v);
         else if (act == REID_ACT_QUICK_GELU) v = quick_gelu_f(v);
-        else if (act == REID_ACT_RELU) v = fmaxf(v, 0.f);
+        else if (act == REID_ACT_RELU) v = relu_f(v);
         float* c = C + (size_t)m * ldc + n;
         *c = beta == 0.f ? v : v + beta * *c;
     }
@@ -370,45 +373,6 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
     }
 }
 
-// y = x / max(||x||, eps): dx (+)= (dy - y (y.dy)) / max(||x||, eps)
-__global__ __launch_bounds__(256) void l2norm_bwd_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ dy, int lddy,
-                                                         float* __restrict__ dx, int lddx, int rows, int D, float eps,
-                                                         int accumulate) {
-    REID_T16_ENTER();
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int nv = D >> 2;
-    f32x4 xv[MAXV], gv[MAXV];
-    float ss = 0.f, dot = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + i * 64;
-        xv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; gv[i] = xv[i];
-        if (c < nv) {
-            xv[i] = *(const f32x4*)(x + (size_t)row * ldx + c * 4);
-            gv[i] = *(const f32x4*)(dy + (size_t)row * lddy + c * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { ss += xv[i][e] * xv[i][e]; dot += xv[i][e] * gv[i][e]; }
-        }
-    }
-    const float n = fmaxf(sqrtf(wave_sum(ss)), eps);
-    const float rn = 1.f / n;
-    dot = wave_sum(dot) * rn * rn;      // (y.dy)/n with y = x/n  ->  x.dy / n^2
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) {
-            float* d = dx + (size_t)row * lddx + c * 4;
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = (gv[i][e] - xv[i][e] * dot) * rn;
-            if (accumulate) o += *(const f32x4*)d;
-            *(f32x4*)d = o;
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------ small fp32 helpers of the head
 // (SDM module models/model.py:57-77 and FeatureFusion :113-183 work on [B,512] / [B,5,512] tensors: latency bound)
 __global__ void eltwise_kernel(int op, const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out, long n, float alpha) {
@@ -418,8 +382,8 @@ __global__ void eltwise_kernel(int op, const float* __restrict__ x, const float*
         float r;
         switch (op) {
             case 0: r = a + alpha * y[i]; break;                       // add
-            case 1: r = fmaxf(a, 0.f); break;                          // relu
-            case 2: r = a > 0.f ? y[i] : 0.f; break;                   // relu backward: x = pre-activation, y = dy
+            case 1: r = relu_f(a); break;                              // relu (NaN stays NaN, as torch.relu)
+            case 2: r = a <= 0.f ? 0.f : y[i]; break;                  // relu backward: x = pre-activation, y = dy (a NaN x passes dy, as torch)
             case 3: r = gelu_erf_f(a); break;                          // gelu
             case 4: r = y[i] * dgelu_erf_f(a); break;                  // gelu backward
             case 5: r = a * y[i]; break;                               // mul
@@ -542,7 +506,7 @@ __global__ __launch_bounds__(256) void masked_mean_kernel(const float* __restric
         if (ml == 0) out[(size_t)b * D + c] = ((ps[0][cl] + ps[1][cl]) + (ps[2][cl] + ps[3][cl])) / cnt;
     } else {
         const float g = x[(size_t)b * D + c] / cnt;      // x = dout [B, D]
-        for (int m = ml; m < M; m += 4) out[((size_t)b * M + m) * D + c] = mk[m] * g;
+        for (int m = ml; m < M; m += 4) { const float w = mk[m]; out[((size_t)b * M + m) * D + c] = w != 0.f ? w * g : 0.f; }   // masked rows: +0, not -0
     }
 }
 
@@ -606,6 +570,7 @@ extern "C" int reid_bnneck_bwd_p1(const float* dy, int32_t lddy, const float* x,
                                   float* sum_dz_xhat, int32_t rows, int32_t D, float scale, void* stream) {
     REID_CHECK_ARG(dy && x && gamma && beta && mean && invstd && rnorm && dz && sum_dz && sum_dz_xhat, "reid_bnneck_bwd_p1: null pointer");
     REID_CHECK_ARG(rows > 0 && D % 4 == 0 && D <= 64 * 4 * MAXV, "reid_bnneck_bwd_p1: shape");
+    REID_CHECK_ARG(lddy % 4 == 0 && ldx % 4 == 0 && lddy >= D && ldx >= D, "reid_bnneck_bwd_p1: lddy=%d ldx=%d (multiples of 4, >= D)", lddy, ldx);
     hipStream_t s = (hipStream_t)stream;
     REID_CHECK_HIP(hipMemsetAsync(sum_dz, 0, D * sizeof(float), s), "hipMemsetAsync");
     REID_CHECK_HIP(hipMemsetAsync(sum_dz_xhat, 0, D * sizeof(float), s), "hipMemsetAsync");
@@ -667,6 +632,8 @@ extern "C" int reid_small_attn_fwd(const float* qkv, int32_t ld, const uint8_t* 
 extern "C" int reid_small_attn_bwd(const float* qkv, int32_t ld, const float* probs, const float* drop, const float* dout, int32_t ldo, float* dqkv,
                                    int32_t lddqkv, int32_t n_seq, int32_t S, int32_t heads, void* stream) {
     REID_CHECK_ARG(qkv && probs && dout && dqkv && n_seq > 0 && S >= 1 && S <= 8 && heads > 0, "reid_small_attn_bwd: bad args");
+    REID_CHECK_ARG(ld >= 3 * heads * 64 && ldo >= heads * 64 && lddqkv >= 3 * heads * 64,
+                   "reid_small_attn_bwd: ld=%d ldo=%d lddqkv=%d narrower than the %d heads", ld, ldo, lddqkv, heads);
     hipLaunchKernelGGL(small_attn_bwd_kernel, dim3((n_seq * heads + 3) / 4), dim3(256), 0, (hipStream_t)stream, qkv, ld, probs, drop, dout, ldo,
                        dqkv, lddqkv, n_seq, S, heads);
     REID_CHECK_LAUNCH("reid_small_attn_bwd");

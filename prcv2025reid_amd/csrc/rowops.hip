@@ -547,7 +547,8 @@ extern "C" int reid_patch_im2col(const float* images, void* patches, int32_t n_i
 
 extern "C" int reid_cls_rows(const float* cls, const float* pos0, float* x, int32_t ldx, int32_t n_img, int32_t tokens,
                              int32_t cols, void* stream) {
-    REID_CHECK_ARG(cls && pos0 && x && n_img > 0 && cols % 4 == 0 && ldx % 4 == 0, "reid_cls_rows: bad args");
+    REID_CHECK_ARG(cls && pos0 && x && n_img > 0 && tokens > 0 && cols > 0 && cols % 4 == 0 && ldx % 4 == 0, "reid_cls_rows: bad args");
+    REID_CHECK_ARG(ldx >= cols, "reid_cls_rows: ldx=%d < cols=%d", ldx, cols);
     const int n = n_img * (cols / 4);
     hipLaunchKernelGGL(cls_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, cls, pos0, x, ldx, n_img, tokens, cols);
     REID_CHECK_LAUNCH("reid_cls_rows");
@@ -631,7 +632,8 @@ extern "C" int reid_embed_tokens(const float* tok, const float* pos, const int64
 
 extern "C" int reid_l2norm_rows(const float* x, int32_t ldx, float* y, void* y_bf16, int32_t ldy, int32_t rows, int32_t D,
                                 float eps, float scale, void* stream) {
-    REID_CHECK_ARG(x && (y || y_bf16) && rows > 0 && D % 4 == 0 && D <= 64 * 4 * MAXV, "reid_l2norm_rows: bad args");
+    REID_CHECK_ARG(x && (y || y_bf16) && rows > 0 && D > 0 && D % 4 == 0 && D <= 64 * 4 * MAXV, "reid_l2norm_rows: bad args");
+    REID_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0 && ldx >= D && ldy >= D, "reid_l2norm_rows: ldx=%d ldy=%d (multiples of 4, >= D)", ldx, ldy);
     hipLaunchKernelGGL(l2norm_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, ldx, y, (bf16_t*)y_bf16, ldy, rows, D, eps, scale);
     REID_CHECK_LAUNCH("reid_l2norm_rows");
     return REID_OK;

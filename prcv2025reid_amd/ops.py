@@ -177,6 +177,12 @@ def cast_f32_bf16(src, dst):
     return dst
 
 
+def cast_bf16_f32(src, dst):
+    """dst (f32) = the values of the flavor's 16-bit ``src``, exactly."""
+    check(lib().reid_cast_bf16_f32(ptr(src), ptr(dst), src.numel(), stream_ptr()))
+    return dst
+
+
 def lora_bwd_fused(dY, T, BT, U, dB, img_mod, rows_per_img, mask_r, scale, u_partial=None):
     """U = mask(dY . B) * scale and dB += dY^T . T from one pass over dY (Rp = 32, or 64 with ``rows_per_img`` >= 32 and ``mask_r`` a
     divisor of 16; N = 768, or a multiple of 768 as column blocks with the fp32 scratch ``u_partial`` [M, Rp]); see reid_lora_bwd_fused."""
@@ -387,6 +393,13 @@ def rerank_jaccard(A, B, cos, out, Ng, N, lambda_value):
     """out[q, :Ng] = (1 - lambda) J + lambda cos, J from sum_j min(A[q, j], B[g, j]) over N columns (reid_rerank_jaccard)."""
     check(lib().reid_rerank_jaccard(ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(cos), cos.stride(0), ptr(out), out.stride(0),
                                     A.shape[0], Ng, N, lambda_value, stream_ptr()))
+
+
+def gather_rows(src, index, dst):
+    """dst[r] = src[index[r]] (f32 rows, cols % 4 == 0; int32 index)."""
+    check(lib().reid_gather_rows_f32(ptr(src), src.stride(0), ptr(index), ptr(dst), dst.stride(0), index.shape[0], dst.shape[1],
+                                     stream_ptr()))
+    return dst
 
 
 def scatter_add_rows(src, index, out):

@@ -1,4 +1,5 @@
 """Shared test helpers: rebuild golden cases from their seeds."""
+import math
 import os
 
 import numpy as np
@@ -169,3 +170,75 @@ def is_sentinel(t, fmt=None):
     if t.dtype == torch.float32:
         return t.view(torch.int32) == SENTINEL32
     return t.view(torch.int16) == SENTINEL16[fmt]
+
+
+# ---- transcendental epilogues (reid_mer_gemm, reid_sgemm, reid_eltwise_f32): derived error bounds ---------------------------------------------------------------------------
+# The kernel applies f to an EXACT fp32 input x, so its error is that of its own evaluation of f, then one rounding to the output
+# format.  u = 2^-24 (fp32 unit roundoff).
+#   * Phi(x) (common.h gauss_cdf_pdf / gelu_both_x2): Abramowitz-Stegun 7.1.26 has |erf error| <= 1.5e-7, so Phi is off by <= 7.5e-8
+#     absolutely; the two-lane form gelu_both_x2 (the lean GELU epilogues) adds <= 6e-8 (its comment: cdf = 0.5 + copysign(0.5 - q)).
+#     fp32 evaluation of q = 0.5 erfc: t = rcp(1 + p z) (v_rcp_f32 1 ulp, z and den rounded, the constants rounded: <= 4u relative),
+#     Horner on five alternating coefficients (sum |a_i| t^i <= 4.5 P(t), d log P / d log t <= 16: <= 11 * 4.5 u + 16 * 4u <= 114u),
+#     exp2 (v_exp_f32 1 ulp = 2u) of xs = -x^2 log2(e)/2 whose own rounding (two products, a rounded constant: 3u relative) moves the
+#     result by ln2 |xs| 3u, two more products: |dq| <= q (130 + 3 ln2 |xs|) u; cdf = 1 - q or 0.5 + (0.5 - q): <= 2u more.
+#   * Phi'(x) x term: x * 0.3989f * e: e as above ((4 + 3 ln2 |xs|) u relative), three roundings.
+#   * quick GELU x / (1 + __expf(-1.702 x)): the exponent a = 1.702 |x| (rounded constant, two products: 2u relative) moves
+#     E = exp(-1.702 x) by a 2u, exp 4u, so s = 1 / (1 + E) has relative error eps_s <= (2a + 4) u (1 - s) + 4u (sum, division).
+#     Where E overflows (x < -52) the kernel returns -0 for a value below 1e-36: an absolute 2^-100 covers it.
+AS_PHI = 7.5e-8
+X2_EXTRA = 6.0e-8
+U = 2.0 ** -24
+LN2 = math.log(2.0)
+FLOOR = 2.0 ** -100
+
+
+def _phi(x):
+    return 0.5 * torch.special.erfc(-x / math.sqrt(2.0))
+
+
+def _cdf_err(x, lean):
+    q = 0.5 * torch.special.erfc(x.abs() / math.sqrt(2.0))
+    xs = x * x * (0.5 / LN2)
+    return AS_PHI + (X2_EXTRA if lean else 0.0) + q * (130.0 + 3.0 * LN2 * xs) * U + 2.0 * U, xs
+
+
+def f_gelu(x, lean):
+    f = x * _phi(x)
+    ec, _ = _cdf_err(x, lean)
+    return f, x.abs() * ec + 2.0 * U * f.abs()
+
+
+def f_dgelu(x, lean):
+    pdf = torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+    d = _phi(x) + x * pdf
+    ec, xs = _cdf_err(x, lean)
+    return d, ec + (x * pdf).abs() * (7.0 + 3.0 * LN2 * xs) * U + 2.0 * U * d.abs()
+
+
+def _sig_err(x):
+    s = torch.sigmoid(1.702 * x)
+    return s, (2.0 * 1.702 * x.abs() + 4.0) * U * (1.0 - s) + 4.0 * U
+
+
+def f_quick(x):
+    s, es = _sig_err(x)
+    f = x * s
+    return f, f.abs() * (es + U) + FLOOR
+
+
+def f_dquick(x):
+    s, es = _sig_err(x)
+    k = 1.702 * x
+    d = s + k * s * (1.0 - s)
+    return d, s * es + k.abs() * s * (s * es + 2.0 * U) + (k * s * (1.0 - s)).abs() * (es + 4.0 * U) + U * d.abs() + FLOOR
+
+
+def check_bounded(out, f, err, fmt):
+    """|out - f| <= err + half a `fmt` spacing at the output (the final rounding).  Returns the worst share of the evaluation bound
+    `err` that an element uses beyond that half spacing, (|out - f| - spacing / 2) / err, which must be <= 1."""
+    o = out.double()
+    assert not bool(torch.isnan(o).any())
+    half = 0.5 * quantum16(torch.maximum(o.abs(), f.abs() + err), fmt)
+    ratio = float((((o - f).abs() - half) / err).max())
+    assert ratio <= 1.0, f'worst (error - rounding) / evaluation bound = {ratio:.3f}'
+    return ratio
