@@ -19,20 +19,14 @@
 // behind the side-stream reductions still own a fixed share of the items.  Per-workgroup timestamps of the forward kernel: K/V/Q
 // landing 3.9 us, first sweep 3.3, second sweep 3.6, stores 1.2; per item and CU the matrix pipe needs 2.2 us, the exponentials ~3 us,
 // HBM 4 us -- they add up rather than overlap with two 7-wave workgroups per CU.
-#include "common.h"
+#include "lds_tile.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short s4;
-typedef __attribute__((address_space(3))) s4* lds_s4_ptr;
+using namespace ldstile;
 
 constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ __forceinline__ int swz(int row, int c) { return c ^ ((row >> 1) & 7); }
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // Stage rows [0, 32 NT) x 64 of one head (column offset already applied to `base`, row stride ld) into a swizzled
 // [32 NT][64] LDS image with 16-byte LDS-DMA: every wave issues its 4 wave-instructions (8 rows each) back to back, so
@@ -47,10 +41,7 @@ __device__ __forceinline__ void stage_head(const bf16_t* __restrict__ base, int 
     for (int i = 0; i < 4; ++i) {
         const int rblk = (i * NT + wave) * 8;
         if (rblk >= row_limit) continue;                    // (wave-uniform) rows nobody will read: query tiles left out by q_tiles
-        const int row = rblk + (lane >> 3);
-        const int c = swz(row, lane & 7);
-        const int grow = row < S ? row : S - 1;
-        __builtin_amdgcn_global_load_lds((gptr_t)(base + (size_t)grow * ld + c * 8), (lptr_t)(lds + rblk * 128), 16, 0, 0);
+        stage_rows8(lds, rblk, lane, [&](int row, int c) { return base + (size_t)(row < S ? row : S - 1) * ld + c * 8; });
     }
 }
 
@@ -69,9 +60,7 @@ __device__ __forceinline__ bf16x8 col_frag(const char* img, int krow0, int col0,
     const int r_lo = krow0 + 4 * h + q, r_hi = r_lo + 8;
     const char* a_lo = img + r_lo * 128 + (swz(r_lo, col >> 3) << 4) + (col & 7) * 2;
     const char* a_hi = img + r_hi * 128 + (swz(r_hi, col >> 3) << 4) + (col & 7) * 2;
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)a_lo);
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)a_hi);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return tr_join(tr_read(a_lo), tr_read(a_hi));
 }
 
 // B operand (16 k x 32 cols) straight from global memory: column = matrix row (row0 + lane&31), k = 8 contiguous elements.
@@ -107,9 +96,7 @@ __device__ __forceinline__ bf16x8 row_frag_o(const char* img, int tile_row0, int
     return *(const bf16x8*)(img + tile_row0 * 128 + f.row[ks]);
 }
 __device__ __forceinline__ bf16x8 col_frag_o(const char* img, int krow0, int dt, const FragOff& f) {
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(img + krow0 * 128 + f.col_lo[dt]));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(img + krow0 * 128 + f.col_hi[dt]));
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return tr_join(tr_read(img + krow0 * 128 + f.col_lo[dt]), tr_read(img + krow0 * 128 + f.col_hi[dt]));
 }
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // v_exp_f32, x <= 0 here
 
@@ -675,9 +662,7 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const AttnParam
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
                 const int krow0 = kt * 32 + 16 * s2;
-                const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(Ds + krow0 * DS_ROW + ds_r));
-                const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(Ds + (krow0 + 8) * DS_ROW + ds_r));
-                const bf16x8 df = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const bf16x8 df = tr_join(tr_read(Ds + krow0 * DS_ROW + ds_r), tr_read(Ds + (krow0 + 8) * DS_ROW + ds_r));
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) dqt[dt] = mfma32(col_frag_o(Ks, krow0, dt, fo), df, dqt[dt]);
             }

@@ -298,7 +298,7 @@ __device__ __forceinline__ void store_tile_fast(const GemmParams& p, f32x4 (&acc
             for (int i = 0; i < TM; ++i) {
                 const int lr = lrow0 + 16 * i + frow;
 #pragma unroll
-                for (int pc = 0; pc < NP; ++pc) av[i][pc] = *(const bf16x8*)(aux_lds + lr * 512 + (((lchunk0 + fq + 4 * pc) ^ (lr & 15)) << 4));
+                for (int pc = 0; pc < NP; ++pc) av[i][pc] = *(const bf16x8*)(aux_lds + lr * 512 + (swz512(lr, lchunk0 + fq + 4 * pc) << 4));
             }
         } else if constexpr (HAS_AUX) {
 #pragma unroll
@@ -473,12 +473,12 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pp_kernel(const GemmParams p)
     GEMM_TRACE(1);
     if constexpr (EPI == EPI_MULAUX) {
         if (aux_staged) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             __syncthreads();
             store_tile_fast<TM, 4, EPI>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end, smem, wm * RW, wn * 8);
             GEMM_TRACE(2);
 #ifdef REID_GEMM_TRACE
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
             GEMM_TRACE(3);
 #endif
             return;
@@ -493,15 +493,15 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pp_kernel(const GemmParams p)
             const int row = 2 * rp + (lane >> 5);
             const int c = lane & 31;                         // destination chunk position; it holds source chunk c ^ (row & 15)
             const int gm = m0 + row < m_end ? m0 + row : m_end - 1;
-            const char* src = (const char*)p.aux + ((size_t)gm * p.ldaux + n0) * 2 + ((c ^ (row & 15)) << 4);
+            const char* src = (const char*)p.aux + ((size_t)gm * p.ldaux + n0) * 2 + (swz512(row, c) << 4);
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + rp * 1024), 16, 0, 0);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __syncthreads();
         store_tile_fast<TM, 4, EPI>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end, smem, wm * RW, wn * 8);
         GEMM_TRACE(2);
 #ifdef REID_GEMM_TRACE
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         GEMM_TRACE(3);
 #endif
         return;
@@ -510,7 +510,7 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pp_kernel(const GemmParams p)
     else store_tile_fast<TM, 4, EPI>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end);
     GEMM_TRACE(2);
 #ifdef REID_GEMM_TRACE
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     GEMM_TRACE(3);
 #endif
 }

@@ -1,17 +1,12 @@
 // Shared MFMA tile main loop of the gfx950 GEMM-shaped kernels (mer_gemm, cosine_topk).
 // See gemm.hip for the design notes.
 #pragma once
-#include "common.h"
+#include "lds_tile.h"
 #include <type_traits>
 
 namespace gemmcore {
 
-// physical 16-byte chunk of logical chunk c in row `row` of a [rows][64] bf16 tile (128-byte rows).
-// Two rows share one 256-byte bank row; rows r and r+2 would otherwise collide on every ds_read_b128.
-__device__ __forceinline__ int swz(int row, int c) { return c ^ ((row >> 1) & 7); }
-
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
+using namespace ldstile;   // swz (the [rows][64] image of every tile here), gptr_t / lptr_t, counted waits
 
 template <int BM, int BN, int WM, int WN>
 struct Cfg {
@@ -42,14 +37,12 @@ __device__ __forceinline__ void stage(const bf16_t* __restrict__ src, int ld, in
     constexpr int INSTR = ROWS / 8 / NW;
 #pragma unroll
     for (int i = 0; i < INSTR; ++i) {
-        const int rblk = (i * NW + wave) * 8;
-        const int r = rblk + (lane >> 3);
-        int c = swz(r, lane & 7);
-        if (HALF) c &= 3;
-        int grow = row0 + (perm ? perm32(r) : r);
-        grow = grow < row_max ? grow : row_max;
-        const bf16_t* g = src + (size_t)grow * ld + k0 + c * 8;
-        __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)(lds + rblk * 128), 16, 0, 0);
+        stage_rows8(lds, (i * NW + wave) * 8, lane, [&](int r, int c) {
+            if (HALF) c &= 3;
+            int grow = row0 + (perm ? perm32(r) : r);
+            grow = grow < row_max ? grow : row_max;
+            return src + (size_t)grow * ld + k0 + c * 8;
+        });
     }
 }
 
@@ -214,9 +207,49 @@ struct PPCfg {
     static constexpr int LDS_BYTES = 2 * BUF_BYTES;
 };
 
-__device__ __forceinline__ void pp_wait_vm4() { asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); }
-__device__ __forceinline__ void pp_wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void pp_wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// The pieces of one ping-pong K-tile that mainloop_pp and stream_pp share: the phase barrier, the fragment reads and the MFMA phase.  (Their
+// lane offsets, stage_a / stage_b and fragment offsets exist once in each: every shared form tried changed the kernels' machine code.)
+__device__ __forceinline__ void pp_bar() {
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+// fragment reads of K-tile buffer `buf`: a_base / b_base = the wave's SA / SB rows, foff = the lane-constant part of the address
+// (NKS, the k-half count, is a compile-time constant: with a run-time count hipcc turns the fragment arrays into scratch memory)
+template <typename C, int NKS>
+__device__ __forceinline__ void pp_read_a(const char* smem, int buf, int a, int a_base, const int (&foff)[2], bf16x8 (&af)[4][2]) {
+    const char* base = smem + buf * C::BUF_BYTES + a_base + a * 64 * 128;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        if (a == 1 && i >= C::TM1) break;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) af[i][ks] = *(const bf16x8*)(base + i * 16 * 128 + foff[ks]);
+    }
+}
+template <typename C, int NKS>
+__device__ __forceinline__ void pp_read_b(const char* smem, int buf, int b_base, const int (&foff)[2], bf16x8 (&bfr)[2][2][2]) {
+    const char* base = smem + buf * C::BUF_BYTES + b_base;
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int ks = 0; ks < NKS; ++ks) bfr[b][j][ks] = *(const bf16x8*)(base + (b * 32 + j * 16) * 128 + foff[ks]);
+}
+template <typename C, int NKS, int a>                                         // 32 MFMAs: output rows a*64 .. a*64+63 of the wave
+__device__ __forceinline__ void pp_half(f32x4 (&acc)[4][C::TM], const bf16x8 (&af)[4][2], const bf16x8 (&bfr)[2][2][2]) {
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int i = 0; i < (a == 0 ? C::TM0 : C::TM1); ++i)
+                    acc[2 * b + j][4 * a + i] = mfma16(bfr[b][j][ks], af[i][ks], acc[2 * b + j][4 * a + i]);
+    __builtin_amdgcn_s_setprio(0);
+}
 
 // AUXPRE (256-row tile, aux != null): the epilogue's [256 rows x 512 B] tile of a second operand (the saved GELU derivative of the
 // multiply-by-derivative epilogue) rides in on the LAST TWO K-tiles' staging slots -- where K-tiles nk and nk + 1 would be staged -- so it
@@ -238,6 +271,8 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
     const int nt = nk + nk2;
     const int rl = lane >> 3, cl = lane & 7;
 
+    // (The lane offsets, stage_a and stage_b below exist a second time in stream_pp, which clamps rows to m_end - 1 instead of M - 1:
+    //  a fix made here belongs there too.)
     // per-lane source byte offsets (row clamp + source swizzle) of this wave's LDS-DMA instructions:
     //   own activation half SA[wm]: 4 instructions, 8 rows each: half-tile rows (j * 4 + wn) * 8 ...
     //   weight halves SB0, SB1:     2 instructions each:          half-tile rows (j * 8 + wave) * 8 ...
@@ -312,7 +347,7 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
     auto stage_aux_piece = [&](int rp, char* dst) {
         const int row = 2 * rp + (lane >> 5), c = lane & 31;
         const int gm = m0 + row < M ? m0 + row : M - 1;
-        const char* src = (const char*)aux + ((size_t)gm * ldaux + n0) * 2 + ((c ^ (row & 15)) << 4);
+        const char* src = (const char*)aux + ((size_t)gm * ldaux + n0) * 2 + (swz512(row, c) << 4);
         __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)dst, 16, 0, 0);
     };
     auto stage_aux_b = [&](int buf) {
@@ -340,77 +375,40 @@ __device__ __forceinline__ void mainloop_pp(const bf16_t* __restrict__ A, int ld
     const int a_base = wm * C::HALF_BYTES;                                   // SA[wm]
     const int b_base = (2 + (wn >> 1)) * C::HALF_BYTES + (wn & 1) * 64 * 128; // SB[wn >> 1], this wave's 64 weight rows
     bf16x8 af[4][2], bfr[2][2][2];
-    // (NKS is a compile-time constant: with a run-time k-half count hipcc turns the fragment arrays into scratch memory)
-    auto read_a = [&](int buf, int a, auto nks_c) {
-        constexpr int NKS = decltype(nks_c)::value;
-        const char* base = smem + buf * C::BUF_BYTES + a_base + a * 64 * 128;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (a == 1 && i >= C::TM1) break;
-#pragma unroll
-            for (int ks = 0; ks < NKS; ++ks) af[i][ks] = *(const bf16x8*)(base + i * 16 * 128 + foff[ks]);
-        }
-    };
-    auto read_b = [&](int buf, auto nks_c) {
-        constexpr int NKS = decltype(nks_c)::value;
-        const char* base = smem + buf * C::BUF_BYTES + b_base;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int ks = 0; ks < NKS; ++ks) bfr[b][j][ks] = *(const bf16x8*)(base + (b * 32 + j * 16) * 128 + foff[ks]);
-    };
-    auto half = [&](auto a_c, auto nks_c) {                                   // 32 MFMAs: output rows a*64 .. a*64+63 of the wave
-        constexpr int NKS = decltype(nks_c)::value, a = decltype(a_c)::value;
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < (a == 0 ? C::TM0 : C::TM1); ++i)
-                        acc[2 * b + j][4 * a + i] = mfma16(bfr[b][j][ks], af[i][ks], acc[2 * b + j][4 * a + i]);
-        __builtin_amdgcn_s_setprio(0);
-    };
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto read_a = [&](int buf, int a, auto nks_c) { pp_read_a<C, decltype(nks_c)::value>(smem, buf, a, a_base, foff, af); };
+    auto read_b = [&](int buf, auto nks_c) { pp_read_b<C, decltype(nks_c)::value>(smem, buf, b_base, foff, bfr); };
+    auto half = [&](auto a_c, auto nks_c) { pp_half<C, decltype(nks_c)::value, decltype(a_c)::value>(acc, af, bfr); };
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
     auto ktile = [&](int T, int cur, auto nks_c, auto fast_c) {
         constexpr bool FAST = decltype(fast_c)::value != 0;                  // T + 2 < nk: one branch-free basic block
         read_a(cur, 0, nks_c); read_b(cur, nks_c);
-        pp_wait_lgkm0(); bar();
-        half(I0{}, nks_c); bar();
+        wait_lgkm0(); pp_bar();
+        half(I0{}, nks_c); pp_bar();
         read_a(cur, 1, nks_c);
-        if constexpr (FAST) { stage_b(T + 2, cur); pp_wait_vm4(); }
-        else if (T + 2 < nt) { stage_b_any(T + 2, cur); pp_wait_vm4(); }
-        else if (AUXPRE && aux_on) { stage_aux_b(cur); pp_wait_vm4(); }
-        else { pp_wait_vm0(); }
-        pp_wait_lgkm0(); bar();
+        if constexpr (FAST) { stage_b(T + 2, cur); wait_vm<4>(); }
+        else if (T + 2 < nt) { stage_b_any(T + 2, cur); wait_vm<4>(); }
+        else if (AUXPRE && aux_on) { stage_aux_b(cur); wait_vm<4>(); }
+        else { wait_vm<0>(); }
+        wait_lgkm0(); pp_bar();
         if constexpr (FAST) stage_a(T + 2, cur); else if (T + 2 < nt) stage_a_any(T + 2, cur); else if (AUXPRE && aux_on) stage_aux_a(cur);
-        half(I1{}, nks_c); bar();
+        half(I1{}, nks_c); pp_bar();
     };
 
     // prologue: K-tiles 0 and 1 in the steady-state issue order
     stage_b_any(0, 0); stage_a_any(0, 0);
     if (nt > 1) {
         stage_b_any(1, 1); stage_a_any(1, 1);
-        if (C::A_INSTR == 16 || a_last) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");     // K-tile 1 = this wave's last 8 (or 7) instructions
-        else asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    } else { pp_wait_vm0(); }
-    bar();
-    if (wm == 1) bar();                                                      // wave row 1 runs one barrier behind
+        if (C::A_INSTR == 16 || a_last) wait_vm<8>();     // K-tile 1 = this wave's last 8 (or 7) instructions
+        else wait_vm<7>();
+    } else { wait_vm<0>(); }
+    pp_bar();
+    if (wm == 1) pp_bar();                                                      // wave row 1 runs one barrier behind
     int cur = 0;
     int T = 0;
     for (; T + 2 < nk; ++T) { ktile(T, cur, I2{}, I1{}); cur ^= 1; }
     for (; T < nk; ++T) { ktile(T, cur, I2{}, I0{}); cur ^= 1; }
     for (; T < nt; ++T) { ktile(T, cur, I1{}, I0{}); cur ^= 1; }             // LoRA half-steps (32 k)
-    if (wm == 0) bar();                                                      // re-align the two wave rows
+    if (wm == 0) pp_bar();                                                      // re-align the two wave rows
 }
 
 
@@ -439,6 +437,8 @@ __device__ __forceinline__ void stream_pp(const bf16_t* __restrict__ A, int lda,
     const int rl = lane >> 3, cl = lane & 7;
     const bool a_last = 12 + wn < C::A_INSTR;                                  // wave-uniform (224-row tile: waves 2, 3 skip j = 3)
 
+    // (set_offsets, stage_a and stage_b below are mainloop_pp's lane offsets, stage_a and stage_b with the row clamp m_end - 1 instead of
+    //  M - 1: a fix made here belongs there too.)
     // geometry (scalars) of a tile and the per-lane source offsets of the tile whose K-tiles are being STAGED
     int m0 = 0, m_end = 0, n0 = 0;
     const bf16_t* Bt = nullptr;                                                // geometry: weight matrix of (m0, n0)'s row group
@@ -494,65 +494,31 @@ __device__ __forceinline__ void stream_pp(const bf16_t* __restrict__ A, int lda,
     const int b_base = (2 + (wn >> 1)) * C::HALF_BYTES + (wn & 1) * 64 * 128;
     f32x4 acc[4][C::TM];
     bf16x8 af[4][2], bfr[2][2][2];
-    auto read_a = [&](int buf, int a) {
-        const char* base = smem + buf * C::BUF_BYTES + a_base + a * 64 * 128;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (a == 1 && i >= C::TM1) break;
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) af[i][ks] = *(const bf16x8*)(base + i * 16 * 128 + foff[ks]);
-        }
-    };
-    auto read_b = [&](int buf) {
-        const char* base = smem + buf * C::BUF_BYTES + b_base;
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks) bfr[b][j][ks] = *(const bf16x8*)(base + (b * 32 + j * 16) * 128 + foff[ks]);
-    };
-    auto half = [&](auto a_c) {
-        constexpr int a = decltype(a_c)::value;
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int b = 0; b < 2; ++b)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < (a == 0 ? C::TM0 : C::TM1); ++i)
-                        acc[2 * b + j][4 * a + i] = mfma16(bfr[b][j][ks], af[i][ks], acc[2 * b + j][4 * a + i]);
-        __builtin_amdgcn_s_setprio(0);
-    };
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
+    auto read_a = [&](int buf, int a) { pp_read_a<C, 2>(smem, buf, a, a_base, foff, af); };
+    auto read_b = [&](int buf) { pp_read_b<C, 2>(smem, buf, b_base, foff, bfr); };
+    auto half = [&](auto a_c) { pp_half<C, 2, decltype(a_c)::value>(acc, af, bfr); };
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
     // one K-tile of the stream; `st` >= 0: K-tile index (of the tile described by offA / offB / Bw) staged into the buffer being
     // freed, st < 0: nothing left to stage (the stream ends)
     auto ktile = [&](int cur, int st) {
         read_a(cur, 0); read_b(cur);
-        pp_wait_lgkm0(); bar();
-        half(I0{}); bar();
+        wait_lgkm0(); pp_bar();
+        half(I0{}); pp_bar();
         read_a(cur, 1);
-        if (st >= 0) { stage_b(st, cur); pp_wait_vm4(); } else { pp_wait_vm0(); }
-        pp_wait_lgkm0(); bar();
+        if (st >= 0) { stage_b(st, cur); wait_vm<4>(); } else { wait_vm<0>(); }
+        wait_lgkm0(); pp_bar();
         if (st >= 0) stage_a(st, cur);
-        half(I1{}); bar();
+        half(I1{}); pp_bar();
     };
     auto ktile_fast = [&](int cur, int st) {                                 // steady state: one branch-free basic block
         read_a(cur, 0); read_b(cur);
-        pp_wait_lgkm0(); bar();
-        half(I0{}); bar();
+        wait_lgkm0(); pp_bar();
+        half(I0{}); pp_bar();
         read_a(cur, 1);
-        stage_b(st, cur); pp_wait_vm4();
-        pp_wait_lgkm0(); bar();
+        stage_b(st, cur); wait_vm<4>();
+        wait_lgkm0(); pp_bar();
         stage_a(st, cur);
-        half(I1{}); bar();
+        half(I1{}); pp_bar();
     };
 
     int v = blockIdx.x;
@@ -560,15 +526,15 @@ __device__ __forceinline__ void stream_pp(const bf16_t* __restrict__ A, int lda,
     set_offsets();
     stage_b(0, 0); stage_a(0, 0);
     stage_b(1, 1); stage_a(1, 1);
-    if (C::A_INSTR == 16 || a_last) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-    bar();
+    if (C::A_INSTR == 16 || a_last) wait_vm<8>();
+    else wait_vm<7>();
+    pp_bar();
     int cur = 0;
     for (;;) {
         // Inside a tile wave row 1 runs ONE BARRIER behind row 0 (the ping-pong); around the epilogue the rows are re-aligned (one extra
         // barrier each) so that both rows store at the same time -- without it row 1's last barrier would wait for row 0's whole epilogue
         // and the two epilogues would run one after the other.
-        if (wm == 1) bar();
+        if (wm == 1) pp_bar();
         const int cm0 = m0, cm_end = m_end, cn0 = n0;                        // the tile being COMPUTED (scalars)
         trace(v, 0);
         init_acc(acc, cn0);
@@ -588,7 +554,7 @@ __device__ __forceinline__ void stream_pp(const bf16_t* __restrict__ A, int lda,
         trace(v, 3);
         ktile(cur, has_next ? 0 : -1); cur ^= 1;
         ktile(cur, has_next ? 1 : -1); cur ^= 1;
-        if (wm == 0) bar();
+        if (wm == 0) pp_bar();
         trace(v, 4);
         epilogue(acc, cm0, cm_end, cn0);
         trace(v, 5);

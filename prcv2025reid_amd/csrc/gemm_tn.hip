@@ -4,17 +4,16 @@
 // for the MFMA (the reduction index m is the slow index of both X and Y), so tiles are staged
 // row-major into LDS (16-byte global loads, 16-byte LDS stores, rows padded by 32 B so the
 // transposed reads are conflict free) and MFMA fragments are fetched with gfx950's hardware
-// transpose read ds_read_b64_tr_b16 (cdna_hip_programming.md T10): lane i of a 16-lane group gets
+// transpose read ds_read_b64_tr_b16 (lds_tile.h tr_frag): lane i of a 16-lane group gets
 // column i of a 4-row x 16-column block, i.e. 4 consecutive k for its own matrix row.
 // The row range is cut into slabs over blockIdx.z-like slices; partial tiles are combined with
 // fp32 atomics (sum order is not fixed: results can differ in the last bits between runs).
-#include "common.h"
+#include "lds_tile.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) short s4;
-typedef __attribute__((address_space(3))) s4* lds_s4_ptr;
+using ldstile::tr_frag;
 
 struct TnParams {
     const bf16_t* X; const bf16_t* Y; float* C;
@@ -22,21 +21,6 @@ struct TnParams {
     float alpha;
     int tiles_p, tiles_q, slab_rows;
 };
-
-__device__ __forceinline__ bf16x8 tr_frag(const char* img, int pitch, int k0, int col0, int lane) {
-    // 16x16x32 operand from a row-major [k][col] bf16 image.  Each tr read covers a 4-row x 16-col
-    // block: lane 4q+p' of a 16-lane group supplies the address of block row q, columns 4p'..4p'+3,
-    // and lane i receives column i of the 4 rows.  The MFMA sums over k, so any assignment of image
-    // rows to (lane group fq, element j) is valid as long as BOTH operands use it: element j<4 is
-    // row 4fq+j, element j>=4 is row 16+4fq+(j-4).  A 32-lane half then touches 8 consecutive rows
-    // per read, which the 32-byte row padding spreads over all 64 banks (conflict free).
-    const int l16 = lane & 15, fq = lane >> 4;
-    const int q = l16 >> 2, pp = l16 & 3;
-    const char* a0 = img + (k0 + 4 * fq + q) * pitch + (col0 + 4 * pp) * 2;
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(a0));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(a0 + 16 * pitch));
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 template <int BP, int BQ, int WP, int WQ>
 __global__ __launch_bounds__(256) void gemm_tn_kernel(const TnParams p) {

@@ -12,10 +12,11 @@
 // the same size as the rounding of W alone that the unmerged form carries (plus its own roundings of T and B).  An update much
 // smaller than one ulp of W moves a fraction |delta| / ulp of the rounded elements by one ulp: unbiased, like the fp32-master /
 // 16-bit-compute weights of ordinary mixed-precision training.
-#include "common.h"
+#include "lds_tile.h"
 #include <type_traits>
 
 namespace {
+using namespace ldstile;
 
 constexpr int MT = 64;   // tile edge (output features x input features)
 
@@ -137,8 +138,6 @@ template <int NW> struct Geo {
     static constexpr int LDS_BYTES = NW * WAVE_LDS + NW * R * RP * 4;
 };
 
-typedef __attribute__((ext_vector_type(4))) short s4;
-typedef __attribute__((address_space(3))) s4* lds_s4_ptr;
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
 struct Params {
@@ -149,16 +148,6 @@ struct Params {
     float* Up;                                            // fp32 [M, Rp] partial sums of U over column blocks of a wider dY (or null)
     int u_mode;                                           // bit 0: add Up to this block's sum; bit 1: store the sum to Up instead of U
 };
-
-// gemm_tn.hip's transposed fragment: 16x16x32 operand whose 16 MFMA rows are image COLUMNS col0.. and whose k are image rows k0..k0+31
-__device__ __forceinline__ bf16x8 tr_frag(const char* img, int pitch, int k0, int col0, int lane) {
-    const int l16 = lane & 15, fq = lane >> 4;
-    const int q = l16 >> 2, pp = l16 & 3;
-    const char* a0 = img + (k0 + 4 * fq + q) * pitch + (col0 + 4 * pp) * 2;
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(a0));
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)(a0 + 16 * pitch));
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
 
 template <int NW>
 __global__ __launch_bounds__(NW * 64, 2) void lora_bwd_fused_kernel(const Params p) {
@@ -302,22 +291,8 @@ template <int RP> struct BwdGeo {
     static constexpr int USTAGE_BYTES = R * RP * 2;        // U tile of a step, row-major, staged for whole-row stores
     static constexpr int LDS_BYTES = NBUF * BUF_BYTES + USTAGE_BYTES;
 };
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-using fused::s4; using fused::lds_s4_ptr; using fused::Params;
-
-// One LDS-DMA wave-instruction (64 lanes x 16 bytes -> 1 KiB of LDS at `lds_base`, wave-uniform) issued from inline assembly: hipcc then
-// has no vector-memory operation of the ring in its scoreboard.  With the builtin it places `s_waitcnt vmcnt(0)` in front of every
-// ds_read_b64_tr_b16 while a DMA is outstanding -- the transposed reads of every step then wait for the WHOLE ring (first form of this
-// kernel: 10 GB/s per workgroup whatever the ring depth).  Consequently no other global access may sit inside the step loops below
-// (the compiler's own waits for it would drain the ring as well): outputs are kept in registers and written after the loop.
-// M0 = LDS base; nothing else in these kernels uses M0.
-typedef __attribute__((address_space(3))) char* lds_cptr;
-__device__ __forceinline__ uint32_t lds_addr(const char* ptr) { return (uint32_t)(uintptr_t)(lds_cptr)(char*)ptr; }
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_base) {
-    const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds_base);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0v) : "memory");
-}
+using fused::Params;
+// The step buffers below are filled by dma16 (lds_tile.h, which says why no compiler-visible global access may sit inside the step loops).
 
 // transposed operand from the swizzled image: 16 MFMA rows = image columns col0 .. col0 + 15, k = image rows 0 .. 31
 __device__ __forceinline__ bf16x8 tr_frag_swz(const char* img, int col0, int lane) {
@@ -325,11 +300,9 @@ __device__ __forceinline__ bf16x8 tr_frag_swz(const char* img, int col0, int lan
     const int q = l16 >> 2, pp = l16 & 3;
     const int col = col0 + 4 * pp;
     const int r0 = 4 * fq + q, r1 = r0 + 16;
-    const char* a0 = img + r0 * ROW_BYTES + (((col >> 3) ^ (r0 & 15)) << 4) + (col & 7) * 2;
-    const char* a1 = img + r1 * ROW_BYTES + (((col >> 3) ^ (r1 & 15)) << 4) + (col & 7) * 2;
-    const s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)a0);
-    const s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4_ptr)a1);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    const char* a0 = img + r0 * ROW_BYTES + (swz512(r0, col >> 3) << 4) + (col & 7) * 2;
+    const char* a1 = img + r1 * ROW_BYTES + (swz512(r1, col >> 3) << 4) + (col & 7) * 2;
+    return tr_join(tr_read(a0), tr_read(a1));
 }
 
 // U = mask(Up) * scale in 16 bits once the last column block of a wide cotangent has added its partial sums (fp32 [M, Rp]) to Up
@@ -374,7 +347,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             const int g = qd * 64 + lane;
             const int row = g / 96, c = g - row * 96;
             int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
-            dma16(p.dY + (size_t)gr * p.lddy + ((c ^ (row & 15)) << 3), base + qd * 1024);
+            dma16(p.dY + (size_t)gr * p.lddy + (swz512(row, c) << 3), base + qd * 1024);
         }
         if constexpr (RP == 32) {
             if (w < 2) {
@@ -449,13 +422,13 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
         // seven in the waves that also fetch T: waves 0 and 1 with RP = 32, wave 0 alone with RP = 64 -- wave 1 forms U there too, but
         // its U stores of the previous step are older than the newest DMA instructions and drain here like those of wave 0)
         if (t + 1 < steps) {
-            if (w < (RP == 32 ? 2 : 1)) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            if (w < (RP == 32 ? 2 : 1)) wait_vm<7>();
+            else wait_vm<6>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
         }
         __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
         __builtin_amdgcn_s_barrier();                         // ... everybody's share; and everybody is done reading the buffer of step t - 1
         __builtin_amdgcn_sched_barrier(0);
         const char* xs = smem + buf * BUF_BYTES;
@@ -471,12 +444,11 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             for (int a = 0; a < 4; ++a) u4[a] = f32x4{0.f, 0.f, 0.f, 0.f};
             const int row = 16 * w + l16;
             const char* xrow = xs + row * ROW_BYTES;
-            const int rsw = row & 15;
 #pragma unroll
             for (int k0 = 0; k0 < 24; k0 += 4) {
                 bf16x8 af[4];
 #pragma unroll
-                for (int a = 0; a < 4; ++a) af[a] = *(const bf16x8*)(xrow + (((4 * (k0 + a) + fq) ^ rsw) << 4));
+                for (int a = 0; a < 4; ++a) af[a] = *(const bf16x8*)(xrow + (swz512(row, 4 * (k0 + a) + fq) << 4));
 #pragma unroll
                 for (int a = 0; a < 4; ++a) u4[a] = mfma16(af[a], bfr[k0 + a], u4[a]);
             }
@@ -499,7 +471,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
                     ul[w0 + l16] = f32_to_bf16(mine ? ua[e] * p.scale : 0.f);
                     if constexpr (RP == 32) ul[(w0 ^ 16) + l16] = f32_to_bf16(0.f);   // the other half of the 32 adapter columns: other modalities
                 }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");        // this wave's 16 rows are in LDS (written and read by this wave only)
+                wait_lgkm0();        // this wave's 16 rows are in LDS (written and read by this wave only)
                 __builtin_amdgcn_wave_barrier();
                 if constexpr (RP == 32) {
                     const int row = 16 * w + (lane >> 2), ch = lane & 3;
@@ -521,7 +493,7 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
             }
         } else {
             // dB[128 columns of this wave, window] += dY^T . T over the rows of this step (rows beyond the image: T fragment zeroed)
-            bf16x8 tf = RP == 32 ? fused::tr_frag(ts, RP * 2, 0, w0, lane) : fused::tr_frag(ts, 32, 0, 0, lane);   // (RP = 64: the window alone is staged)
+            bf16x8 tf = RP == 32 ? tr_frag(ts, RP * 2, 0, w0, lane) : tr_frag(ts, 32, 0, 0, lane);   // (RP = 64: the window alone is staged)
             const int nvalid = rend - r0;                     // >= 32 except in the last step
             if (nvalid < R) {
 #pragma unroll
@@ -599,7 +571,7 @@ __global__ __launch_bounds__(512, 2) void lora_da_image_kernel(const DaParams p)
             const int g = qd * 64 + lane;
             const int row = g / 96, c = g - row * 96;
             int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
-            dma16(Xb + (size_t)gr * p.ldx + ((c ^ (row & 15)) << 3), base + qd * 1024);
+            dma16(Xb + (size_t)gr * p.ldx + (swz512(row, c) << 3), base + qd * 1024);
         }
         if (w < G) {                                          // group w's window: 32 rows x 2 chunks, lane-linear (row pitch 32 bytes)
             const int row = lane >> 1, c = lane & 1;
@@ -617,13 +589,13 @@ __global__ __launch_bounds__(512, 2) void lora_da_image_kernel(const DaParams p)
     int buf = 0;
     for (int t = 0; t < steps; ++t) {
         if (t + 1 < steps) {                                  // all but the newest step's DMA instructions (six, seven in the waves that fetch U)
-            if (w < G) asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            if (w < G) wait_vm<7>();
+            else wait_vm<6>();
         } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vm<0>();
         }
         __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        wait_lgkm0();
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
         const char* xs = smem + buf * BUF;
@@ -632,7 +604,7 @@ __global__ __launch_bounds__(512, 2) void lora_da_image_kernel(const DaParams p)
         bf16x8 uf[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-            uf[g] = fused::tr_frag(us + g * 1024, 32, 0, 0, lane);
+            uf[g] = tr_frag(us + g * 1024, 32, 0, 0, lane);
             if (nvalid < R) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j)

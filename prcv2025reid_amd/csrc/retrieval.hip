@@ -482,34 +482,8 @@ __device__ __forceinline__ uint32_t key_of(float f) { const uint32_t u = __float
 __device__ __forceinline__ float key_value(uint32_t key) {
     return key == 0 ? -INFINITY : __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
 }
-typedef __attribute__((address_space(3))) char* lds_cptr;
 typedef __attribute__((address_space(3))) uint32_t* lds_u32ptr;
-__device__ __forceinline__ uint32_t lds_addr(const void* ptr) { return (uint32_t)(uintptr_t)(lds_cptr)(char*)ptr; }
-// LDS-DMA from inline assembly (see lora.hip dma16: hipcc then keeps no scoreboard entry for the ring and places no waits of its own)
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_base) {
-    const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds_base);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0v) : "memory");
-}
-__device__ __forceinline__ void dma16_coherent(const void* src, uint32_t lds_base) {      // sc1: past the non-coherent caches (atomics' home)
-    const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds_base);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1" ::"v"(src), "s"(m0v) : "memory");
-}
-__device__ __forceinline__ void dma4(const void* src, uint32_t lds_base) {
-    const uint32_t m0v = __builtin_amdgcn_readfirstlane(lds_base);
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off" ::"v"(src), "s"(m0v) : "memory");
-}
-
-// `s_waitcnt vmcnt(n)` with a run-time, wave-uniform n (the counter completes in issue order: n = the operations allowed to stay in flight)
-__device__ __forceinline__ void wait_vm(int n) {
-    switch (n) {
-#define REID_VM_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-        REID_VM_CASE(1) REID_VM_CASE(2) REID_VM_CASE(3) REID_VM_CASE(4) REID_VM_CASE(5) REID_VM_CASE(6) REID_VM_CASE(7) REID_VM_CASE(8)
-        REID_VM_CASE(9) REID_VM_CASE(10) REID_VM_CASE(11) REID_VM_CASE(12) REID_VM_CASE(13) REID_VM_CASE(14) REID_VM_CASE(15) REID_VM_CASE(16)
-        REID_VM_CASE(17) REID_VM_CASE(18) REID_VM_CASE(19) REID_VM_CASE(20)
-#undef REID_VM_CASE
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-}
+// LDS-DMA from inline assembly, counted waits (run-time wait_vm(n) included): lds_tile.h
 
 template <int KS /* D / 32 */, bool EXCL>
 __global__ __launch_bounds__(512) void scan_filter_kernel(const ScanParams p) {
@@ -556,7 +530,7 @@ __global__ __launch_bounds__(512) void scan_filter_kernel(const ScanParams p) {
             const int r = j * RPI + lane / CPR, pos = lane % CPR;
             int gr = tile_row0(t) + r;
             gr = gr < row_end ? gr : row_end - 1;
-            dma16(p.G + (size_t)gr * D + ((pos ^ (r & 15)) << 3), base + j * 1024);
+            dma16(p.G + (size_t)gr * D + (swz512(r, pos) << 3), base + j * 1024);
         }
         if (EXCL && wave == 7) {
             int gr = tile_row0(t) + (lane & 31);
@@ -605,7 +579,7 @@ __global__ __launch_bounds__(512) void scan_filter_kernel(const ScanParams p) {
     // chunk 4 ks + rb of row 16 rh + qa sits at position (4 ks + rb) ^ qa: four per-lane offsets (ks & 3) + an immediate (ks >> 2)
     int aoff[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) aoff[j] = (rh * 16 + qa) * ROWB + (((4 * j + rb) ^ qa) << 4);
+    for (int j = 0; j < 4; ++j) aoff[j] = (rh * 16 + qa) * ROWB + (swz512(qa, 4 * j + rb) << 4);
     float mx[2] = {-INFINITY, -INFINITY}, mx_loc[2] = {-INFINITY, -INFINITY}, bar[2] = {INFINITY, INFINITY};
     uint32_t pub_key = 0;
     bool valid = false;                                   // (wave-uniform) every group of every query of this wave has reported
@@ -766,7 +740,7 @@ __global__ __launch_bounds__(512) void scan_filter_kernel(const ScanParams p) {
     // Tail.  A workgroup that is through before every group has reported (short scans: all workgroups finish together) polls a bounded
     // number of times -- it never depends on another workgroup to terminate.
     for (int poll = 0;; ++poll) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __syncthreads();
         if (active) read_bars();
         if (lane == 0) fv[8 + wave] = (!active || valid) ? 1 : 0;
@@ -801,7 +775,7 @@ __global__ __launch_bounds__(512) void scan_filter_kernel(const ScanParams p) {
     for (int t0 = 0; t0 < 2 * nrev; t0 += 4) {            // four tiles per round trip
         if (t0 > 0) __syncthreads();
         for (int u = 0; u < 4 && t0 + u < 2 * nrev; ++u) stage(t0 + u);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
         __syncthreads();
         for (int u = 0; u < 4 && t0 + u < 2 * nrev; ++u) {
             const int t = t0 + u;
