@@ -487,7 +487,36 @@ int reid_augment_images(const void* src, int64_t src_bytes, const int32_t* table
  *         16-byte aligned; cosr f32 [nq, ldc >= Ng]; out f32 [nq, ldo >= Ng], ldo % 4 == 0 (what reid_rank_metrics accepts),
  *         columns >= Ng are not written.
  * All fp32, deterministic (no atomics), nothing allocated or synchronised.
+ *
+ * The sparse form computes the same V, V2 and out from the same nbr and X, stores the non-zeros only and has no limit on N
+ * other than int32 row indices (offsets into the arrays of non-zeros are int64).  W = (k1 + 1)(kh + 2) >= |R*(i)|.
+ *   V, padded rows    vcols i32 [N, ldw], vvals f32 [N, ldw], vcnt i32 [N], ldw >= W: row i holds the members of R*(i) once each
+ *         (in the order the set is built) with exactly the value the dense call writes; positions >= vcnt[i] are not written.
+ *   V2, CSR           rowptr i64 [N + 1], cols i32 [nnz], vals f32 [nnz]: columns strictly ascending inside a row, every value > 0
+ *         and the dense call's value bit for bit (the terms present, added in ascending t, then divided by (float)k2).
+ *   gallery rows of V2, transposed (CSC of rows Nq .. N - 1)   colptr i64 [N + 1], rows i32 [nnzc] (g = row - Nq, ascending inside
+ *         a column), cvals f32 [nnzc].  The caller builds it from the CSR (a stable sort of the column indices).
+ *   reid_rerank_weights_sparse   writes the padded rows and vcnt; nothing is zero-filled.
+ *   reid_rerank_expand_count     cnt[i] = number of distinct columns in the padded rows nbr[i, t], t < k2: the row lengths of V2.
+ *         The caller turns them into rowptr (an exclusive prefix sum) and sizes cols / vals by rowptr[N].
+ *   reid_rerank_expand_sparse    fills cols / vals of every row at rowptr[i]; never writes at or past rowptr[i + 1].
+ *         Both hold one row's merge in LDS: k2 W <= 8192 entries (REID_RERANK_MERGE_MAX), else REID_ERR_ARG.
+ *   reid_rerank_jaccard_sparse   out[q, g] for q < nq and EVERY g < Ng, m summed over the columns both rows hold, in ascending
+ *         column order; rowptr points at the first of the nq + 1 offsets of the query chunk (absolute offsets into cols / vals,
+ *         which hold nnz entries in all); columns >= Ng of out are not written.  One workgroup owns one out row.  The two
+ *         matrices need not come from a pooled problem; an index outside its range is skipped.
  * ------------------------------------------------------------------------------------------ */
+#define REID_RERANK_MERGE_MAX 8192
+int reid_rerank_weights_sparse(const int32_t* nbr, int32_t ldn, const float* X, int32_t ldx, int32_t* vcols, float* vvals,
+                               int32_t* vcnt, int64_t ldw, int32_t N, int32_t D, int32_t k1, void* stream);
+int reid_rerank_expand_count(const int32_t* vcols, const float* vvals, const int32_t* vcnt, int64_t ldw, const int32_t* nbr,
+                             int32_t ldn, int32_t* cnt, int32_t N, int32_t k1, int32_t k2, void* stream);
+int reid_rerank_expand_sparse(const int32_t* vcols, const float* vvals, const int32_t* vcnt, int64_t ldw, const int32_t* nbr,
+                              int32_t ldn, const int64_t* rowptr, int32_t* cols, float* vals, int32_t N, int32_t k1, int32_t k2,
+                              void* stream);
+int reid_rerank_jaccard_sparse(const int64_t* rowptr, const int32_t* cols, const float* vals, int64_t nnz, const int64_t* colptr,
+                               const int32_t* rows, const float* cvals, int64_t nnzc, const float* cosr, int64_t ldc, float* out,
+                               int64_t ldo, int32_t nq, int32_t Ng, int32_t N, float lambda, void* stream);
 int reid_rerank_weights(const int32_t* nbr, int32_t ldn, const float* X, int32_t ldx, float* V, int64_t ldv, int32_t N,
                         int32_t D, int32_t k1, void* stream);
 int reid_rerank_expand(const float* V, int64_t ldv, const int32_t* nbr, int32_t ldn, float* V2, int64_t ldo, int32_t N,

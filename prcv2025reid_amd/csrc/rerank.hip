@@ -10,6 +10,18 @@
 //                         every lane reads its 8 + 8 values with four ds_read_b128) whose inner operation is v_min_f32 + v_add_f32.
 //                         A k-step in which the A tile or the B tile holds no non-zero adds exactly +0 to every accumulator (the
 //                         rows are non-negative) and is skipped: V2 is > 99 % zeros at protocol scale.
+//
+// The sparse form (any N that int32 row indices hold; layout: include/reid_hip.h) stores only the non-zeros:
+//   reid_rerank_weights_sparse   the same kernel; its last loop writes the R*(i) list and its weights as one padded row of
+//                                (column, value) plus vcnt[i], in place of the scatter into a zero-filled dense row.
+//   reid_rerank_expand_count /   one workgroup per pooled row: the <= k2 W entries of the padded rows nbr[i, t], t < k2, as
+//   reid_rerank_expand_sparse    (column << 8 | t) keys in LDS, one bitonic sort, then every run of one column is summed in ascending
+//                                t and divided by k2 -- the dense kernel's value bit for bit.  The count pass writes the number of
+//                                runs; the fill pass writes them, columns ascending, at rowptr[i].
+//   reid_rerank_jaccard_sparse   the hot path: one workgroup owns one out row.  It zero-fills the row, walks the query's CSR columns
+//                                in ascending order and for each the column's CSC list across the threads (gallery rows of one
+//                                column are distinct: no two threads touch one element), a barrier between columns, so m[q, g]
+//                                accumulates in the out row in ascending column order; one finishing pass blends in the cosine row.
 #include "common.h"
 
 namespace {
@@ -25,9 +37,11 @@ __device__ __forceinline__ int lanes_below(unsigned long long m) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // One wave (64 threads) per pooled row.  An index outside [0, N) in nbr (never produced for k1 + 1 <= N) is treated as absent.
+// SPARSE: V is vvals and vcols its columns, both [N, ldv]; row i gets R*(i) in list order at positions < vcnt[i] = |R*(i)|.
+template <bool SPARSE>
 __global__ __launch_bounds__(64) void rerank_weights_kernel(const int32_t* __restrict__ nbr, int ldn, const float* __restrict__ X,
-                                                            int ldx, float* __restrict__ V, long long ldv, int N, int D, int k1,
-                                                            int kh) {
+                                                            int ldx, float* __restrict__ V, long long ldv, int32_t* __restrict__ vcols,
+                                                            int32_t* __restrict__ vcnt, int N, int D, int k1, int kh) {
     __shared__ int Li[LIST_MAX];        // nbr[i, :k1+1]
     __shared__ int Ri[LIST_MAX];        // R(i, k1) in list order
     extern __shared__ int dyn[];        // 2 x (k1 + 1)(kh + 2) words
@@ -96,7 +110,15 @@ __global__ __launch_bounds__(64) void rerank_weights_kernel(const int32_t* __res
     float sum = 0.f;
     for (int s = lane; s < nS; s += 64) sum += Es[s];               // fixed order: strided partials, then the butterfly
     sum = wave_sum(sum);
-    for (int s = lane; s < nS; s += 64) V[(long long)i * ldv + Rs[s]] = Es[s] / sum;
+    if constexpr (SPARSE) {
+        for (int s = lane; s < nS; s += 64) {
+            vcols[(long long)i * ldv + s] = Rs[s];
+            V[(long long)i * ldv + s] = Es[s] / sum;
+        }
+        if (lane == 0) vcnt[i] = nS;
+    } else {
+        for (int s = lane; s < nS; s += 64) V[(long long)i * ldv + Rs[s]] = Es[s] / sum;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -226,6 +248,159 @@ __global__ __launch_bounds__(256, 2) void rerank_jaccard_kernel(const JaccardPar
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SPARSE_MERGE_MAX = REID_RERANK_MERGE_MAX;   // entries one row's merge holds in LDS: 12 bytes each, 96 KB of the CU's 160 KB at the most.
+// A call takes what its own bound needs: cap = k2 W rounded up to a power of two (the defaults: 2048 entries, 24 KB, six workgroups per CU).
+constexpr int XT = 256;                  // threads of the merge workgroup
+
+// Exclusive prefix of v over the workgroup's XT threads in thread order (ws: one int per wave); total: the sum over all threads.
+__device__ __forceinline__ int block_excl_scan(int v, int* ws, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) ws[w] = inc;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int u = 0; u < XT / 64; ++u) {
+        if (u < w) base += ws[u];
+        total += ws[u];
+    }
+    return base + inc - v;
+}
+
+// One workgroup per pooled row i.  FILL = false: cnt[i] = number of distinct columns in the union of the padded rows nbr[i, t], t < k2.
+// FILL = true: those columns ascending and their values at rowptr[i] (never past rowptr[i + 1]).  A list entry outside [0, N) is
+// skipped, as in the dense kernel; a vcnt outside [0, W] is clamped, so the merge never exceeds k2 * W <= cap entries.
+template <bool FILL>
+__global__ __launch_bounds__(XT) void rerank_expand_sparse_kernel(const int32_t* __restrict__ vcols, const float* __restrict__ vvals,
+                                                                  const int32_t* __restrict__ vcnt, long long ldw,
+                                                                  const int32_t* __restrict__ nbr, int ldn, int32_t* __restrict__ cnt,
+                                                                  const long long* __restrict__ rowptr, int32_t* __restrict__ cols,
+                                                                  float* __restrict__ vals, int N, int k2, int W, int cap) {
+    extern __shared__ unsigned long long merge_lds[];              // cap keys, then cap values
+    unsigned long long* key = merge_lds;                           // column << 8 | t: one sort orders the columns and, inside one, t
+    float* val = (float*)(merge_lds + cap);
+    __shared__ int src[LIST_MAX], off[LIST_MAX + 1], ws[XT / 64];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (tid < k2) {
+        const int j = nbr[(long long)i * ldn + tid];
+        const bool ok = j >= 0 && j < N;
+        src[tid] = ok ? j : -1;
+        off[tid + 1] = ok ? min(max(vcnt[j], 0), W) : 0;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        off[0] = 0;
+        for (int t = 0; t < k2; ++t) off[t + 1] += off[t];
+    }
+    __syncthreads();
+    const int n = off[k2];
+    int P = 1;
+    while (P < n) P <<= 1;
+    for (int t = tid >> 6; t < k2; t += XT / 64) {                  // a wave per source row
+        const int j = src[t], o = off[t], c = off[t + 1] - o;
+        for (int s = tid & 63; s < c; s += 64) {
+            key[o + s] = ((unsigned long long)(uint32_t)vcols[(long long)j * ldw + s] << 8) | (unsigned)t;
+            val[o + s] = vvals[(long long)j * ldw + s];
+        }
+    }
+    for (int e = n + tid; e < P; e += XT) key[e] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int e = tid; e < P / 2; e += XT) {
+                const int a = ((e & ~(j - 1)) << 1) | (e & (j - 1)), b = a | j;
+                const unsigned long long ka = key[a], kb = key[b];
+                if ((ka > kb) == ((a & k) == 0)) {
+                    key[a] = kb; key[b] = ka;
+                    const float v = val[a]; val[a] = val[b]; val[b] = v;
+                }
+            }
+            __syncthreads();
+        }
+    // thread tid owns entries [e0, e1): the heads of the column runs among them
+    const int per = (n + XT - 1) / XT, e0 = min(n, tid * per), e1 = min(n, e0 + per);
+    int heads = 0;
+    for (int e = e0; e < e1; ++e) heads += e == 0 || (key[e] >> 8) != (key[e - 1] >> 8);
+    int total;
+    int rank = block_excl_scan(heads, ws, total);
+    if constexpr (!FILL) {
+        if (tid == 0) cnt[i] = total;
+    } else {
+        const long long base = rowptr[i], room = rowptr[i + 1] - base;
+        const float k2f = (float)k2;
+        for (int e = e0; e < e1; ++e) {
+            const unsigned long long c = key[e] >> 8;
+            if (e != 0 && c == (key[e - 1] >> 8)) continue;
+            float acc = val[e];                                     // ascending t; the absent terms are the dense kernel's exact + 0
+            for (int u = e + 1; u < n && (key[u] >> 8) == c; ++u) acc += val[u];
+            if (rank < room) {
+                cols[base + rank] = (int32_t)c;
+                vals[base + rank] = acc / k2f;
+            }
+            ++rank;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int SJ = 128;            // threads per out row: the CSC lists are a few hundred entries, and more rows are in flight per CU
+
+struct JaccardSparseParams {
+    const long long* rowptr; const int32_t* cols; const float* vals;        // CSR of the query rows (absolute offsets)
+    const long long* colptr; const int32_t* rows; const float* cvals;       // CSC of the gallery rows
+    const float* cosr; float* out;
+    long long ldc, ldo, nnz, nnzc;
+    int nq, Ng, N;
+    float lambda;
+};
+
+__global__ __launch_bounds__(SJ) void rerank_jaccard_sparse_kernel(const JaccardSparseParams p) {
+    __shared__ long long cb[SJ], ce[SJ];                            // a batch of the query's columns: CSC list bounds and the query's value
+    __shared__ float ca[SJ];
+    const int q = blockIdx.x, tid = threadIdx.x;
+    float* out = p.out + (long long)q * p.ldo;                      // read and written by every thread, between barriers
+    const float* __restrict__ cosr = p.cosr + (long long)q * p.ldc;
+    for (int g = tid; g < p.Ng; g += SJ) out[g] = 0.f;
+    const long long r0 = min(max(p.rowptr[q], 0ll), p.nnz), r1 = min(max(p.rowptr[q + 1], r0), p.nnz);
+    for (long long b0 = r0; b0 < r1; b0 += SJ) {
+        const int nb = (int)min((long long)SJ, r1 - b0);
+        __syncthreads();                                            // the zero fill, or the last column of the batch before
+        if (tid < nb) {
+            const int j = p.cols[b0 + tid];
+            long long lo = 0, hi = 0;
+            if (j >= 0 && j < p.N) {
+                lo = min(max(p.colptr[j], 0ll), p.nnzc);
+                hi = min(max(p.colptr[j + 1], lo), p.nnzc);
+            }
+            cb[tid] = lo; ce[tid] = hi; ca[tid] = p.vals[b0 + tid];
+        }
+        __syncthreads();
+        for (int c = 0; c < nb; ++c) {
+            const long long lo = cb[c], hi = ce[c];
+            if (lo == hi) continue;                                 // workgroup-uniform
+            const float a = ca[c];
+            for (long long e = lo + tid; e < hi; e += SJ) {
+                const int g = p.rows[e];
+                if (g >= 0 && g < p.Ng) out[g] += fminf(a, p.cvals[e]);
+            }
+            __syncthreads();                                        // the next column may touch the same gallery rows
+        }
+    }
+    __syncthreads();
+    const float lam = p.lambda, one_m = 1.0f - p.lambda;
+    for (int g = tid; g < p.Ng; g += SJ) {
+        const float m = out[g];
+        out[g] = one_m * (m / (2.0f - m)) + lam * cosr[g];
+    }
+}
+
 }  // namespace
 
 static int rerank_kh(int k1) {           // round-half-to-even(k1 / 2)
@@ -242,8 +417,8 @@ extern "C" int reid_rerank_weights(const int32_t* nbr, int32_t ldn, const float*
                    (long long)ldv);
     REID_CHECK_HIP(hipMemset2DAsync(V, (size_t)ldv * 4, 0, (size_t)N * 4, (size_t)N, (hipStream_t)stream), "reid_rerank_weights: zero fill");
     const int kh = rerank_kh(k1);
-    hipLaunchKernelGGL(rerank_weights_kernel, dim3(N), dim3(64), 8 * (k1 + 1) * (kh + 2), (hipStream_t)stream, nbr, ldn, X, ldx, V,
-                       (long long)ldv, N, D, k1, kh);
+    hipLaunchKernelGGL(rerank_weights_kernel<false>, dim3(N), dim3(64), 8 * (k1 + 1) * (kh + 2), (hipStream_t)stream, nbr, ldn, X, ldx, V,
+                       (long long)ldv, (int32_t*)nullptr, (int32_t*)nullptr, N, D, k1, kh);
     REID_CHECK_LAUNCH("reid_rerank_weights");
     return REID_OK;
 }
@@ -273,5 +448,74 @@ extern "C" int reid_rerank_jaccard(const float* A, int64_t lda, const float* B, 
     JaccardParams p{A, B, cosr, out, (long long)lda, (long long)ldb, (long long)ldc, (long long)ldo, nq, Ng, N, lambda};
     hipLaunchKernelGGL(rerank_jaccard_kernel, dim3((Ng + JT - 1) / JT, (nq + JT - 1) / JT), dim3(256), 0, (hipStream_t)stream, p);
     REID_CHECK_LAUNCH("reid_rerank_jaccard");
+    return REID_OK;
+}
+
+extern "C" int reid_rerank_weights_sparse(const int32_t* nbr, int32_t ldn, const float* X, int32_t ldx, int32_t* vcols, float* vvals,
+                                          int32_t* vcnt, int64_t ldw, int32_t N, int32_t D, int32_t k1, void* stream) {
+    REID_CHECK_ARG(nbr && X && vcols && vvals && vcnt, "reid_rerank_weights_sparse: null pointer");
+    REID_CHECK_ARG(k1 >= 1 && k1 <= K1_MAX, "reid_rerank_weights_sparse: k1=%d outside 1..%d", k1, K1_MAX);
+    REID_CHECK_ARG(N >= 1 && k1 + 1 <= N, "reid_rerank_weights_sparse: N=%d (k1 + 1 = %d <= N)", N, k1 + 1);
+    const int kh = rerank_kh(k1), W = (k1 + 1) * (kh + 2);
+    REID_CHECK_ARG(D >= 1 && ldx >= D && ldn >= k1 + 1 && ldw >= W, "reid_rerank_weights_sparse: D=%d ldx=%d ldn=%d ldw=%lld (ldw >= W = %d)", D,
+                   ldx, ldn, (long long)ldw, W);
+    hipLaunchKernelGGL(rerank_weights_kernel<true>, dim3(N), dim3(64), 8 * W, (hipStream_t)stream, nbr, ldn, X, ldx, vvals, (long long)ldw,
+                       vcols, vcnt, N, D, k1, kh);
+    REID_CHECK_LAUNCH("reid_rerank_weights_sparse");
+    return REID_OK;
+}
+
+static int rerank_expand_sparse_args(const char* name, const void* vcols, const void* vvals, const void* vcnt, int64_t ldw, const void* nbr,
+                                     int32_t ldn, int32_t N, int32_t k1, int32_t k2, int* W, int* cap) {
+    REID_CHECK_ARG(vcols && vvals && vcnt && nbr, "%s: null pointer", name);
+    REID_CHECK_ARG(k1 >= 1 && k1 <= K1_MAX && k2 >= 1 && k2 <= k1 + 1, "%s: k1=%d k2=%d (1 <= k1 <= %d, 1 <= k2 <= k1 + 1)", name, k1, k2,
+                   K1_MAX);
+    *W = (k1 + 1) * (rerank_kh(k1) + 2);
+    REID_CHECK_ARG(k2 * *W <= SPARSE_MERGE_MAX, "%s: k1=%d k2=%d merge k2 (k1 + 1)(kh + 2) = %d entries per row, at most %d", name, k1, k2,
+                   k2 * *W, SPARSE_MERGE_MAX);
+    REID_CHECK_ARG(N >= 1 && ldn >= k2 && ldw >= *W, "%s: N=%d ldn=%d ldw=%lld (ldw >= W = %d)", name, N, ldn, (long long)ldw, *W);
+    *cap = 64;
+    while (*cap < k2 * *W) *cap <<= 1;
+    return REID_OK;
+}
+
+extern "C" int reid_rerank_expand_count(const int32_t* vcols, const float* vvals, const int32_t* vcnt, int64_t ldw, const int32_t* nbr,
+                                        int32_t ldn, int32_t* cnt, int32_t N, int32_t k1, int32_t k2, void* stream) {
+    int W, cap;
+    if (int rc = rerank_expand_sparse_args("reid_rerank_expand_count", vcols, vvals, vcnt, ldw, nbr, ldn, N, k1, k2, &W, &cap)) return rc;
+    REID_CHECK_ARG(cnt, "reid_rerank_expand_count: null pointer");
+    REID_MAX_LDS(rerank_expand_sparse_kernel<false>, 12 * SPARSE_MERGE_MAX);
+    hipLaunchKernelGGL(rerank_expand_sparse_kernel<false>, dim3(N), dim3(XT), 12 * cap, (hipStream_t)stream, vcols, vvals, vcnt, (long long)ldw, nbr,
+                       ldn, cnt, (const long long*)nullptr, (int32_t*)nullptr, (float*)nullptr, N, k2, W, cap);
+    REID_CHECK_LAUNCH("reid_rerank_expand_count");
+    return REID_OK;
+}
+
+extern "C" int reid_rerank_expand_sparse(const int32_t* vcols, const float* vvals, const int32_t* vcnt, int64_t ldw, const int32_t* nbr,
+                                         int32_t ldn, const int64_t* rowptr, int32_t* cols, float* vals, int32_t N, int32_t k1, int32_t k2,
+                                         void* stream) {
+    int W, cap;
+    if (int rc = rerank_expand_sparse_args("reid_rerank_expand_sparse", vcols, vvals, vcnt, ldw, nbr, ldn, N, k1, k2, &W, &cap)) return rc;
+    REID_CHECK_ARG(rowptr && cols && vals, "reid_rerank_expand_sparse: null pointer");
+    REID_MAX_LDS(rerank_expand_sparse_kernel<true>, 12 * SPARSE_MERGE_MAX);
+    hipLaunchKernelGGL(rerank_expand_sparse_kernel<true>, dim3(N), dim3(XT), 12 * cap, (hipStream_t)stream, vcols, vvals, vcnt, (long long)ldw, nbr,
+                       ldn, (int32_t*)nullptr, (const long long*)rowptr, cols, vals, N, k2, W, cap);
+    REID_CHECK_LAUNCH("reid_rerank_expand_sparse");
+    return REID_OK;
+}
+
+extern "C" int reid_rerank_jaccard_sparse(const int64_t* rowptr, const int32_t* cols, const float* vals, int64_t nnz, const int64_t* colptr,
+                                          const int32_t* rows, const float* cvals, int64_t nnzc, const float* cosr, int64_t ldc, float* out,
+                                          int64_t ldo, int32_t nq, int32_t Ng, int32_t N, float lambda, void* stream) {
+    REID_CHECK_ARG(rowptr && colptr && cosr && out, "reid_rerank_jaccard_sparse: null pointer");
+    REID_CHECK_ARG(nnz >= 0 && nnzc >= 0 && (nnz == 0 || (cols && vals)) && (nnzc == 0 || (rows && cvals)),
+                   "reid_rerank_jaccard_sparse: nnz=%lld nnzc=%lld (null array of non-zeros)", (long long)nnz, (long long)nnzc);
+    REID_CHECK_ARG(nq >= 1 && Ng >= 1 && N >= 1, "reid_rerank_jaccard_sparse: nq=%d Ng=%d N=%d", nq, Ng, N);
+    REID_CHECK_ARG(ldc >= Ng && ldo >= Ng && ldo % 4 == 0, "reid_rerank_jaccard_sparse: ldc=%lld ldo=%lld (>= Ng, ldo %% 4 == 0)", (long long)ldc,
+                   (long long)ldo);
+    JaccardSparseParams p{(const long long*)rowptr, cols, vals, (const long long*)colptr, rows, cvals, cosr, out, (long long)ldc, (long long)ldo,
+                          (long long)nnz, (long long)nnzc, nq, Ng, N, lambda};
+    hipLaunchKernelGGL(rerank_jaccard_sparse_kernel, dim3(nq), dim3(SJ), 0, (hipStream_t)stream, p);
+    REID_CHECK_LAUNCH("reid_rerank_jaccard_sparse");
     return REID_OK;
 }

@@ -100,9 +100,9 @@ class ProtocolEvaluator:
 
     def _reranker(self, q_feats: torch.Tensor, rerank: 'RerankParams', normalized: bool = False):
         """Pooled state of one re-ranked evaluation (rerank.py): every query of the call at once."""
-        from .rerank import Reranker
+        from .rerank import Reranker, SparseReranker
         Qf = q_feats.contiguous().float().to(self.dev)
-        return Reranker(Qf if normalized else l2_normalize(Qf), self.Gf, rerank, self._Gcat)
+        return (SparseReranker if rerank.sparse else Reranker)(Qf if normalized else l2_normalize(Qf), self.Gf, rerank, self._Gcat)
 
     def per_query(self, q_feats: torch.Tensor, q_pids: torch.Tensor, q_img_ids: Optional[Sequence] = None,
                   ignore_same_img: bool = True, chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None):

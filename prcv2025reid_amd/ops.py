@@ -395,6 +395,32 @@ def rerank_jaccard(A, B, cos, out, Ng, N, lambda_value):
                                     A.shape[0], Ng, N, lambda_value, stream_ptr()))
 
 
+def rerank_weights_sparse(nbr, X, vcols, vvals, vcnt, k1):
+    """Padded rows of V: vcols / vvals[i, :vcnt[i]] = members of R*(i) and their weights (reid_rerank_weights_sparse)."""
+    check(lib().reid_rerank_weights_sparse(ptr(nbr), nbr.stride(0), ptr(X), X.stride(0), ptr(vcols), ptr(vvals), ptr(vcnt), vvals.stride(0),
+                                           X.shape[0], X.shape[1], k1, stream_ptr()))
+
+
+def rerank_expand_count(vcols, vvals, vcnt, nbr, cnt, k1, k2):
+    """cnt[i] = non-zeros of row i of V2 (reid_rerank_expand_count)."""
+    check(lib().reid_rerank_expand_count(ptr(vcols), ptr(vvals), ptr(vcnt), vvals.stride(0), ptr(nbr), nbr.stride(0), ptr(cnt), vcnt.shape[0],
+                                         k1, k2, stream_ptr()))
+
+
+def rerank_expand_sparse(vcols, vvals, vcnt, nbr, rowptr, cols, vals, k1, k2):
+    """CSR rows of V2 at rowptr (int64 [N + 1]): columns ascending, the dense values (reid_rerank_expand_sparse)."""
+    check(lib().reid_rerank_expand_sparse(ptr(vcols), ptr(vvals), ptr(vcnt), vvals.stride(0), ptr(nbr), nbr.stride(0), ptr(rowptr), ptr(cols),
+                                          ptr(vals), vcnt.shape[0], k1, k2, stream_ptr()))
+
+
+def rerank_jaccard_sparse(rowptr, cols, vals, colptr, rows, cvals, cos, out, Ng, lambda_value):
+    """out[q, :Ng] = (1 - lambda) J + lambda cos for the len(rowptr) - 1 CSR rows at rowptr (absolute offsets into cols / vals)
+    against the gallery's CSC arrays (reid_rerank_jaccard_sparse)."""
+    check(lib().reid_rerank_jaccard_sparse(ptr(rowptr), ptr(cols), ptr(vals), cols.shape[0], ptr(colptr), ptr(rows), ptr(cvals), rows.shape[0],
+                                           ptr(cos), cos.stride(0), ptr(out), out.stride(0), rowptr.shape[0] - 1, Ng, colptr.shape[0] - 1,
+                                           lambda_value, stream_ptr()))
+
+
 def gather_rows(src, index, dst):
     """dst[r] = src[index[r]] (f32 rows, cols % 4 == 0; int32 index)."""
     check(lib().reid_gather_rows_f32(ptr(src), src.stride(0), ptr(index), ptr(dst), dst.stride(0), index.shape[0], dst.shape[1],

@@ -1,6 +1,7 @@
 """k-reciprocal re-ranking (prcv2025reid_amd/rerank.py, csrc/rerank.hip) per stage at protocol scale.
 
     python tools/bench_rerank.py [--shapes 4096x16384,2048x8192] [--D 512] [--k1 20] [--k2 6] [--runs 10] [--yard-runs 10]
+    python tools/bench_rerank.py --sparse [--shapes 4096x16384,2048x8192,10000x200000] ...
 
 Seeded clustered rows (16 images per identity), warm-up, then ``--runs`` timed runs per stage with device events: median, min and
 max in ms.  Stages: pooled kNN lists, cosine rows (all query chunks), weights, expand, Jaccard (all query chunks).  The Jaccard
@@ -9,7 +10,12 @@ stage does Nq * Ng * N min-add pairs; its rate is pairs over the median time.
 Yardstick of the Jaccard stage (there is no older implementation): the same definition in torch ops on the same GPU and the same
 V2, chunked ``torch.minimum(A[:, None, :], B[None, :, :]).sum(-1)``, then J and the blend.  Its result is compared with the
 kernel's before it is timed.  Last, the accuracy line: mAP of the small Gaussian test fixture before and after re-ranking, fp64
-reference against the evaluator.  One JSON line per shape and one for the accuracy line."""
+reference against the evaluator.  One JSON line per shape and one for the accuracy line.
+
+``--sparse``: the same stages of the sparse form (RerankParams(sparse=True): padded weights, count + cumsum + fill, the transposition
+of the gallery rows, the sparse Jaccard), the whole call, the whole evaluation through ``ProtocolEvaluator.per_query``, nnz(V2) / N,
+the s* row traffic of the Jaccard stage against its three-pass budget, and the peak device memory of one whole call
+(``torch.cuda.max_memory_allocated``).  No torch yardstick (it needs the dense V2); the accuracy line runs the sparse form."""
 import argparse
 import json
 import os
@@ -22,7 +28,7 @@ import torch
 
 from prcv2025reid_amd import ops
 from prcv2025reid_amd.evaluate import ProtocolEvaluator, split_gallery, split_scores
-from prcv2025reid_amd.rerank import RerankParams, Reranker
+from prcv2025reid_amd.rerank import RerankParams, Reranker, SparseReranker, csc_of_rows, list_width
 from prcv2025reid_amd.retrieval import GalleryIndex
 
 
@@ -96,7 +102,74 @@ def run_shape(Nq, Ng, D, params, runs, yard_runs, chunk):
     return res
 
 
-def accuracy_line():
+def run_shape_sparse(Nq, Ng, D, params, runs, chunk):
+    dev = torch.device('cuda', 0)
+    X, pid = clustered(Nq, Ng, D, dev)
+    N = Nq + Ng
+    k1, k2, lam = params.k1, params.k2, params.lambda_value
+    res = {'form': 'sparse', 'Nq': Nq, 'Ng': Ng, 'N': N, 'D': D, 'k1': k1, 'k2': k2, 'lambda': lam, 'chunk': chunk}
+    few = max(3, runs // 3)
+    index = GalleryIndex(X, normalized=True)
+    index.exact_scratch_bytes = 2 << 30
+    res['knn_lists'] = timed(lambda: index.topk(X, k=k1 + 1, normalized=True), runs if N <= 65536 else few, warmup=1)
+    nbr = index.topk(X, k=k1 + 1, normalized=True)[0]
+    del index
+    Gcat = split_gallery(X[Nq:])
+    res['cosine_rows'] = timed(lambda: [split_scores(X[a:a + chunk], Gcat) for a in range(0, Nq, chunk)], runs)
+    W = list_width(k1)
+    vcols = torch.empty(N, W, dtype=torch.int32, device=dev); vvals = torch.empty(N, W, device=dev)
+    vcnt = torch.empty(N, dtype=torch.int32, device=dev); cnt = torch.empty(N, dtype=torch.int32, device=dev)
+    res['weights'] = timed(lambda: ops.rerank_weights_sparse(nbr, X, vcols, vvals, vcnt, k1), runs)
+    res['expand_count'] = timed(lambda: ops.rerank_expand_count(vcols, vvals, vcnt, nbr, cnt, k1, k2), runs)
+    rowptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), cnt.long().cumsum(0)])
+    nnz, first = int(rowptr[N]), int(rowptr[Nq])
+    cols = torch.empty(nnz, dtype=torch.int32, device=dev); vals = torch.empty(nnz, device=dev)
+    res['expand_fill'] = timed(lambda: ops.rerank_expand_sparse(vcols, vvals, vcnt, nbr, rowptr, cols, vals, k1, k2), runs)
+    res['nnz_v2_per_row'] = nnz / N
+    res['v2_nonzero_fraction'] = nnz / N / N
+    res['transpose'] = timed(lambda: csc_of_rows(cols[first:], vals[first:], cnt[Nq:], N), runs)
+    colptr, grows, cvals = csc_of_rows(cols[first:], vals[first:], cnt[Nq:], N)
+    res['longest_csc_column'] = int((colptr[1:] - colptr[:-1]).max())
+    starts = list(range(0, Nq, chunk))
+    few_rows = Nq * Ng > (1 << 28)                              # the cosine rows of every chunk at once would be Nq * Ng * 8 bytes
+    cos = None if few_rows else [split_scores(X[a:a + chunk], Gcat) for a in starts]
+    outs = None if few_rows else [torch.empty_like(c) for c in cos]
+    if few_rows:
+        cos1 = split_scores(X[:chunk], Gcat); out1 = torch.empty_like(cos1)
+
+    def jaccard():
+        for i, a in enumerate(starts):
+            b = min(Nq, a + chunk)
+            if few_rows:                                        # one cosine chunk for every query chunk: the same traffic, not the same values
+                ops.rerank_jaccard_sparse(rowptr[a:b + 1], cols, vals, colptr, grows, cvals, cos1[:b - a], out1[:b - a], Ng, lam)
+            else:
+                ops.rerank_jaccard_sparse(rowptr[a:b + 1], cols, vals, colptr, grows, cvals, cos[i], outs[i], Ng, lam)
+    res['jaccard'] = timed(jaccard, runs)
+    # the budget: three passes over every s* row (zero fill, accumulate in place, finish) plus the cosine row read once
+    res['jaccard_row_bytes'] = float(Nq) * Ng * 4 * 4
+    res['jaccard_row_GBps'] = res['jaccard_row_bytes'] / (res['jaccard']['median_ms'] * 1e-3) / 1e9
+    stages = ('knn_lists', 'cosine_rows', 'weights', 'expand_count', 'expand_fill', 'transpose', 'jaccard')
+    res['total_median_ms'] = sum(res[s]['median_ms'] for s in stages)
+    res['jaccard_share'] = res['jaccard']['median_ms'] / res['total_median_ms']
+    del vcols, vvals, cols, vals, colptr, grows, cvals, cos, outs
+    torch.cuda.empty_cache()
+
+    def whole():
+        rr = SparseReranker(X[:Nq], X[Nq:], params, Gcat)
+        return [rr.rows(a, min(Nq, a + chunk)) for a in starts][-1]
+    res['whole_call'] = timed(whole, few, warmup=1)
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    whole()
+    torch.cuda.synchronize()
+    res['peak_memory_bytes'] = torch.cuda.max_memory_allocated()
+    res['peak_memory_over_inputs_bytes'] = res['peak_memory_bytes'] - base
+    ev = ProtocolEvaluator(X[Nq:], pid[Nq:], normalized=True)
+    res['per_query_evaluation'] = timed(lambda: ev.per_query(X[:Nq], pid[:Nq], normalized=True, chunk=chunk, rerank=params), few, warmup=1)
+    return res
+
+
+def accuracy_line(sparse=False):
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     import numpy as np
     import rerank_ref as R
@@ -112,7 +185,7 @@ def accuracy_line():
     return {'fixture': 'gaussian seed 422, 32 x 219, D 64, k1 8, k2 3, lambda 0.3',
             'ref_mAP_cosine': mean_ap(ref['cos'][:Nq, Nq:]), 'ref_mAP_reranked': mean_ap(ref['s']),
             'gpu_mAP_cosine': ev.rank_and_metrics(Q, qpt)['mAP'],
-            'gpu_mAP_reranked': ev.rank_and_metrics(Q, qpt, rerank=RerankParams(k1, k2, lam))['mAP']}
+            'gpu_mAP_reranked': ev.rank_and_metrics(Q, qpt, rerank=RerankParams(k1, k2, lam, sparse=sparse))['mAP']}
 
 
 if __name__ == '__main__':
@@ -125,10 +198,14 @@ if __name__ == '__main__':
     ap.add_argument('--runs', type=int, default=10)
     ap.add_argument('--yard-runs', type=int, default=10)
     ap.add_argument('--chunk', type=int, default=1024)
+    ap.add_argument('--sparse', action='store_true', help='the sparse form (RerankParams(sparse=True)); takes shapes beyond 65 536 pooled rows')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_rerank.py needs the GPU: nothing is measured without one')
     for shape in a.shapes.split(','):
         Nq, Ng = (int(v) for v in shape.split('x'))
-        print(json.dumps(run_shape(Nq, Ng, a.D, RerankParams(a.k1, a.k2, a.lambda_value), a.runs, a.yard_runs, a.chunk)), flush=True)
-    print(json.dumps(accuracy_line()), flush=True)
+        if a.sparse:
+            print(json.dumps(run_shape_sparse(Nq, Ng, a.D, RerankParams(a.k1, a.k2, a.lambda_value, sparse=True), a.runs, a.chunk)), flush=True)
+        else:
+            print(json.dumps(run_shape(Nq, Ng, a.D, RerankParams(a.k1, a.k2, a.lambda_value), a.runs, a.yard_runs, a.chunk)), flush=True)
+    print(json.dumps(accuracy_line(a.sparse)), flush=True)
