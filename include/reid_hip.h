@@ -454,6 +454,26 @@ int reid_rank_metrics(const float* scores, int64_t ld, const int32_t* g_pid, con
                       int32_t* npos, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exact top-k lists of fp32 score rows (csrc/select.hip): the ranked lists of the rows reid_rank_metrics scores, without a sort
+ * of the row.
+ *   scores  f32 [nq, ld], ld >= n, ld % 4 == 0, base 16-byte aligned (what reid_rank_metrics accepts and the re-ranking kernels
+ *           write); columns >= n are never candidates and may hold any bits, NaN and +inf included
+ *   g_img   i32 [n], q_excl i32 [nq, 4]: when BOTH are given, column j is dropped for row q iff g_img[j] >= 0 and g_img[j] is one of
+ *           q_excl[q, 0..3] (reid_rank_metrics' exclusion); either NULL = no masking
+ *   out_idx i32 [nq, k], out_score f32 [nq, k], contiguous: position r of row q is the r-th entry of a stable descending sort of
+ *           scores[q, :n] restricted to the eligible columns; the score is the unchanged bits of scores[q, idx]; positions at or
+ *           beyond the number of eligible columns hold index -1 and score -inf
+ * Order: by key descending, then column ascending; key(x) is the order-preserving u32 image of x + 0.0f (-0 and +0 are equal):
+ *   bits | 0x80000000 for non-negative values, ~bits for negative ones, 0xFFFFFFFF for every NaN (NaNs come first and are equal
+ *   to each other) -- the order of torch.sort(descending=True, stable=True).
+ * Limits: 1 <= k <= REID_ROWS_TOPK_MAX_K (k > n is allowed), nq >= 1, 1 <= n < 2^31; anything else is refused before a launch.
+ * One workgroup per row; deterministic (integer LDS counters only); nothing is allocated, nothing is synchronised.
+ * ------------------------------------------------------------------------------------------ */
+#define REID_ROWS_TOPK_MAX_K 1024
+int reid_rows_topk(const float* scores, int64_t ld, int32_t nq, int32_t n, int32_t k, const int32_t* g_img,
+                   const int32_t* q_excl, int32_t* out_idx, float* out_score, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Image transforms of the training input (datasets/dataset.py:284-307, train.py:1634-1641; eval: dataset.py:300-307,
  * tools/eval_mm_protocol.py:171-173), bit-exact against PIL + torch for given parameters, per image in this order:
  *   Image.crop(box).resize((S, S), BILINEAR) -> horizontal flip -> ImageEnhance.Brightness / .Contrast (Image.blend) in the

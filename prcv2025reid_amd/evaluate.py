@@ -104,6 +104,19 @@ class ProtocolEvaluator:
         Qf = q_feats.contiguous().float().to(self.dev)
         return (SparseReranker if rerank.sparse else Reranker)(Qf if normalized else l2_normalize(Qf), self.Gf, rerank, self._Gcat)
 
+    def _exclusions(self, q_img_ids: Optional[Sequence], ignore_same_img: bool) -> Optional[torch.Tensor]:
+        """i32 [Nq, 4] gallery image ids each query ignores (-1 = unused), or None when nothing is masked."""
+        if not (ignore_same_img and q_img_ids is not None and self.g_img is not None):
+            return None
+        rows = []
+        for ids in q_img_ids:
+            ids = ids if isinstance(ids, (set, list, tuple)) else [ids]
+            known = [self._img_map[x] for x in ids if x is not None and x in self._img_map]   # unknown ids mask nothing
+            if len(known) > 4:
+                raise ValueError('at most 4 image ids per query (one per modality sample)')
+            rows.append(known + [-1] * (4 - len(known)))
+        return torch.tensor(rows, dtype=torch.int32, device=self.dev)
+
     def per_query(self, q_feats: torch.Tensor, q_pids: torch.Tensor, q_img_ids: Optional[Sequence] = None,
                   ignore_same_img: bool = True, chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None):
         """(ap f64 [Nq], rank1 i32 [Nq], npos i32 [Nq]) on the device.  ``rerank``: a ``RerankParams`` ranks by the k-reciprocal
@@ -113,16 +126,7 @@ class ProtocolEvaluator:
         pos = torch.searchsorted(self._uniq, qp).clamp(max=self._uniq.numel() - 1)
         slot = torch.where(self._uniq[pos] == qp, pos, torch.full_like(pos, -1)).to(torch.int32).contiguous()
         qp32 = qp.to(torch.int32).contiguous()
-        excl = None
-        if ignore_same_img and q_img_ids is not None and self.g_img is not None:
-            rows = []
-            for ids in q_img_ids:
-                ids = ids if isinstance(ids, (set, list, tuple)) else [ids]
-                known = [self._img_map[x] for x in ids if x is not None and x in self._img_map]   # unknown ids mask nothing
-                if len(known) > 4:
-                    raise ValueError('at most 4 image ids per query (one per modality sample)')
-                rows.append(known + [-1] * (4 - len(known)))
-            excl = torch.tensor(rows, dtype=torch.int32, device=self.dev)
+        excl = self._exclusions(q_img_ids, ignore_same_img)
         ap = torch.zeros(Nq, dtype=torch.float64, device=self.dev)
         rank1 = torch.zeros(Nq, dtype=torch.int32, device=self.dev)
         npos = torch.zeros(Nq, dtype=torch.int32, device=self.dev)
@@ -133,6 +137,26 @@ class ProtocolEvaluator:
             ops.rank_metrics(S, self.g_pid, self.g_img, qp32[a:b], slot[a:b], None if excl is None else excl[a:b].contiguous(),
                              self.csr_off, self.csr_idx, self.Ng, self.max_pos, ap[a:b], rank1[a:b], npos[a:b])
         return ap, rank1, npos
+
+    def ranked_lists(self, q_feats: torch.Tensor, k: int = 100, q_img_ids: Optional[Sequence] = None, ignore_same_img: bool = True,
+                     chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None):
+        """(idx i32 [Nq, k], score f32 [Nq, k]) on the device: every query's first k gallery rows, score descending and gallery index
+        ascending on ties, of the very rows ``per_query`` ranks (``scores``, or s* with ``rerank``) under the same same-image
+        exclusion; positions past the eligible gallery rows hold -1 / -inf.  1 <= k <= 1024 (``ops.rows_topk``)."""
+        if not q_feats.is_cuda:
+            raise _lib.ReidHipError('ranked_lists needs device tensors (there is no CPU path)')
+        if not 1 <= k <= ops.ROWS_TOPK_MAX_K:
+            raise _lib.ReidHipError(f'ranked_lists: k={k} outside 1..{ops.ROWS_TOPK_MAX_K} (the limit of ops.rows_topk)')
+        Nq = q_feats.shape[0]
+        excl = self._exclusions(q_img_ids, ignore_same_img)
+        idx = torch.empty(Nq, k, dtype=torch.int32, device=self.dev)
+        score = torch.empty(Nq, k, dtype=torch.float32, device=self.dev)
+        rr = None if rerank is None else self._reranker(q_feats, rerank, normalized)
+        for a in range(0, Nq, chunk):
+            b = min(Nq, a + chunk)
+            S = self.scores(q_feats[a:b], normalized) if rr is None else rr.rows(a, b)
+            ops.rows_topk(S, self.Ng, k, self.g_img, None if excl is None else excl[a:b].contiguous(), out=(idx[a:b], score[a:b]))
+        return idx, score
 
     def rank_and_metrics(self, q_feats, q_pids, q_img_ids=None, ignore_same_img: bool = True, chunk: int = 1024,
                          rerank: Optional['RerankParams'] = None) -> Dict[str, float]:
@@ -159,13 +183,16 @@ class ProtocolEvaluator:
     def export_submission_csv(self, q_feats, query_keys: Sequence[str], gallery_img_names: Sequence, output_path: str,
                               top_k: int = 100, rerank: Optional['RerankParams'] = None, chunk: int = 1024):
         """eval_mm_protocol.py:595-649: one row per query, the top_k gallery image ids of the unmasked ranking.  ``rerank``: a
-        ``RerankParams`` lists by the re-ranked similarity s* (stable descending sort of the s* rows on the device)."""
+        ``RerankParams`` lists by the re-ranked similarity s* in the order of a stable descending sort of the s* rows (``ranked_lists``
+        without exclusion; the sort itself only for a top_k outside 1..1024, the list lengths of ``ops.rows_topk``)."""
         import csv
         if rerank is None:
             if self.index is None:
                 self.index = GalleryIndex(self.Gf, normalized=True)
             idx, _ = self.index.topk(q_feats.to(self.dev), k=min(top_k, self.Ng))
-        else:
+        elif 1 <= top_k <= ops.ROWS_TOPK_MAX_K:                    # (host features are moved here, as the other branches do)
+            idx, _ = self.ranked_lists(q_feats.to(self.dev), k=top_k, chunk=chunk, rerank=rerank)   # -1 past the gallery's end (top_k > Ng)
+        else:                                                      # outside ops.rows_topk's list lengths (top_k <= 0 included): the sort
             rr = self._reranker(q_feats, rerank)
             idx = torch.cat([torch.sort(rr.rows(a, min(rr.Nq, a + chunk))[:, :self.Ng], dim=1, descending=True, stable=True)[1][:, :top_k]
                              for a in range(0, rr.Nq, chunk)], 0)
@@ -174,7 +201,7 @@ class ProtocolEvaluator:
             w = csv.writer(f)
             w.writerow(['query_key', 'ranked_gallery_ids'])
             for key, row in zip(query_keys, idx):
-                w.writerow([key, ' '.join(str(gallery_img_names[i]) for i in row if gallery_img_names[i] is not None)])
+                w.writerow([key, ' '.join(str(gallery_img_names[i]) for i in row if i >= 0 and gallery_img_names[i] is not None)])
 
 
 def competition_metrics(all_metrics: Dict[str, Dict[str, float]]) -> Dict[str, float]:

@@ -378,6 +378,38 @@ def rank_metrics(scores, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, 
                                   stream_ptr()))
 
 
+ROWS_TOPK_MAX_K = 1024        # REID_ROWS_TOPK_MAX_K: the longest list reid_rows_topk writes
+
+
+def rows_topk(scores, n, k, g_img=None, q_excl=None, out=None):
+    """(idx i32 [nq, k], score f32 [nq, k]): the first k entries of a stable descending sort of scores[:, :n] per row, without the
+    sort (reid_rows_topk, include/reid_hip.h); n <= scores.shape[1].  ``g_img`` [n] and ``q_excl`` [nq, 4] together drop a row's excluded images as
+    ``rank_metrics`` does; positions past the eligible columns hold -1 / -inf.  ``out``: the (idx, score) pair to write into."""
+    L._req(scores, torch.float32, 'scores')
+    if scores.dim() != 2:
+        raise ValueError(f'scores: expected [nq, ld], got {tuple(scores.shape)}')
+    nq = scores.shape[0]
+    if n > scores.shape[1]:
+        raise ValueError(f'scores: n={n} columns asked of a [{nq}, {scores.shape[1]}] tensor')
+    if g_img is not None:
+        L._req(g_img, torch.int32, 'g_img')
+        if g_img.numel() < n or not g_img.is_contiguous():
+            raise ValueError(f'g_img: expected contiguous [>= {n}], got {tuple(g_img.shape)}')
+    if q_excl is not None:
+        L._req(q_excl, torch.int32, 'q_excl')
+        if tuple(q_excl.shape) != (nq, 4) or not q_excl.is_contiguous():
+            raise ValueError(f'q_excl: expected contiguous [{nq}, 4], got {tuple(q_excl.shape)}')
+    if out is None:
+        out = (torch.empty(nq, max(k, 0), dtype=torch.int32, device=scores.device),
+               torch.empty(nq, max(k, 0), dtype=torch.float32, device=scores.device))
+    idx, score = out
+    L._req(idx, torch.int32, 'out idx'); L._req(score, torch.float32, 'out score')
+    if not (tuple(idx.shape) == tuple(score.shape) == (nq, k) and idx.is_contiguous() and score.is_contiguous()):
+        raise ValueError(f'out: expected two contiguous [{nq}, {k}] tensors, got {tuple(idx.shape)}, {tuple(score.shape)}')
+    check(lib().reid_rows_topk(ptr(scores), scores.stride(0), nq, n, k, ptr(g_img), ptr(q_excl), ptr(idx), ptr(score), stream_ptr()))
+    return idx, score
+
+
 def rerank_weights(nbr, X, V, k1):
     """V[i, :N] = k-reciprocal weights of pooled row i (reid_rerank_weights, include/reid_hip.h); zero-fills V[:, :N] first."""
     check(lib().reid_rerank_weights(ptr(nbr), nbr.stride(0), ptr(X), X.stride(0), ptr(V), V.stride(0), X.shape[0], X.shape[1], k1,

@@ -15,6 +15,9 @@ non-zeros only (layout: include/reid_hip.h), no limit on N other than int32 row 
   3. V2 as CSR                  reid_rerank_expand_count, a cumsum, reid_rerank_expand_sparse; then the gallery rows transposed
                                 to CSC with torch ops (bincount, cumsum, one stable sort): a cold step
   4. s* rows per query chunk    reid_rerank_jaccard_sparse: one workgroup per s* row, m accumulated in the row itself
+
+Ranked lists of either form (``topk``, ``rerank_topk``): reid_rows_topk on the s* rows, an exact top-k select in the order of a stable
+descending sort, without the sort.
 """
 from dataclasses import dataclass
 from typing import Iterator, Optional, Tuple
@@ -67,7 +70,16 @@ def check_shapes(Nq: int, Ng: int, params: RerankParams):
                                 f'{params.k2 * list_width(params.k1)} entries per row, more than SPARSE_MERGE_MAX = {SPARSE_MERGE_MAX}')
 
 
-class Reranker:
+class _RankedRows:
+    """What both forms share once ``rows(a, b)`` exists."""
+
+    def topk(self, a: int, b: int, k: int, g_img: Optional[torch.Tensor] = None, q_excl: Optional[torch.Tensor] = None):
+        """(idx i32 [b - a, k], s* f32 [b - a, k]): the first k gallery rows of queries a..b-1 by s* descending, gallery index ascending
+        on ties (``ops.rows_topk`` on ``rows(a, b)``); ``g_img`` [Ng] and ``q_excl`` [b - a, 4] drop images as ``ops.rank_metrics`` does."""
+        return ops.rows_topk(self.rows(a, b), self.Ng, k, g_img, q_excl)
+
+
+class Reranker(_RankedRows):
     """Steps 1-3 for one (query set, gallery) pair, built once; ``rows(a, b)`` then returns the s* rows of queries a..b-1."""
 
     def __init__(self, Qf: torch.Tensor, Gf: torch.Tensor, params: RerankParams, Gcat: Optional[torch.Tensor] = None):
@@ -95,7 +107,7 @@ class Reranker:
         return out
 
 
-class SparseReranker:
+class SparseReranker(_RankedRows):
     """``Reranker`` on the sparse form: the same ``rows(a, b)``, V2 as CSR (``rowptr``, ``cols``, ``vals``) and its gallery rows as
     CSC (``colptr``, ``grows``, ``cvals``).  Building it synchronises once, to size the arrays of non-zeros."""
 
@@ -148,20 +160,36 @@ def csc_of_rows(cols: torch.Tensor, vals: torch.Tensor, cnt: torch.Tensor, N: in
     return colptr, row_of[order].contiguous(), vals[order].contiguous()
 
 
-def rerank_scores(q_feats: torch.Tensor, g_feats: torch.Tensor, params: RerankParams = RerankParams(), normalized: bool = False,
-                  chunk: int = 1024) -> Iterator[Tuple[int, torch.Tensor]]:
-    """Yields ``(a, S)`` chunk by chunk: S [<= chunk, ld >= Ng] holds the re-ranked similarities s* of queries a, a + 1, ...
-    against the gallery (re-ranked distance = 1 - s*; rank by s* descending, gallery index ascending on ties).  Arguments are
-    checked and steps 1-3 run at the call, the Jaccard step as the chunks are drawn."""
+def _pooled(q_feats: torch.Tensor, g_feats: torch.Tensor, params: RerankParams, normalized: bool):
+    """The checks of the public calls, then steps 1-3."""
     check_shapes(q_feats.shape[0], g_feats.shape[0], params)
     if not (q_feats.is_cuda and g_feats.is_cuda):
         raise _lib.ReidHipError('re-ranking needs device tensors (there is no CPU path)')
     Qf, Gf = q_feats.contiguous().float(), g_feats.contiguous().float()
     if not normalized:
         Qf, Gf = l2_normalize(Qf), l2_normalize(Gf)
-    rr = (SparseReranker if params.sparse else Reranker)(Qf, Gf, params)
+    return (SparseReranker if params.sparse else Reranker)(Qf, Gf, params)
+
+
+def rerank_scores(q_feats: torch.Tensor, g_feats: torch.Tensor, params: RerankParams = RerankParams(), normalized: bool = False,
+                  chunk: int = 1024) -> Iterator[Tuple[int, torch.Tensor]]:
+    """Yields ``(a, S)`` chunk by chunk: S [<= chunk, ld >= Ng] holds the re-ranked similarities s* of queries a, a + 1, ...
+    against the gallery (re-ranked distance = 1 - s*; rank by s* descending, gallery index ascending on ties).  Arguments are
+    checked and steps 1-3 run at the call, the Jaccard step as the chunks are drawn."""
+    rr = _pooled(q_feats, g_feats, params, normalized)
 
     def chunks():
         for a in range(0, rr.Nq, chunk):
             yield a, rr.rows(a, min(rr.Nq, a + chunk))
     return chunks()
+
+
+def rerank_topk(q_feats: torch.Tensor, g_feats: torch.Tensor, params: RerankParams = RerankParams(), k: int = 100,
+                normalized: bool = False, chunk: int = 1024) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(idx i32 [Nq, k], s* f32 [Nq, k]): every query's first k gallery rows by the re-ranked similarity, the order of a stable
+    descending sort of the rows ``rerank_scores`` yields for the same call (positions past Ng hold -1 / -inf).  1 <= k <= 1024."""
+    if not 1 <= k <= ops.ROWS_TOPK_MAX_K:
+        raise _lib.ReidHipError(f're-ranking: k={k} outside 1..{ops.ROWS_TOPK_MAX_K} (the limit of ops.rows_topk)')
+    rr = _pooled(q_feats, g_feats, params, normalized)
+    parts = [rr.topk(a, min(rr.Nq, a + chunk), k) for a in range(0, rr.Nq, chunk)]
+    return torch.cat([p[0] for p in parts], 0), torch.cat([p[1] for p in parts], 0)

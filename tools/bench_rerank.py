@@ -2,6 +2,7 @@
 
     python tools/bench_rerank.py [--shapes 4096x16384,2048x8192] [--D 512] [--k1 20] [--k2 6] [--runs 10] [--yard-runs 10]
     python tools/bench_rerank.py --sparse [--shapes 4096x16384,2048x8192,10000x200000] ...
+    python tools/bench_rerank.py [--sparse] --lists 100 [--lists-only] ...
 
 Seeded clustered rows (16 images per identity), warm-up, then ``--runs`` timed runs per stage with device events: median, min and
 max in ms.  Stages: pooled kNN lists, cosine rows (all query chunks), weights, expand, Jaccard (all query chunks).  The Jaccard
@@ -15,7 +16,13 @@ reference against the evaluator.  One JSON line per shape and one for the accura
 ``--sparse``: the same stages of the sparse form (RerankParams(sparse=True): padded weights, count + cumsum + fill, the transposition
 of the gallery rows, the sparse Jaccard), the whole call, the whole evaluation through ``ProtocolEvaluator.per_query``, nnz(V2) / N,
 the s* row traffic of the Jaccard stage against its three-pass budget, and the peak device memory of one whole call
-(``torch.cuda.max_memory_allocated``).  No torch yardstick (it needs the dense V2); the accuracy line runs the sparse form."""
+(``torch.cuda.max_memory_allocated``).  No torch yardstick (it needs the dense V2); the accuracy line runs the sparse form.
+
+``--lists K`` (default 100; 0 skips it), in both modes: the ranked lists of the s* rows.  Every chunk's rows stay on the device
+(Nq * Ng * 4 bytes); ``ops.rows_topk`` and the yardstick -- the stable descending sort ``export_submission_csv`` used before,
+``torch.sort(..., stable=True)[1][:, :K]`` on the same rows -- must give identical lists, then take turns for 2 warm-up and ``--runs``
+timed runs each (device events).  Reported: both timings, Nq * Ng * 4 bytes over the kernel's median as TB/s, the peak device memory
+of each, and the whole ``ProtocolEvaluator.ranked_lists`` call.  ``--lists-only`` runs nothing else."""
 import argparse
 import json
 import os
@@ -45,6 +52,71 @@ def timed(fn, runs, warmup=2):
     return {'median_ms': statistics.median(ms), 'min_ms': min(ms), 'max_ms': max(ms), 'runs': runs}
 
 
+def timed_alternating(fns, runs, warmup=2):
+    """``timed`` for several callables measured in ONE session, taking turns run by run, so that a change of the GPU's state
+    (clocks, other tenants) falls on all of them alike."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in fns}
+    for _ in range(runs):
+        for name, fn in fns.items():
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(); fn(); e1.record()
+            torch.cuda.synchronize()
+            ms[name].append(e0.elapsed_time(e1))
+    return {name: {'median_ms': statistics.median(v), 'min_ms': min(v), 'max_ms': max(v), 'runs': runs} for name, v in ms.items()}
+
+
+def peak_over_base(fn):
+    """Peak device memory of one call above what was allocated before it, in bytes."""
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    out = fn()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated() - base
+    del out
+    return peak
+
+
+def lists_stage(X, pid, Nq, Ng, params, K, runs, chunk):
+    """Ranked lists of length K from the s* rows of every query chunk, resident on the device: ``ops.rows_topk`` against the stable
+    sort it replaces in ``export_submission_csv`` (compared before anything is timed, then timed in turns), the whole
+    ``ProtocolEvaluator.ranked_lists`` call, and the peak device memory of each."""
+    starts = list(range(0, Nq, chunk))
+    rr = (SparseReranker if params.sparse else Reranker)(X[:Nq], X[Nq:], params)
+    rows = [rr.rows(a, min(Nq, a + chunk)) for a in starts]
+    del rr
+    torch.cuda.empty_cache()
+
+    def kernel():
+        return torch.cat([ops.rows_topk(S, Ng, K)[0] for S in rows], 0)
+
+    def sort():
+        return torch.cat([torch.sort(S[:, :Ng], dim=1, descending=True, stable=True)[1][:, :K] for S in rows], 0)     # the line it replaces
+    assert torch.equal(kernel().long(), sort()), 'ops.rows_topk and the stable sort disagree'
+    res = {'K': K, 'row_bytes': float(Nq) * Ng * 4}
+    res.update(timed_alternating({'kernel': kernel, 'stable_sort': sort}, runs))
+    res['kernel_TBps'] = res['row_bytes'] / (res['kernel']['median_ms'] * 1e-3) / 1e12
+    res['sort_min_over_kernel_median'] = res['stable_sort']['min_ms'] / res['kernel']['median_ms']
+    res['kernel_peak_memory_bytes'] = peak_over_base(kernel)
+    res['stable_sort_peak_memory_bytes'] = peak_over_base(sort)
+    zeros = [float((S[:, :Ng] == 0).float().mean()) for S in rows[:1]]
+    res['zero_fraction_first_chunk'] = zeros[0]
+    del rows
+    torch.cuda.empty_cache()
+    ev = ProtocolEvaluator(X[Nq:], pid[Nq:], normalized=True)
+
+    def whole():
+        return ev.ranked_lists(X[:Nq], k=K, chunk=chunk, normalized=True, rerank=params)
+    res['ranked_lists_call'] = timed(whole, max(3, runs // 3), warmup=1)
+    res['ranked_lists_peak_memory_bytes'] = peak_over_base(whole)
+    return res
+
+
 def clustered(Nq, Ng, D, dev, seed=0, per_id=16, noise=1.0):
     g = torch.Generator(device=dev).manual_seed(seed)
     N = Nq + Ng
@@ -63,12 +135,16 @@ def torch_jaccard(A, B, cos, lam, qc=64, gc=1024):
     return out
 
 
-def run_shape(Nq, Ng, D, params, runs, yard_runs, chunk):
+def run_shape(Nq, Ng, D, params, runs, yard_runs, chunk, lists=0, lists_only=False):
     dev = torch.device('cuda', 0)
-    X, _ = clustered(Nq, Ng, D, dev)
+    X, pid = clustered(Nq, Ng, D, dev)
     N = Nq + Ng
     k1, k2, lam = params.k1, params.k2, params.lambda_value
     res = {'Nq': Nq, 'Ng': Ng, 'N': N, 'D': D, 'k1': k1, 'k2': k2, 'lambda': lam, 'chunk': chunk}
+    if lists:
+        res['lists'] = lists_stage(X, pid, Nq, Ng, params, lists, runs, chunk)
+    if lists_only:
+        return res
     index = GalleryIndex(X, normalized=True)
     res['knn_lists'] = timed(lambda: index.topk(X, k=k1 + 1, normalized=True), runs)
     nbr = index.topk(X, k=k1 + 1, normalized=True)[0]
@@ -102,12 +178,16 @@ def run_shape(Nq, Ng, D, params, runs, yard_runs, chunk):
     return res
 
 
-def run_shape_sparse(Nq, Ng, D, params, runs, chunk):
+def run_shape_sparse(Nq, Ng, D, params, runs, chunk, lists=0, lists_only=False):
     dev = torch.device('cuda', 0)
     X, pid = clustered(Nq, Ng, D, dev)
     N = Nq + Ng
     k1, k2, lam = params.k1, params.k2, params.lambda_value
     res = {'form': 'sparse', 'Nq': Nq, 'Ng': Ng, 'N': N, 'D': D, 'k1': k1, 'k2': k2, 'lambda': lam, 'chunk': chunk}
+    if lists:
+        res['lists'] = lists_stage(X, pid, Nq, Ng, params, lists, runs, chunk)
+    if lists_only:
+        return res
     few = max(3, runs // 3)
     index = GalleryIndex(X, normalized=True)
     index.exact_scratch_bytes = 2 << 30
@@ -199,13 +279,18 @@ if __name__ == '__main__':
     ap.add_argument('--yard-runs', type=int, default=10)
     ap.add_argument('--chunk', type=int, default=1024)
     ap.add_argument('--sparse', action='store_true', help='the sparse form (RerankParams(sparse=True)); takes shapes beyond 65 536 pooled rows')
+    ap.add_argument('--lists', type=int, default=100, help='length K of the ranked lists stage (ops.rows_topk against the stable sort); 0 = skip it')
+    ap.add_argument('--lists-only', action='store_true', help='the ranked lists stage alone')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit('bench_rerank.py needs the GPU: nothing is measured without one')
     for shape in a.shapes.split(','):
         Nq, Ng = (int(v) for v in shape.split('x'))
         if a.sparse:
-            print(json.dumps(run_shape_sparse(Nq, Ng, a.D, RerankParams(a.k1, a.k2, a.lambda_value, sparse=True), a.runs, a.chunk)), flush=True)
+            print(json.dumps(run_shape_sparse(Nq, Ng, a.D, RerankParams(a.k1, a.k2, a.lambda_value, sparse=True), a.runs, a.chunk, a.lists,
+                                              a.lists_only)), flush=True)
         else:
-            print(json.dumps(run_shape(Nq, Ng, a.D, RerankParams(a.k1, a.k2, a.lambda_value), a.runs, a.yard_runs, a.chunk)), flush=True)
-    print(json.dumps(accuracy_line(a.sparse)), flush=True)
+            print(json.dumps(run_shape(Nq, Ng, a.D, RerankParams(a.k1, a.k2, a.lambda_value), a.runs, a.yard_runs, a.chunk, a.lists,
+                                       a.lists_only)), flush=True)
+    if not a.lists_only:
+        print(json.dumps(accuracy_line(a.sparse)), flush=True)
