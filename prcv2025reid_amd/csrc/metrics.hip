@@ -13,9 +13,11 @@
 //   3. prefix sum of the histogram -> rank of the r-th positive = 1 + r + #non-positives before it;
 //      AP = mean_r (r + 1) / rank_r (double), first-positive rank for CMC@k.
 // HBM-bound: 4 bytes of score + 8 bytes of L2-resident pid / image id per gallery entry per query.
-#include "common.h"
+#include "rank.h"
 
 namespace {
+
+using namespace ranking;
 
 constexpr int NBUCKET = 2048;      // score buckets between the weakest and the strongest positive of a query
 constexpr int MAXP_LIMIT = 8192;    // positives per query held in LDS (12 bytes each; more -> npos = -1, not evaluated)
@@ -30,10 +32,6 @@ struct MetricParams {
     int nq, Ng, cap;                           // cap: power of two >= the longest CSR row, LDS capacity of this launch
 };
 
-__device__ __forceinline__ bool before(float sa, int ia, float sb, int ib) {   // (sa, ia) ranks before (sb, ib)
-    return sa > sb || (sa == sb && ia < ib);
-}
-
 __global__ __launch_bounds__(256) void rank_metrics_kernel(const MetricParams p) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     float* ps = (float*)dyn;
@@ -45,17 +43,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const MetricParams p)
     const int q = blockIdx.x, tid = threadIdx.x;
     const float* row = p.S + (long long)q * p.lds_;
     const int slot = p.q_slot[q];
-    int ex[4] = {-1, -1, -1, -1};
-    if (p.q_excl && p.g_img) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ex[k] = p.q_excl[q * 4 + k];
-    }
-    const bool has_ex = (ex[0] & ex[1] & ex[2] & ex[3]) != -1;      // any id other than -1
-    auto excluded = [&](int j) {
-        if (!has_ex) return false;
-        const int g = p.g_img[j];
-        return g >= 0 && (g == ex[0] || g == ex[1] || g == ex[2] || g == ex[3]);
-    };
+    const Excluded4 excluded(p.q_excl, p.g_img, q);
     if (tid == 0) cnt = 0;
     __syncthreads();
     if (slot >= 0) {
@@ -78,20 +66,7 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const MetricParams p)
     for (int t = np + tid; t < n2; t += 256) { ps[t] = -INFINITY; pi[t] = 0x7fffffff; }
     for (int t = tid; t <= np; t += 256) hist[t] = 0;
     __syncthreads();
-    for (int k = 2; k <= n2; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < n2; t += 256) {
-                const int u = t ^ j;
-                if (u > t) {
-                    const bool up = (t & k) == 0;              // ascending position = earlier rank
-                    const float sa = ps[t], sb = ps[u];
-                    const int ia = pi[t], ib = pi[u];
-                    const bool swap = up ? before(sb, ib, sa, ia) : before(sa, ia, sb, ib);
-                    if (swap) { ps[t] = sb; ps[u] = sa; pi[t] = ib; pi[u] = ia; }
-                }
-            }
-            __syncthreads();
-        }
+    lds_rank_sort(ps, pi, n2, tid);
     const float s_last = ps[np - 1];
     const int i_last = pi[np - 1];
     const int pid = p.q_pid[q];
@@ -130,13 +105,13 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const MetricParams p)
     }
     __syncthreads();
     auto visit = [&](int j, float s) {
-        if (!before(s, j, s_last, i_last)) return;             // behind every positive: affects no rank we need
+        if (!ranks_before(s, j, s_last, i_last)) return;             // behind every positive: affects no rank we need
         if (p.g_pid[j] == pid || excluded(j)) return;          // positives are counted by their own position; masked rows rank last
         const int b = bucket(s);
         int lo = bstart[b], hi = bstart[b + 1];                 // first position whose positive is NOT before (s, j)
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (before(ps[mid], pi[mid], s, j)) lo = mid + 1; else hi = mid;
+            if (ranks_before(ps[mid], pi[mid], s, j)) lo = mid + 1; else hi = mid;
         }
         atomicAdd(&hist[lo], 1);
     };

@@ -22,9 +22,11 @@
 //                                in ascending order and for each the column's CSC list across the threads (gallery rows of one
 //                                column are distinct: no two threads touch one element), a barrier between columns, so m[q, g]
 //                                accumulates in the out row in ascending column order; one finishing pass blends in the cosine row.
-#include "common.h"
+#include "rank.h"
 
 namespace {
+
+using ranking::block_excl_scan;
 
 constexpr int K1_MAX = 64;
 constexpr int LIST_MAX = K1_MAX + 1;                       // entries of a kNN list that are read: k1 + 1
@@ -251,28 +253,7 @@ __global__ __launch_bounds__(256, 2) void rerank_jaccard_kernel(const JaccardPar
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int SPARSE_MERGE_MAX = REID_RERANK_MERGE_MAX;   // entries one row's merge holds in LDS: 12 bytes each, 96 KB of the CU's 160 KB at the most.
 // A call takes what its own bound needs: cap = k2 W rounded up to a power of two (the defaults: 2048 entries, 24 KB, six workgroups per CU).
-constexpr int XT = 256;                  // threads of the merge workgroup
-
-// Exclusive prefix of v over the workgroup's XT threads in thread order (ws: one int per wave); total: the sum over all threads.
-__device__ __forceinline__ int block_excl_scan(int v, int* ws, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) ws[w] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int u = 0; u < XT / 64; ++u) {
-        if (u < w) base += ws[u];
-        total += ws[u];
-    }
-    return base + inc - v;
-}
+constexpr int XT = 256;                  // threads of the merge workgroup (block_excl_scan's workgroup size)
 
 // One workgroup per pooled row i.  FILL = false: cnt[i] = number of distinct columns in the union of the padded rows nbr[i, t], t < k2.
 // FILL = true: those columns ascending and their values at rowptr[i] (never past rowptr[i + 1]).  A list entry outside [0, N) is

@@ -14,14 +14,54 @@
 // A query whose list overflowed is flagged (out_idx[q][0] = -2) and handled by the caller's exact
 // fallback (brute-force kernel below), so the result never silently degrades.
 #include "gemm_core.h"
+#include "rank.h"
 #include <stdlib.h>
 
 namespace {
 
 using namespace gemmcore;
+using namespace ranking;
 
 constexpr float EPS_BF16 = REID_T16_EPS * 1.01f;   // |q~.g~ - q.g| <= 2u (+1 %) for unit q, g rounded to the 16-bit format (Cauchy-Schwarz)
 
+constexpr int SAMPLE = 8192;
+inline int cap_for(int Ng, int k) {
+    // expected survivors ~ k*Ng/SAMPLE (the sample's k-th best is about the (k*Ng/SAMPLE)-th best overall) times ~1.7 for the
+    // 2*eps safety margin; 6x head-room
+    long c = 6L * k * ((Ng + SAMPLE - 1) / SAMPLE) + 64;
+    if (c < 256) c = 256;
+    if (c > 8192) c = 8192;
+    return (int)c;
+}
+
+// The fp32 score of a (query, gallery row) pair is DEFINED by this evaluation order (explicit fma chain: the compiler has no
+// contraction freedom), lane l taking elements 4l + 256 j, then the xor butterfly of wave_sum.  Every path that produces a final
+// score (select_kernel, the brute-force fallback, the streaming form) uses it, so they agree bit for bit.
+__device__ __forceinline__ float dot4_acc(float s, const f32x4 a, const f32x4 b) {
+    float t = a[0] * b[0];
+    t = __builtin_fmaf(a[1], b[1], t);
+    t = __builtin_fmaf(a[2], b[2], t);
+    t = __builtin_fmaf(a[3], b[3], t);
+    return s + t;
+}
+
+// One gallery row against the query row held in LDS, by the calling wave: the score in every lane.
+__device__ __forceinline__ float row_dot(const float* qrow, const float* g, int D, int lane) {
+    float s = 0.f;
+    for (int i = lane * 4; i < D; i += 256) {
+        const f32x4 a = *(const f32x4*)(qrow + i), b = *(const f32x4*)(g + i);
+        s = dot4_acc(s, a, b);
+    }
+    return wave_sum(s);
+}
+
+// The overflow mark of query q (its candidates did not fit): the caller takes the exact fallback for it.  One thread calls this.
+__device__ __forceinline__ void flag_overflow(int32_t* out_idx, float* out_score, int q, int k) {
+    out_idx[(size_t)q * k] = -2;
+    out_score[(size_t)q * k] = 0.f;
+}
+
+// ------------------------------------------------------------------------------------------ phases A and B, tiled: the MFMA score kernel
 struct TopkParams {
     const bf16_t* Q; const bf16_t* G;
     int Nq, Ng, D;
@@ -173,6 +213,7 @@ __global__ __launch_bounds__(256) void kth_kernel(const float* __restrict__ dens
     for (int r = 0; r < rounds; ++r) {
         float best = -INFINITY; int bi = -1;
         for (int i = lane; i < n; i += 64) if (v[i] > best) { best = v[i]; bi = i; }
+        // (not wave_best: only the k-th VALUE is used, so among equal values any position will do; a lane without an entry has bi < 0)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
@@ -230,197 +271,6 @@ __global__ __launch_bounds__(256) void kth_fast_kernel(const float* __restrict__
     if (lane == 0) thr[q] = (n < k ? -INFINITY : kth - 2.f * EPS_BF16);
 }
 
-// The fp32 score of a (query, gallery row) pair is DEFINED by this evaluation order (explicit fma chain: the compiler has no
-// contraction freedom), lane l taking elements 4l + 256 j, then the xor butterfly of wave_sum.  Every path that produces a final
-// score (select_kernel, the brute-force fallback, the streaming form) uses it, so they agree bit for bit.
-__device__ __forceinline__ float dot4_acc(float s, const f32x4 a, const f32x4 b) {
-    float t = a[0] * b[0];
-    t = __builtin_fmaf(a[1], b[1], t);
-    t = __builtin_fmaf(a[2], b[2], t);
-    t = __builtin_fmaf(a[3], b[3], t);
-    return s + t;
-}
-
-// phase C: exact fp32 re-score of the candidates + top-k by (score desc, index asc)
-__global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ Qf, const float* __restrict__ Gf, int D,
-                                                     const int32_t* __restrict__ exq, const int32_t* __restrict__ exg,
-                                                     const int32_t* __restrict__ cand_idx, const float* __restrict__ cand_score,
-                                                     const int32_t* __restrict__ cand_cnt, int cap, int k,
-                                                     int32_t* __restrict__ out_idx, float* __restrict__ out_score, int Nq) {
-    extern __shared__ char sm2[];
-    __shared__ float thr2;
-    volatile float* sc = (volatile float*)sm2;                  // [cap]
-    volatile int32_t* ix = (volatile int32_t*)(sc + cap);       // [cap]
-    float* qrow = (float*)((float*)sm2 + 2 * cap);         // [D]
-    const int q = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int cnt = cand_cnt[q];
-    if (cnt > cap) {                          // overflow: caller must take the exact fallback
-        if (tid == 0) { out_idx[(size_t)q * k] = -2; out_score[(size_t)q * k] = 0.f; }
-        return;
-    }
-    for (int i = tid; i < D; i += 256) qrow[i] = Qf[(size_t)q * D + i];
-    // Second-level filter on the 16-bit-operand scores the filter pass saved: with a = k-th largest of them, a candidate below
-    // a - 2 eps cannot be in the exact top k (its true score is < a - eps <= the true score of each of the k candidates at or
-    // above a).  Only the survivors (about k + a few) pay the 2 KB fp32 gallery-row gather of the exact re-score; before,
-    // all ~250 candidates per query did (5 GB of gathers at 10k x 200k).
-    const float* cs = cand_score + (size_t)q * cap;
-    for (int c = tid; c < cnt; c += 256) sc[c] = cs[c];
-    __syncthreads();
-    if (w == 0) {
-        float kth = -INFINITY;
-        const int rounds = k < cnt ? k : cnt;
-        for (int r = 0; r < rounds; ++r) {
-            float best = -INFINITY; int bpos = -1;
-            for (int c = lane; c < cnt; c += 64) {
-                const float v = sc[c];
-                if (v > best || bpos < 0) { best = v; bpos = c; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ob = __shfl_xor(best, o, 64); const int op = __shfl_xor(bpos, o, 64);
-                if (op >= 0 && (bpos < 0 || ob > best)) { best = ob; bpos = op; }
-            }
-            kth = best;
-            if (bpos >= 0 && (bpos & 63) == lane) sc[bpos] = -INFINITY;
-        }
-        if (lane == 0) thr2 = cnt < k ? -INFINITY : kth - 2.f * EPS_BF16;
-    }
-    __syncthreads();
-    const float t2 = thr2;
-    const int eq = exq ? exq[q] : -1;
-    for (int c = w; c < cnt; c += 4) {
-        const int gi = cand_idx[(size_t)q * cap + c];
-        if (cs[c] < t2) {                                      // wave-uniform
-            if (lane == 0) { sc[c] = -INFINITY; ix[c] = -1; }
-            continue;
-        }
-        const float* g = Gf + (size_t)gi * D;
-        float s = 0.f;
-        for (int i = lane * 4; i < D; i += 256) {
-            const f32x4 a = *(const f32x4*)(qrow + i), b = *(const f32x4*)(g + i);
-            s = dot4_acc(s, a, b);
-        }
-        s = wave_sum(s);
-        if (eq >= 0 && exg[gi] == eq) s = -1e9f;
-        if (lane == 0) { sc[c] = s; ix[c] = gi; }
-    }
-    __syncthreads();
-    if (w != 0) return;
-    for (int r = 0; r < k; ++r) {
-        float best = -INFINITY; int bi = 0x7fffffff, bpos = -1;
-        for (int c = lane; c < cnt; c += 64) {
-            const float s = sc[c]; const int gi = ix[c];
-            if (gi >= 0 && (s > best || (s == best && gi < bi))) { best = s; bi = gi; bpos = c; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64); const int op = __shfl_xor(bpos, o, 64);
-            if (op >= 0 && (bpos < 0 || ob > best || (ob == best && oi < bi))) { best = ob; bi = oi; bpos = op; }
-        }
-        if (lane == 0) {
-            out_idx[(size_t)q * k + r] = bpos >= 0 ? bi : -1;
-            out_score[(size_t)q * k + r] = bpos >= 0 ? best : -INFINITY;
-        }
-        if (bpos >= 0 && (bpos & 63) == lane) ix[bpos] = -1;
-    }
-}
-
-// exact brute force for flagged queries, fp32 throughout: (1) scores of every gallery row, 64 workgroups per query;
-// (2) one workgroup per query extracts the k best by (score desc, index asc)
-// (slots != nullptr: the flagged queries are the list slots[1 .. slots[0]] (compacted on the device, slots[0] <= n_slots = capacity of the
-//  list); entry e uses scratch row e and is taken by workgroup row e % gridDim.y -- ANY number of flagged queries is resolved by the one
-//  launch, nothing is read back.  slots == nullptr: blockIdx.y is the query, flagged or not, and the scratch row is the query's.)
-__global__ __launch_bounds__(256) void brute_score_kernel(const float* __restrict__ Qf, const float* __restrict__ Gf, int Ng, int D,
-                                                          const int32_t* __restrict__ exq, const int32_t* __restrict__ exg, int k,
-                                                          const int32_t* __restrict__ out_idx, float* __restrict__ scratch,
-                                                          const int32_t* __restrict__ slots, int n_slots) {
-    __shared__ float qrow[1024];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int n_ent = slots ? min(slots[0], n_slots) : (int)gridDim.y;
-    for (int e = blockIdx.y; e < n_ent; e += gridDim.y) {
-        const int q = slots ? slots[1 + e] : e;
-        if (out_idx[(size_t)q * k] != -2) continue;                  // (workgroup-uniform)
-        __syncthreads();                                             // the previous entry's readers of qrow are done
-        for (int i = tid; i < D; i += 256) qrow[i] = Qf[(size_t)q * D + i];
-        __syncthreads();
-        float* sc = scratch + (size_t)e * Ng;
-        const int eq = exq ? exq[q] : -1;
-        for (int gi = blockIdx.x * 4 + w; gi < Ng; gi += gridDim.x * 4) {
-            const float* g = Gf + (size_t)gi * D;
-            float s = 0.f;
-            for (int i = lane * 4; i < D; i += 256) {
-                const f32x4 a = *(const f32x4*)(qrow + i), b = *(const f32x4*)(g + i);
-                s = dot4_acc(s, a, b);
-            }
-            s = wave_sum(s);
-            if (eq >= 0 && exg[gi] == eq) s = -1e9f;
-            if (lane == 0) sc[gi] = s;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void brute_select_kernel(int Ng, int k, int32_t* __restrict__ out_idx, float* __restrict__ out_score,
-                                                           float* __restrict__ scratch, const int32_t* __restrict__ slots, int n_slots) {
-    __shared__ float rbest[4]; __shared__ int ridx[4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int n_ent = slots ? min(slots[0], n_slots) : (int)gridDim.x;
-    for (int e = blockIdx.x; e < n_ent; e += gridDim.x) {
-        const int q = slots ? slots[1 + e] : e;
-        if (out_idx[(size_t)q * k] != -2) continue;                  // (workgroup-uniform)
-        float* sc = scratch + (size_t)e * Ng;
-        for (int r = 0; r < k; ++r) {
-            float best = -INFINITY; int bi = 0x7fffffff;
-            for (int gi = tid; gi < Ng; gi += 256) {
-                const float s = sc[gi];
-                if (s > best || (s == best && gi < bi)) { best = s; bi = gi; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                const float ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
-                if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-            }
-            if (lane == 0) { rbest[w] = best; ridx[w] = bi; }
-            __syncthreads();
-            if (tid == 0) {
-                for (int i = 1; i < 4; ++i)
-                    if (rbest[i] > rbest[0] || (rbest[i] == rbest[0] && ridx[i] < ridx[0])) { rbest[0] = rbest[i]; ridx[0] = ridx[i]; }
-                const bool ok = ridx[0] != 0x7fffffff;
-                out_idx[(size_t)q * k + r] = ok ? ridx[0] : -1;      // (r = 0 overwrites the -2 marker: tested once per entry, above)
-                out_score[(size_t)q * k + r] = ok ? rbest[0] : -INFINITY;
-                if (ok) sc[ridx[0]] = -INFINITY;
-            }
-            __syncthreads();
-        }
-    }
-}
-
-constexpr int SAMPLE = 8192;
-inline int cap_for(int Ng, int k) {
-    // expected survivors ~ k*Ng/SAMPLE (the sample's k-th best is about the (k*Ng/SAMPLE)-th best overall) times ~1.7 for the
-    // 2*eps safety margin; 6x head-room
-    long c = 6L * k * ((Ng + SAMPLE - 1) / SAMPLE) + 64;
-    if (c < 256) c = 256;
-    if (c > 8192) c = 8192;
-    return (int)c;
-}
-
-}  // namespace
-
-extern "C" int64_t reid_topk_ws_bytes(int32_t Nq, int32_t Ng, int32_t k) {
-    const int64_t cap = cap_for(Ng, k);
-    const int64_t ns = Ng < SAMPLE ? Ng : SAMPLE;
-    // thr[Nq] | cnt[Nq] | cand_idx[Nq*cap] | cand_score[Nq*cap] | dense[Nq*ns]
-    return (int64_t)Nq * 8 + (int64_t)Nq * cap * 8 + (int64_t)Nq * ns * 4 + 256;
-}
-
-namespace {
-// fast form of phase C for k <= STREAM_K_MAX (defined with the sorting helpers of the streaming section below)
-int launch_select_fast(const float* Qf, const float* Gf, int D, const int32_t* exq, const int32_t* exg, const int32_t* cand_idx,
-                       const float* cand_score, const int32_t* cand_cnt, int cap, int k, int32_t* out_idx, float* out_score, int Nq,
-                       hipStream_t s, int cnt_stride = 1);
-constexpr int SELECT_FAST_K_MAX = 32;
-
 template <int BM, int BN, int WM, int WN>
 int launch_filter(TopkParams p, hipStream_t s) {
     using C = Cfg<BM, BN, WM, WN>;
@@ -431,11 +281,10 @@ int launch_filter(TopkParams p, hipStream_t s) {
     REID_CHECK_LAUNCH("reid_cosine_topk(filter)");
     return REID_OK;
 }
-}  // namespace
 
 // ------------------------------------------------------------------------------------------ query-resident scan (<= 128 queries)
 // The reference ranks its queries one at a time or in small groups (tools/eval_mm_protocol.py:401-455); between the one-pass fp32 form
-// (<= 4 queries) and the tiled filter pass (hundreds of queries) the batched pipeline above re-stages the query panel for every gallery
+// (<= 4 queries) and the tiled filter pass (hundreds of queries) the tiled pipeline above re-stages the query panel for every gallery
 // tile and spends four launches on what is ONE pass over the 16-bit gallery.  Here (phases A and B of reid_cosine_topk in one launch):
 //   * one workgroup per compute unit; the gallery's 64-row chunks are dealt round-robin (chunk i * grid + b to workgroup b), so the chip
 //     reads one contiguous window at a time; each chunk is two 32-row tiles that pass through a ring of four LDS slots, three in flight
@@ -454,7 +303,6 @@ int launch_filter(TopkParams p, hipStream_t s) {
 //   * survivors wait in a 4-entry queue per lane in LDS; at the end the lanes reserve places per workgroup and query in LDS and ONE lane
 //     per query adds the workgroup's total to the query's counter (one counter per 128-byte line).  cand_idx / cand_score / cand_cnt are
 //     those of the filter pass (cand_cnt strided): phase C is unchanged.
-namespace {
 namespace scan {
 constexpr int KG = 16;            // bound groups held per query (k <= KG)
 constexpr int QCAP = 4;           // queued survivors per lane between flushes
@@ -477,11 +325,6 @@ struct ScanParams {
 #endif
 #define SCAN_STAMP(slot) SCAN_TRACE(slot, __builtin_amdgcn_s_memrealtime())
 
-// order-preserving unsigned key of a float; 0 is below every float
-__device__ __forceinline__ uint32_t key_of(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float key_value(uint32_t key) {
-    return key == 0 ? -INFINITY : __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
-}
 typedef __attribute__((address_space(3))) uint32_t* lds_u32ptr;
 // LDS-DMA from inline assembly, counted waits (run-time wait_vm(n) included): lds_tile.h
 
@@ -820,7 +663,211 @@ __global__ __launch_bounds__(512) void scan_filter_kernel(const ScanParams p) {
 unsigned long long* g_scan_trace = nullptr;
 #endif
 }  // namespace scan
+
+// ------------------------------------------------------------------------------------------ phase C
+// exact fp32 re-score of the candidates + top-k by (score desc, index asc)
+__global__ __launch_bounds__(256) void select_kernel(const float* __restrict__ Qf, const float* __restrict__ Gf, int D,
+                                                     const int32_t* __restrict__ exq, const int32_t* __restrict__ exg,
+                                                     const int32_t* __restrict__ cand_idx, const float* __restrict__ cand_score,
+                                                     const int32_t* __restrict__ cand_cnt, int cap, int k,
+                                                     int32_t* __restrict__ out_idx, float* __restrict__ out_score, int Nq) {
+    extern __shared__ char sm2[];
+    __shared__ float thr2;
+    volatile float* sc = (volatile float*)sm2;                  // [cap]
+    volatile int32_t* ix = (volatile int32_t*)(sc + cap);       // [cap]
+    float* qrow = (float*)((float*)sm2 + 2 * cap);         // [D]
+    const int q = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int cnt = cand_cnt[q];
+    if (cnt > cap) {                          // overflow: caller must take the exact fallback
+        if (tid == 0) flag_overflow(out_idx, out_score, q, k);
+        return;
+    }
+    for (int i = tid; i < D; i += 256) qrow[i] = Qf[(size_t)q * D + i];
+    // Second-level filter on the 16-bit-operand scores the filter pass saved: with a = k-th largest of them, a candidate below
+    // a - 2 eps cannot be in the exact top k (its true score is < a - eps <= the true score of each of the k candidates at or
+    // above a).  Only the survivors (about k + a few) pay the 2 KB fp32 gallery-row gather of the exact re-score; before,
+    // all ~250 candidates per query did (5 GB of gathers at 10k x 200k).
+    const float* cs = cand_score + (size_t)q * cap;
+    for (int c = tid; c < cnt; c += 256) sc[c] = cs[c];
+    __syncthreads();
+    if (w == 0) {
+        float kth = -INFINITY;
+        const int rounds = k < cnt ? k : cnt;
+        for (int r = 0; r < rounds; ++r) {
+            float best = -INFINITY; int bpos = -1;
+            for (int c = lane; c < cnt; c += 64) {
+                const float v = sc[c];
+                if (v > best || bpos < 0) { best = v; bpos = c; }
+            }
+            // (not wave_best: only the k-th VALUE is used, so equal values are not ordered by index; the positions only mark the entry taken)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ob = __shfl_xor(best, o, 64); const int op = __shfl_xor(bpos, o, 64);
+                if (op >= 0 && (bpos < 0 || ob > best)) { best = ob; bpos = op; }
+            }
+            kth = best;
+            if (bpos >= 0 && (bpos & 63) == lane) sc[bpos] = -INFINITY;
+        }
+        if (lane == 0) thr2 = cnt < k ? -INFINITY : kth - 2.f * EPS_BF16;
+    }
+    __syncthreads();
+    const float t2 = thr2;
+    const int eq = exq ? exq[q] : -1;
+    for (int c = w; c < cnt; c += 4) {
+        const int gi = cand_idx[(size_t)q * cap + c];
+        if (cs[c] < t2) {                                      // wave-uniform
+            if (lane == 0) { sc[c] = -INFINITY; ix[c] = -1; }
+            continue;
+        }
+        float s = row_dot(qrow, Gf + (size_t)gi * D, D, lane);
+        if (eq >= 0 && exg[gi] == eq) s = -1e9f;
+        if (lane == 0) { sc[c] = s; ix[c] = gi; }
+    }
+    __syncthreads();
+    if (w != 0) return;
+    for (int r = 0; r < k; ++r) {
+        float best = -INFINITY; int bi = 0x7fffffff, bpos = -1;
+        for (int c = lane; c < cnt; c += 64) {
+            const float s = sc[c]; const int gi = ix[c];
+            if (gi >= 0 && ranks_before(s, gi, best, bi)) { best = s; bi = gi; bpos = c; }
+        }
+        wave_best(best, bi, bpos);
+        if (lane == 0) {
+            out_idx[(size_t)q * k + r] = bpos >= 0 ? bi : -1;
+            out_score[(size_t)q * k + r] = bpos >= 0 ? best : -INFINITY;
+        }
+        if (bpos >= 0 && (bpos & 63) == lane) ix[bpos] = -1;
+    }
+}
+
+// Fast form for k <= SELECT_FAST_K_MAX (the window of wave_select_lds).
+// select_kernel walked ALL candidates of a query (~400 at 200k rows) four at a time, each step a dependent global load of the
+// candidate's index and a wave-uniform branch: ~100 steps of ~1 us = 105 us per call at 128 queries, the largest kernel of a
+// mid-size retrieval and ~0.5 ms of the 10k-query one (rocprofv3, r03).  Here every phase is one parallel sweep:
+//   1. candidate scores -> LDS; every thread keeps the two largest of its share, one wave takes the k-th largest of those 512
+//      values: a lower bound a of the k-th largest candidate score (exact unless three of the top k share a thread);
+//   2. survivors (score >= a - 2 eps: about k + a few) are compacted with one LDS atomic each, their gallery indices fetched
+//      in ONE round of loads;
+//   3. the waves re-score the survivors from the fp32 rows, four rows in flight per wave (row_dot's loop for four rows
+//      at once: same bits as everywhere);
+//   4. one wave sorts them by (score desc, index asc).
+// More than SELECT_SV survivors (thousands of exact ties): the query is flagged like a candidate-list overflow (exact fallback).
+constexpr int SELECT_SV = 512;
+constexpr int SELECT_FAST_K_MAX = 32;
+
+__global__ __launch_bounds__(256) void select_fast_kernel(const float* __restrict__ Qf, const float* __restrict__ Gf, int D,
+                                                          const int32_t* __restrict__ exq, const int32_t* __restrict__ exg,
+                                                          const int32_t* __restrict__ cand_idx, const float* __restrict__ cand_score,
+                                                          const int32_t* __restrict__ cand_cnt, int cap, int k,
+                                                          int32_t* __restrict__ out_idx, float* __restrict__ out_score, int Nq, int cnt_stride) {
+    extern __shared__ __attribute__((aligned(16))) char smf[];
+    float* sc = (float*)smf;                               // [cap] 16-bit-operand scores of the candidates
+    float* qrow = sc + ((cap + 3) & ~3);                   // [D], 16-byte aligned
+    float* t2s = qrow + D;                                 // [512] per-thread top two
+    int32_t* t2i = (int32_t*)(t2s + 512);                  // [512] (positions: distinct keys for the sort)
+    float* svs = (float*)(t2i + 512);                      // [SELECT_SV] survivors: exact scores
+    int32_t* svi = (int32_t*)(svs + SELECT_SV);            // [SELECT_SV] gallery indices
+    int32_t* svc = svi + SELECT_SV;                        // [SELECT_SV] candidate positions
+    __shared__ int nsv;
+    __shared__ float thr2;
+    const int q = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int cnt = cand_cnt[(size_t)q * cnt_stride];
+    if (cnt > cap) {                                       // overflow: caller takes the exact fallback
+        if (tid == 0) flag_overflow(out_idx, out_score, q, k);
+        return;
+    }
+    if (tid == 0) nsv = 0;
+    for (int i = tid * 4; i < D; i += 1024) *(f32x4*)(qrow + i) = *(const f32x4*)(Qf + (size_t)q * D + i);
+    const float* cs = cand_score + (size_t)q * cap;
+    float a0 = -INFINITY, a1 = -INFINITY;
+    for (int c = tid; c < cnt; c += 256) {
+        const float v = cs[c];
+        sc[c] = v;
+        const float hi = fmaxf(a0, v);
+        a1 = fmaxf(a1, fminf(a0, v));
+        a0 = hi;
+    }
+    t2s[tid] = a0; t2i[tid] = a0 > -INFINITY ? tid : -1;
+    t2s[256 + tid] = a1; t2i[256 + tid] = a1 > -INFINITY ? 256 + tid : -1;
+    __syncthreads();
+    if (w == 0) {
+        LaneList e;
+        const int real = wave_select_lds(t2s, t2i, 512, k, lane, e);
+        const float kth = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, e.s), real > 0 ? real - 1 : 0));
+        if (lane == 0) thr2 = (real < k || cnt < k) ? -INFINITY : kth - 2.f * EPS_BF16;
+    }
+    __syncthreads();
+    const float t2 = thr2;
+    for (int c = tid; c < cnt; c += 256) {
+        if (sc[c] >= t2) {
+            const int pos = atomicAdd(&nsv, 1);
+            if (pos < SELECT_SV) svc[pos] = c;
+        }
+    }
+    __syncthreads();
+    const int n = nsv;
+    if (n > SELECT_SV) {
+        if (tid == 0) flag_overflow(out_idx, out_score, q, k);
+        return;
+    }
+    for (int i = tid; i < n; i += 256) svi[i] = cand_idx[(size_t)q * cap + svc[i]];
+    __syncthreads();
+    const int eq = exq ? exq[q] : -1;
+    const int nd = D >> 8;                                 // 16-byte pieces per lane (D = 256 nd; D % 64 == 0: a ragged tail below)
+    for (int i0 = w * 4; i0 < n; i0 += 16) {               // four rows in flight per wave
+        float s[4] = {0.f, 0.f, 0.f, 0.f};
+        int gi[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) gi[u] = svi[i0 + u < n ? i0 + u : n - 1];
+        for (int j = 0; j <= nd; ++j) {
+            const int i = lane * 4 + j * 256;
+            if (i >= D) break;
+            const f32x4 a = *(const f32x4*)(qrow + i);
+            f32x4 b[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) b[u] = *(const f32x4*)(Gf + (size_t)gi[u] * D + i);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) s[u] = dot4_acc(s[u], a, b[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            float v = wave_sum(s[u]);
+            if (eq >= 0 && exg[gi[u]] == eq) v = -1e9f;
+            if (lane == 0 && i0 + u < n) svs[i0 + u] = v;
+        }
+    }
+    __syncthreads();
+    if (w != 0) return;
+    LaneList e;
+    const int real = wave_select_lds(svs, svi, n, k, lane, e);
+    if (lane < k) {
+        out_idx[(size_t)q * k + lane] = lane < real ? e.i : -1;
+        out_score[(size_t)q * k + lane] = lane < real ? e.s : -INFINITY;
+    }
+}
+
+int launch_select_fast(const float* Qf, const float* Gf, int D, const int32_t* exq, const int32_t* exg, const int32_t* cand_idx,
+                       const float* cand_score, const int32_t* cand_cnt, int cap, int k, int32_t* out_idx, float* out_score, int Nq,
+                       hipStream_t s, int cnt_stride = 1) {
+    const size_t lds = (size_t)((cap + 3) & ~3) * 4 + (size_t)D * 4 + 512 * 8 + (size_t)SELECT_SV * 12;
+    REID_MAX_LDS((select_fast_kernel), 8192 * 4 + 1024 * 4 + 512 * 8 + SELECT_SV * 12);
+    hipLaunchKernelGGL(select_fast_kernel, dim3(Nq), dim3(256), lds, s, Qf, Gf, D, exq, exg, cand_idx, cand_score, cand_cnt, cap, k, out_idx,
+                       out_score, Nq, cnt_stride);
+    REID_CHECK_LAUNCH("reid_cosine_topk(select)");
+    return REID_OK;
+}
+
 }  // namespace
+
+extern "C" int64_t reid_topk_ws_bytes(int32_t Nq, int32_t Ng, int32_t k) {
+    const int64_t cap = cap_for(Ng, k);
+    const int64_t ns = Ng < SAMPLE ? Ng : SAMPLE;
+    // thr[Nq] | cnt[Nq] | cand_idx[Nq*cap] | cand_score[Nq*cap] | dense[Nq*ns]
+    return (int64_t)Nq * 8 + (int64_t)Nq * cap * 8 + (int64_t)Nq * ns * 4 + 256;
+}
+
 #ifdef REID_SCAN_TRACE
 extern "C" void reid_debug_scan_trace(void* buf) { scan::g_scan_trace = (unsigned long long*)buf; }
 #endif
@@ -941,53 +988,9 @@ constexpr int SQ = 4;               // queries per pass over the gallery
 constexpr int STREAM_K_MAX = 32;    // a sort window of 64 lanes holds the best k plus at least as many new entries
 constexpr int STREAM_LIST_BUDGET = 16384;   // list entries per query over all workgroups (bounds the merge pass and the workspace)
 
-__device__ __forceinline__ bool ranks_before(float sa, int ia, float sb, int ib) { return sa > sb || (sa == sb && ia < ib); }
-
 inline int stream_groups(int k) {
     int g = STREAM_LIST_BUDGET / k;
     return g > 1024 ? 1024 : g;
-}
-
-// A wave's candidates of one query live in REGISTERS, one entry per lane: appending is two v_cndmask (no LDS, no shuffles).
-// When all 64 lanes are taken, the entries are ranked against each other (64 readlane broadcasts), moved to the lane of their
-// rank with one ds_permute -- i.e. sorted -- and everything behind rank k is dropped; the k-th entry becomes the bar a row has
-// to clear from then on.  Rows that clear the bar get rarer as the scan proceeds (~k ln(rows/k) in total).
-struct LaneList { float s; int i; };
-constexpr int INVALID_IDX0 = 0x7fffffc0;     // 64 distinct "after everything" keys for unused lanes
-
-// sort the wave's entries best-first across the lanes; entries of lanes >= cnt or with a negative index are void and end up
-// last.  Returns the number of real entries.
-__device__ __forceinline__ int lanelist_sort(LaneList& e, int cnt, int lane) {
-    const bool real = lane < cnt && e.i >= 0;
-    const float ms = real ? e.s : -INFINITY;
-    const int mi = real ? e.i : INVALID_IDX0 + lane;
-    int rank = 0;
-#pragma unroll
-    for (int m = 0; m < 64; ++m) {
-        const float os = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, ms), m));
-        const int oi = __builtin_amdgcn_readlane(mi, m);
-        rank += ranks_before(os, oi, ms, mi) ? 1 : 0;
-    }
-    e.s = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(rank * 4, __builtin_bit_cast(int, ms)));
-    e.i = __builtin_amdgcn_ds_permute(rank * 4, mi);
-    return __builtin_popcountll(__ballot(real));
-}
-
-// the k best of n entries in LDS (void entries: index < 0), sorted into lanes [0, k) of the calling wave; k <= STREAM_K_MAX <= 32:
-// a window of 64 lanes = the best k so far + up to 64 - k new entries per sort
-__device__ __forceinline__ int wave_select_lds(const float* sc, const int32_t* ix, int n, int k, int lane, LaneList& e) {
-    int have = n < 64 ? n : 64;
-    e = lane < have ? LaneList{sc[lane], ix[lane]} : LaneList{-INFINITY, -1};
-    int next = have;
-    int real = lanelist_sort(e, have, lane);
-    while (next < n) {
-        const int keep = real < k ? real : k;
-        const int take = (n - next) < (64 - keep) ? (n - next) : (64 - keep);
-        if (lane >= keep && lane < keep + take) e = LaneList{sc[next + lane - keep], ix[next + lane - keep]};
-        next += take;
-        real = lanelist_sort(e, keep + take, lane);
-    }
-    return real < k ? real : k;
 }
 
 __host__ __device__ inline int merge_survivor_cap(int n, int k) { const int c = 16 * k * k + 64; return c < n ? c : n; }
@@ -1105,8 +1108,8 @@ __global__ __launch_bounds__(256) void stream_topk_kernel(const float* __restric
     }
 }
 
-
-// (all entries in LDS: sc / ix [groups * k], lists sorted best-first; ssc / six: survivor region; *lcnt == 0 on entry; 256 threads)
+// The merge of `groups` lists of k entries, each sorted best-first, by a workgroup of 256 threads (see stream_merge_lds_kernel).  sc / ix
+// [groups * k]: the lists, in LDS or in global memory; ssc / six: survivor region in LDS; *lcnt == 0 and visible to all threads on entry.
 __device__ __forceinline__ void merge_lists_in_lds(const float* sc, const int32_t* ix, float* ssc, int32_t* six, int* lcnt, int groups, int k,
                                                    int32_t* __restrict__ out_idx, float* __restrict__ out_score, int tid, int lane) {
     // every wave derives the bar for itself (no cross-wave exchange)
@@ -1175,10 +1178,8 @@ __global__ __launch_bounds__(256) void stream_merge_lds_kernel(const float* __re
     merge_lists_in_lds(sc, ix, ssc, six, &lcnt, groups, k, out_idx + (size_t)q * k, out_score + (size_t)q * k, tid, lane);
 }
 
-// One workgroup per query merges the workgroups' lists, each sorted best-first.  The k-th best of 64 list heads (the best head
-// each lane sees) is a bar no result can rank behind, and only lists whose head clears it can hold entries that do: one pass
-// over the lists leaves a few dozen survivors in LDS (n in the worst case: the buffer holds them all), from which one wave
-// takes the k best.
+// The same merge with the lists left in global memory, for when they do not fit the LDS next to a survivor region: the LDS then
+// holds survivors only, n entries (all of them, in the worst case).
 __global__ __launch_bounds__(256) void stream_merge_kernel(const float* __restrict__ part_score, const int32_t* __restrict__ part_idx,
                                                            int groups, int k, int32_t* __restrict__ out_idx, float* __restrict__ out_score) {
     extern __shared__ char smm[];
@@ -1190,152 +1191,8 @@ __global__ __launch_bounds__(256) void stream_merge_kernel(const float* __restri
     const float* ps = part_score + (size_t)q * n;
     const int32_t* pi = part_idx + (size_t)q * n;
     if (tid == 0) lcnt = 0;
-    // every wave derives the bar for itself (no cross-wave exchange)
-    LaneList hb{-INFINITY, -1};
-    for (int g = lane; g < groups; g += 64) {
-        const float hs = ps[(size_t)g * k]; const int hi = pi[(size_t)g * k];
-        if (hi >= 0 && (hb.i < 0 || ranks_before(hs, hi, hb.s, hb.i))) hb = LaneList{hs, hi};
-    }
-    const int nh = lanelist_sort(hb, 64, lane);
-    float bar_s = -INFINITY; int bar_i = 0x7fffffff;                // fewer than k non-empty lanes: no bar
-    if (nh >= k) {
-        bar_s = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, hb.s), k - 1));
-        bar_i = __builtin_amdgcn_readlane(hb.i, k - 1);
-    }
     __syncthreads();
-    for (int g = tid; g < groups; g += 256) {
-        const float* ls = ps + (size_t)g * k; const int32_t* li = pi + (size_t)g * k;
-        for (int c = 0; c < k; ++c) {                               // lists are sorted: stop at the first entry behind the bar
-            const float s = ls[c]; const int gi = li[c];
-            if (gi < 0 || ranks_before(bar_s, bar_i, s, gi)) break;
-            const int pos = atomicAdd(&lcnt, 1);
-            sc[pos] = s; ix[pos] = gi;
-        }
-    }
-    __syncthreads();
-    if (tid >= 64) return;
-    LaneList e;
-    const int real = wave_select_lds(sc, ix, lcnt, k, lane, e);
-    if (lane < k) {
-        out_idx[(size_t)q * k + lane] = lane < real ? e.i : -1;
-        out_score[(size_t)q * k + lane] = lane < real ? e.s : -INFINITY;
-    }
-}
-
-// ------------------------------------------------------------------------------------------ phase C, fast form (k <= 32)
-// select_kernel walked ALL candidates of a query (~400 at 200k rows) four at a time, each step a dependent global load of the
-// candidate's index and a wave-uniform branch: ~100 steps of ~1 us = 105 us per call at 128 queries, the largest kernel of a
-// mid-size retrieval and ~0.5 ms of the 10k-query one (rocprofv3, r03).  Here every phase is one parallel sweep:
-//   1. candidate scores -> LDS; every thread keeps the two largest of its share, one wave takes the k-th largest of those 512
-//      values: a lower bound a of the k-th largest candidate score (exact unless three of the top k share a thread);
-//   2. survivors (score >= a - 2 eps: about k + a few) are compacted with one LDS atomic each, their gallery indices fetched
-//      in ONE round of loads;
-//   3. the waves re-score the survivors from the fp32 rows, four rows in flight per wave (dot4_acc order: same bits as everywhere);
-//   4. one wave sorts them by (score desc, index asc).
-// More than SELECT_SV survivors (thousands of exact ties): the query is flagged like a candidate-list overflow (exact fallback).
-constexpr int SELECT_SV = 512;
-
-__global__ __launch_bounds__(256) void select_fast_kernel(const float* __restrict__ Qf, const float* __restrict__ Gf, int D,
-                                                          const int32_t* __restrict__ exq, const int32_t* __restrict__ exg,
-                                                          const int32_t* __restrict__ cand_idx, const float* __restrict__ cand_score,
-                                                          const int32_t* __restrict__ cand_cnt, int cap, int k,
-                                                          int32_t* __restrict__ out_idx, float* __restrict__ out_score, int Nq, int cnt_stride) {
-    extern __shared__ __attribute__((aligned(16))) char smf[];
-    float* sc = (float*)smf;                               // [cap] 16-bit-operand scores of the candidates
-    float* qrow = sc + ((cap + 3) & ~3);                   // [D], 16-byte aligned
-    float* t2s = qrow + D;                                 // [512] per-thread top two
-    int32_t* t2i = (int32_t*)(t2s + 512);                  // [512] (positions: distinct keys for the sort)
-    float* svs = (float*)(t2i + 512);                      // [SELECT_SV] survivors: exact scores
-    int32_t* svi = (int32_t*)(svs + SELECT_SV);            // [SELECT_SV] gallery indices
-    int32_t* svc = svi + SELECT_SV;                        // [SELECT_SV] candidate positions
-    __shared__ int nsv;
-    __shared__ float thr2;
-    const int q = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int cnt = cand_cnt[(size_t)q * cnt_stride];
-    if (cnt > cap) {                                       // overflow: caller takes the exact fallback
-        if (tid == 0) { out_idx[(size_t)q * k] = -2; out_score[(size_t)q * k] = 0.f; }
-        return;
-    }
-    if (tid == 0) nsv = 0;
-    for (int i = tid * 4; i < D; i += 1024) *(f32x4*)(qrow + i) = *(const f32x4*)(Qf + (size_t)q * D + i);
-    const float* cs = cand_score + (size_t)q * cap;
-    float a0 = -INFINITY, a1 = -INFINITY;
-    for (int c = tid; c < cnt; c += 256) {
-        const float v = cs[c];
-        sc[c] = v;
-        const float hi = fmaxf(a0, v);
-        a1 = fmaxf(a1, fminf(a0, v));
-        a0 = hi;
-    }
-    t2s[tid] = a0; t2i[tid] = a0 > -INFINITY ? tid : -1;
-    t2s[256 + tid] = a1; t2i[256 + tid] = a1 > -INFINITY ? 256 + tid : -1;
-    __syncthreads();
-    if (w == 0) {
-        LaneList e;
-        const int real = wave_select_lds(t2s, t2i, 512, k, lane, e);
-        const float kth = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, e.s), real > 0 ? real - 1 : 0));
-        if (lane == 0) thr2 = (real < k || cnt < k) ? -INFINITY : kth - 2.f * EPS_BF16;
-    }
-    __syncthreads();
-    const float t2 = thr2;
-    for (int c = tid; c < cnt; c += 256) {
-        if (sc[c] >= t2) {
-            const int pos = atomicAdd(&nsv, 1);
-            if (pos < SELECT_SV) svc[pos] = c;
-        }
-    }
-    __syncthreads();
-    const int n = nsv;
-    if (n > SELECT_SV) {
-        if (tid == 0) { out_idx[(size_t)q * k] = -2; out_score[(size_t)q * k] = 0.f; }
-        return;
-    }
-    for (int i = tid; i < n; i += 256) svi[i] = cand_idx[(size_t)q * cap + svc[i]];
-    __syncthreads();
-    const int eq = exq ? exq[q] : -1;
-    const int nd = D >> 8;                                 // 16-byte pieces per lane (D = 256 nd; D % 64 == 0: a ragged tail below)
-    for (int i0 = w * 4; i0 < n; i0 += 16) {               // four rows in flight per wave
-        float s[4] = {0.f, 0.f, 0.f, 0.f};
-        int gi[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) gi[u] = svi[i0 + u < n ? i0 + u : n - 1];
-        for (int j = 0; j <= nd; ++j) {
-            const int i = lane * 4 + j * 256;
-            if (i >= D) break;
-            const f32x4 a = *(const f32x4*)(qrow + i);
-            f32x4 b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) b[u] = *(const f32x4*)(Gf + (size_t)gi[u] * D + i);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) s[u] = dot4_acc(s[u], a, b[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float v = wave_sum(s[u]);
-            if (eq >= 0 && exg[gi[u]] == eq) v = -1e9f;
-            if (lane == 0 && i0 + u < n) svs[i0 + u] = v;
-        }
-    }
-    __syncthreads();
-    if (w != 0) return;
-    LaneList e;
-    const int real = wave_select_lds(svs, svi, n, k, lane, e);
-    if (lane < k) {
-        out_idx[(size_t)q * k + lane] = lane < real ? e.i : -1;
-        out_score[(size_t)q * k + lane] = lane < real ? e.s : -INFINITY;
-    }
-}
-
-int launch_select_fast(const float* Qf, const float* Gf, int D, const int32_t* exq, const int32_t* exg, const int32_t* cand_idx,
-                       const float* cand_score, const int32_t* cand_cnt, int cap, int k, int32_t* out_idx, float* out_score, int Nq,
-                       hipStream_t s, int cnt_stride) {
-    const size_t lds = (size_t)((cap + 3) & ~3) * 4 + (size_t)D * 4 + 512 * 8 + (size_t)SELECT_SV * 12;
-    REID_MAX_LDS((select_fast_kernel), 8192 * 4 + 1024 * 4 + 512 * 8 + SELECT_SV * 12);
-    hipLaunchKernelGGL(select_fast_kernel, dim3(Nq), dim3(256), lds, s, Qf, Gf, D, exq, exg, cand_idx, cand_score, cand_cnt, cap, k, out_idx,
-                       out_score, Nq, cnt_stride);
-    REID_CHECK_LAUNCH("reid_cosine_topk(select)");
-    return REID_OK;
+    merge_lists_in_lds(ps, pi, sc, ix, &lcnt, groups, k, out_idx + (size_t)q * k, out_score + (size_t)q * k, tid, lane);
 }
 
 }  // namespace
@@ -1399,6 +1256,75 @@ extern "C" int reid_cosine_topk_stream(const float* Qf, const float* Gf, int32_t
     return REID_OK;
 }
 
+// ------------------------------------------------------------------------------------------ exact fallback
+namespace {
+// exact brute force for flagged queries, fp32 throughout: (1) scores of every gallery row, 64 workgroups per query;
+// (2) one workgroup per query extracts the k best by (score desc, index asc)
+// (slots != nullptr: the flagged queries are the list slots[1 .. slots[0]] (compacted on the device, slots[0] <= n_slots = capacity of the
+//  list); entry e uses scratch row e and is taken by workgroup row e % gridDim.y -- ANY number of flagged queries is resolved by the one
+//  launch, nothing is read back.  slots == nullptr: blockIdx.y is the query, flagged or not, and the scratch row is the query's.)
+__global__ __launch_bounds__(256) void brute_score_kernel(const float* __restrict__ Qf, const float* __restrict__ Gf, int Ng, int D,
+                                                          const int32_t* __restrict__ exq, const int32_t* __restrict__ exg, int k,
+                                                          const int32_t* __restrict__ out_idx, float* __restrict__ scratch,
+                                                          const int32_t* __restrict__ slots, int n_slots) {
+    __shared__ float qrow[1024];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int n_ent = slots ? min(slots[0], n_slots) : (int)gridDim.y;
+    for (int e = blockIdx.y; e < n_ent; e += gridDim.y) {
+        const int q = slots ? slots[1 + e] : e;
+        if (out_idx[(size_t)q * k] != -2) continue;                  // (workgroup-uniform)
+        __syncthreads();                                             // the previous entry's readers of qrow are done
+        for (int i = tid; i < D; i += 256) qrow[i] = Qf[(size_t)q * D + i];
+        __syncthreads();
+        float* sc = scratch + (size_t)e * Ng;
+        const int eq = exq ? exq[q] : -1;
+        for (int gi = blockIdx.x * 4 + w; gi < Ng; gi += gridDim.x * 4) {
+            float s = row_dot(qrow, Gf + (size_t)gi * D, D, lane);
+            if (eq >= 0 && exg[gi] == eq) s = -1e9f;
+            if (lane == 0) sc[gi] = s;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void brute_select_kernel(int Ng, int k, int32_t* __restrict__ out_idx, float* __restrict__ out_score,
+                                                           float* __restrict__ scratch, const int32_t* __restrict__ slots, int n_slots) {
+    __shared__ float rbest[4]; __shared__ int ridx[4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int n_ent = slots ? min(slots[0], n_slots) : (int)gridDim.x;
+    for (int e = blockIdx.x; e < n_ent; e += gridDim.x) {
+        const int q = slots ? slots[1 + e] : e;
+        if (out_idx[(size_t)q * k] != -2) continue;                  // (workgroup-uniform)
+        float* sc = scratch + (size_t)e * Ng;
+        for (int r = 0; r < k; ++r) {
+            float best = -INFINITY; int bi = 0x7fffffff;
+            for (int gi = tid; gi < Ng; gi += 256) {
+                const float s = sc[gi];
+                if (ranks_before(s, gi, best, bi)) { best = s; bi = gi; }
+            }
+            wave_best(best, bi);
+            if (lane == 0) { rbest[w] = best; ridx[w] = bi; }
+            __syncthreads();
+            if (tid == 0) {
+                for (int i = 1; i < 4; ++i)
+                    if (ranks_before(rbest[i], ridx[i], rbest[0], ridx[0])) { rbest[0] = rbest[i]; ridx[0] = ridx[i]; }
+                const bool ok = ridx[0] != 0x7fffffff;
+                out_idx[(size_t)q * k + r] = ok ? ridx[0] : -1;      // (r = 0 overwrites the -2 marker: tested once per entry, above)
+                out_score[(size_t)q * k + r] = ok ? rbest[0] : -INFINITY;
+                if (ok) sc[ridx[0]] = -INFINITY;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void flag_compact_kernel(const int32_t* __restrict__ out_idx, int Nq, int k, int32_t* __restrict__ slots, int n_slots) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= Nq || out_idx[(size_t)q * k] != -2) return;
+    const int pos = atomicAdd(slots, 1);
+    if (pos < n_slots) slots[1 + pos] = q;
+}
+}  // namespace
+
 /* Exact fp32 pass for queries flagged -2 by reid_cosine_topk (candidate overflow).  scratch: Nq*Ng floats. */
 extern "C" int reid_cosine_topk_exact(const float* Qf, const float* Gf, int32_t Nq, int32_t Ng, int32_t D, int32_t k,
                                       const int32_t* exclude_q, const int32_t* exclude_g, float* scratch, int32_t* out_idx,
@@ -1412,15 +1338,6 @@ extern "C" int reid_cosine_topk_exact(const float* Qf, const float* Gf, int32_t 
     REID_CHECK_LAUNCH("reid_cosine_topk_exact(select)");
     return REID_OK;
 }
-
-namespace {
-__global__ __launch_bounds__(256) void flag_compact_kernel(const int32_t* __restrict__ out_idx, int Nq, int k, int32_t* __restrict__ slots, int n_slots) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= Nq || out_idx[(size_t)q * k] != -2) return;
-    const int pos = atomicAdd(slots, 1);
-    if (pos < n_slots) slots[1 + pos] = q;
-}
-}  // namespace
 
 extern "C" int reid_cosine_topk_exact_slots(const float* Qf, const float* Gf, int32_t Nq, int32_t Ng, int32_t D, int32_t k,
                                             const int32_t* exclude_q, const int32_t* exclude_g, int32_t n_slots, int32_t* slots,

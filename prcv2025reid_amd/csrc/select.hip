@@ -13,9 +13,11 @@
 //   3. a bitonic sort of the buffer (at most 2048 (key, column) pairs) by (key descending, column ascending), then the k outputs.
 // The row is read two to four times (16-byte loads); after the first pass it comes from L2 / the Infinity Cache.  Integer LDS atomics
 // only: the slot a candidate lands in varies from run to run, the sorted output does not.
-#include "common.h"
+#include "rank.h"
 
 namespace {
+
+using namespace ranking;
 
 constexpr int SEL_BINS = 4096;      // histogram bins of one digit (12 bits; the last digit has 8)
 constexpr int SEL_CAP = 2048;       // candidate buffer, >= REID_ROWS_TOPK_MAX_K
@@ -28,15 +30,6 @@ struct SelectParams {
     int n, k;
 };
 
-// Order-preserving image of x + 0.0f; never 0 (the smallest, -inf, is 0x007fffff), so 0 marks a column that is no candidate.
-__device__ __forceinline__ uint32_t order_key(uint32_t b) {
-    if ((b & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;      // NaN
-    if ((b << 1) == 0) b = 0;                                      // -0 -> +0
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-__device__ __forceinline__ bool key_before(uint32_t ka, int ia, uint32_t kb, int ib) { return ka > kb || (ka == kb && ia < ib); }
-
 __global__ __launch_bounds__(256) void rows_topk_kernel(const SelectParams p) {
     __shared__ int hist[SEL_BINS];
     __shared__ uint32_t ckey[SEL_CAP];
@@ -48,17 +41,7 @@ __global__ __launch_bounds__(256) void rows_topk_kernel(const SelectParams p) {
     const int k = p.k;
     const uint32_t n = (uint32_t)p.n, nvec = (n + 3u) >> 2;         // the last 16 bytes may reach into the padding: ld % 4 == 0
     const uint32_t* row = (const uint32_t*)(p.S + (long long)q * p.ld);
-    int ex[4] = {-1, -1, -1, -1};
-    if (p.q_excl && p.g_img) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) ex[u] = p.q_excl[(long long)q * 4 + u];
-    }
-    const bool has_ex = (ex[0] & ex[1] & ex[2] & ex[3]) != -1;      // any id other than -1
-    auto excluded = [&](uint32_t j) {
-        if (!has_ex) return false;
-        const int g = p.g_img[j];
-        return g >= 0 && (g == ex[0] || g == ex[1] || g == ex[2] || g == ex[3]);
-    };
+    const Excluded4 excluded(p.q_excl, p.g_img, (long long)q);
     typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
     auto keys4 = [&](uint32_t t, uint32_t kk[4]) {                  // keys of columns 4t .. 4t + 3; 0 = past n or excluded
         const u32x4 v = *(const u32x4*)(row + 4 * (size_t)t);
@@ -164,22 +147,8 @@ __global__ __launch_bounds__(256) void rows_topk_kernel(const SelectParams p) {
                 if (kk[u] > prefix) take(kk[u], 4 * t + u);
                 mine += kk[u] == prefix;
             }
-            int incl = mine;                                        // this thread's equal entries and those of the lower lanes
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int v = __shfl_up(incl, o, 64);
-                if (lane >= o) incl += v;
-            }
-            if (lane == 63) wsum[it & 1][wave] = incl;
-            __syncthreads();            // one barrier per step: the next step writes the other half of wsum
-            int rank = found + incl - mine;
-            int total = 0;
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int x = wsum[it & 1][w];
-                total += x;
-                if (w < wave) rank += x;
-            }
+            int total;                  // one barrier per step: the next step writes the other half of wsum
+            int rank = found + block_excl_scan(mine, wsum[it & 1], total);   // this step's equal entries of the lower threads
 #pragma unroll
             for (int u = 0; u < 4; ++u)
                 if (kk[u] == prefix) {
@@ -204,20 +173,7 @@ __global__ __launch_bounds__(256) void rows_topk_kernel(const SelectParams p) {
     while (n2 < total) n2 <<= 1;
     for (int t = total + tid; t < n2; t += 256) { ckey[t] = 0u; cidx[t] = 0x7fffffff; }
     __syncthreads();
-    for (int kb = 2; kb <= n2; kb <<= 1)
-        for (int j = kb >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < n2; t += 256) {
-                const int u = t ^ j;
-                if (u > t) {
-                    const bool up = (t & kb) == 0;                  // ascending position = earlier rank
-                    const uint32_t ka = ckey[t], kc = ckey[u];
-                    const int ia = cidx[t], ic = cidx[u];
-                    const bool swap = up ? key_before(kc, ic, ka, ia) : key_before(ka, ia, kc, ic);
-                    if (swap) { ckey[t] = kc; ckey[u] = ka; cidx[t] = ic; cidx[u] = ia; }
-                }
-            }
-            __syncthreads();
-        }
+    lds_rank_sort(ckey, cidx, n2, tid);
     int32_t* oi = p.out_idx + (long long)q * k;
     uint32_t* os = p.out_score + (long long)q * k;
     for (int r = tid; r < k; r += 256) {

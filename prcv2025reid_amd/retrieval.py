@@ -57,7 +57,7 @@ class GalleryIndex:
             stream = ops.topk_stream_ok(Nq, Ng, Qf.shape[1], k) and (Nq == 1 or not ops.topk_scan_ok(Nq, Ng, Qf.shape[1], k))
         if stream:
             # a handful of queries: one pass over the fp32 gallery (the reference's per-query form), no host sync
-            need = ops.topk_stream_ws_bytes(k)             # (its own buffer, zero-filled once: it holds the arrival counter of the fused merge)
+            need = ops.topk_stream_ws_bytes(k)             # (its own buffer: the per-workgroup lists, which the scan kernel writes in full)
             if self._ws_stream is None or self._ws_stream.numel() != need:
                 self._ws_stream = torch.zeros(need, dtype=torch.uint8, device=Qf.device)
             idx = torch.empty(Nq, k, dtype=torch.int32, device=Qf.device)

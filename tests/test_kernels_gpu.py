@@ -1046,7 +1046,8 @@ def test_sdm(ops, P, N, Mg, D):
     assert ops.sdm_ws_floats(1, 8192, 8192, 512) < 3 * (8192 + 8192) * 512          # O((N + M) D): no N x M term
 
 
-@pytest.mark.parametrize('Nq,Ng,k', [(64, 4096, 10), (200, 20000, 10), (33, 777, 100), (130, 5000, 1)])
+# (40, 3000, 200): k > 128 takes kth_kernel (4 x 3000 floats = 48 KB of LDS) and, k > 32, select_kernel without the knob
+@pytest.mark.parametrize('Nq,Ng,k', [(64, 4096, 10), (200, 20000, 10), (33, 777, 100), (130, 5000, 1), (40, 3000, 200)])
 def test_cosine_topk_matches_fp32_stable_argsort(ops, Nq, Ng, k):
     g = torch.Generator(device='cuda').manual_seed(Nq + Ng)
     D = 512
@@ -1299,7 +1300,13 @@ def test_cosine_topk_query_resident_scan_without_a_bar(ops):
 
 
 @pytest.mark.parametrize('Nq,Ng,D,k', [(1, 5000, 512, 10), (3, 20001, 512, 10), (4, 777, 256, 32), (3, 13, 512, 10), (2, 4096, 1024, 1),
-                                        (4, 100000, 512, 10)])
+                                        (4, 100000, 512, 10),
+                                        # The merge runs from global memory (stream_merge_kernel) when all n = groups * k entries plus the
+                                        # min(16 k^2 + 64, n) survivors, 8 bytes each, exceed 160 KiB - 64 = 163776 B of LDS:
+                                        #   k = 32: groups = min(16384 / 32, ceil(8200 / 16)) = 512, n = 16384, 131072 + 131072 = 262144 B;
+                                        #   k = 16: groups = min(1024, ceil(16400 / 16)) = 1024, n = 16384, 131072 + 4160 * 8 = 164352 B,
+                                        #           just past the switch.
+                                        (2, 8200, 256, 32), (3, 16400, 512, 16)])
 def test_cosine_topk_stream_equals_batched_path(ops, Nq, Ng, D, k):
     """The one-pass form for a few queries (reference: one query at a time, eval_mm_protocol.py:401-455) returns the very
     lists and fp32 scores of the batched pipeline, ties and same-image exclusion included."""

@@ -5,7 +5,8 @@
 A tree (a checkout, or any directory above a csrc/ with .hip files) is compiled with build.py's flags plus
 --cuda-device-only -S into DIR/a or DIR/b (default: a temporary directory) as <file>.<flavor>.s; a directory that
 already holds such .s files is used as it is.  Prints `<file> <flavor>: N kernels, N identical`, every kernel that
-differs, and exits non-zero on any difference.
+differs, and exits non-zero on any difference.  Local labels carry the ordinal of their function in the file (.LBB<f>_<n>,
+.Lfunc_end<f>); the ordinal is dropped, so moving a kernel inside its file is no difference.
 """
 import argparse, glob, os, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
@@ -42,7 +43,8 @@ def kernels(path):
         if '.name' not in keys:                                                 # (an amdhsa.printf entry)
             continue
         body = re.search(rf'^{re.escape(keys[".name"])}:.*?^\.Lfunc_end\d+:', text, re.M | re.S).group(0)
-        lines = [l for l in (re.sub(r'\s*;.*', '', l).strip() for l in body.split('\n')) if l and '__hip_cuid_' not in l]
+        lines = [re.sub(r'\.L(BB|func_end)\d+', r'.L\1', l) for l in (re.sub(r'\s*;.*', '', l).strip() for l in body.split('\n'))
+                 if l and '__hip_cuid_' not in l]
         out[keys['.name']] = (lines, tuple(keys.get(k) for k in META))
     return out
 
