@@ -22,9 +22,10 @@ Text (reference: encode_text clip_backbone.py:288-313 -> HF CLIPTextModel): same
 key-padding attention, quick_gelu, EOS pooling; forward only (the tower carries no LoRA and is frozen
 by train.py:1418-1425).
 """
-from collections import OrderedDict
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
+import math
 import os
 
 import torch
@@ -32,10 +33,49 @@ import torch
 from . import _lib, ops
 
 LIN = ('qkv', 'out', 'fc1', 'fc2')
+# reference MERLinear -> (linear of this executor, its projection group within that linear)
+REF_LIN = {'attn.q_proj': ('qkv', 0), 'attn.k_proj': ('qkv', 1), 'attn.v_proj': ('qkv', 2), 'attn.out_proj': ('out', 0),
+           'mlp.fc1': ('fc1', 0), 'mlp.fc2': ('fc2', 0)}
 
 
 def round_up(a, b):
     return (a + b - 1) // b * b
+
+
+def grad_scale(amax):
+    """Power of two that brings ``amax``, the largest |entry| of a cotangent (a 0-dim device tensor), into [256, 512), clamped to
+    2^-20 .. 2^40 and chosen ON DEVICE: what a backward pass through 16-bit gradients multiplies in at its entry and divides out of
+    its results."""
+    return torch.exp2(torch.floor(torch.log2(512.0 / amax))).clamp(2.0 ** -20, 2.0 ** 40)
+
+
+class DenseGrads:
+    """Gradients of the dense tensors in one backward pass over ``rows`` rows, collected in ``out`` {reference key: fp32 gradient}."""
+
+    def __init__(self, rows, f32, b16):
+        self.out: Dict[str, torch.Tensor] = {}
+        self.f32 = f32
+        self.ones8 = torch.ones(rows, 8, **b16)
+
+    def wgrad(self, dY, X):                                 # dW [N, K] = dY^T X  (rows reduced on the matrix cores)
+        out = torch.empty(dY.shape[1], X.shape[1], **self.f32)
+        ops.gemm_tn(dY, X, out)
+        return out
+
+    def colsum(self, dY):                                   # db [N] = column sums of dY (same kernel against a block of ones)
+        out = torch.empty(dY.shape[1], 8, **self.f32)
+        ops.gemm_tn(dY, self.ones8[:dY.shape[0]], out)
+        return out[:, 0].contiguous()
+
+    def ln_pair(self, key, n):                              # zero-filled (dgamma, dbeta) of a LayerNorm: its backward kernel accumulates
+        self.out[key + '.weight'] = torch.zeros(n, **self.f32); self.out[key + '.bias'] = torch.zeros(n, **self.f32)
+        return self.out[key + '.weight'], self.out[key + '.bias']
+
+
+def wait_for(waiter, src):
+    """The one stream rule of the executor: everything enqueued on stream ``src`` so far completes before anything enqueued on
+    stream ``waiter`` from here on starts."""
+    waiter.wait_event(src.record_event())
 
 
 class LoraLayout:
@@ -79,52 +119,50 @@ class LoraLayout:
             rows.append([ob, rb, cb, e['pB'], e['pBT']])
         return torch.tensor(rows, dtype=torch.int64)
 
-    # reference key <-> arena slice ------------------------------------------------------------
-    def ref_slices(self, l: int, ref_lin: str, modality: str):
-        """(arena offset/shape info) of lora_A [r, K] and lora_B [N, r] of one reference adapter."""
-        nm, g = {'attn.q_proj': ('qkv', 0), 'attn.k_proj': ('qkv', 1), 'attn.v_proj': ('qkv', 2),
-                 'attn.out_proj': ('out', 0), 'mlp.fc1': ('fc1', 0), 'mlp.fc2': ('fc2', 0)}[ref_lin]
-        e = self.ent[(l, nm)]
-        mu = self.vmods.index(modality)
-        n_out = e['N'] // e['G']
-        return e, g, mu, n_out
+    @staticmethod
+    def _view(arena, off, shape):
+        return arena[off:off + math.prod(shape)].view(shape)
 
     def view_A(self, arena, l, nm):
-        o, shp = self.ent[(l, nm)]['A']
-        return arena[o:o + shp[0] * shp[1]].view(shp)
+        return self._view(arena, *self.ent[(l, nm)]['A'])
 
     def view_B(self, arena, l, nm):
-        o, shp = self.ent[(l, nm)]['B']
-        return arena[o:o + shp[0] * shp[1]].view(shp)
+        return self._view(arena, *self.ent[(l, nm)]['B'])
+
+    def ref_view(self, arena, key: str):
+        """Arena view of one reference adapter tensor ``clip_encoder.vision_layers.{l}.{lin}.loras.{m}.lora_{A|B}.weight``:
+        lora_A [r, K] is modality m's rows of its projection's block of A, lora_B [N / G, r] its columns of that projection's rows of B."""
+        parts = key.split('.')
+        l, (nm, g), mu = int(parts[2]), REF_LIN[parts[3] + '.' + parts[4]], self.vmods.index(parts[6])
+        r, Rp = self.r, self.Rp
+        if parts[7] == 'lora_A':
+            return self.view_A(arena, l, nm)[g * Rp + mu * r:g * Rp + (mu + 1) * r]
+        e = self.ent[(l, nm)]
+        n_out = e['N'] // e['G']
+        return self.view_B(arena, l, nm)[g * n_out:(g + 1) * n_out, mu * r:(mu + 1) * r]
 
     def weff(self, arena, l, nm, transposed=False):
         """Merged weight stack of one linear: [nmod, N, K] (forward operand) or [nmod, K, N] (dX operand)."""
         e = self.ent[(l, nm)]
         N, K = e['N'], e['K']
-        o = e['wET'] if transposed else e['wE']
-        return arena[o:o + self.nmod * N * K].view((self.nmod, K, N) if transposed else (self.nmod, N, K))
+        return self._view(arena, e['wET' if transposed else 'wE'], (self.nmod, K, N) if transposed else (self.nmod, N, K))
 
     def pk(self, pack, l, nm, which):
+        """16-bit pack of one adapter set: ``which`` = 'A' [G Rp, K], 'AT' [K, G Rp], 'B' [N, Rp] or 'BT' [Rp, N]."""
         e = self.ent[(l, nm)]
         G, K, N, Rp = e['G'], e['K'], e['N'], self.Rp
-        if which == 'A':
-            return pack[e['pA']:e['pA'] + G * Rp * K].view(G * Rp, K)
-        if which == 'AT':
-            return pack[e['pAT']:e['pAT'] + G * Rp * K].view(K, G * Rp)
-        if which == 'B':
-            return pack[e['pB']:e['pB'] + N * Rp].view(N, Rp)
-        return pack[e['pBT']:e['pBT'] + N * Rp].view(Rp, N)
+        return self._view(pack, e['p' + which], {'A': (G * Rp, K), 'AT': (K, G * Rp), 'B': (N, Rp), 'BT': (Rp, N)}[which])
 
 
 class Engine:
     """Owns packed bf16 weights and runs the encoders.  ``P`` maps reference names -> fp32 tensors."""
 
-    def __init__(self, arch: dict, P: Dict[str, torch.Tensor], lora_arena: torch.Tensor, device):
+    def __init__(self, arch: dict, P: Dict[str, torch.Tensor], lora_arena: torch.Tensor, device, layout: Optional[LoraLayout] = None):
         self.arch = arch
         self.P = P
         self.lora_arena = lora_arena
         self.dev = device
-        self.lay = LoraLayout(arch)
+        self.lay = layout if layout is not None else LoraLayout(arch)
         self.S = (arch['image_size'] // arch['patch_size']) ** 2 + 1
         self.scaling = arch['lora_alpha'] / arch['lora_rank']
         # f16 operands need the backward pass scaled into half's range (gradients of a mean loss are ~1e-6..1e-3, f16
@@ -146,15 +184,18 @@ class Engine:
         self._weff = None
         self._merge_table = None
         self._table = None
-        self._side = None
-        self._tside = None
+        # Streams beside the caller's, created on first use (_stream): pack_lora's two launches, the forward-only text tower, the
+        # adapter-gradient kernels.  An event field is set while that stream has work nobody has waited for yet.
+        self._pack = self._text = self._side = None
+        self._pack_event = None
+        self._text_pending = None                      # (features, event) of a text tower forked by text_forward_beside, until text_join
         self._consts = {}
         self._rng = torch.Generator(device=device)
         self._rng.manual_seed(777)
         self.pending_drop_scales = None
-        self.text_backward_ready = True
         self._text_packed = None
         self.overlap_tn = os.environ.get('REID_TN_STREAM', '1') != '0'
+        self.overlap_text = os.environ.get('REID_TEXT_STREAM', '1') != '0'
         self.W = {}
         self.W32 = {}
 
@@ -169,21 +210,33 @@ class Engine:
             self._consts[key] = t
         return t
 
-    def _text_stream(self):
-        if self._tside is None:
-            self._tside = torch.cuda.Stream(self.dev)
-        return self._tside
+    def _stream(self, field):
+        """The stream kept in ``field`` ('_pack', '_text' or '_side').  The adapter-gradient stream (_side) has the LOWEST priority,
+        so its workgroups are dispatched only where the main stream has none pending (the partly filled last round of a GEMM, gaps
+        between kernels) instead of taking compute units from it."""
+        if getattr(self, field) is None:
+            least = 0
+            if field == '_side':
+                try:
+                    least, _greatest = torch.cuda.Stream.priority_range()
+                except Exception:
+                    pass
+            setattr(self, field, torch.cuda.Stream(self.dev, priority=int(least)))
+        return getattr(self, field)
 
     def _side_stream(self):
-        """Stream of the adapter-gradient kernels: LOWEST priority, so its workgroups are dispatched only where the main stream has
-        none pending (the partly filled last round of a GEMM, gaps between kernels) instead of taking compute units from it."""
-        if self._side is None:
-            try:
-                least, _greatest = torch.cuda.Stream.priority_range()
-            except Exception:
-                least = 0
-            self._side = torch.cuda.Stream(self.dev, priority=int(least))
-        return self._side
+        return self._stream('_side')
+
+    def _kw(self):
+        """torch.empty keywords of an fp32 and of a 16-bit tensor of the current flavor on this device."""
+        return dict(dtype=torch.float32, device=self.dev), dict(dtype=_lib.t16(), device=self.dev)
+
+    def _rows(self, img_mod, M, rpi, rg):
+        """One row set of a packed batch: all ``M`` = n_img * S rows (``rpi`` = S rows per image), or the n_img class rows (1 per image)
+        that the out-projection and MLP of the LAST block run on.  ``rg``: row groups of the merged-weight GEMMs; ``mask``: what the
+        adapter-side GEMMs (T = x A^T, U = dY B) need to keep each row's own modality and scale by alpha / r."""
+        return SimpleNamespace(M=M, rpi=rpi, rg=rg, img_mod=img_mod,
+                               mask=dict(img_mod=img_mod, mask_r=self.lay.r, mask_period=self.lay.Rp, rows_per_img=rpi, alpha=self.scaling))
 
     # ------------------------------------------------------------------------------- packing
     def _bf(self, t):
@@ -248,31 +301,24 @@ class Engine:
         self.wait_packed()                                   # (a previous pack nobody consumed must not overlap writers of the arena)
         # Both launches go to a stream of their own, forked from the caller's: the merge (~1.7 GB of traffic) then runs beside the
         # patch embedding and the text tower instead of in front of them; the first vision block waits for it (wait_packed).
-        main = torch.cuda.current_stream(self.dev)
-        ps = self._pack_stream()
-        ev = torch.cuda.Event(); ev.record(main); ps.wait_event(ev)
+        ps = self._stream('_pack')
+        wait_for(ps, torch.cuda.current_stream(self.dev))
         if self._side is not None:
             # deferred T = x A^T launches of a forward whose backward never ran may still be reading the 16-bit adapter pack
-            ev_s = torch.cuda.Event(); ev_s.record(self._side); ps.wait_event(ev_s)
+            wait_for(ps, self._side)
         with torch.cuda.stream(ps):
             ops.pack_bf16_table(arena, self._lora_pack, self._table, self._table.shape[0])
             ops.merge_lora_table(self._merge_table, self._merge_table.shape[0], self._merge_tiles, arena, self._weff, lay.Rp, lay.r,
                                  lay.nmod, self.scaling)
-            self._pack_event = torch.cuda.Event(); self._pack_event.record(ps)
+            self._pack_event = ps.record_event()
 
     def wait_packed(self):
         """Make the current stream (and the adapter-gradient side stream) wait for the last pack_lora."""
-        ev = getattr(self, '_pack_event', None)
-        if ev is not None:
-            torch.cuda.current_stream(self.dev).wait_event(ev)
+        if self._pack_event is not None:
+            torch.cuda.current_stream(self.dev).wait_event(self._pack_event)
             if self._side is not None:
-                self._side.wait_event(ev)
+                self._side.wait_event(self._pack_event)
             self._pack_event = None
-
-    def _pack_stream(self):
-        if getattr(self, '_pstream', None) is None:
-            self._pstream = torch.cuda.Stream(self.dev)
-        return self._pstream
 
     def refresh(self):
         dv = sum(p._version for k, p in self.P.items() if k.startswith('clip_encoder.') and p is not self.lora_arena)
@@ -300,7 +346,7 @@ class Engine:
         ``drop_scales``: per layer (s_attn, s_mlp) per-image DropPath factors or None."""
         a, P, W, lay = self.arch, self.P, self.W, self.lay
         dev = self.dev
-        S, d, ff, Rp, r = self.S, lay.d, lay.ff, lay.Rp, lay.r
+        S, d, ff, Rp = self.S, lay.d, lay.ff, lay.Rp
         heads = a['vision_heads']
         n_img = sum(g[1].shape[0] for g in groups)
         M = n_img * S
@@ -309,7 +355,7 @@ class Engine:
         for mu, img in groups:
             mods += [mu] * img.shape[0]
         img_mod = self._const(('img_mod', tuple(mods)), lambda: torch.tensor(mods, dtype=torch.int32))
-        f32 = dict(dtype=torch.float32, device=dev); b16 = dict(dtype=_lib.t16(), device=dev)
+        f32, b16 = self._kw()
         x = torch.empty(M, d, **f32)
         pos = P[ce + 'vision_pos_embed']
         start = 0
@@ -324,7 +370,6 @@ class Engine:
                      c_group=S - 1, c_group_stride=S, c_row_off=1)
             start += n
         ops.cls_rows(P[ce + 'cls_token'].view(-1), pos[0], x, n_img, S)
-        mk = dict(img_mod=img_mod, mask_r=r, mask_period=Rp, rows_per_img=S, alpha=self.scaling)
         pk = lambda l, nm, w: lay.pk(self._lora_pack, l, nm, w)
         we = lambda l, nm: lay.weff(self._weff, l, nm)
         # row groups of the merged-weight GEMMs: images are packed modality by modality
@@ -333,8 +378,8 @@ class Engine:
         ends = [0]
         for c in counts:
             ends.append(ends[-1] + c)
-        rg_full = ([e * S for e in ends[1:]], mus)
-        rg_cls = (ends[1:], mus)
+        full = self._rows(img_mod, M, S, ([e * S for e in ends[1:]], mus))
+        cls = self._rows(img_mod, n_img, 1, (ends[1:], mus))
         saved = []
         buf = {}
         idxl = self._const(('cls_idx64', n_img, S), lambda: torch.arange(n_img, dtype=torch.int64) * S)
@@ -366,7 +411,7 @@ class Engine:
         def flush_lora_down():
             if not deferred:
                 return
-            ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
+            wait_for(side, main)
             with torch.cuda.stream(side):
                 for xin_, A_, T_, kw in deferred:
                     ops.gemm(xin_, A_, T_, **kw)
@@ -389,21 +434,17 @@ class Engine:
                 h, mean1, rstd1 = nxt
                 nxt = None
             qkv = new('qkv', (M, 3 * d), b16)
-            ops.gemm(h, we(l, 'qkv'), qkv, bias=W[('v', l, 'bqkv')], row_groups=rg_full)
+            ops.gemm(h, we(l, 'qkv'), qkv, bias=W[('v', l, 'bqkv')], row_groups=full.rg)
             last = l == L - 1
             o = new('o', (M, d), b16); lse = new('lse', (n_img, heads, S), f32)
             ops.attn_fwd(qkv, o, lse, n_img, S, heads, q_tiles=1 if last else 0)
             sa, sm_ = (None, None) if drop_scales is None else drop_scales[l]
-            if last:
-                # Only the class-token row of the last block's output is ever used (clip_backbone.py:281: x[:, 0]), and rows do
-                # not mix after the attention core: out-projection, LN2 and the MLP of the LAST block run on the n_img class rows
-                # instead of all n_img*197 (same function; the reference computes and discards the other 196/197).
-                Mr, rpi, rg = n_img, 1, rg_cls
-                xin = x.index_select(0, idxl); oin = o.index_select(0, idxl)
-            else:
-                Mr, rpi, rg = M, S, rg_full
-                xin, oin = x, o
-            mkr = dict(img_mod=img_mod, mask_r=r, mask_period=Rp, rows_per_img=rpi, alpha=self.scaling)
+            # Only the class-token row of the last block's output is ever used (clip_backbone.py:281: x[:, 0]), and rows do
+            # not mix after the attention core: out-projection, LN2 and the MLP of the LAST block run on the n_img class rows
+            # instead of all n_img*197 (same function; the reference computes and discards the other 196/197).
+            rows = cls if last else full
+            xin, oin = (x.index_select(0, idxl), o.index_select(0, idxl)) if last else (x, o)
+            Mr, rpi, rg = rows.M, rows.rpi, rows.rg
             xm = new('xm', (Mr, d), f32)
             h2 = new('h2', (Mr, d), b16); mean2 = new('m2', (Mr,), f32); rstd2 = new('r2', (Mr,), f32)
             if not last:
@@ -427,8 +468,8 @@ class Engine:
             if save:
                 T = torch.empty(M, 3 * Rp, **b16); To = torch.empty(Mr, Rp, **b16)
                 T1 = torch.empty(Mr, Rp, **b16); T2 = torch.empty(Mr, Rp, **b16)
-                lora_down([(h, pk(l, 'qkv', 'A'), T, mk), (oin, pk(l, 'out', 'A'), To, mkr), (h2, pk(l, 'fc1', 'A'), T1, mkr),
-                           (g, pk(l, 'fc2', 'A'), T2, mkr)])
+                lora_down([(h, pk(l, 'qkv', 'A'), T, full.mask), (oin, pk(l, 'out', 'A'), To, rows.mask),
+                           (h2, pk(l, 'fc1', 'A'), T1, rows.mask), (g, pk(l, 'fc2', 'A'), T2, rows.mask)])
             xn = torch.empty(Mr, d, **f32) if save else new('xn' + str(l & 1) + ('c' if last else ''), (Mr, d), f32)
             if not last:
                 np_ = f'{ce}vision_layers.{l + 1}.'
@@ -450,8 +491,8 @@ class Engine:
         feats = torch.empty(n_img, a['fusion_dim'], **f32)
         ops.gemm(cls_h, W['vproj'], feats)
         flush_lora_down()
-        state = dict(layers=saved, x_final=x, idxl=idxl, mf=mf, rf=rf, img_mod=img_mod, n_img=n_img, cls_h=cls_h,
-                     groups=groups, rg_full=rg_full, rg_cls=rg_cls) if save else None
+        state = dict(layers=saved, x_final=x, idxl=idxl, mf=mf, rf=rf, n_img=n_img, cls_h=cls_h, groups=groups,
+                     rows=(full, cls)) if save else None
         return feats, state
 
     # ------------------------------------------------------------------------------- vision backward
@@ -473,16 +514,13 @@ class Engine:
         heads = a['vision_heads']
         n_img = st['n_img']; M = n_img * S
         ce = 'clip_encoder.'
-        f32 = dict(dtype=torch.float32, device=dev); b16 = dict(dtype=_lib.t16(), device=dev)
+        f32, b16 = self._kw()
         grad = torch.zeros(lay.size, **f32)               # the dA/dB GEMMs accumulate (beta=1): no per-call fill
-        mk = dict(img_mod=st['img_mod'], mask_r=r, mask_period=Rp, rows_per_img=S, alpha=self.scaling)
         pk = lambda l, nm, w: lay.pk(self._lora_pack, l, nm, w)
-        gA = lambda l, nm: lay.view_A(grad, l, nm)
-        gB = lambda l, nm: lay.view_B(grad, l, nm)
         scale_t = None
         if self.loss_scaling or self.dx_half:
             amax = dfeat.abs().amax().clamp_min(1e-30)
-            scale_t = torch.exp2(torch.floor(torch.log2(512.0 / amax))).clamp(2.0 ** -20, 2.0 ** 40)
+            scale_t = grad_scale(amax)
             dfeat = dfeat * scale_t
         dfb = ops.to_bf16(dfeat)
         gx = dict(dtype=torch.float16 if self.dx_half else torch.float32, device=dev)      # the residual-stream gradient
@@ -496,28 +534,12 @@ class Engine:
         # class rows only until the last block's attention (see vision_forward)
         dx = torch.empty(M, d, **gx); dxb = torch.empty(M, d, **b16)            # first written (all rows) by the last block's LN1 backward
         dx_c = torch.empty(n_img, d, **gx); dxb_c = torch.empty(n_img, d, **b16)
-        dense = {} if want_dense else None
-        ones8 = torch.ones(M, 8, **b16) if want_dense else None
-
-        def wgrad(dY, X):                                   # dW [N, K] = dY^T X  (rows reduced on the matrix cores)
-            out = torch.empty(dY.shape[1], X.shape[1], **f32)
-            ops.gemm_tn(dY, X, out)
-            return out
-
-        def colsum(dY):                                     # db [N] = column sums of dY (same kernel against a block of ones)
-            out = torch.empty(dY.shape[1], 8, **f32)
-            ops.gemm_tn(dY, ones8[:dY.shape[0]], out)
-            return out[:, 0].contiguous()
-
-        def ln_grads(key):
-            if not want_dense:
-                return None, None
-            dense[key + '.weight'] = torch.zeros(d, **f32); dense[key + '.bias'] = torch.zeros(d, **f32)
-            return dense[key + '.weight'], dense[key + '.bias']
-
+        dg = DenseGrads(M, f32, b16) if want_dense else None
+        dense = dg.out if want_dense else None
+        ln_pair = dg.ln_pair if want_dense else (lambda key, n: (None, None))
         if want_dense:
-            dense[ce + 'vision_proj.weight'] = wgrad(dfb, st['cls_h'])
-        dgf, dbf = ln_grads(ce + 'vision_ln_final')
+            dense[ce + 'vision_proj.weight'] = dg.wgrad(dfb, st['cls_h'])
+        dgf, dbf = ln_pair(ce + 'vision_ln_final', d)
         # dxb always holds the gradient ENTERING the next residual branch: dx times that branch's DropPath factor
         ops.layernorm_bwd(dcls, st['x_final'], P[ce + 'vision_ln_final.weight'], st['mf'], st['rf'], dx_c, dx_bf16=dxb_c,
                           bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=1, dgamma=dgf, dbeta=dbf, overflow=ovf)
@@ -534,128 +556,113 @@ class Engine:
         delta = torch.empty(n_img, heads, S, **f32)
         dxm = torch.empty(M, d, **gx)
         weT = lambda l, nm: lay.weff(self._weff, l, nm, transposed=True)
-        rg_full, rg_cls = st['rg_full'], st['rg_cls']
         main = torch.cuda.current_stream(dev)
         side = self._side_stream() if self.overlap_tn else None
         side_done = {}
         L = a['vision_layers']
         # the gradient ENTERING layer l (dx times that layer's MLP DropPath factor, 16-bit) lives in dxb2[l & 1]
         u_part = torch.empty(M, Rp, **f32)                  # fp32 partial U of fc1's four column blocks (side stream only)
-        # Class-row scratch of the pruned last block.  Read and written by the SIDE stream (lora_grads) long after the main stream has
+        # The scratch of a block's MLP / out-projection, on all rows and on the class rows: a row set of the forward (_rows) plus the
+        # incoming gradient gy / gyb, the rank-r cotangents U*, and du, dh, do, dxm, dxmb.  gyb, du and dxmb are pairs indexed by l & 1
+        # (above); only the last block runs on the class rows, so there both entries of a pair are one tensor.
+        rows_full, rows_cls = st['rows']
+        full = SimpleNamespace(**vars(rows_full), gy=dx, gyb=dxb2, U2=U2, U1=U1, Uo=Uo, du=du2, dh=dh, do=do, dxm=dxm, dxmb=dxmb2)
+        # Class-row scratch of the pruned last block.  Read and written by the SIDE stream (adapter_grads) long after the main stream has
         # moved on, so it must not be released inside the loop: a block freed by the main stream is handed to the main stream's next
-        # allocation at once (wgrad / colsum / ln_grads with want_dense), whatever other streams still have pending on it (r03 found
+        # allocation at once (wgrad / colsum / ln_pair with want_dense), whatever other streams still have pending on it (r03 found
         # this hazard for forward-only calls).  Allocated here, these tensors die when this function returns -- after the join of the
         # side stream into the main stream below has been enqueued, which orders every later main-stream use behind the side kernels.
-        cls_tmp = dict(U2=torch.empty(n_img, Rp, **b16), U1=torch.empty(n_img, Rp, **b16), Uo=torch.empty(n_img, Rp, **b16),
-                       du=torch.empty(n_img, ff, **b16), dh=torch.empty(n_img, d, **b16), do=torch.empty(n_img, d, **b16),
-                       dxm=torch.empty(n_img, d, **gx), dxmb=torch.empty(n_img, d, **b16))
+        cls = SimpleNamespace(**vars(rows_cls), gy=dx_c, gyb=[dxb_c] * 2,
+                              U2=torch.empty(n_img, Rp, **b16), U1=torch.empty(n_img, Rp, **b16), Uo=torch.empty(n_img, Rp, **b16),
+                              du=[torch.empty(n_img, ff, **b16)] * 2, dh=torch.empty(n_img, d, **b16), do=torch.empty(n_img, d, **b16),
+                              dxm=torch.empty(n_img, d, **gx), dxmb=[torch.empty(n_img, d, **b16)] * 2)
 
-        def lora_grads(l, calls):
-            """Adapter gradients of one linear on the side stream: U = mask(dY . Bcat) * (alpha/r), dB += dY^T T, dA += U^T X.
-            ``calls`` = [(dY, BT, U, mask kwargs, [(X operand, Y operand, out), ...])]."""
-            def run():
-                for dY, BT, U, kw, tns in calls:
-                    # tns[0] = (dY, T, dB): with N = 768 output columns (every linear but fc1) U and dB come out of ONE pass over dY
-                    same = tns[0][0].data_ptr() == dY.data_ptr() and tns[0][0].shape == dY.shape and tns[0][0].stride() == dY.stride()
-                    if same and ops.lora_bwd_fused_ok(dY.shape[1], tns[0][1].shape[1], kw['rows_per_img'], kw['mask_r']):
-                        ops.lora_bwd_fused(dY, tns[0][1], BT, U, tns[0][2], kw['img_mod'], kw['rows_per_img'], kw['mask_r'], kw['alpha'],
-                                           u_partial=u_part[:dY.shape[0]] if dY.shape[1] > 768 else None)
-                        rest = tns[1:]
-                    else:
-                        ops.gemm(dY, BT, U, **kw)
-                        rest = tns
-                    for xx, yy, out in rest:
-                        # (xx, yy, out) = (U [M, G Rp], the linear's input X [M, K], dA [G Rp, K]): one pass over X, one image per workgroup
-                        ng = xx.shape[1] // Rp
-                        if xx.shape[1] == ng * Rp and out.shape[0] == ng * Rp and \
-                                ops.lora_da_fused_ok(yy.shape[1], Rp, kw['rows_per_img'], kw['mask_r'], ng):
-                            ops.lora_da_fused(yy, xx, out, kw['img_mod'], kw['rows_per_img'], kw['mask_r'], n_groups=ng)
-                        else:
-                            ops.gemm_tn(xx, yy, out, beta=1.0)
-            if side is None:
-                run()
-                return
-            ev = torch.cuda.Event(); ev.record(main); side.wait_event(ev)
-            with torch.cuda.stream(side):
-                run()
-
-        def layer_done(l):
+        def adapter_grads(l, nm, dY, X, T, U, rows):
+            """Adapter gradients of linear ``nm`` of layer ``l`` on the side stream, from its cotangent dY [M, N], its saved input X [M, K]
+            and the saved T = mask(X . Acat^T) * (alpha/r) [M, G Rp]; ``U`` [M, G Rp] is scratch.  Per projection (G = 3 column blocks
+            of q|k|v, else 1): U = mask(dY . Bcat) * (alpha/r) and dB += dY^T T -- out of ONE pass over dY where reid_lora_bwd_fused takes
+            the shape (768 output columns per launch; fc1's 3072 as four column blocks through ``u_part``), else a masked GEMM and a
+            reduce-over-rows GEMM.  Then dA += U^T X for all G groups: one pass over X, one image per workgroup (reid_lora_da_fused),
+            else a reduce-over-rows GEMM."""
             if side is not None:
-                ev = torch.cuda.Event(); ev.record(side); side_done[l] = ev
-
-        def wait_side(l):
-            ev = side_done.pop(l, None)
-            if ev is not None:
-                main.wait_event(ev)
+                wait_for(side, main)
+            with torch.cuda.stream(side):                   # (no stream: in line on the current one)
+                BT, dB = pk(l, nm, 'BT'), lay.view_B(grad, l, nm)
+                G = lay.ent[(l, nm)]['G']
+                n = dY.shape[1] // G
+                for g in range(G):
+                    dYg, Tg, BTg, Ug, dBg = dY[:, g * n:(g + 1) * n], T[:, g * Rp:(g + 1) * Rp], BT[:, g * n:(g + 1) * n], \
+                        U[:, g * Rp:(g + 1) * Rp], dB[g * n:(g + 1) * n]
+                    if ops.lora_bwd_fused_ok(n, Rp, rows.rpi, r):
+                        ops.lora_bwd_fused(dYg, Tg, BTg, Ug, dBg, rows.img_mod, rows.rpi, r, self.scaling,
+                                           u_partial=u_part[:dY.shape[0]] if n > 768 else None)
+                    else:
+                        ops.gemm(dYg, BTg, Ug, **rows.mask)
+                        ops.gemm_tn(dYg, Tg, dBg, beta=1.0)
+                if ops.lora_da_fused_ok(X.shape[1], Rp, rows.rpi, r, G):
+                    ops.lora_da_fused(X, U, lay.view_A(grad, l, nm), rows.img_mod, rows.rpi, r, n_groups=G)
+                else:
+                    ops.gemm_tn(U, X, lay.view_A(grad, l, nm), beta=1.0)
 
         for l in reversed(range(L)):
             s = st['layers'][l]
             lp = f'{ce}vision_layers.{l}.'
             b = l & 1
-            c = bool(s.get('cls'))                          # this block's MLP / out-projection ran on the class rows only
-            if c:
-                Mr, rg = n_img, rg_cls
-                mkr = dict(img_mod=st['img_mod'], mask_r=r, mask_period=Rp, rows_per_img=1, alpha=self.scaling)
-                gy, gyb = dx_c, dxb_c
-                U2r, U1r, Uor, dur, dhr, dor, dxmr, dxmbr = (cls_tmp[k_] for k_ in ('U2', 'U1', 'Uo', 'du', 'dh', 'do', 'dxm', 'dxmb'))
-                rpi = 1
-            else:
-                Mr, mkr, gy, gyb, rg = M, mk, dx, dxb2[b], rg_full
-                U2r, U1r, Uor, dur, dhr, dor, dxmr, dxmbr, rpi = U2, U1, Uo, du2[b], dh, do, dxm, dxmb2[b], S
+            c = s['cls']                                    # this block's MLP / out-projection ran on the class rows only
+            sc = cls if c else full
+            gy, gyb, du, dxmb, rg = sc.gy, sc.gyb[b], sc.du[b], sc.dxmb[b], sc.rg
             dqkv = dqkv2[b]
             # ---- fc2:  x_next = xm + g W2_eff^T + b2
-            lora_grads(l, [(gyb, pk(l, 'fc2', 'BT'), U2r, mkr, [(gyb, s['T2'], gB(l, 'fc2')), (U2r, s['g'], gA(l, 'fc2'))])])
-            ops.gemm(gyb, weT(l, 'fc2'), dur, act='mul_aux', aux=s['u'], row_groups=rg)
+            adapter_grads(l, 'fc2', gyb, s['g'], s['T2'], sc.U2, sc)
+            ops.gemm(gyb, weT(l, 'fc2'), du, act='mul_aux', aux=s['u'], row_groups=rg)
             if want_dense:
-                dense[lp + 'mlp.fc2.shared_linear.weight'] = wgrad(gyb, s['g'])
-                dense[lp + 'mlp.fc2.shared_linear.bias'] = colsum(gyb)
+                dense[lp + 'mlp.fc2.shared_linear.weight'] = dg.wgrad(gyb, s['g'])
+                dense[lp + 'mlp.fc2.shared_linear.bias'] = dg.colsum(gyb)
             # ---- fc1:  u = h2 W1_eff^T + b1
-            lora_grads(l, [(dur, pk(l, 'fc1', 'BT'), U1r, mkr, [(dur, s['T1'], gB(l, 'fc1')), (U1r, s['h2'], gA(l, 'fc1'))])])
-            ops.gemm(dur, weT(l, 'fc1'), dhr, row_groups=rg)
+            adapter_grads(l, 'fc1', du, s['h2'], s['T1'], sc.U1, sc)
+            ops.gemm(du, weT(l, 'fc1'), sc.dh, row_groups=rg)
             if want_dense:
-                dense[lp + 'mlp.fc1.shared_linear.weight'] = wgrad(dur, s['h2'])
-                dense[lp + 'mlp.fc1.shared_linear.bias'] = colsum(dur)
+                dense[lp + 'mlp.fc1.shared_linear.weight'] = dg.wgrad(du, s['h2'])
+                dense[lp + 'mlp.fc1.shared_linear.bias'] = dg.colsum(du)
             # ---- LN2
-            dg2, db2 = ln_grads(lp + 'ln2')
-            ops.layernorm_bwd(dhr, s['xm'], P[lp + 'ln2.weight'], s['mean2'], s['rstd2'], dxmr, dx_bf16=dxmbr, dres=gy,
-                              bf16_row_scale=s['sa'], rows_per_img=rpi, dgamma=dg2, dbeta=db2, overflow=ovf)
+            dg2, db2 = ln_pair(lp + 'ln2', d)
+            ops.layernorm_bwd(sc.dh, s['xm'], P[lp + 'ln2.weight'], s['mean2'], s['rstd2'], sc.dxm, dx_bf16=dxmb, dres=gy,
+                              bf16_row_scale=s['sa'], rows_per_img=sc.rpi, dgamma=dg2, dbeta=db2, overflow=ovf)
             # ---- out proj:  xm = x + o Wo_eff^T + bo
-            lora_grads(l, [(dxmbr, pk(l, 'out', 'BT'), Uor, mkr, [(dxmbr, s['To'], gB(l, 'out')), (Uor, s['o_rows'], gA(l, 'out'))])])
-            ops.gemm(dxmbr, weT(l, 'out'), dor, row_groups=rg)
+            adapter_grads(l, 'out', dxmb, s['o_rows'], s['To'], sc.Uo, sc)
+            ops.gemm(dxmb, weT(l, 'out'), sc.do, row_groups=rg)
             if want_dense:
-                dense[lp + 'attn.out_proj.shared_linear.weight'] = wgrad(dxmbr, s['o_rows'])
-                dense[lp + 'attn.out_proj.shared_linear.bias'] = colsum(dxmbr)
+                dense[lp + 'attn.out_proj.shared_linear.weight'] = dg.wgrad(dxmb, s['o_rows'])
+                dense[lp + 'attn.out_proj.shared_linear.bias'] = dg.colsum(dxmb)
             if c:                                           # back to all rows: zero everywhere but the class rows
-                do.zero_(); do.index_copy_(0, idxl, dor)
-                dxm.zero_(); dxm.index_copy_(0, idxl, dxmr)
+                do.zero_(); do.index_copy_(0, idxl, sc.do)
+                dxm.zero_(); dxm.index_copy_(0, idxl, sc.dxm)
             # ---- attention
             ops.attn_bwd(s['qkv'], s['o'], do, s['lse'], dqkv, delta, n_img, S, heads, q_tiles=1 if c else 0)
             # ---- qkv:  qkv = h Wqkv_eff^T + b (one adapter set per projection)
-            bT = pk(l, 'qkv', 'BT')                         # [Rp, 3d]
-            gBq = gB(l, 'qkv')                              # [3d, Rp]
-            lora_grads(l, [(dqkv[:, g * d:(g + 1) * d], bT[:, g * d:(g + 1) * d], Uq[:, g * Rp:(g + 1) * Rp], mk,
-                            [(dqkv[:, g * d:(g + 1) * d], s['T'][:, g * Rp:(g + 1) * Rp], gBq[g * d:(g + 1) * d])] +
-                            ([(Uq, s['h'], gA(l, 'qkv'))] if g == 2 else [])) for g in range(3)])
-            layer_done(l)
+            adapter_grads(l, 'qkv', dqkv, s['h'], s['T'], Uq, full)
+            if side is not None:
+                side_done[l] = side.record_event()
             if l == 0 and not want_dense:
                 # nothing below layer 0 trains under the default freeze: the gradient of the embedded sequence (dX of the
                 # q|k|v projection and the LN1 backward) would be computed only to be thrown away
                 break
-            ops.gemm(dqkv, weT(l, 'qkv'), dh, row_groups=rg_full)
+            ops.gemm(dqkv, weT(l, 'qkv'), dh, row_groups=full.rg)
             if want_dense:
-                gw = wgrad(dqkv, s['h']); gb_ = colsum(dqkv)
+                gw = dg.wgrad(dqkv, s['h']); gb_ = dg.colsum(dqkv)
                 for gi, nm in enumerate('qkv'):
                     dense[lp + f'attn.{nm}_proj.shared_linear.weight'] = gw[gi * d:(gi + 1) * d]
                     dense[lp + f'attn.{nm}_proj.shared_linear.bias'] = gb_[gi * d:(gi + 1) * d]
             # ---- LN1: writes the gradient entering layer l - 1 into the OTHER buffer set; its previous readers on the side stream
             # are the adapter-gradient kernels of layer l + 1 (and this layer's successor will overwrite du / dxmb / dqkv of that set)
-            wait_side(l + 1)
-            dg1, db1 = ln_grads(lp + 'ln1')
+            if l + 1 in side_done:
+                main.wait_event(side_done.pop(l + 1))
+            dg1, db1 = ln_pair(lp + 'ln1', d)
             ops.layernorm_bwd(dh, s['x'], P[lp + 'ln1.weight'], s['mean1'], s['rstd1'], dx, dx_bf16=dxb2[(l - 1) & 1], dres=dxm,
                               bf16_row_scale=st['layers'][l - 1]['sm'] if l > 0 else None, rows_per_img=S, dgamma=dg1, dbeta=db1,
                               overflow=ovf)
         if side is not None:                                # the gradient arena is complete only when the side stream is
-            ev = torch.cuda.Event(); ev.record(side); main.wait_event(ev)
+            wait_for(main, side)
         if want_dense:
             # embedded sequence x0[img, t] = (cls | patch_t) + pos[t]: dx now holds d loss / d x0
             ones_r = torch.ones(1, n_img, **f32)
@@ -675,7 +682,7 @@ class Engine:
                 patches = torch.empty(n * (S - 1), wpe.shape[1], **b16)
                 ops.patch_im2col(img.contiguous(), patches, a['patch_size'], cin)
                 dP = ops.to_bf16(dx.view(n_img, S, d)[start:start + n, 1:, :].reshape(n * (S - 1), d).contiguous())
-                gw = wgrad(dP, patches); gb_ = colsum(dP)
+                gw = dg.wgrad(dP, patches); gb_ = dg.colsum(dP)
                 kw, kb = f'{ce}patch_embeds.{m}.proj.weight', f'{ce}patch_embeds.{m}.proj.bias'
                 acc_w[kw] = gw if kw not in acc_w else acc_w[kw] + gw
                 acc_b[kb] = gb_ if kb not in acc_b else acc_b[kb] + gb_
@@ -710,7 +717,7 @@ class Engine:
         tp = 'clip_encoder.clip_model.text_model.'
         B, T = input_ids.shape
         td, tff, heads = a['text_hidden_dim'], a['text_mlp_dim'], a['text_heads']
-        f32 = dict(dtype=torch.float32, device=dev); b16 = dict(dtype=_lib.t16(), device=dev)
+        f32, b16 = self._kw()
         ids = input_ids.to(dev).long().contiguous()
         x = torch.empty(B * T, td, **f32)
         ops.embed_tokens(P[tp + 'embeddings.token_embedding.weight'].detach(), P[tp + 'embeddings.position_embedding.weight'].detach(),
@@ -756,40 +763,47 @@ class Engine:
             return feats
         return feats, dict(layers=layers, x_final=x, idx=idx, mf=mf, rf=rf, pooled=pooled, ids=ids, km=km, B=B, T=T)
 
+    def text_forward_beside(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor]):
+        """``text_forward`` without saved state, beside the vision pass that the caller enqueues next: the (frozen) text tower is
+        independent of it and made of small launches (B*T ~ 5k rows), so it runs on the text stream, forked from the current one,
+        underneath the vision encoder's big GEMMs.  ``text_join`` must be given the features before anything reads them."""
+        if not self.overlap_text:
+            return self.text_forward(input_ids, attention_mask)
+        ts = self._stream('_text')
+        ts.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(ts):
+            feats = self.text_forward(input_ids.to(self.dev), None if attention_mask is None else attention_mask.to(self.dev))
+        self._text_pending = (feats, ts.record_event())
+        return feats
+
+    def text_join(self, feats: torch.Tensor):
+        """Make the current stream wait for the text tower that produced ``feats`` (no-op unless ``text_forward_beside`` forked it:
+        the pending event belongs to the very tensor that call returned)."""
+        pending, self._text_pending = self._text_pending, None
+        if pending is not None and pending[0] is feats:
+            main = torch.cuda.current_stream(self.dev)
+            main.wait_event(pending[1])
+            feats.record_stream(main)
+
     def text_backward(self, st, dfeat: torch.Tensor) -> Dict[str, torch.Tensor]:
         """dfeat f32 [B, D] -> {reference key: fp32 gradient} for every tensor of ``text_keys()`` (freeze_backbone=False /
         freeze_text_backbone=False).  Same scheme as the vision backward without LoRA: dX through transposed 16-bit packs,
         dW = dY^T X on the reduce-over-rows GEMM, biases as column sums, LayerNorm pairs from the LN backward kernel, causal
         attention backward, embedding tables by scatter-add / batch sum."""
         a, P, W = self.arch, self.P, self.W
-        dev = self.dev
         tp = 'clip_encoder.clip_model.text_model.'
         B, T = st['B'], st['T']
         M = B * T
         td, tff, heads = a['text_hidden_dim'], a['text_mlp_dim'], a['text_heads']
-        f32 = dict(dtype=torch.float32, device=dev); b16 = dict(dtype=_lib.t16(), device=dev)
-        G: Dict[str, torch.Tensor] = {}
+        f32, b16 = self._kw()
         scale_t = None
         if self.loss_scaling:
             amax = dfeat.abs().amax().clamp_min(1e-30)
-            scale_t = torch.exp2(torch.floor(torch.log2(512.0 / amax))).clamp(2.0 ** -20, 2.0 ** 40)
+            scale_t = grad_scale(amax)
             dfeat = dfeat * scale_t
-        ones8 = torch.ones(M, 8, **b16)
-
-        def wgrad(dY, X):
-            out = torch.empty(dY.shape[1], X.shape[1], **f32)
-            ops.gemm_tn(dY, X, out)
-            return out
-
-        def colsum(dY):
-            out = torch.empty(dY.shape[1], 8, **f32)
-            ops.gemm_tn(dY, ones8[:dY.shape[0]], out)
-            return out[:, 0].contiguous()
-
-        def ln_pair(key):
-            G[key + '.weight'] = torch.zeros(td, **f32); G[key + '.bias'] = torch.zeros(td, **f32)
-            return G[key + '.weight'], G[key + '.bias']
-
+        dg = DenseGrads(M, f32, b16)
+        G, wgrad, colsum = dg.out, dg.wgrad, dg.colsum
+        ln_pair = lambda key: dg.ln_pair(key, td)
         dfb = ops.to_bf16(dfeat)
         G['clip_encoder.text_proj.weight'] = wgrad(dfb, st['pooled'])
         dpool = torch.empty(B, td, **b16)

@@ -44,7 +44,6 @@ from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_ke
 logger = logging.getLogger(__name__)
 
 LORA_PARAM_NAME = 'clip_encoder.vision_layers.loras.arena'
-_REF_LIN = ('attn.q_proj', 'attn.k_proj', 'attn.v_proj', 'attn.out_proj', 'mlp.fc1', 'mlp.fc2')
 
 
 class LazyCount:
@@ -110,19 +109,18 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         for k, shp in param_spec(self.arch, None).items():
             v = init_state[k] if init_state is not None else seeded_tensor(k, shp, seed)
             if '.loras.' in k:
-                self._lora_put(lora_host, k, v)
+                self.layout.ref_view(lora_host, k).copy_(v)
             else:
                 self._add_param(k, v.to(dev))
         self.lora_arena = nn.Parameter(lora_host.to(dev))
         self.register_parameter('p/' + LORA_PARAM_NAME.replace('.', '/'), self.lora_arena)
         self._ref[LORA_PARAM_NAME] = self.lora_arena
-        self.engine = Engine(self.arch, self._ref, self.lora_arena, dev)
+        self.engine = Engine(self.arch, self._ref, self.lora_arena, dev, layout=self.layout)
         self._plans = {}
         self._plan_ids = {}
         self._fusion_cache = {}
         self._loss_cache = {}
         self._forced_keep = None       # tests only: fixed keep decisions of the next modality-dropout draws
-        self._overlap_text = os.environ.get('REID_TEXT_STREAM', '1') != '0'
         # Stochastic regularisers of the reference's training forward (all inactive in eval mode):
         #   DropPath in the vision blocks (clip_backbone.py:137-141,204), dropout in the SDM module (hard-coded 0.1: model.py:35,43),
         #   in the fusion block (fusion_dropout: model.py:95,104,106), before the classifier (dropout_rate: model.py:200,221),
@@ -156,34 +154,9 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self._ref[ref_name] = p
         self.register_parameter('p/' + ref_name.replace('.', '/'), p)
 
-    def _lora_slot(self, key: str):
-        # clip_encoder.vision_layers.{l}.{lin}.loras.{m}.lora_{A|B}.weight
-        parts = key.split('.')
-        l = int(parts[2]); lin = parts[3] + '.' + parts[4]; m = parts[6]; which = parts[7]
-        e, g, mu, n_out = self.layout.ref_slices(l, lin, m)
-        r, Rp = self.layout.r, self.layout.Rp
-        return e, g, mu, n_out, r, Rp, which
-
-    def _lora_put(self, arena: torch.Tensor, key: str, v: torch.Tensor):
-        e, g, mu, n_out, r, Rp, which = self._lora_slot(key)
-        if which == 'lora_A':
-            o, (rows, K) = e['A']
-            arena[o:o + rows * K].view(rows, K)[g * Rp + mu * r: g * Rp + (mu + 1) * r].copy_(v)
-        else:
-            o, (N, _) = e['B']
-            arena[o:o + N * Rp].view(N, Rp)[g * n_out:(g + 1) * n_out, mu * r:(mu + 1) * r].copy_(v)
-
-    def _lora_get(self, arena: torch.Tensor, key: str) -> torch.Tensor:
-        e, g, mu, n_out, r, Rp, which = self._lora_slot(key)
-        if which == 'lora_A':
-            o, (rows, K) = e['A']
-            return arena[o:o + rows * K].view(rows, K)[g * Rp + mu * r: g * Rp + (mu + 1) * r]
-        o, (N, _) = e['B']
-        return arena[o:o + N * Rp].view(N, Rp)[g * n_out:(g + 1) * n_out, mu * r:(mu + 1) * r]
-
     def lora_grad_view(self, key: str) -> Optional[torch.Tensor]:
         """Gradient of one reference adapter tensor (view into the arena gradient)."""
-        return None if self.lora_arena.grad is None else self._lora_get(self.lora_arena.grad, key)
+        return None if self.lora_arena.grad is None else self.layout.ref_view(self.lora_arena.grad, key)
 
     def named_parameters(self, prefix: str = '', recurse: bool = True, remove_duplicate: bool = True):
         for k, p in self._ref.items():
@@ -194,7 +167,7 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         arena = self.lora_arena if keep_vars else self.lora_arena.detach()
         for k in param_spec(self.arch, self.num_classes).keys():
             if '.loras.' in k:
-                out[prefix + k] = self._lora_get(arena, k).clone()
+                out[prefix + k] = self.layout.ref_view(arena, k).clone()
             elif k in self._ref:
                 out[prefix + k] = self._ref[k] if keep_vars else self._ref[k].detach()
             elif k in self._bufs:
@@ -213,7 +186,7 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
                     continue
                 v = torch.as_tensor(v)
                 if '.loras.' in k:
-                    self._lora_get(self.lora_arena, k).copy_(v.to(self.lora_arena.device))
+                    self.layout.ref_view(self.lora_arena, k).copy_(v.to(self.lora_arena.device))
                 elif k in self._ref:
                     self._ref[k].copy_(v.to(self._ref[k].device))
                 else:
@@ -251,17 +224,13 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
     def set_epoch(self, epoch: int):
         self.current_epoch = epoch
 
-    def _check_trainable(self):
-        for k, p in self._ref.items():
-            if p.requires_grad and k.startswith('clip_encoder.clip_model.text_model.') and not self.engine.text_backward_ready:
-                raise NotImplementedError(f'gradient of {k} requested: the text tower has no backward pass in this build')
-
-    def _text_apply(self, ids, am):
+    def _text_apply(self, ids, am, beside_vision: bool = False):
         """Text tower + projection; through TextEncodeFn (activations saved, backward available) only when one of its tensors
-        trains (freeze_backbone=False and freeze_text_backbone=False) -- the reference default runs it forward-only."""
+        trains (freeze_backbone=False and freeze_text_backbone=False) -- the reference default runs it forward-only, and
+        ``beside_vision`` (a vision pass follows) then lets the engine overlap the two; ``engine.text_join`` ends the overlap."""
         if torch.is_grad_enabled() and self.engine.text_trains():
             return TextEncodeFn.apply(self.engine, ids, am, *[self._ref[k] for k in self.engine.text_keys()])
-        return self.engine.text_forward(ids, am)
+        return self.engine.text_forward_beside(ids, am) if beside_vision else self.engine.text_forward(ids, am)
 
     def _vision_apply(self, mods, images):
         """VisionEncodeFn with the backbone tensors as extra autograd inputs only when one of them trains
@@ -491,8 +460,6 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             batch_size = texts['input_ids'].shape[0] if isinstance(texts, dict) else len(texts)
         if batch_size is None:
             raise ValueError('cannot determine batch size')
-        if torch.is_grad_enabled():
-            self._check_trainable()
         _lib.set_flavor(self.compute_dtype)
         self.engine.refresh()
         B = batch_size
@@ -514,21 +481,11 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
                     sel = img.to(dev) if kind == 'all' else img.to(dev)[sel_idx]
                     groups.append((self.vision_modalities.index(m), sel.float()))
                     order.append((m, None if kind == 'all' else sel_idx, mask_dev))
-        # The (frozen) text tower is independent of the vision pass and made of small launches (B*T ~ 5k rows): it runs on a
-        # second HIP stream underneath the vision encoder's big GEMMs and is joined before the head.
+        # A forward-only text tower runs underneath the vision pass (engine.text_forward_beside) and is joined before the head.
         n_text = 0 if texts is None else (texts['input_ids'].shape[0] if isinstance(texts, dict) else len(texts))
-        tf = None; text_ev = None
+        tf = None
         if texts is not None and n_text > 0:
-            ids, am = self._tokens(texts)
-            if self._overlap_text and not (torch.is_grad_enabled() and self.engine.text_trains()) and groups:
-                main = torch.cuda.current_stream(dev)
-                side = self.engine._text_stream()
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    tf = self.engine.text_forward(ids.to(dev), None if am is None else am.to(dev))
-                text_ev = torch.cuda.Event(); text_ev.record(side)
-            else:
-                tf = self._text_apply(ids, am)
+            tf = self._text_apply(*self._tokens(texts), beside_vision=bool(groups))
         feats = None
         if groups:
             if self.training and self.drop_path > 0 and torch.is_grad_enabled():
@@ -546,9 +503,7 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
                 full = null.expand(B, -1).clone().index_copy(0, idx, feats[start:start + n]); start += n
             raw[m] = full; fmask[m] = mask
         if tf is not None:
-            if text_ev is not None:
-                torch.cuda.current_stream(dev).wait_event(text_ev)
-                tf.record_stream(torch.cuda.current_stream(dev))
+            self.engine.text_join(tf)
             tmd = plan['text'][2]
             if plan['text'][0] != 'all':
                 tf = torch.where(tmd.bool().view(B, 1), tf, self._ref['null_tokens.text'].expand(B, -1))

@@ -52,6 +52,27 @@ def test_lora_layout_is_a_partition():
     assert t.shape == (2 * 12 * 4, 5) and int(t[:, 3:].max()) < lay.pack_size
     assert LoraLayout(arch_of(TrainingConfig(mer_lora_rank=4))).Rp == 32
     assert LoraLayout(arch_of(TrainingConfig(mer_lora_rank=16))).Rp == 64
+    # Every reference adapter tensor has its own arena view (LoraLayout.ref_view): the spec's shape, no element shared with another
+    # key's (a distinct constant written through each view is read back through all), and together the views cover exactly the
+    # 4 * r live ones of every Rp adapter rows (A) or columns (B); the padding stays untouched.
+    for r in (4, 8, 16):
+        arch = arch_of(TrainingConfig(mer_lora_rank=r))
+        lay = LoraLayout(arch)
+        spec = {k: shp for k, shp in param_spec(arch, None).items() if '.loras.' in k}
+        assert len(spec) == 12 * 6 * 4 * 2
+        arena = torch.zeros(lay.size)
+        for i, (k, shp) in enumerate(spec.items()):
+            v = lay.ref_view(arena, k)
+            assert tuple(v.shape) == tuple(shp), k
+            v.fill_(i + 1)
+        for i, k in enumerate(spec):
+            assert bool((lay.ref_view(arena, k) == i + 1).all()), k
+        live = (torch.arange(lay.Rp) < 4 * r)
+        for (l, nm), e in lay.ent.items():
+            A = lay.view_A(arena, l, nm).view(e['G'], lay.Rp, e['K'])
+            B = lay.view_B(arena, l, nm)
+            assert torch.equal(A != 0, live.view(1, -1, 1).expand_as(A)), (l, nm)
+            assert torch.equal(B != 0, live.view(1, -1).expand_as(B)), (l, nm)
 
 
 def test_hash_tokenizer_layout():
