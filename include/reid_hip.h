@@ -325,6 +325,34 @@ int reid_sdm_bwd(const float* q, int32_t ldq, const float* g, int32_t ldg, const
 int64_t reid_sdm_ws_floats(int32_t P, int32_t N, int32_t Mg, int32_t D);
 
 /* ------------------------------------------------------------------------------------------
+ * Batch-hard triplet loss (Hermans et al. 2017; the reference has no such loss) on x [rows, D] f32 (leading dimension ldx), the
+ * fused feature in front of the BN-neck:
+ *   labels [rows] int64; valid [rows] uint8 or NULL (rows with valid == 0 are neither anchors nor candidates);
+ *   d2(i,j) = sum_c (x_ic - x_jc)^2 in the DIFFERENCE form (never |x|^2 + |y|^2 - 2 x.y: the feature is mostly batch mean),
+ *   d(i,j) = sqrt(max(d2, 1e-12)); where d2 <= 1e-12 that term's gradient is zero (clamp(min=1e-12).sqrt()).
+ *   Hardest positive of anchor i: the valid j != i with labels[j] == labels[i] and the largest d2; hardest negative: the valid j with
+ *   another label and the smallest d2; ties on the fp32 d2 go to the lowest index, for both.  An anchor is active if it is valid and
+ *   has both; otherwise idx_p = idx_n = -1 and d_ap = d_an = row_loss = 0.
+ *   row_loss[i] = max(0, d_ap - d_an + margin) for margin >= 0, softplus(d_ap - d_an) for margin < 0 (the soft-margin form);
+ *   result[0] = sum of the active rows' losses / max(1, n_active), result[1] = n_active (a float: no host read-back; no active anchor
+ *   gives loss 0 and a zero gradient).  The sum is taken in a fixed order in fp64 by a one-workgroup second launch.
+ *   bwd: dx [rows, D] (leading dimension lddx) is OVERWRITTEN with dloss[0] * d result[0] / dx, gathered per output row from the saved
+ *   d_ap, d_an, idx_p, idx_n in ascending anchor order (one launch); a saved distance equal to the clamp value contributes nothing
+ *   (that also covers a d2 a few ulp above 1e-12 whose square root rounds to the same float).  Non-finite features: a d2 that
+ *   overflowed to +inf is an ordinary candidate (it can be the hardest positive, and the hardest negative when it is the only one);
+ *   a NaN d2 never ranks before anything.
+ *   No atomics in either direction: two runs give the same bits.  The features are not L2-normalised inside the loss.
+ * Requirements: D % 4 == 0, 4 <= D <= 1024, 1 <= rows <= 8192, ldx / lddx multiples of 4 and >= D, rows * ld < 2^31, x and dx 16-byte
+ * aligned.
+ * ------------------------------------------------------------------------------------------ */
+int reid_triplet_hard_fwd(const float* x, int32_t ldx, const int64_t* labels, const uint8_t* valid, int32_t rows, int32_t D,
+                          float margin, float* d_ap, float* d_an, int32_t* idx_p, int32_t* idx_n, float* row_loss,
+                          float* result, void* stream);
+int reid_triplet_hard_bwd(const float* x, int32_t ldx, int32_t rows, int32_t D, float margin, const float* d_ap,
+                          const float* d_an, const int32_t* idx_p, const int32_t* idx_n, const float* result,
+                          const float* dloss, float* dx, int32_t lddx, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Retrieval (train.py:499 + :463; tools/eval_mm_protocol.py:50-53,401-423,622-625):
  *   sim = Q . G^T on L2-normalised rows, per-query top-k in (score desc, index asc) order.
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;

@@ -82,6 +82,9 @@ class TrainingConfig:
     sdm_weight_final: float = 0.5
     sdm_weight_max: float = 0.5
     contrastive_weight: float = 0.0
+    # not reference config fields (the reference has no triplet loss): batch-hard triplet loss on the pre-BN fused feature
+    triplet_weight: float = 0.0
+    triplet_margin: Optional[float] = 0.3      # None: soft margin
     sdm_semantic_dim: int = 512
     sdm_num_heads: int = 8
     sdm_dropout: float = 0.1   # not a reference config field: hard-coded in SemanticDisentanglementModule (models/model.py:35,43)

@@ -1,11 +1,11 @@
-"""Autograd boundaries of the head kernels: BN-neck, classifier, label-smoothed CE, SDM loss.
+"""Autograd boundaries of the head kernels: BN-neck, classifier, label-smoothed CE, SDM loss, batch-hard triplet loss.
 
 Reference: BNNeck.forward models/model.py:208-224; compute_loss :512-659; sdm_loss_stable
 models/sdm_loss.py:13-149.  All arithmetic is in libreid_hip.so (fp32); torch only carries the tensors.
 """
 import torch
 
-from . import ops
+from . import _lib, ops
 
 
 class BNNeckFn(torch.autograd.Function):
@@ -118,6 +118,57 @@ class SDMFn(torch.autograd.Function):
         dq = torch.zeros_like(q2); dg = torch.zeros_like(g)
         ops.sdm_bwd(q2, g, ql, gl, qv, gv, ctx.tau, ws, dloss.reshape(P).float().contiguous(), dq, dg, P=P)
         return dq.view(P, q2.shape[0] // P, q2.shape[1]), dg, None, None, None, None, None
+
+
+class TripletHardFn(torch.autograd.Function):
+    """(loss, n_active) of the batch-hard triplet loss of x [B, D] (csrc/triplet.hip; the reference has no such loss).  ``margin`` None:
+    the soft-margin form softplus(d_ap - d_an).  n_active is a float tensor; nothing is read back to the host.  ``rows_out``: an optional
+    trailing dict that receives COPIES of the per-row arrays ``d_ap``, ``d_an``, ``idx_p``, ``idx_n`` (batch_hard_triplet); the call the
+    model makes is ``apply(x, labels, valid, margin)``."""
+
+    @staticmethod
+    def forward(ctx, x, labels, valid, margin, rows_out=None):
+        m = -1.0 if margin is None else float(margin)
+        if m < 0 and margin is not None:
+            raise ValueError('TripletHardFn: margin must be >= 0, or None for the soft-margin form')
+        x = x.contiguous().float()
+        B, dev = x.shape[0], x.device
+        fl = torch.empty(3, B, device=dev); ix = torch.empty(2, B, dtype=torch.int32, device=dev)      # d_ap | d_an | row_loss, idx_p | idx_n
+        res = torch.empty(2, device=dev)
+        labels = labels.contiguous()
+        ops.triplet_hard_fwd(x, labels, valid, m, fl[0], fl[1], ix[0], ix[1], fl[2], res)
+        ctx.save_for_backward(x, fl, ix, res)
+        ctx.margin = m
+        loss, n_active = res[0], res[1]
+        ctx.mark_non_differentiable(n_active)
+        if rows_out is not None:
+            flc, ixc = fl[:2].clone(), ix.clone()          # copies: the saved arrays belong to the backward
+            rows_out.update(d_ap=flc[0], d_an=flc[1], idx_p=ixc[0], idx_n=ixc[1])
+        return loss, n_active
+
+    @staticmethod
+    def backward(ctx, dloss, _dn):
+        x, fl, ix, res = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        ops.triplet_hard_bwd(x, ctx.margin, fl[0], fl[1], ix[0], ix[1], res, dloss.reshape(1).float().contiguous(), dx)
+        return dx, None, None, None, None
+
+
+def batch_hard_triplet(features, labels, valid=None, margin=0.3):
+    """Batch-hard triplet loss of ``features`` [B, D] for users with their own loop: hardest positive / negative per anchor by the
+    Euclidean distance (difference form, fp32), mean over the active anchors.  ``valid``: optional bool / uint8 [B], rows that take part;
+    ``margin`` None: soft margin.  The features are NOT L2-normalised here.  Returns (loss, LazyCount(n_active), {'d_ap', 'd_an',
+    'idx_p', 'idx_n'}); the loss carries the gradient to ``features``."""
+    from .model import LazyCount
+    if not (features.is_cuda and labels.is_cuda and (valid is None or valid.is_cuda)):
+        raise _lib.ReidHipError('batch_hard_triplet needs device tensors (there is no CPU path)')
+    if features.dim() != 2 or labels.shape != features.shape[:1]:
+        raise ValueError('batch_hard_triplet: features [B, D], labels [B]')
+    if valid is not None:
+        valid = valid.to(torch.uint8).contiguous()
+    rows = {}
+    loss, n_active = TripletHardFn.apply(features, labels.long(), valid, margin, rows)
+    return loss, LazyCount(n_active), rows
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -37,7 +37,7 @@ from . import _lib, ops
 from .config import arch_of
 from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CrossEntropyLSFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn,
-                   NanToNumFn, SDMFn, SmallAttnFn)
+                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -91,6 +91,8 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.sdm_temperature = getattr(config, 'sdm_temperature', 0.2)
         self.ce_weight = getattr(config, 'ce_weight', 1.0)
         self.contrastive_weight = getattr(config, 'contrastive_weight', 0.1)
+        self.triplet_weight = getattr(config, 'triplet_weight', 0.0)          # batch-hard triplet loss (not in the reference): off by default
+        self.triplet_margin = getattr(config, 'triplet_margin', 0.3)          # None: soft margin
         self.num_classes = None
         self.bn_neck = None
         self._ref: "OrderedDict[str, nn.Parameter]" = OrderedDict()
@@ -597,7 +599,15 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
                 L, flag = SDMFn.apply(q, raw['vis'], labels, labels, qv, gv, float(self.sdm_temperature))
                 sdm = L.sum() / flag.sum().clamp_min(1.0)                                        # mean over the pairs that contribute (model.py:617-622)
         total = self.ce_weight * ce + self.contrastive_weight * sdm
-        return {'total_loss': total, 'ce_loss': ce, 'sdm_loss': sdm, 'contrastive_loss': sdm, 'ce_valid_cnt': LazyCount(cnt)}
+        out = {'total_loss': total, 'ce_loss': ce, 'sdm_loss': sdm, 'contrastive_loss': sdm, 'ce_valid_cnt': LazyCount(cnt)}
+        if self.triplet_weight > 0:
+            # batch-hard triplet loss on the fused feature in front of the BN-neck (csrc/triplet.hip); under DataParallel features and
+            # labels are the global batch, so mining is global on every rank
+            tri, n_act = TripletHardFn.apply(outputs['features'], labels, valid, self.triplet_margin)
+            out['total_loss'] = total + self.triplet_weight * tri
+            out['triplet_loss'] = tri
+            out['triplet_active_cnt'] = LazyCount(n_act)
+        return out
 
     # ------------------------------------------------------------------ optimiser groups
     def get_learnable_params(self) -> List[Dict[str, Any]]:

@@ -309,6 +309,37 @@ def sdm_bwd(q, g, q_label, g_label, q_valid, g_valid, tau, ws, gscale, dq, dg, P
                              ptr(dg), dg.stride(0), stream_ptr()))
 
 
+def triplet_hard_fwd(x, labels, valid, margin, d_ap, d_an, idx_p, idx_n, row_loss, result):
+    """Batch-hard triplet loss of x [B, D] f32; margin < 0 selects the soft-margin form; result f32 [2] = (loss, n_active)."""
+    L._req(x, torch.float32, 'x'); L._req(labels, torch.int64, 'labels')
+    for n, t, d in (('d_ap', d_ap, torch.float32), ('d_an', d_an, torch.float32), ('idx_p', idx_p, torch.int32),
+                    ('idx_n', idx_n, torch.int32), ('row_loss', row_loss, torch.float32), ('result', result, torch.float32)):
+        L._req(t, d, n)
+    B = x.shape[0]
+    if x.dim() != 2 or labels.numel() != B or min(d_ap.numel(), d_an.numel(), idx_p.numel(), idx_n.numel(), row_loss.numel()) < B \
+            or result.numel() < 2:
+        raise ValueError('triplet_hard_fwd: x [B, D], labels [B], per-row outputs [B], result [2]')
+    if valid is not None:
+        L._req(valid, torch.uint8, 'valid')
+        if valid.numel() != B:
+            raise ValueError('triplet_hard_fwd: valid [B]')
+    check(lib().reid_triplet_hard_fwd(ptr(x), x.stride(0), ptr(labels), ptr(valid), B, x.shape[1], margin, ptr(d_ap), ptr(d_an),
+                                      ptr(idx_p), ptr(idx_n), ptr(row_loss), ptr(result), stream_ptr()))
+
+
+def triplet_hard_bwd(x, margin, d_ap, d_an, idx_p, idx_n, result, dloss, dx):
+    """dx [B, D] = dloss * d loss / dx from the arrays triplet_hard_fwd saved (overwritten, one launch); dloss a device scalar."""
+    L._req(x, torch.float32, 'x'); L._req(dx, torch.float32, 'dx'); L._req(dloss, torch.float32, 'dloss'); L._req(result, torch.float32, 'result')
+    for n, t, d in (('d_ap', d_ap, torch.float32), ('d_an', d_an, torch.float32), ('idx_p', idx_p, torch.int32), ('idx_n', idx_n, torch.int32)):
+        L._req(t, d, n)
+    B = x.shape[0]
+    if x.dim() != 2 or dx.shape != x.shape or min(d_ap.numel(), d_an.numel(), idx_p.numel(), idx_n.numel()) < B or result.numel() < 2 \
+            or dloss.numel() < 1:
+        raise ValueError('triplet_hard_bwd: x and dx [B, D], per-row arrays [B], result [2], dloss [1]')
+    check(lib().reid_triplet_hard_bwd(ptr(x), x.stride(0), B, x.shape[1], margin, ptr(d_ap), ptr(d_an), ptr(idx_p), ptr(idx_n),
+                                      ptr(result), ptr(dloss), ptr(dx), dx.stride(0), stream_ptr()))
+
+
 # ----------------------------------------------------------------------------------------- retrieval
 def topk_ws_bytes(Nq, Ng, k):
     return int(lib().reid_topk_ws_bytes(Nq, Ng, k))
