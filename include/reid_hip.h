@@ -522,6 +522,36 @@ int reid_augment_images(const void* src, int64_t src_bytes, const int32_t* table
                         int32_t S, const float* lut, void* ws, int64_t ws_bytes, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Query expansion (AQE, Chum et al. ICCV 2007; alpha-QE, Radenovic et al. TPAMI 2018) and database-side augmentation (DBA) in
+ * one call (csrc/expand.hip): every row becomes itself plus a weighted sum of the table rows its ranked list names.  The reference
+ * has neither; this comment is the definition (DESIGN.md "Query expansion and database-side augmentation").
+ *   x      f32 [rows, ldx >= D]  the rows being expanded, L2-normalised by the caller
+ *   table  f32 [M, ldt >= D]     the rows the lists index (the gallery)
+ *   nbr i32, score f32 [rows, ldn >= kl]  row i's list, score descending, as reid_cosine_topk* / reid_rows_topk write it
+ *   out    f32 [rows, ldo >= D]; columns >= D and rows >= rows are not written
+ * Eligibility: the kl entries of row i are walked in list order.  An entry is eligible when 0 <= nbr < M, its score is not NaN,
+ *   and nbr != self_base + i when self_base >= 0 (DBA: row i of a gallery chunk that starts at row self_base is its own leading
+ *   term; it is recognised by index, not by position, so an exact duplicate that outranks it on the index tie rule is still used);
+ *   self_base = -1: no such row.  The first k eligible entries are used.  The table row of an entry that is not used is never read.
+ * Weight: alpha == 0: w = 1 (AQE).  alpha in 1..REID_EXPAND_MAX_ALPHA: with s = max(score, 0), w = s; repeat alpha - 1 times:
+ *   w = w * s (fp32 products).  A used entry with w == 0 is not added at all.
+ * Raw sum, per column d: raw = x[i][d]; then for each added entry in list order raw = raw + w * table[nbr][d], the product rounded to
+ *   fp32 before the sum (no fused multiply-add): a float32 loop on the host reproduces the bits.
+ * Output: normalize == 0: out = raw.  normalize == 1: out = raw * (1 / max(sqrt(sum_d raw^2), eps)), evaluated as reid_l2norm_rows
+ *   does (per-lane partial sums, a wave reduction, sqrtf, one division, one product per element).
+ * Limits: 1 <= k <= kl <= REID_EXPAND_MAX_LIST, D % 4 == 0, D <= 1024 (reid_l2norm_rows' limits), rows >= 1, M >= 1, eps >= 0;
+ *   ldx, ldt, ldo multiples of 4 and >= D; x, table, out 16-byte aligned.  out must not overlap table or x: out == table and
+ *   out == x are refused, any other overlap is the caller's to avoid (rows are read while other rows are written).  Anything else is
+ *   refused before a launch.  One wavefront per row; 64-bit row offsets; deterministic (no atomics); nothing is allocated or
+ *   synchronised.
+ * ------------------------------------------------------------------------------------------ */
+#define REID_EXPAND_MAX_LIST 64
+#define REID_EXPAND_MAX_ALPHA 16
+int reid_expand_rows(const float* x, int64_t ldx, const float* table, int64_t ldt, int32_t M, const int32_t* nbr,
+                     const float* score, int32_t ldn, int32_t kl, int32_t k, int32_t alpha, int64_t self_base,
+                     int32_t normalize, float eps, float* out, int64_t ldo, int32_t rows, int32_t D, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * k-reciprocal re-ranking (Zhong et al., CVPR 2017) of pooled unit rows X = [Q; G], N = Nq + Ng <= 65 536, dense; the
  * definition is DESIGN.md "k-reciprocal re-ranking" (the reference has none).  kh = round-half-to-even(k1 / 2).
  *   nbr   i32 [N, ldn >= k1 + 1]: row i of the pooled ranking (score descending, index ascending; i itself is an entry)

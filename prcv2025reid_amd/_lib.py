@@ -115,6 +115,7 @@ SIGNATURES = {
     'reid_rows_topk': (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _P]),
     'reid_augment_ws_bytes': (_I64, [_I, _I]),
     'reid_augment_images': (_I, [_P, _I64, _P, _P, _I, _I, _P, _P, _I64, _P, _P]),
+    'reid_expand_rows': (_I, [_P, _I64, _P, _I64, _I, _P, _P, _I, _I, _I, _I, _I64, _I, _F, _P, _I64, _I, _I, _P]),
     'reid_rerank_weights_sparse': (_I, [_P, _I, _P, _I, _P, _P, _P, _I64, _I, _I, _I, _P]),
     'reid_rerank_expand_count': (_I, [_P, _P, _P, _I64, _P, _I, _P, _I, _I, _I, _P]),
     'reid_rerank_expand_sparse': (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _I, _I, _I, _P]),

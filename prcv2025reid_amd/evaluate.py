@@ -18,7 +18,8 @@ import torch
 from . import _lib, ops
 from .retrieval import GalleryIndex, l2_normalize
 
-if TYPE_CHECKING:          # (rerank.py imports this module: the class is only named in annotations here)
+if TYPE_CHECKING:          # (rerank.py imports this module: the classes are only named in annotations here)
+    from .expansion import ExpansionParams
     from .rerank import RerankParams
 
 _SCALE = 16.0        # features are scaled into the 16-bit formats' comfortable range before splitting (undone by alpha)
@@ -61,12 +62,17 @@ class ProtocolEvaluator:
     """Gallery-side state built once: normalised features, split 16-bit operand, pid CSR, image ids."""
 
     def __init__(self, gallery_feats: torch.Tensor, gallery_pids: torch.Tensor, gallery_img_ids: Optional[Sequence] = None,
-                 normalized: bool = False):
+                 normalized: bool = False, augment: Optional['ExpansionParams'] = None):
+        """``augment``: an ``ExpansionParams`` replaces the gallery features by ``expansion.augment_gallery`` of them (database-side
+        augmentation) before anything else is built from them."""
         g = gallery_feats.contiguous().float()
         if not g.is_cuda:
             raise _lib.ReidHipError('ProtocolEvaluator needs device tensors (there is no CPU path)')
         self.dev = g.device
         self.Gf = g if normalized else l2_normalize(g)
+        if augment is not None:
+            from .expansion import augment_gallery
+            self.Gf = augment_gallery(self.Gf, augment, normalized=True)
         self.Ng, self.D = self.Gf.shape
         self._Gcat = split_gallery(self.Gf)                   # only the gallery half is kept
         pids = gallery_pids.to(self.dev).long()
@@ -117,10 +123,28 @@ class ProtocolEvaluator:
             rows.append(known + [-1] * (4 - len(known)))
         return torch.tensor(rows, dtype=torch.int32, device=self.dev)
 
+    def _expanded(self, q_feats: torch.Tensor, expand: 'ExpansionParams', q_img_ids: Optional[Sequence], ignore_same_img: bool,
+                  chunk: int, normalized: bool) -> torch.Tensor:
+        """Query expansion inside an evaluation: the L2-normalised queries plus their first ``expand.k`` gallery rows of this
+        evaluator's own ``ranked_lists`` -- the ranking ``per_query`` scores, under the same same-image exclusion, so an excluded
+        gallery image is never averaged into its own query."""
+        if not q_feats.is_cuda:
+            raise _lib.ReidHipError('query expansion needs device tensors (there is no CPU path)')
+        Qf = q_feats.contiguous().float().to(self.dev)
+        if not normalized:
+            Qf = l2_normalize(Qf)
+        nbr, score = self.ranked_lists(Qf, k=expand.k, q_img_ids=q_img_ids, ignore_same_img=ignore_same_img, chunk=chunk, normalized=True)
+        return ops.expand_rows(Qf, self.Gf, nbr, score, expand.k, expand.alpha)
+
     def per_query(self, q_feats: torch.Tensor, q_pids: torch.Tensor, q_img_ids: Optional[Sequence] = None,
-                  ignore_same_img: bool = True, chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None):
+                  ignore_same_img: bool = True, chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None,
+                  expand: Optional['ExpansionParams'] = None):
         """(ap f64 [Nq], rank1 i32 [Nq], npos i32 [Nq]) on the device.  ``rerank``: a ``RerankParams`` ranks by the k-reciprocal
-        re-ranked similarity s* (rerank.py) instead of the cosine; the same-image exclusion is the same."""
+        re-ranked similarity s* (rerank.py) instead of the cosine; the same-image exclusion is the same.  ``expand``: an
+        ``ExpansionParams`` first replaces the queries by their expansion (``_expanded``); with ``rerank`` as well, the expanded queries
+        are what the re-ranker receives."""
+        if expand is not None:
+            q_feats, normalized = self._expanded(q_feats, expand, q_img_ids, ignore_same_img, chunk, normalized), True
         Nq = q_feats.shape[0]
         qp = q_pids.to(self.dev).long()
         pos = torch.searchsorted(self._uniq, qp).clamp(max=self._uniq.numel() - 1)
@@ -139,14 +163,18 @@ class ProtocolEvaluator:
         return ap, rank1, npos
 
     def ranked_lists(self, q_feats: torch.Tensor, k: int = 100, q_img_ids: Optional[Sequence] = None, ignore_same_img: bool = True,
-                     chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None):
+                     chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None,
+                     expand: Optional['ExpansionParams'] = None):
         """(idx i32 [Nq, k], score f32 [Nq, k]) on the device: every query's first k gallery rows, score descending and gallery index
-        ascending on ties, of the very rows ``per_query`` ranks (``scores``, or s* with ``rerank``) under the same same-image
-        exclusion; positions past the eligible gallery rows hold -1 / -inf.  1 <= k <= 1024 (``ops.rows_topk``)."""
+        ascending on ties, of the very rows ``per_query`` ranks (``scores``, or s* with ``rerank``; of the expanded queries with
+        ``expand``) under the same same-image exclusion; positions past the eligible gallery rows hold -1 / -inf.
+        1 <= k <= 1024 (``ops.rows_topk``)."""
         if not q_feats.is_cuda:
             raise _lib.ReidHipError('ranked_lists needs device tensors (there is no CPU path)')
         if not 1 <= k <= ops.ROWS_TOPK_MAX_K:
             raise _lib.ReidHipError(f'ranked_lists: k={k} outside 1..{ops.ROWS_TOPK_MAX_K} (the limit of ops.rows_topk)')
+        if expand is not None:
+            q_feats, normalized = self._expanded(q_feats, expand, q_img_ids, ignore_same_img, chunk, normalized), True
         Nq = q_feats.shape[0]
         excl = self._exclusions(q_img_ids, ignore_same_img)
         idx = torch.empty(Nq, k, dtype=torch.int32, device=self.dev)
@@ -159,9 +187,9 @@ class ProtocolEvaluator:
         return idx, score
 
     def rank_and_metrics(self, q_feats, q_pids, q_img_ids=None, ignore_same_img: bool = True, chunk: int = 1024,
-                         rerank: Optional['RerankParams'] = None) -> Dict[str, float]:
+                         rerank: Optional['RerankParams'] = None, expand: Optional['ExpansionParams'] = None) -> Dict[str, float]:
         """Same dictionary as eval_mm_protocol.py:455-469: queries without an (unmasked) positive are skipped."""
-        ap, rank1, npos = self.per_query(q_feats, q_pids, q_img_ids, ignore_same_img, chunk, rerank=rerank)
+        ap, rank1, npos = self.per_query(q_feats, q_pids, q_img_ids, ignore_same_img, chunk, rerank=rerank, expand=expand)
         if bool((npos < 0).any()):
             raise _lib.ReidHipError('a query has more than 8192 positives in the gallery: not supported by reid_rank_metrics')
         valid = npos > 0
@@ -181,11 +209,16 @@ class ProtocolEvaluator:
 
     # ---------------------------------------------------------------------------------------------------------
     def export_submission_csv(self, q_feats, query_keys: Sequence[str], gallery_img_names: Sequence, output_path: str,
-                              top_k: int = 100, rerank: Optional['RerankParams'] = None, chunk: int = 1024):
+                              top_k: int = 100, rerank: Optional['RerankParams'] = None, chunk: int = 1024,
+                              expand: Optional['ExpansionParams'] = None):
         """eval_mm_protocol.py:595-649: one row per query, the top_k gallery image ids of the unmasked ranking.  ``rerank``: a
         ``RerankParams`` lists by the re-ranked similarity s* in the order of a stable descending sort of the s* rows (``ranked_lists``
-        without exclusion; the sort itself only for a top_k outside 1..1024, the list lengths of ``ops.rows_topk``)."""
+        without exclusion; the sort itself only for a top_k outside 1..1024, the list lengths of ``ops.rows_topk``).  ``expand``: an
+        ``ExpansionParams`` first replaces the queries by their expansion from ``ranked_lists(q, k=expand.k)``, unmasked like the export
+        itself (no query image ids reach this call)."""
         import csv
+        if expand is not None:
+            q_feats = self._expanded(q_feats.to(self.dev), expand, None, True, chunk, False)
         if rerank is None:
             if self.index is None:
                 self.index = GalleryIndex(self.Gf, normalized=True)

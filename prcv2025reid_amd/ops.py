@@ -441,6 +441,34 @@ def rows_topk(scores, n, k, g_img=None, q_excl=None, out=None):
     return idx, score
 
 
+EXPAND_MAX_LIST = 64          # REID_EXPAND_MAX_LIST: the longest ranked list reid_expand_rows walks
+EXPAND_MAX_ALPHA = 16         # REID_EXPAND_MAX_ALPHA
+
+
+def expand_rows(x, table, nbr, score, k, alpha, self_base=-1, normalize=True, eps=1e-12, out=None):
+    """out[i] = x[i] + sum of w * table[nbr[i, t]] over the first k eligible entries of row i's list, L2-normalised unless
+    ``normalize`` is false (reid_expand_rows, include/reid_hip.h: query expansion with ``self_base`` = -1, database-side augmentation
+    of the rows ``self_base`` .. of the table otherwise).  ``nbr`` i32 / ``score`` f32 [rows, kl] as ``rows_topk`` and
+    ``GalleryIndex.topk`` return them; w = 1 for ``alpha`` = 0, else max(score, 0) ** alpha.  ``out``: the [rows, D] tensor to write."""
+    L._req(x, torch.float32, 'x'); L._req(table, torch.float32, 'table')
+    L._req(nbr, torch.int32, 'nbr'); L._req(score, torch.float32, 'score')
+    if x.dim() != 2 or table.dim() != 2 or table.shape[1] != x.shape[1]:
+        raise ValueError(f'x, table: expected [rows, D] and [M, D], got {tuple(x.shape)}, {tuple(table.shape)}')
+    rows, D = x.shape
+    if nbr.dim() != 2 or nbr.shape[0] != rows or tuple(score.shape) != tuple(nbr.shape) or (rows > 1 and score.stride(0) != nbr.stride(0)):
+        raise ValueError(f'nbr, score: expected two [{rows}, kl] tensors of one row stride, got {tuple(nbr.shape)}, {tuple(score.shape)}')
+    if out is None:
+        out = torch.empty(rows, D, dtype=torch.float32, device=x.device)
+    L._req(out, torch.float32, 'out')
+    if tuple(out.shape) != (rows, D):
+        raise ValueError(f'out: expected [{rows}, {D}], got {tuple(out.shape)}')
+    ld = lambda t: t.stride(0) if t.shape[0] > 1 else t.shape[1]           # (the row stride of a one-row tensor says nothing)
+    check(lib().reid_expand_rows(ptr(x), ld(x), ptr(table), ld(table), table.shape[0], ptr(nbr), ptr(score), ld(nbr),
+                                 nbr.shape[1], k, alpha, self_base, int(bool(normalize)), eps, ptr(out), ld(out), rows, D,
+                                 stream_ptr()))
+    return out
+
+
 def rerank_weights(nbr, X, V, k1):
     """V[i, :N] = k-reciprocal weights of pooled row i (reid_rerank_weights, include/reid_hip.h); zero-fills V[:, :N] first."""
     check(lib().reid_rerank_weights(ptr(nbr), nbr.stride(0), ptr(X), X.stride(0), ptr(V), V.stride(0), X.shape[0], X.shape[1], k1,
