@@ -353,6 +353,54 @@ int reid_triplet_hard_bwd(const float* x, int32_t ldx, int32_t rows, int32_t D, 
                           const float* dloss, float* dx, int32_t lddx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cross-modal batch-hard triplet loss (bi-directional cross-modality triplet of Ye et al., AGW 2021, with the mining of Hermans et
+ * al. 2017; the reference has no such loss): every non-vis modality against vis, on the raw modality features.  All fp32.
+ *   q [P*N, D] (leading dimension ldq) = the P query sides stacked, rows [p*N, (p+1)*N) = pair p; g [Mg, D] (ldg) = the shared vis
+ *   side; q_label [N] int64 (shared by the pairs), g_label [Mg]; q_valid [P*N] / g_valid [Mg] uint8 or NULL (rows with 0 are neither
+ *   anchors nor candidates) -- the conventions of reid_sdm_fwd.
+ *   Unit rows (normalize == 1): x^ = x * (1 / max(sqrt(sum_c x_c^2), eps)), evaluated as reid_l2norm_rows evaluates it (bit-equal rows
+ *   give bit-equal unit rows); normalize == 0: the rows are used as they are.
+ *   d2(a,b) = sum_c (a^_c - b^_c)^2 in the DIFFERENCE form (never 2 - 2 cos: the modality features share a large common mean),
+ *   d = sqrt(max(d2, 1e-12)); a term whose saved d equals the clamp value has no gradient (the rule of reid_triplet_hard_*).
+ *   Mining compares the fp32 d2 (a D-term sum).  The two distances an anchor KEEPS are then re-evaluated from the same fp32 rows with
+ *   an fp64 sum, rounded once to fp32 and rooted there: l'(d_ap - d_an) of the backward inherits the absolute error of the saved
+ *   distances, and the few ulp of the fp32 sum at d = 40 are already 1e-5 of the soft margin's gradient.
+ *   Mining, per pair p, in two directions.  q->g: every valid q row i of pair p is an anchor; hardest positive = the valid g row j
+ *   with g_label[j] == q_label[i] and the largest d2, hardest negative = the valid g row with another label and the smallest d2.
+ *   g->q: every valid g row j is an anchor against the valid q rows of pair p by the same rules, indices pair-local (0..N-1).  Ties on
+ *   the fp32 d2 go to the lowest index in both directions.  There is NO self-exclusion: row i of q and row i of g are one person in
+ *   two modalities, a legitimate positive.  An anchor is active when it is valid and has both a positive and a negative; otherwise
+ *   its indices are -1 and its distances and row loss 0.  A +inf d2 is an ordinary candidate, a NaN d2 never ranks before anything.
+ *   Row loss l = max(0, d_ap - d_an + margin) for margin >= 0, softplus(d_ap - d_an) for margin < 0 (the soft-margin form).
+ *   L_p = 0.5 * (sum over the active q anchors of l / max(1, n_qg[p]) + sum over the active g anchors of l / max(1, n_gq[p])), the
+ *   sums taken in a fixed order in fp64 by a small last launch; result [P, 4] = {L_p, flag_p, n_qg[p], n_gq[p]} with flag_p = 1 iff
+ *   n_qg + n_gq > 0 (L_p = 0 otherwise).  Nothing is read back to the host.
+ *   Saved: q_d [2, P*N] = d_ap | d_an, q_idx [2, P*N] = idx_p | idx_n (rows of g); g_d [2, P*Mg], g_idx [2, P*Mg] (rows 0..N-1 of
+ *   pair p's q side); ws (reid_cross_triplet_ws_floats(P, N, Mg, D) floats, kept from fwd to bwd):
+ *     unit rows (P N + Mg) D | 1 / max(|x|, eps) (P N + Mg) | |x| (P N + Mg) | row losses P N + P Mg   (a negative count = bad shape).
+ *   bwd: dq [P*N, D] (lddq) and dg [Mg, D] (lddg) are OVERWRITTEN (every row is written, invalid rows with zeros) in a gather form
+ *   without atomics.  The unit-space gradient G of q row (p, i): its own two terms as an anchor, then every g anchor j of pair p in
+ *   ascending j whose idx_p or idx_n is i.  Of g row j, for p ascending: its own two terms as an anchor of pair p, then the q anchors
+ *   of pair p in ascending i that chose j.  A term is c (x^_i - x^_a) / d with c = gscale[p] * 0.5 * l' / max(1, n), n the count of
+ *   the ANCHOR's direction; gscale f32 [P] on the device = dLoss / dL_p.  normalize == 1: dx = (G - x^ (x^ . G)) / max(|x|, eps)
+ *   where |x| >= eps and dx = G / eps where |x| < eps (what autograd gives for x / norm.clamp_min(eps)); normalize == 0: dx = G.
+ *   Two runs give the same bits in every output.  Nothing is allocated or synchronised inside a call.
+ * Requirements: 1 <= P <= 8; 1 <= N, Mg <= 8192; D % 4 == 0, 4 <= D <= 1024; ldq / ldg / lddq / lddg multiples of 4 and >= D;
+ * rows * ld < 2^31; q, g, ws, dq, dg 16-byte aligned; margin not NaN; normalize 0 or 1; eps >= 0.  Anything else: REID_ERR_ARG
+ * before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int64_t reid_cross_triplet_ws_floats(int32_t P, int32_t N, int32_t Mg, int32_t D);
+int reid_cross_triplet_fwd(const float* q, int32_t ldq, const float* g, int32_t ldg, const int64_t* q_label,
+                           const int64_t* g_label, const uint8_t* q_valid, const uint8_t* g_valid, int32_t P, int32_t N,
+                           int32_t Mg, int32_t D, float margin, int32_t normalize, float eps, float* q_d, int32_t* q_idx,
+                           float* g_d, int32_t* g_idx, float* ws, float* result, void* stream);
+int reid_cross_triplet_bwd(const float* q, int32_t ldq, const float* g, int32_t ldg, const uint8_t* q_valid,
+                           const uint8_t* g_valid, int32_t P, int32_t N, int32_t Mg, int32_t D, float margin,
+                           int32_t normalize, float eps, const float* q_d, const int32_t* q_idx, const float* g_d,
+                           const int32_t* g_idx, const float* ws, const float* result, const float* gscale, float* dq,
+                           int32_t lddq, float* dg, int32_t lddg, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Retrieval (train.py:499 + :463; tools/eval_mm_protocol.py:50-53,401-423,622-625):
  *   sim = Q . G^T on L2-normalised rows, per-query top-k in (score desc, index asc) order.
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;

@@ -85,6 +85,10 @@ class TrainingConfig:
     # not reference config fields (the reference has no triplet loss): batch-hard triplet loss on the pre-BN fused feature
     triplet_weight: float = 0.0
     triplet_margin: Optional[float] = 0.3      # None: soft margin
+    # not reference config fields either: cross-modal batch-hard triplet loss, every non-vis modality against vis on the raw features
+    cross_triplet_weight: float = 0.0
+    cross_triplet_margin: Optional[float] = 0.3      # None: soft margin
+    cross_triplet_normalize: bool = True             # distances between unit rows
     sdm_semantic_dim: int = 512
     sdm_num_heads: int = 8
     sdm_dropout: float = 0.1   # not a reference config field: hard-coded in SemanticDisentanglementModule (models/model.py:35,43)

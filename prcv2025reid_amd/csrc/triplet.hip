@@ -5,154 +5,24 @@
 //   hardest and the second-hardest candidate -- while the difference form stays at D * 2^-24 whatever the mean.
 //   The whole problem is 3 B^2 D flop (1.6 GFLOP at B = 1024): the matrix cores are not needed.
 //
-// Forward, launch 1 (triplet_fwd_kernel): a workgroup owns TA = 4 anchors.  Its four waves walk the candidate rows 256 at a time, ONE
-//   CANDIDATE PER LANE: a [256][32]-float piece of the candidates is staged once per workgroup in LDS (16-byte global reads into
-//   registers while the previous piece is computed; rows padded by 16 bytes so that the per-lane ds_read_b128 of "my row" is conflict free) and shared by the tile's anchors, whose columns sit beside them and are read
-//   as LDS broadcasts (as scalar loads they cost a scalar-cache round trip per 16 bytes: 16 serial waits per piece).  Every lane keeps four partial sums per anchor (one per column mod 4): a chain of D / 4
-//   additions, well inside the D * 2^-24 bound, and the same instruction sequence for every (i, j) -- equal rows give bit-equal d2.
-//   Each lane keeps a running (key, index) best per anchor under the tie rule of rank.h (key descending, index ascending; the key is d2
-//   for the hardest positive and -d2 for the hardest negative, so equal d2 go to the lowest index for both); the lanes are merged by
-//   ranking::wave_best, the four waves through LDS.  (lds_tile.h's staging helpers build 128-byte-row swizzled 16-bit tiles for MFMA
-//   fragments; a padded fp32 image read row-per-lane is a different layout, so they are not used here.)
+// Forward, launch 1 (triplet_fwd_kernel): a workgroup owns TA = 4 anchors and mines them against all rows with triplet::mine_tile
+//   (triplet_mine.h, shared with cross_triplet.hip: one candidate per lane, 256-row pieces staged through padded LDS rows).
 // Forward, launch 2 (triplet_finalize_kernel): ONE workgroup adds row_loss in a fixed order in fp64 -> result = {loss, n_active}.
 // Backward (triplet_bwd_kernel): gather form, one wave per output row i: its own two terms, then every anchor a in ascending order whose
 //   idx_p[a] or idx_n[a] is i.  No atomics anywhere: two runs give the same bits in every output.
-#include "rank.h"
+#include "triplet_mine.h"
 
 namespace {
 
-constexpr int TA = 4;                    // anchors per workgroup
-constexpr int DK = 32;                   // columns per staged piece
-constexpr int PITCH = DK + 4;            // padded LDS row (floats)
-constexpr int CB = 256;                  // candidates per piece: one per thread
-constexpr float D2_MIN = 1e-12f;         // clamp(min=1e-12).sqrt()
-// "no candidate yet": ranks behind every real index at an equal key, so a candidate whose d2 overflowed to +inf (key -inf for a
-// negative) is still taken when it is the only one
-constexpr int NONE = 0x7fffffff;
-
-// l = max(0, z + margin) (margin >= 0) or softplus(z) (margin < 0), z = d_ap - d_an; dl = its derivative
-__device__ __forceinline__ float triplet_row_loss(float z, float margin) {
-    if (margin >= 0.f) return fmaxf(z + margin, 0.f);
-    return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z)));
-}
-__device__ __forceinline__ float triplet_row_dloss(float z, float margin) {
-    if (margin >= 0.f) return z + margin > 0.f ? 1.f : 0.f;
-    const float e = expf(-fabsf(z));
-    return z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
+using namespace triplet;
 
 __global__ __launch_bounds__(256) void triplet_fwd_kernel(const float* __restrict__ x, int ldx, const int64_t* __restrict__ labels,
                                                           const uint8_t* __restrict__ valid, int rows, int D, float margin,
                                                           float* __restrict__ d_ap, float* __restrict__ d_an, int* __restrict__ idx_p,
                                                           int* __restrict__ idx_n, float* __restrict__ row_loss) {
-    __shared__ __attribute__((aligned(16))) float cand[CB * PITCH];
-    __shared__ __attribute__((aligned(16))) float anch[TA * DK];
-    __shared__ float m_key[4][TA][2];
-    __shared__ int m_idx[4][TA][2];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const Rows all{x, ldx, labels, valid, rows};
     const int a0 = blockIdx.x * TA;
-    float bp[TA], bn[TA];
-    int ip[TA], in[TA];
-#pragma unroll
-    for (int a = 0; a < TA; ++a) { bp[a] = -1.f; ip[a] = NONE; bn[a] = -INFINITY; in[a] = NONE; }
-    int64_t alab[TA];                    // the anchors' labels, read once
-#pragma unroll
-    for (int a = 0; a < TA; ++a) alab[a] = labels[min(a0 + a, rows - 1)];
-
-    // One piece = DK columns of CB candidates.  The next piece travels global -> registers while this one is computed from LDS.
-    // (columns past D are staged as zeros on both sides: they add exactly 0 to every sum, and the inner loop has one shape)
-    constexpr int NST = CB * (DK / 4) / 256;
-    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 stage[NST], astage = zero4;
-#pragma unroll
-    for (int u = 0; u < NST; ++u) stage[u] = zero4;
-    auto fetch = [&](int c0, int k0) {
-        const int nc4 = min(DK / 4, (D - k0) >> 2);                  // 16-byte chunks of this piece
-#pragma unroll
-        for (int u = 0; u < NST; ++u) {
-            const int e = tid + 256 * u, r = e >> 3, c4 = e & 7;
-            if (c0 + (r & ~63) < rows) stage[u] = c4 < nc4 ? *(const f32x4*)(x + min(c0 + r, rows - 1) * ldx + k0 + 4 * c4) : zero4;
-        }
-        if (tid < TA * (DK / 4))                                     // the anchors' columns (rows past the end: clamped, dropped later)
-            astage = (tid & 7) < nc4 ? *(const f32x4*)(x + min(a0 + (tid >> 3), rows - 1) * ldx + k0 + 4 * (tid & 7)) : zero4;
-    };
-    float acc[TA][4];
-#pragma unroll
-    for (int a = 0; a < TA; ++a) acc[a][0] = acc[a][1] = acc[a][2] = acc[a][3] = 0.f;
-    int c0 = 0, k0 = 0;
-    fetch(0, 0);
-    for (;;) {
-        __syncthreads();                                             // the previous piece has been read
-#pragma unroll
-        for (int u = 0; u < NST; ++u) {                              // (slots fetch() skipped hold stale values nobody reads)
-            const int e = tid + 256 * u;
-            *(f32x4*)(cand + (e >> 3) * PITCH + 4 * (e & 7)) = stage[u];
-        }
-        if (tid < TA * (DK / 4)) *(f32x4*)(anch + 4 * tid) = astage;
-        __syncthreads();
-        int c0n = c0, k0n = k0 + DK;
-        if (k0n >= D) { k0n = 0; c0n += CB; }
-        const bool more = c0n < rows;
-        if (more) fetch(c0n, k0n);
-        if (c0 + wave * 64 < rows) {                                 // uniform: this wave has at least one real candidate
-#pragma unroll
-            for (int c4 = 0; c4 < DK / 4; ++c4) {
-                const f32x4 y = *(const f32x4*)(cand + tid * PITCH + 4 * c4);
-#pragma unroll
-                for (int a = 0; a < TA; ++a) {
-                    const f32x4 xa = *(const f32x4*)(anch + a * DK + 4 * c4);      // one address per wave: an LDS broadcast
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float d = xa[e] - y[e];
-                        acc[a][e] = fmaf(d, d, acc[a][e]);
-                    }
-                }
-            }
-        }
-        if (k0n == 0) {                                              // all columns of these candidates are in
-            const int j = c0 + tid;
-            if (j < rows && (!valid || valid[j])) {
-                const int64_t lj = labels[j];
-#pragma unroll
-                for (int a = 0; a < TA; ++a) {
-                    const float d2 = (acc[a][0] + acc[a][1]) + (acc[a][2] + acc[a][3]);
-                    if (lj == alab[a]) {
-                        if (j != a0 + a && ranking::ranks_before(d2, j, bp[a], ip[a])) { bp[a] = d2; ip[a] = j; }
-                    } else if (ranking::ranks_before(-d2, j, bn[a], in[a])) { bn[a] = -d2; in[a] = j; }
-                }
-            }
-#pragma unroll
-            for (int a = 0; a < TA; ++a) acc[a][0] = acc[a][1] = acc[a][2] = acc[a][3] = 0.f;
-        }
-        if (!more) break;
-        c0 = c0n; k0 = k0n;
-    }
-#pragma unroll
-    for (int a = 0; a < TA; ++a) {
-        ranking::wave_best(bp[a], ip[a]);
-        ranking::wave_best(bn[a], in[a]);
-        if (lane == 0) {
-            m_key[wave][a][0] = bp[a]; m_idx[wave][a][0] = ip[a];
-            m_key[wave][a][1] = bn[a]; m_idx[wave][a][1] = in[a];
-        }
-    }
-    __syncthreads();
-    if (tid < TA && a0 + tid < rows) {
-        const int i = a0 + tid;
-        float kp = m_key[0][tid][0], kn = m_key[0][tid][1];
-        int jp = m_idx[0][tid][0], jn = m_idx[0][tid][1];
-        for (int w = 1; w < 4; ++w) {
-            if (ranking::ranks_before(m_key[w][tid][0], m_idx[w][tid][0], kp, jp)) { kp = m_key[w][tid][0]; jp = m_idx[w][tid][0]; }
-            if (ranking::ranks_before(m_key[w][tid][1], m_idx[w][tid][1], kn, jn)) { kn = m_key[w][tid][1]; jn = m_idx[w][tid][1]; }
-        }
-        const bool active = (!valid || valid[i]) && jp != NONE && jn != NONE;
-        const float dp = active ? sqrtf(fmaxf(kp, D2_MIN)) : 0.f;
-        const float dn = active ? sqrtf(fmaxf(-kn, D2_MIN)) : 0.f;
-        d_ap[i] = dp; d_an[i] = dn;
-        idx_p[i] = active ? jp : -1; idx_n[i] = active ? jn : -1;
-        row_loss[i] = active ? triplet_row_loss(dp - dn, margin) : 0.f;
-    }
+    mine_tile(all, all, a0, a0, D, margin, d_ap, d_an, idx_p, idx_n, row_loss);      // a row is no positive of itself
 }
 
 // one workgroup: thread t adds rows t, t + 256, ... in fp64, the 256 sums are added in index order
@@ -176,24 +46,6 @@ __global__ __launch_bounds__(256) void triplet_finalize_kernel(const float* __re
     }
 }
 
-constexpr int NV = 4;                    // 16-byte column chunks per lane of the backward: D <= 256 NV
-
-// acc += s * (x_i - x_a) over this lane's columns
-__device__ __forceinline__ void add_term(f32x4 (&acc)[NV], const f32x4 (&xi)[NV], const float* __restrict__ xa, float s, int lane, int D) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int c = 4 * lane + 256 * v;
-        if (c < D) {
-            const f32x4 y = *(const f32x4*)(xa + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[v][e] = fmaf(s, xi[v][e] - y[e], acc[v][e]);
-        }
-    }
-}
-
-// c_a / d of one saved distance; 0 for a clamped distance (d2 <= 1e-12: the saved d is the clamp value itself)
-__device__ __forceinline__ float term_scale(float c, float d) { return d > sqrtf(D2_MIN) ? c / d : 0.f; }
-
 // one wave per output row
 __global__ __launch_bounds__(256) void triplet_bwd_kernel(const float* __restrict__ x, int ldx, int rows, int D, float margin,
                                                           const float* __restrict__ d_ap, const float* __restrict__ d_an,
@@ -215,24 +67,11 @@ __global__ __launch_bounds__(256) void triplet_bwd_kernel(const float* __restric
     const int jp = idx_p[i], jn = idx_n[i];
     if (jp >= 0 && jp < rows && jn >= 0 && jn < rows) {              // i is an active anchor: its own two terms
         const float dp = d_ap[i], dn = d_an[i];
-        const float c = g * triplet_row_dloss(dp - dn, margin);
+        const float c = g * row_dloss_of(dp - dn, margin);
         add_term(acc, xi, x + (size_t)jp * ldx, term_scale(c, dp), lane, D);
         add_term(acc, xi, x + (size_t)jn * ldx, -term_scale(c, dn), lane, D);
     }
-    for (int b = 0; b < rows; b += 64) {                             // anchors that chose i, in ascending order
-        const int a = b + lane;
-        const int pa = a < rows ? idx_p[a] : -1, na = a < rows ? idx_n[a] : -1;
-        unsigned long long hit = __ballot(pa == i || na == i);
-        while (hit) {
-            const int l = __builtin_ctzll(hit);
-            hit &= hit - 1;
-            const int aa = b + l;
-            const bool pos = __shfl(pa, l, 64) == i;
-            const float dp = d_ap[aa], dn = d_an[aa];
-            const float c = g * triplet_row_dloss(dp - dn, margin);
-            add_term(acc, xi, x + (size_t)aa * ldx, pos ? term_scale(c, dp) : -term_scale(c, dn), lane, D);
-        }
-    }
+    add_chosen_by(acc, xi, i, x, ldx, rows, idx_p, idx_n, d_ap, d_an, g, margin, lane, D);      // anchors that chose i, in ascending order
     float* o = dx + (size_t)i * lddx;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
@@ -248,7 +87,6 @@ int triplet_check_shape(const char* who, int32_t rows, int32_t D, int32_t ld, co
     REID_CHECK_ARG((int64_t)rows * ld < (1ll << 31), "%s: rows * %s beyond 2^31 elements", who, ld_name);
     return REID_OK;
 }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 

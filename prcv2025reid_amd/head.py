@@ -1,4 +1,5 @@
-"""Autograd boundaries of the head kernels: BN-neck, classifier, label-smoothed CE, SDM loss, batch-hard triplet loss.
+"""Autograd boundaries of the head kernels: BN-neck, classifier, label-smoothed CE, SDM loss, batch-hard triplet loss, cross-modal
+batch-hard triplet loss.
 
 Reference: BNNeck.forward models/model.py:208-224; compute_loss :512-659; sdm_loss_stable
 models/sdm_loss.py:13-149.  All arithmetic is in libreid_hip.so (fp32); torch only carries the tensors.
@@ -169,6 +170,77 @@ def batch_hard_triplet(features, labels, valid=None, margin=0.3):
     rows = {}
     loss, n_active = TripletHardFn.apply(features, labels.long(), valid, margin, rows)
     return loss, LazyCount(n_active), rows
+
+
+class CrossTripletFn(torch.autograd.Function):
+    """(loss [P], flag [P], n_active [P, 2]) of the cross-modal batch-hard triplet loss between P stacked modality feature sets
+    q [P, N, D] and the vis features g [Mg, D] (csrc/cross_triplet.hip; the reference has no such loss): unit rows, difference-form
+    distances, hardest positive / negative in both directions, L_p the mean of the two directions' means.  ``margin`` None: the
+    soft-margin form.  n_active = (q->g, g->q) active anchors as floats; nothing is read back to the host.  ``rows_out``: an optional
+    trailing dict that receives COPIES of the saved arrays (cross_modal_triplet); the call the model makes is
+    ``apply(q, g, q_label, g_label, q_valid, g_valid, margin, normalize)``."""
+    EPS = 1e-12                                               # F.normalize's default
+
+    @staticmethod
+    def forward(ctx, q, g, q_label, g_label, q_valid, g_valid, margin, normalize: bool, rows_out=None):
+        m = -1.0 if margin is None else float(margin)
+        if m < 0 and margin is not None:
+            raise ValueError('CrossTripletFn: margin must be >= 0, or None for the soft-margin form')
+        P, N, D = q.shape
+        q2 = q.reshape(P * N, D).contiguous().float(); g = g.contiguous().float()
+        Mg, dev = g.shape[0], q.device
+        ws = torch.empty(ops.cross_triplet_ws_floats(P, N, Mg, D), device=dev)
+        qd = torch.empty(2, P * N, device=dev); qi = torch.empty(2, P * N, dtype=torch.int32, device=dev)
+        gd = torch.empty(2, P * Mg, device=dev); gi = torch.empty(2, P * Mg, dtype=torch.int32, device=dev)
+        res = torch.empty(P, 4, device=dev)
+        qv = None if q_valid is None else q_valid.reshape(P * N).contiguous()
+        ops.cross_triplet_fwd(q2, g, q_label.contiguous(), g_label.contiguous(), qv, g_valid, m, normalize, CrossTripletFn.EPS,
+                              qd, qi, gd, gi, ws, res, P=P)
+        ctx.save_for_backward(q2, g, qv, g_valid, qd, qi, gd, gi, ws, res)
+        ctx.margin, ctx.normalize, ctx.P = m, bool(normalize), P
+        loss, flag, n_active = res[:, 0].contiguous(), res[:, 1].contiguous(), res[:, 2:].contiguous()
+        ctx.mark_non_differentiable(flag, n_active)
+        if rows_out is not None:                              # copies: the saved arrays belong to the backward
+            rows_out.update(q_d_ap=qd[0].view(P, N).clone(), q_d_an=qd[1].view(P, N).clone(), q_idx_p=qi[0].view(P, N).clone(),
+                            q_idx_n=qi[1].view(P, N).clone(), g_d_ap=gd[0].view(P, Mg).clone(), g_d_an=gd[1].view(P, Mg).clone(),
+                            g_idx_p=gi[0].view(P, Mg).clone(), g_idx_n=gi[1].view(P, Mg).clone())
+        return loss, flag, n_active
+
+    @staticmethod
+    def backward(ctx, dloss, _dflag, _dn):
+        q2, g, qv, gv, qd, qi, gd, gi, ws, res = ctx.saved_tensors
+        P = ctx.P
+        dq = torch.empty_like(q2); dg = torch.empty_like(g)
+        gs = torch.empty(P, device=q2.device)                 # (a copy: the cotangent of L.sum() is an expanded scalar with stride 0)
+        gs.copy_(dloss.reshape(P))
+        ops.cross_triplet_bwd(q2, g, qv, gv, ctx.margin, ctx.normalize, CrossTripletFn.EPS, qd, qi, gd, gi, ws, res, gs, dq, dg, P=P)
+        return dq.view(P, q2.shape[0] // P, q2.shape[1]), dg, None, None, None, None, None, None, None
+
+
+def cross_modal_triplet(q, g, q_labels, g_labels, q_valid=None, g_valid=None, margin=0.3, normalize=True):
+    """Cross-modal batch-hard triplet loss for users with their own loop: ``q`` [P, N, D] (P query modalities stacked; [N, D] = one)
+    against the vis features ``g`` [Mg, D].  Per pair, every valid q row mines its hardest positive / negative among the g rows and
+    every valid g row among the pair's q rows (Euclidean distance of the unit rows, difference form, fp32; no self-exclusion);
+    L_p = 0.5 * (mean over the active q anchors + mean over the active g anchors).  ``q_valid`` [P, N] / ``g_valid`` [Mg]: optional
+    bool / uint8, rows that take part; ``margin`` None: soft margin; ``normalize`` False: the rows are used as they are.  Returns
+    (losses [P], flags [P], rows): flag 1 where the pair has an active anchor, rows = {'q_d_ap', 'q_d_an', 'q_idx_p', 'q_idx_n'} [P, N]
+    and {'g_d_ap', 'g_d_an', 'g_idx_p', 'g_idx_n'} [P, Mg] (g indices into 0..N-1) plus 'n_active' [P, 2]; the losses carry the
+    gradient to ``q`` and ``g``."""
+    tensors = (q, g, q_labels, g_labels) + tuple(t for t in (q_valid, g_valid) if t is not None)
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.ReidHipError('cross_modal_triplet needs device tensors (there is no CPU path)')
+    if q.dim() == 2:
+        q = q.unsqueeze(0)
+    if q.dim() != 3 or g.dim() != 2 or g.shape[1] != q.shape[2] or q_labels.shape != q.shape[1:2] or g_labels.shape != g.shape[:1]:
+        raise ValueError('cross_modal_triplet: q [P, N, D] or [N, D], g [Mg, D], q_labels [N], g_labels [Mg]')
+    if q_valid is not None:
+        q_valid = q_valid.to(torch.uint8).reshape(q.shape[0], q.shape[1]).contiguous()
+    if g_valid is not None:
+        g_valid = g_valid.to(torch.uint8).contiguous()
+    rows = {}
+    loss, flag, n_active = CrossTripletFn.apply(q, g, q_labels.long(), g_labels.long(), q_valid, g_valid, margin, bool(normalize), rows)
+    rows['n_active'] = n_active
+    return loss, flag, rows
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -37,7 +37,7 @@ from . import _lib, ops
 from .config import arch_of
 from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CrossEntropyLSFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn,
-                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn)
+                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -93,6 +93,9 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.contrastive_weight = getattr(config, 'contrastive_weight', 0.1)
         self.triplet_weight = getattr(config, 'triplet_weight', 0.0)          # batch-hard triplet loss (not in the reference): off by default
         self.triplet_margin = getattr(config, 'triplet_margin', 0.3)          # None: soft margin
+        self.cross_triplet_weight = getattr(config, 'cross_triplet_weight', 0.0)      # cross-modal batch-hard triplet loss (not in the reference)
+        self.cross_triplet_margin = getattr(config, 'cross_triplet_margin', 0.3)
+        self.cross_triplet_normalize = getattr(config, 'cross_triplet_normalize', True)
         self.num_classes = None
         self.bn_neck = None
         self._ref: "OrderedDict[str, nn.Parameter]" = OrderedDict()
@@ -587,17 +590,20 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         sdm = zero
         use_sdm = (self.current_epoch >= self.config.sdm_weight_warmup_epochs) and (self.contrastive_weight > 0)
         raw = outputs.get('raw_modality_features', {})
-        if use_sdm and 'vis' in raw and 'vis' in fm:
+        use_xt = self.cross_triplet_weight > 0
+        q = None
+        if (use_sdm or use_xt) and 'vis' in raw and 'vis' in fm:
             gv = cent['gv']
             mods = [m for m in raw if m != 'vis' and m in fm]
             if mods:
-                # every non-vis modality against vis in ONE fused launch (csrc/sdm.hip): the query sides are stacked
+                # every non-vis modality against vis in ONE fused launch per loss: the query sides are stacked (built once for both)
                 q = torch.stack([raw[m] for m in mods], dim=0)                                   # [P, B, D]
                 qv = cent.get(('qv', tuple(mods)))
                 if qv is None:
                     qv = cent[('qv', tuple(mods))] = torch.stack([(fm[m] > 0) for m in mods], dim=0).to(torch.uint8).contiguous()
-                L, flag = SDMFn.apply(q, raw['vis'], labels, labels, qv, gv, float(self.sdm_temperature))
-                sdm = L.sum() / flag.sum().clamp_min(1.0)                                        # mean over the pairs that contribute (model.py:617-622)
+        if use_sdm and q is not None:
+            L, flag = SDMFn.apply(q, raw['vis'], labels, labels, qv, gv, float(self.sdm_temperature))   # csrc/sdm.hip
+            sdm = L.sum() / flag.sum().clamp_min(1.0)                                            # mean over the pairs that contribute (model.py:617-622)
         total = self.ce_weight * ce + self.contrastive_weight * sdm
         out = {'total_loss': total, 'ce_loss': ce, 'sdm_loss': sdm, 'contrastive_loss': sdm, 'ce_valid_cnt': LazyCount(cnt)}
         if self.triplet_weight > 0:
@@ -607,6 +613,15 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             out['total_loss'] = total + self.triplet_weight * tri
             out['triplet_loss'] = tri
             out['triplet_active_cnt'] = LazyCount(n_act)
+        if use_xt and q is not None:
+            # cross-modal batch-hard triplet loss (csrc/cross_triplet.hip) on the stack the SDM branch uses, not tied to its warm-up epoch;
+            # under DataParallel the raw features and labels are the global batch (the path SDM takes), so mining is global on every rank
+            L, flag, n_act = CrossTripletFn.apply(q, raw['vis'], labels, labels, qv, gv, self.cross_triplet_margin,
+                                                  bool(self.cross_triplet_normalize))
+            xt = L.sum() / flag.sum().clamp_min(1.0)                                             # mean over the pairs with an active anchor
+            out['total_loss'] = out['total_loss'] + self.cross_triplet_weight * xt
+            out['cross_triplet_loss'] = xt
+            out['cross_triplet_active_cnt'] = LazyCount(n_act.sum())
         return out
 
     # ------------------------------------------------------------------ optimiser groups

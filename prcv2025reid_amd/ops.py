@@ -340,6 +340,58 @@ def triplet_hard_bwd(x, margin, d_ap, d_an, idx_p, idx_n, result, dloss, dx):
                                       ptr(result), ptr(dloss), ptr(dx), dx.stride(0), stream_ptr()))
 
 
+def cross_triplet_ws_floats(P, N, Mg, D):
+    n = int(lib().reid_cross_triplet_ws_floats(P, N, Mg, D))
+    if n < 0:
+        check(n)
+    return n
+
+
+def _cross_triplet_shapes(who, q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, ws, result, P):
+    for n, t, d in (('q', q, torch.float32), ('g', g, torch.float32), ('q_d', q_d, torch.float32), ('q_idx', q_idx, torch.int32),
+                    ('g_d', g_d, torch.float32), ('g_idx', g_idx, torch.int32), ('ws', ws, torch.float32), ('result', result, torch.float32)):
+        L._req(t, d, n)
+    if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] % P or g.shape[1] != q.shape[1]:
+        raise ValueError(f'{who}: q [P*N, D], g [Mg, D]')
+    N, Mg = q.shape[0] // P, g.shape[0]
+    for n, t, rows in (('q_valid', q_valid, P * N), ('g_valid', g_valid, Mg)):
+        if t is not None:
+            L._req(t, torch.uint8, n)
+            if t.numel() != rows:
+                raise ValueError(f'{who}: {n} has {t.numel()} elements, not {rows}')
+    if min(q_d.numel(), q_idx.numel()) < 2 * P * N or min(g_d.numel(), g_idx.numel()) < 2 * P * Mg or result.numel() < 4 * P \
+            or not (q_d.is_contiguous() and q_idx.is_contiguous() and g_d.is_contiguous() and g_idx.is_contiguous()
+                    and ws.is_contiguous() and result.is_contiguous()):
+        raise ValueError(f'{who}: q_d / q_idx [2, P*N], g_d / g_idx [2, P*Mg], result [P, 4], all contiguous')
+    if ws.numel() < cross_triplet_ws_floats(P, N, Mg, q.shape[1]):
+        raise ValueError(f'{who}: ws holds fewer than cross_triplet_ws_floats(P, N, Mg, D) floats')
+    return N, Mg
+
+
+def cross_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, g_d, g_idx, ws, result, P=1):
+    """Cross-modal batch-hard triplet loss: q [P*N, D] (P query sides stacked) against g [Mg, D], mined in both directions; margin < 0
+    selects the soft-margin form.  q_d / q_idx [2, P*N] = (d_ap | d_an), (idx_p | idx_n) of the q anchors, g_d / g_idx [2, P*Mg] of the
+    g anchors (indices pair-local); result f32 [P, 4] = (L_p, flag_p, n_qg, n_gq); ws is kept for cross_triplet_bwd."""
+    N, Mg = _cross_triplet_shapes('cross_triplet_fwd', q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, ws, result, P)
+    L._req(q_label, torch.int64, 'q_label'); L._req(g_label, torch.int64, 'g_label')
+    if q_label.numel() != N or g_label.numel() != Mg:
+        raise ValueError('cross_triplet_fwd: q_label [N], g_label [Mg]')
+    check(lib().reid_cross_triplet_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_label), ptr(g_label), ptr(q_valid), ptr(g_valid),
+                                       P, N, Mg, q.shape[1], margin, int(normalize), eps, ptr(q_d), ptr(q_idx), ptr(g_d), ptr(g_idx),
+                                       ptr(ws), ptr(result), stream_ptr()))
+
+
+def cross_triplet_bwd(q, g, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, g_d, g_idx, ws, result, gscale, dq, dg, P=1):
+    """dq [P*N, D], dg [Mg, D] (both overwritten, one launch) from what cross_triplet_fwd saved; gscale f32 [P] on the device."""
+    N, Mg = _cross_triplet_shapes('cross_triplet_bwd', q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, ws, result, P)
+    L._req(gscale, torch.float32, 'gscale'); L._req(dq, torch.float32, 'dq'); L._req(dg, torch.float32, 'dg')
+    if dq.shape != q.shape or dg.shape != g.shape or gscale.numel() < P:
+        raise ValueError('cross_triplet_bwd: dq as q, dg as g, gscale [P]')
+    check(lib().reid_cross_triplet_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_valid), ptr(g_valid), P, N, Mg, q.shape[1], margin,
+                                       int(normalize), eps, ptr(q_d), ptr(q_idx), ptr(g_d), ptr(g_idx), ptr(ws), ptr(result), ptr(gscale),
+                                       ptr(dq), dq.stride(0), ptr(dg), dg.stride(0), stream_ptr()))
+
+
 # ----------------------------------------------------------------------------------------- retrieval
 def topk_ws_bytes(Nq, Ng, k):
     return int(lib().reid_topk_ws_bytes(Nq, Ng, k))
