@@ -65,7 +65,8 @@ int reid_check_device(int dev);
  * "not set" (the built-in default).  The knobs: "GEMM_TILE" (3 = the 128 x 128 tile, 12 / 14 = the 256 / 224-row ping-pong
  * tile), "ATTN_BWD" (1 = the two-kernel backward), "LORA_IMPL" (1 = the slab kernel), "LN_IMPL" (1 = the four-column
  * LayerNorm backward), "TOPK_TILE" (9 = select_kernel for phase C), "TOPK_SCAN" (0 = the tiled filter instead of the
- * query-resident scan).  Any other name: REID_ERR_ARG. */
+ * query-resident scan), "LORA_SPAN" (1, 2, 4, 8 = images per workgroup of the adapter-gradient image kernels).  Any other name:
+ * REID_ERR_ARG. */
 int reid_set_knob(const char* name, int value);
 
 /* ------------------------------------------------------------------------------------------
@@ -217,14 +218,18 @@ int reid_pack_bf16_table(const float* src, void* dst_bf16, const int64_t* table,
  * Other shapes: reid_mer_gemm (U) + reid_gemm_tn (dB).
  * T must be modality-masked (T[m, c] = 0 unless c / mask_r == img_mod[m / rows_per_img]) -- it is how reid_mer_gemm's mask epilogue
  * produces it: with rows_per_img >= 32 and mask_r a divisor of 16 one workgroup streams one image (one modality) and touches only the
- * aligned 16-column group of adapter columns that holds the modality's; elsewhere dB stays as it was. */
+ * aligned 16-column group of adapter columns that holds the modality's; elsewhere dB stays as it was.  A workgroup owns a span of G
+ * consecutive images and streams each maximal run of one modality inside it as one row range (one flush of dB atomics per run: a batch
+ * packed modality by modality pays G times fewer of them); any img_mod is correct.  G: knob "LORA_SPAN" = 1, 2, 4 or 8 (1 = one image
+ * per workgroup, the reference form of the tests); unset or -1, a rule of the image count and the device's compute units. */
 int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, int32_t ldt, const void* BT, int32_t ldbt, void* U, int32_t ldu,
                         float* dB, int32_t lddb, const int32_t* img_mod, int32_t rows_per_img, int32_t mask_r, int32_t M, int32_t N,
                         int32_t Rp, float scale, float* u_partial, int32_t u_mode, void* stream);
 /* The other adapter gradient of a MERLinear, dA += U^T . X (autograd of lora_A, mer_lora.py:40-49), as one pass over the linear's INPUT
  * X [M, K] (16-bit; K a multiple of 768): dA[g Rp + c, k] += sum_m U[m, g Rp + c] X[m, k] for the n_groups (1, or 3 for the fused q|k|v
  * projection) adapter groups of Rp = 32 or 64 columns of U [M, n_groups Rp] (16-bit, modality-masked as reid_lora_bwd_fused writes it).
- * dA: fp32 [n_groups Rp, K] (row stride ldda), accumulated with atomics.  One workgroup per (image, 768-column block): rows_per_img >= 32,
+ * dA: fp32 [n_groups Rp, K] (row stride ldda), accumulated with atomics.  One workgroup per (span of G images, 768-column block), the
+ * span worked through as runs of one modality like reid_lora_bwd_fused's (knob "LORA_SPAN", or the entry's own rule): rows_per_img >= 32,
  * mask_r a divisor of 16; other shapes: reid_gemm_tn(U, X). */
 int reid_lora_da_fused(const void* X, int32_t ldx, const void* U, int32_t ldu, float* dA, int32_t ldda, const int32_t* img_mod,
                        int32_t rows_per_img, int32_t mask_r, int32_t M, int32_t K, int32_t Rp, int32_t n_groups, void* stream);

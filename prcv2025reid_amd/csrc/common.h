@@ -16,7 +16,7 @@ __attribute__((visibility("hidden"))) void reid_set_error(const char* fmt, ...);
 // Knobs that force one kernel form over the one the dispatch would pick -- the reference forms the tests compare against, and the tile
 // A/B of the benchmarks: ONE cached table per process, filled from the environment (REID_<NAME>) on first use and changed afterwards only
 // through reid_set_knob() -- no getenv() on the launch path.
-enum reid_knob_id { KNOB_GEMM_TILE, KNOB_ATTN_BWD, KNOB_LORA_IMPL, KNOB_LN_IMPL, KNOB_TOPK_TILE, KNOB_TOPK_SCAN, KNOB_COUNT };
+enum reid_knob_id { KNOB_GEMM_TILE, KNOB_ATTN_BWD, KNOB_LORA_IMPL, KNOB_LN_IMPL, KNOB_TOPK_TILE, KNOB_TOPK_SCAN, KNOB_LORA_SPAN, KNOB_COUNT };
 // (internal C++ symbols of the library: hidden, only the extern "C" entry points of include/reid_hip.h are exported)
 __attribute__((visibility("hidden"))) int reid_knob(int id);
 __attribute__((visibility("hidden"))) int reid_num_cus();   // compute units of the current device (cached)

@@ -147,6 +147,7 @@ struct Params {
     float scale;
     float* Up;                                            // fp32 [M, Rp] partial sums of U over column blocks of a wider dY (or null)
     int u_mode;                                           // bit 0: add Up to this block's sum; bit 1: store the sum to Up instead of U
+    int span, n_img;                                      // image kernels: images per workgroup, images in all
 };
 
 template <int NW>
@@ -294,6 +295,18 @@ template <int RP> struct BwdGeo {
 using fused::Params;
 // The step buffers below are filled by dma16 (lds_tile.h, which says why no compiler-visible global access may sit inside the step loops).
 
+// The modalities of a workgroup's span of images (at most MAX_SPAN), eight bits each in one scalar, all read BEFORE the workgroup's first
+// store: the loads are then scalar loads, and no run waits on its predecessor's atomics to find out where it ends (a modality index is
+// below 64: mu mask_r + mask_r <= Rp).
+constexpr int MAX_SPAN = 8;
+__device__ __forceinline__ uint64_t span_mods(const int32_t* img_mod, int i0, int cnt) {
+    uint64_t m = 0;
+#pragma unroll
+    for (int i = 0; i < MAX_SPAN; ++i) m |= (uint64_t)(img_mod[i0 + (i < cnt ? i : cnt - 1)] & 255) << (8 * i);
+    return m;
+}
+__device__ __forceinline__ int span_mod(uint64_t mods, int i) { return (int)(mods >> (8 * i)) & 255; }
+
 // transposed operand from the swizzled image: 16 MFMA rows = image columns col0 .. col0 + 15, k = image rows 0 .. 31
 __device__ __forceinline__ bf16x8 tr_frag_swz(const char* img, int col0, int lane) {
     const int l16 = lane & 15, fq = lane >> 4;
@@ -318,20 +331,16 @@ __global__ __launch_bounds__(256) void u_finish_kernel(const float* __restrict__
     *(uint32_t*)(U + (size_t)m * ldu + c) = pack_bf16x2(c / mask_r == mu ? a * scale : 0.f, (c + 1) / mask_r == mu ? b * scale : 0.f);
 }
 
+// One RUN of a workgroup: the rows [rbeg, rend) of consecutive images of one modality mu -- one ring prologue, one step loop, one pending-U
+// flush and one dB flush whatever the number of images in it (a step may straddle an image boundary: U and T are per row).
 template <int RP>
-__global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) {
-    REID_T16_ENTER();
-    static_assert(RP == 32 || RP == 64, "adapter columns");
+__device__ __forceinline__ void lora_bwd_image_run(const Params& p, char* smem, const int rbeg, const int rend, const int mu) {
     constexpr int BUF_BYTES = BwdGeo<RP>::BUF_BYTES;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));                             // per run and opaque: see `ftid` at the flush
+    const int lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l16 = lane & 15, fq = lane >> 4;
-    const int img = blockIdx.x;
-    const int rbeg = img * p.rows_per_img;
-    const int rend = min(p.M, rbeg + p.rows_per_img);
-    if (rbeg >= rend) return;                                 // (whole workgroup)
-    const int mu = p.img_mod[img];
     const int w0 = (mu * p.mask_r) & ~15;                     // first adapter column of the 16-column window
     const int c_lo = mu * p.mask_r - w0, c_hi = c_lo + p.mask_r;   // this modality's columns inside the window
     const int steps = (rend - rbeg + R - 1) / R;
@@ -386,7 +395,8 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
     void* pend_ptr = nullptr;
     int pend_n = 0;                                            // rows (u_mode != 0) / "this lane has a row" (u_mode == 0; RP = 64: bit per piece) still to go out
     if constexpr (RP == 64) {
-        // U staging rows of this wave: all 64 columns +0.0 once -- the steps rewrite the window columns only, the other 48 stay zero
+        // U staging rows of this wave: all 64 columns +0.0 once per run (the window moves with the modality) -- the steps rewrite the window
+        // columns only, the other 48 stay zero
         if (w < 2 && p.u_mode == 0) {
             char* ub = smem + NBUF * BUF_BYTES + w * (16 * RP * 2);
             *(u32x4_t*)(ub + lane * 16) = u32x4_t{0u, 0u, 0u, 0u};
@@ -515,21 +525,48 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
     // dB of this image: through LDS (the ring is idle now) so that every atomic wave-instruction has 64 active lanes = eight dY columns x the
     // modality's r adapter columns -- straight from the accumulator layout half of the lanes of each of 192 instructions were masked out
     __syncthreads();
+    // (the thread index anew, opaque to the compiler: the flush's per-lane addresses are the same in every run of a workgroup, and hoisted
+    //  out of the run loop they would stay live through the step loop, which has no register to spare)
+    int ftid = threadIdx.x;
+    asm volatile("" : "+v"(ftid));
     float* fl = (float*)smem;                                 // [768 dY columns][16 window columns]
     if (w >= 2) {
-        const int cbase = (w - 2) * 128;
+        const int cbase = (w - 2) * 128, fl16 = ftid & 15, ffq = (ftid & 63) >> 4;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) fl[(cbase + i * 16 + 4 * fq + e) * 16 + l16] = acc[i][e];
+            for (int e = 0; e < 4; ++e) fl[(cbase + i * 16 + 4 * ffq + e) * 16 + fl16] = acc[i][e];
     }
     __syncthreads();
     {
         const int rr = p.mask_r, total = N * rr;
-        for (int idx = tid; idx < total; idx += 512) {
+        for (int idx = ftid; idx < total; idx += 512) {
             const int col = idx / rr, j = idx - col * rr;
             atomicAdd(p.dB + (size_t)col * p.lddb + mu * rr + j, fl[col * 16 + c_lo + j]);
         }
+    }
+}
+
+// A workgroup owns the images [s span, min(n_img, s span + span)) and works through them as maximal runs of equal img_mod (a packed batch is
+// ordered modality by modality: one run per workgroup, span times fewer dB atomics and prologues than one image per workgroup, and 25
+// steps for four 197-row images instead of 28).  Any img_mod is correct: an alternating one gives runs of one image each.
+template <int RP>
+__global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) {
+    REID_T16_ENTER();
+    static_assert(RP == 32 || RP == 64, "adapter columns");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int i0 = blockIdx.x * p.span, cnt = min(p.n_img - i0, p.span);
+    const uint64_t mods = span_mods(p.img_mod, i0, cnt);
+    for (int a = 0; a < cnt;) {                               // (workgroup-uniform: scalar shifts and compares)
+        const int mu = span_mod(mods, a);
+        int b = a + 1;
+        while (b < cnt && span_mod(mods, b) == mu) ++b;
+        const int rbeg = (i0 + a) * p.rows_per_img;
+        const int rend = min(p.M, (i0 + b) * p.rows_per_img);
+        if (rbeg >= rend) break;                              // (whole workgroup)
+        lora_bwd_image_run<RP>(p, smem, rbeg, rend, mu);
+        a = b;
+        if (a < cnt) __syncthreads();                         // the flush has read its sums from `smem` before the next run's DMA lands there
     }
 }
 
@@ -541,22 +578,17 @@ __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) 
 struct DaParams {
     const bf16_t* X; const bf16_t* U; float* dA;
     const int32_t* img_mod;
-    int ldx, ldu, ldda, rows_per_img, mask_r, M, Rp;
+    int ldx, ldu, ldda, rows_per_img, mask_r, M, Rp, span, n_img;
 };
+// one run of a workgroup (see lora_bwd_image_run): rows [rbeg, rend) of modality mu; `more`: another run follows
 template <int G>
-__global__ __launch_bounds__(512, 2) void lora_da_image_kernel(const DaParams p) {
-    REID_T16_ENTER();
+__device__ __forceinline__ void lora_da_image_run(const DaParams& p, char* smem, const int rbeg, const int rend, const int mu, const bool more) {
     constexpr int UB = 4096;                                  // U windows of a step: G x [32 rows][16 columns] 16-bit (<= 3 KiB), padded
     constexpr int BUF = IMG_BYTES + UB;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l16 = lane & 15, fq = lane >> 4;
-    const int img = blockIdx.x, cblk = blockIdx.y;
-    const int rbeg = img * p.rows_per_img;
-    const int rend = min(p.M, rbeg + p.rows_per_img);
-    if (rbeg >= rend) return;
-    const int mu = p.img_mod[img];
+    const int cblk = blockIdx.y;
     const int w0 = (mu * p.mask_r) & ~15;
     const int c_lo = mu * p.mask_r - w0, c_hi = c_lo + p.mask_r;
     const int steps = (rend - rbeg + R - 1) / R;
@@ -621,6 +653,7 @@ __global__ __launch_bounds__(512, 2) void lora_da_image_kernel(const DaParams p)
         if (t + 2 < steps) issue(t + 2, nb);
         buf = buf + 1 == NBUF ? 0 : buf + 1;
     }
+    if (more) __syncthreads();                                // every wave is done reading the ring before the next run's DMA lands in it
     // acc[g][i]: row = window column 4 fq + e of group g (an adapter row of dA), column = X column w 96 + 16 i + l16: an atomic wave-instruction
     // covers 16 consecutive k of up to four adapter rows (64-byte runs).  The first form had the operands the other way round -- every lane a
     // different ROW of dA, 3 KiB apart: the 17x-slower atomic shape of MI355X_MICROARCH.md, and the step 0.85 ms slower than with reid_gemm_tn.
@@ -635,9 +668,39 @@ __global__ __launch_bounds__(512, 2) void lora_da_image_kernel(const DaParams p)
                 atomicAdd(p.dA + (size_t)(g * p.Rp + w0 + c) * p.ldda + (size_t)cblk * N + w * 96 + i * 16 + l16, acc[g][i][e]);
     }
 }
+
+template <int G>
+__global__ __launch_bounds__(512, 2) void lora_da_image_kernel(const DaParams p) {
+    REID_T16_ENTER();
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int i0 = blockIdx.x * p.span, cnt = min(p.n_img - i0, p.span);
+    const uint64_t mods = span_mods(p.img_mod, i0, cnt);
+    for (int a = 0; a < cnt;) {                               // maximal runs of equal img_mod, as in lora_bwd_image_kernel
+        const int mu = span_mod(mods, a);
+        int b = a + 1;
+        while (b < cnt && span_mod(mods, b) == mu) ++b;
+        const int rbeg = (i0 + a) * p.rows_per_img;
+        const int rend = min(p.M, (i0 + b) * p.rows_per_img);
+        if (rbeg >= rend) break;
+        a = b;
+        lora_da_image_run<G>(p, smem, rbeg, rend, mu, a < cnt);
+    }
+}
 }  // namespace image
 
 }  // namespace
+
+// Images per workgroup of the two image kernels.  REID_LORA_SPAN = 1, 2, 4 or 8 forces it (1: one image per workgroup, the reference form of
+// the tests).  Default: 4 where that still leaves a workgroup for every fourth compute unit, else 1 -- measured in the training step at 256
+// and 512 images on 256 CUs (profiles/lora_span_summary.md): 4 images per workgroup -0.44 / -0.41 ms per step, 2 a little less, 8 slower
+// than one at 256 images (32 workgroups, each at the rate its two steps in flight allow) and equal to 4 at 512; forced separately, the
+// U + dB kernel brings 0.4 ms of it and the dA kernel 0.08, the same for 2, 4 and 8: one rule for both.  A function of the image count
+// and the device's compute units only.
+static int lora_span(int n_img) {
+    const int k = reid_knob(KNOB_LORA_SPAN);
+    if (k == 1 || k == 2 || k == 4 || k == 8) return k;
+    return n_img >= reid_num_cus() ? 4 : 1;
+}
 
 extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, int32_t ldt, const void* BT, int32_t ldbt, void* U,
                                    int32_t ldu, float* dB, int32_t lddb, const int32_t* img_mod, int32_t rows_per_img, int32_t mask_r,
@@ -650,7 +713,7 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
                    "reid_lora_bwd_fused: leading dimensions");
     REID_CHECK_ARG(((uintptr_t)dY | (uintptr_t)T | (uintptr_t)BT) % 16 == 0 && (uintptr_t)U % 4 == 0, "reid_lora_bwd_fused: operand alignment");
     fused::Params p{(const bf16_t*)dY, (const bf16_t*)T, (const bf16_t*)BT, (bf16_t*)U, dB, img_mod, lddy, ldt, ldbt, ldu, lddb, rows_per_img,
-                    mask_r, M, 0, scale, u_partial, u_mode};
+                    mask_r, M, 0, scale, u_partial, u_mode, 1, 0};
     // REID_LORA_IMPL: 1 = the slab kernel always; default: one image per workgroup where an image spans at least one 32-row step
     const bool use_image = reid_knob(KNOB_LORA_IMPL) != 1 && rows_per_img >= image::R && mask_r <= 16 && 16 % mask_r == 0;
     // the slab kernel exists for Rp = 32 only: the class-row form (rows_per_img < 32) of 64 adapter columns is reid_mer_gemm + reid_gemm_tn
@@ -658,12 +721,15 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
                    "divisor of 16, and REID_LORA_IMPL not 1 (the slab kernel is built for Rp = 32)", rows_per_img, mask_r);
     if (use_image) {
         const int n_img = (M + rows_per_img - 1) / rows_per_img;
+        p.n_img = n_img;
+        p.span = lora_span(n_img);
+        const int grid = (n_img + p.span - 1) / p.span;
         if (Rp == 32) {
             REID_MAX_LDS((image::lora_bwd_image_kernel<32>), image::BwdGeo<32>::LDS_BYTES);
-            hipLaunchKernelGGL(image::lora_bwd_image_kernel<32>, dim3(n_img), dim3(512), image::BwdGeo<32>::LDS_BYTES, (hipStream_t)stream, p);
+            hipLaunchKernelGGL(image::lora_bwd_image_kernel<32>, dim3(grid), dim3(512), image::BwdGeo<32>::LDS_BYTES, (hipStream_t)stream, p);
         } else {
             REID_MAX_LDS((image::lora_bwd_image_kernel<64>), image::BwdGeo<64>::LDS_BYTES);
-            hipLaunchKernelGGL(image::lora_bwd_image_kernel<64>, dim3(n_img), dim3(512), image::BwdGeo<64>::LDS_BYTES, (hipStream_t)stream, p);
+            hipLaunchKernelGGL(image::lora_bwd_image_kernel<64>, dim3(grid), dim3(512), image::BwdGeo<64>::LDS_BYTES, (hipStream_t)stream, p);
         }
         REID_CHECK_LAUNCH("reid_lora_bwd_fused(image)");
         if (u_mode == 1) {                                    // last column block of a wide cotangent: every partial sum is in Up now
@@ -690,15 +756,17 @@ extern "C" int reid_lora_da_fused(const void* X, int32_t ldx, const void* U, int
     REID_CHECK_ARG(rows_per_img >= image::R && mask_r > 0 && mask_r <= 16 && 16 % mask_r == 0, "reid_lora_da_fused: rows_per_img=%d (>= 32) mask_r=%d (a divisor of 16)", rows_per_img, mask_r);
     REID_CHECK_ARG(ldx % 8 == 0 && ldu % 8 == 0 && ldx >= K && ldu >= n_groups * Rp && ldda >= K, "reid_lora_da_fused: leading dimensions");
     REID_CHECK_ARG(((uintptr_t)X | (uintptr_t)U) % 16 == 0, "reid_lora_da_fused: operand alignment");
-    image::DaParams p{(const bf16_t*)X, (const bf16_t*)U, dA, img_mod, ldx, ldu, ldda, rows_per_img, mask_r, M, Rp};
     const int n_img = (M + rows_per_img - 1) / rows_per_img;
+    const int span = lora_span(n_img);
+    image::DaParams p{(const bf16_t*)X, (const bf16_t*)U, dA, img_mod, ldx, ldu, ldda, rows_per_img, mask_r, M, Rp, span, n_img};
+    const dim3 grid((n_img + span - 1) / span, K / 768);
     constexpr int LDS = image::NBUF * (image::IMG_BYTES + 4096);
     if (n_groups == 1) {
         REID_MAX_LDS((image::lora_da_image_kernel<1>), LDS);
-        hipLaunchKernelGGL(image::lora_da_image_kernel<1>, dim3(n_img, K / 768), dim3(512), LDS, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(image::lora_da_image_kernel<1>, grid, dim3(512), LDS, (hipStream_t)stream, p);
     } else {
         REID_MAX_LDS((image::lora_da_image_kernel<3>), LDS);
-        hipLaunchKernelGGL(image::lora_da_image_kernel<3>, dim3(n_img, K / 768), dim3(512), LDS, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(image::lora_da_image_kernel<3>, grid, dim3(512), LDS, (hipStream_t)stream, p);
     }
     REID_CHECK_LAUNCH("reid_lora_da_fused");
     return REID_OK;

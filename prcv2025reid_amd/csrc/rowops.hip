@@ -18,7 +18,7 @@ extern "C" const char* reid_last_error(void) { return g_err; }
 extern "C" int reid_version(void) { return REID_ABI_VERSION; }
 
 // ---------------------------------------------------------------- knobs (common.h)
-static const char* const g_knob_names[] = {"GEMM_TILE", "ATTN_BWD", "LORA_IMPL", "LN_IMPL", "TOPK_TILE", "TOPK_SCAN"};
+static const char* const g_knob_names[] = {"GEMM_TILE", "ATTN_BWD", "LORA_IMPL", "LN_IMPL", "TOPK_TILE", "TOPK_SCAN", "LORA_SPAN"};
 static_assert(sizeof(g_knob_names) / sizeof(g_knob_names[0]) == KNOB_COUNT, "one name per reid_knob_id");
 static int g_knobs[KNOB_COUNT];
 static int* knob_table() {

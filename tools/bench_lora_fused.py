@@ -1,4 +1,5 @@
-"""The fused adapter-gradient kernel alone on the chip (step shape: 50 432 rows, N = 768, Rp = 32) against the two launches it replaces."""
+"""The fused adapter-gradient kernels alone on the chip (step shape: 50 432 rows, N = 768, Rp = 32) against the launches they replace,
+then both image kernels per LORA_SPAN (images per workgroup) at 256 and 512 images, and the K = 3072 dA launch against reid_gemm_tn."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -45,3 +46,32 @@ for K, G in ((768, 1), (3072, 1), (768, 3)):
     t1 = timeit(lambda: ops.lora_da_fused(X, UU, dA, mods, 197, r, n_groups=G))
     t2 = timeit(lambda: ops.gemm_tn(UU, X, dA, beta=1.0))
     print(f'dA K={K} groups={G}: image kernel {t1:6.1f} us = {M * K * 2 / t1 / 1e6:5.2f} TB/s of X | gemm_tn {t2:6.1f} us = {M * K * 2 / t2 / 1e6:5.2f} TB/s')
+
+
+# ---- images per workgroup (knob LORA_SPAN; -1 = the default rule of the host entries) at the default batch and at --P 32
+def set_span(v):
+    _lib.check(_lib.lib().reid_set_knob(b'LORA_SPAN', v))
+
+
+for n_img in (256, 512):
+    M = n_img * 197
+    mods = (torch.arange(n_img, device='cuda', dtype=torch.int32) // (n_img // 4)).contiguous()
+    mods_row = mods.long().repeat_interleave(197).view(-1, 1)
+    dY = torch.randn(M, N, device='cuda', generator=g).to(_lib.t16())
+    T = (torch.randn(M, Rp, device='cuda', generator=g) * ((torch.arange(Rp, device='cuda').view(1, -1) // r) == mods_row)).to(_lib.t16())
+    U = torch.empty(M, Rp, device='cuda', dtype=_lib.t16()); dB = torch.zeros(N, Rp, device='cuda')
+    X3 = torch.randn(M, 3072, device='cuda', generator=g).to(_lib.t16())
+    U3 = (torch.randn(M, 3 * Rp, device='cuda', generator=g) * (((torch.arange(3 * Rp, device='cuda').view(1, -1) % Rp) // r) == mods_row)).to(_lib.t16())
+    dA1 = torch.zeros(Rp, 768, device='cuda'); dA3 = torch.zeros(3 * Rp, 768, device='cuda'); dA4 = torch.zeros(Rp, 3072, device='cuda')
+    for span in (1, 2, 4, 8, -1):
+        set_span(span)
+        try:
+            tb = timeit(lambda: ops.lora_bwd_fused(dY, T, BT, U, dB, mods, 197, r, 2.0))
+            t1 = timeit(lambda: ops.lora_da_fused(X3[:, :768], U3[:, :Rp], dA1, mods, 197, r, n_groups=1))
+            t3 = timeit(lambda: ops.lora_da_fused(X3[:, :768], U3, dA3, mods, 197, r, n_groups=3))
+            t4 = timeit(lambda: ops.lora_da_fused(X3, U3[:, :Rp], dA4, mods, 197, r, n_groups=1))
+        finally:
+            set_span(-1)
+        print(f'n_img={n_img} LORA_SPAN={span:2d}: U+dB {tb:6.1f} us | dA K=768 one group {t1:6.1f} us, three groups {t3:6.1f} us | dA K=3072 {t4:6.1f} us')
+    t2 = timeit(lambda: ops.gemm_tn(U3[:, :Rp], X3, dA4, beta=1.0))
+    print(f'n_img={n_img}: dA K=3072 by reid_gemm_tn on the same operands {t2:6.1f} us')
