@@ -1,4 +1,5 @@
-// MER-LoRA weight merge for gfx950 (see include/reid_hip.h: reid_merge_lora_table).
+// MER-LoRA on gfx950: the weight merge (reid_merge_lora_table) and the adapter gradients of one linear -- the slab kernel and the image
+// kernels behind reid_lora_bwd_fused (U and dB) and reid_lora_da_fused (dA).  See include/reid_hip.h.
 //
 // MERLinear (mer_lora.py:80-99) is  y = W x + (alpha/r) B_mu A_mu x  with one adapter pair per modality mu.  A batch is packed
 // modality by modality, so every row tile of the big GEMMs belongs to ONE modality and the low-rank update can live inside the
@@ -127,16 +128,14 @@ __global__ __launch_bounds__(256) void merge_lora_kernel(const int64_t* __restri
 namespace fused {
 constexpr int N = 768, RP = 32, R = 32;                  // columns of dY, adapter columns, rows per step
 constexpr int TP = RP * 2 + 32;                           // LDS row pitch of the T tile (bytes): padded for the transpose reads (gemm_tn.hip)
-// NW waves per workgroup, each owning N / NW columns.  NW = 8 (96 columns, 113 KB of LDS: one workgroup per CU) is what runs: every
-// 32-row step is one exposed HBM round trip (~4.5 us in the train step = 14 GB/s per CU).  NW = 4 (192 columns, 80 KB: TWO workgroups
-// per CU, each waiting for its own loads) compiles to 256 VGPRs + 40 spilled (96 accumulator + 48 B^T-fragment + 56 staging registers):
-// not instantiated; the staging registers would have to go (LDS-DMA) first.
-template <int NW> struct Geo {
-    static constexpr int CPW = N / NW, MT = CPW / 16, KS = CPW / 32, CH = CPW / 8, XL = R * CH / 64;
-    static constexpr int XP = CPW * 2 + 32;
-    static constexpr int WAVE_LDS = R * XP + R * TP;
-    static constexpr int LDS_BYTES = NW * WAVE_LDS + NW * R * RP * 4;
-};
+// NW waves per workgroup, each owning N / NW columns.  NW = 8 (96 columns, 113 KB of LDS: one workgroup per CU): every 32-row step is one
+// exposed HBM round trip (~4.5 us in the train step = 14 GB/s per CU).  The form with NW = 4 (192 columns, 80 KB: TWO workgroups per CU,
+// each waiting for its own loads) compiles to 256 VGPRs + 40 spilled (96 accumulator + 48 B^T-fragment + 56 staging registers) and is
+// not built; the staging registers would have to go (LDS-DMA) first.
+constexpr int NW = 8, CPW = N / NW, MT = CPW / 16, KS = CPW / 32, CH = CPW / 8, XL = R * CH / 64;
+constexpr int XP = CPW * 2 + 32;                          // LDS row pitch of a wave's dY columns (bytes)
+constexpr int WAVE_LDS = R * XP + R * TP;
+constexpr int LDS_BYTES = NW * WAVE_LDS + NW * R * RP * 4;
 
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 
@@ -150,11 +149,8 @@ struct Params {
     int span, n_img;                                      // image kernels: images per workgroup, images in all
 };
 
-template <int NW>
 __global__ __launch_bounds__(NW * 64, 2) void lora_bwd_fused_kernel(const Params p) {
     REID_T16_ENTER();
-    using G = Geo<NW>;
-    constexpr int CPW = G::CPW, MT = G::MT, KS = G::KS, CH = G::CH, XL = G::XL, XP = G::XP, WAVE_LDS = G::WAVE_LDS;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -318,6 +314,71 @@ __device__ __forceinline__ bf16x8 tr_frag_swz(const char* img, int col0, int lan
     return tr_join(tr_read(a0), tr_read(a1));
 }
 
+// A workgroup owns the images [s span, min(n_img, s span + span)) and works through them as maximal runs of equal img_mod (a packed batch is
+// ordered modality by modality: one run per workgroup, span times fewer atomics and prologues than one image per workgroup, and 25
+// steps for four 197-row images instead of 28).  Any img_mod is correct: an alternating one gives runs of one image each.
+// run(rbeg, rend, mu, more): the rows [rbeg, rend) of consecutive images of one modality mu.  `more`: another run follows and its DMA lands
+// in `smem`, so the run has `if (more) __syncthreads()` where every wave has read all it wants from there: behind the step loop in the dA
+// run (the ring; its atomics come from registers), behind the flush in the U + dB run (it reads its sums from `smem`).
+// (The callables capture by value: by reference, the dA kernels' prologue computes its two base pointers in the other order.)
+template <class P, class Run>
+__device__ __forceinline__ void for_each_run(const P& p, Run run) {
+    const int i0 = blockIdx.x * p.span, cnt = min(p.n_img - i0, p.span);
+    const uint64_t mods = span_mods(p.img_mod, i0, cnt);
+    for (int a = 0; a < cnt;) {                               // (workgroup-uniform: scalar shifts and compares)
+        const int mu = span_mod(mods, a);
+        int b = a + 1;
+        while (b < cnt && span_mod(mods, b) == mu) ++b;
+        const int rbeg = (i0 + a) * p.rows_per_img;
+        const int rend = min(p.M, (i0 + b) * p.rows_per_img);
+        if (rbeg >= rend) break;                              // (whole workgroup)
+        a = b;
+        run(rbeg, rend, mu, a < cnt);
+    }
+}
+
+// One step's tile -> LDS: rows r0 .. r0 + 31 (past the run's end: row rend - 1 again) x 768 columns of `src` into the source-swizzled image
+// at `base`, 48 wave-instructions, six per wave.  (Parameters by reference: by value, the U + dB kernels swap two instructions of the run prologue.)
+__device__ __forceinline__ void dma_tile(const bf16_t* const& src, const int& ld, const int& r0, const int& rend, const int& w, const int& lane, const uint32_t& base) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const int qd = w * 6 + j;                             // wave-instruction: linear chunks [64 qd, 64 qd + 64)
+        const int g = qd * 64 + lane;
+        const int row = g / 96, c = g - row * 96;
+        int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
+        dma16(src + (size_t)gr * ld + (swz512(row, c) << 3), base + qd * 1024);
+    }
+}
+
+// The step ring of a run: NBUF buffers, two steps in flight while one is read, ONE barrier per step.  issue(t, buf) sends step t's DMA
+// instructions to buffer buf: six per wave (dma_tile), seven in the waves `extra` that also fetch the step's small operand.
+template <class Issue>
+__device__ __forceinline__ void ring_prologue(int steps, Issue& issue) { issue(0, 0); if (steps > 1) issue(1, 1); }
+// Head of step t: this wave's share of the step has landed -- everything but the DMA instructions of step t + 1 (the newest this wave has
+// issued: six, seven in the `extra` waves; a wave's stores of the previous step are older than those and drain here too) -- then
+// everybody's share has, and everybody is done reading the buffer of step t - 1.
+__device__ __forceinline__ void ring_wait(int t, int steps, bool extra) {
+    if (t + 1 < steps) {
+        if (extra) wait_vm<7>();
+        else wait_vm<6>();
+    } else {
+        wait_vm<0>();
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    wait_lgkm0();
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+}
+// Tail of step t: step t + 2 into the buffer step t - 1 was read from (every wave is past this step's barrier, hence done with it); issued
+// AFTER the step's own vector-memory operations (the U stores) so that the counted wait has exactly one step's DMA instructions behind
+// everything it waits for.  Then on to the next buffer.
+template <class Issue>
+__device__ __forceinline__ int ring_refill(int t, int steps, int buf, Issue& issue) {
+    const int nb = buf == 0 ? NBUF - 1 : buf - 1;            // (t + 2) % NBUF == (t - 1) % NBUF
+    if (t + 2 < steps) issue(t + 2, nb);
+    return buf + 1 == NBUF ? 0 : buf + 1;
+}
+
 // U = mask(Up) * scale in 16 bits once the last column block of a wide cotangent has added its partial sums (fp32 [M, Rp]) to Up
 __global__ __launch_bounds__(256) void u_finish_kernel(const float* __restrict__ Up, bf16_t* __restrict__ U, int ldu, const int32_t* __restrict__ img_mod,
                                                        int rows_per_img, int mask_r, float scale, int M, int Rp) {
@@ -344,20 +405,12 @@ __device__ __forceinline__ void lora_bwd_image_run(const Params& p, char* smem, 
     const int w0 = (mu * p.mask_r) & ~15;                     // first adapter column of the 16-column window
     const int c_lo = mu * p.mask_r - w0, c_hi = c_lo + p.mask_r;   // this modality's columns inside the window
     const int steps = (rend - rbeg + R - 1) / R;
-
-    // one step's operands -> LDS: 48 dY instructions (eight waves x six) + the T instructions (RP = 32: two, waves 0 and 1; RP = 64: one, wave 0)
+    // one step's operands -> LDS: the dY tile + the T instructions (RP = 32: two, waves 0 and 1; RP = 64: one, wave 0)
     const uint32_t smem_a = lds_addr(smem);
     auto issue = [&](int t, int buf) {
         const uint32_t base = smem_a + buf * BUF_BYTES;
         const int r0 = rbeg + t * R;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const int qd = w * 6 + j;                         // wave-instruction: linear chunks [64 qd, 64 qd + 64)
-            const int g = qd * 64 + lane;
-            const int row = g / 96, c = g - row * 96;
-            int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
-            dma16(p.dY + (size_t)gr * p.lddy + (swz512(row, c) << 3), base + qd * 1024);
-        }
+        dma_tile(p.dY, p.lddy, r0, rend, w, lane, base);
         if constexpr (RP == 32) {
             if (w < 2) {
                 const int g = w * 64 + lane;                  // T tile: 32 rows x 4 chunks, lane-linear
@@ -373,8 +426,7 @@ __device__ __forceinline__ void lora_bwd_image_run(const Params& p, char* smem, 
             }
         }
     };
-    issue(0, 0);
-    if (steps > 1) issue(1, 1);
+    ring_prologue(steps, issue);
     // B^T fragments of the window (waves 0, 1: B operand of U = dY . B: n = adapter column w0 + l16, k = dY column)
     bf16x8 bfr[24];
     if (w < 2) {
@@ -428,19 +480,9 @@ __device__ __forceinline__ void lora_bwd_image_run(const Params& p, char* smem, 
     };
     int buf = 0;
     for (int t = 0; t < steps; ++t) {
-        // this wave's share of step t has landed: everything but the DMA instructions of step t + 1 (the newest this wave has issued: six,
-        // seven in the waves that also fetch T: waves 0 and 1 with RP = 32, wave 0 alone with RP = 64 -- wave 1 forms U there too, but
-        // its U stores of the previous step are older than the newest DMA instructions and drain here like those of wave 0)
-        if (t + 1 < steps) {
-            if (w < (RP == 32 ? 2 : 1)) wait_vm<7>();
-            else wait_vm<6>();
-        } else {
-            wait_vm<0>();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        wait_lgkm0();
-        __builtin_amdgcn_s_barrier();                         // ... everybody's share; and everybody is done reading the buffer of step t - 1
-        __builtin_amdgcn_sched_barrier(0);
+        // the waves that also fetch T: waves 0 and 1 with RP = 32, wave 0 alone with RP = 64 (wave 1 forms U there too: its U stores drain
+        // at the counted wait like those of wave 0)
+        ring_wait(t, steps, w < (RP == 32 ? 2 : 1));
         const char* xs = smem + buf * BUF_BYTES;
         const char* ts = xs + IMG_BYTES;
         const int r0 = rbeg + t * R;
@@ -515,11 +557,7 @@ __device__ __forceinline__ void lora_bwd_image_run(const Params& p, char* smem, 
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[i] = mfma16(tr_frag_swz(xs, cbase + i * 16, lane), tf, acc[i]);
         }
-        // step t + 2 into the buffer step t - 1 was read from (every wave is past this step's barrier, hence done with it); issued AFTER
-        // this step's U stores so that the counted wait above has exactly one step's DMA instructions behind everything it waits for
-        const int nb = buf == 0 ? NBUF - 1 : buf - 1;        // (t + 2) % NBUF == (t - 1) % NBUF
-        if (t + 2 < steps) issue(t + 2, nb);
-        buf = buf + 1 == NBUF ? 0 : buf + 1;
+        buf = ring_refill(t, steps, buf, issue);
     }
     if (w < 2) flush_pending();                               // the last step's U rows
     // dB of this image: through LDS (the ring is idle now) so that every atomic wave-instruction has 64 active lanes = eight dY columns x the
@@ -547,27 +585,12 @@ __device__ __forceinline__ void lora_bwd_image_run(const Params& p, char* smem, 
     }
 }
 
-// A workgroup owns the images [s span, min(n_img, s span + span)) and works through them as maximal runs of equal img_mod (a packed batch is
-// ordered modality by modality: one run per workgroup, span times fewer dB atomics and prologues than one image per workgroup, and 25
-// steps for four 197-row images instead of 28).  Any img_mod is correct: an alternating one gives runs of one image each.
 template <int RP>
 __global__ __launch_bounds__(512, 2) void lora_bwd_image_kernel(const Params p) {
     REID_T16_ENTER();
     static_assert(RP == 32 || RP == 64, "adapter columns");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int i0 = blockIdx.x * p.span, cnt = min(p.n_img - i0, p.span);
-    const uint64_t mods = span_mods(p.img_mod, i0, cnt);
-    for (int a = 0; a < cnt;) {                               // (workgroup-uniform: scalar shifts and compares)
-        const int mu = span_mod(mods, a);
-        int b = a + 1;
-        while (b < cnt && span_mod(mods, b) == mu) ++b;
-        const int rbeg = (i0 + a) * p.rows_per_img;
-        const int rend = min(p.M, (i0 + b) * p.rows_per_img);
-        if (rbeg >= rend) break;                              // (whole workgroup)
-        lora_bwd_image_run<RP>(p, smem, rbeg, rend, mu);
-        a = b;
-        if (a < cnt) __syncthreads();                         // the flush has read its sums from `smem` before the next run's DMA lands there
-    }
+    for_each_run(p, [=](int rbeg, int rend, int mu, bool more) { lora_bwd_image_run<RP>(p, smem, rbeg, rend, mu); if (more) __syncthreads(); });
 }
 
 // dA of one MERLinear in the same form: dA[g Rp + c, k] += sum_m U[m, g Rp + c] . X[m, k] -- one image (one modality) per workgroup and
@@ -580,7 +603,7 @@ struct DaParams {
     const int32_t* img_mod;
     int ldx, ldu, ldda, rows_per_img, mask_r, M, Rp, span, n_img;
 };
-// one run of a workgroup (see lora_bwd_image_run): rows [rbeg, rend) of modality mu; `more`: another run follows
+// one run of a workgroup (see lora_bwd_image_run): rows [rbeg, rend) of modality mu; `more`: see for_each_run
 template <int G>
 __device__ __forceinline__ void lora_da_image_run(const DaParams& p, char* smem, const int rbeg, const int rend, const int mu, const bool more) {
     constexpr int UB = 4096;                                  // U windows of a step: G x [32 rows][16 columns] 16-bit (<= 3 KiB), padded
@@ -597,22 +620,14 @@ __device__ __forceinline__ void lora_da_image_run(const DaParams& p, char* smem,
     auto issue = [&](int t, int buf) {
         const uint32_t base = smem_a + buf * BUF;
         const int r0 = rbeg + t * R;
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const int qd = w * 6 + j;
-            const int g = qd * 64 + lane;
-            const int row = g / 96, c = g - row * 96;
-            int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
-            dma16(Xb + (size_t)gr * p.ldx + (swz512(row, c) << 3), base + qd * 1024);
-        }
+        dma_tile(Xb, p.ldx, r0, rend, w, lane, base);
         if (w < G) {                                          // group w's window: 32 rows x 2 chunks, lane-linear (row pitch 32 bytes)
             const int row = lane >> 1, c = lane & 1;
             int gr = r0 + row; gr = gr < rend ? gr : rend - 1;
             dma16(p.U + (size_t)gr * p.ldu + w * p.Rp + w0 + c * 8, base + IMG_BYTES + w * 1024);
         }
     };
-    issue(0, 0);
-    if (steps > 1) issue(1, 1);
+    ring_prologue(steps, issue);
     f32x4 acc[G][6];
 #pragma unroll
     for (int g = 0; g < G; ++g)
@@ -620,16 +635,7 @@ __device__ __forceinline__ void lora_da_image_run(const DaParams& p, char* smem,
         for (int i = 0; i < 6; ++i) acc[g][i] = f32x4{0.f, 0.f, 0.f, 0.f};
     int buf = 0;
     for (int t = 0; t < steps; ++t) {
-        if (t + 1 < steps) {                                  // all but the newest step's DMA instructions (six, seven in the waves that fetch U)
-            if (w < G) wait_vm<7>();
-            else wait_vm<6>();
-        } else {
-            wait_vm<0>();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        wait_lgkm0();
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
+        ring_wait(t, steps, w < G);                           // (the waves that also fetch a U window)
         const char* xs = smem + buf * BUF;
         const char* us = xs + IMG_BYTES;
         const int nvalid = rend - (rbeg + t * R);
@@ -649,11 +655,9 @@ __device__ __forceinline__ void lora_da_image_run(const DaParams& p, char* smem,
 #pragma unroll
             for (int g = 0; g < G; ++g) acc[g][i] = mfma16(uf[g], xf, acc[g][i]);      // (U first: a lane then owns ONE X column, l16 = 16 consecutive k of dA)
         }
-        const int nb = buf == 0 ? NBUF - 1 : buf - 1;
-        if (t + 2 < steps) issue(t + 2, nb);
-        buf = buf + 1 == NBUF ? 0 : buf + 1;
+        buf = ring_refill(t, steps, buf, issue);
     }
-    if (more) __syncthreads();                                // every wave is done reading the ring before the next run's DMA lands in it
+    if (more) __syncthreads();                                // every wave is done reading the ring (for_each_run)
     // acc[g][i]: row = window column 4 fq + e of group g (an adapter row of dA), column = X column w 96 + 16 i + l16: an atomic wave-instruction
     // covers 16 consecutive k of up to four adapter rows (64-byte runs).  The first form had the operands the other way round -- every lane a
     // different ROW of dA, 3 KiB apart: the 17x-slower atomic shape of MI355X_MICROARCH.md, and the step 0.85 ms slower than with reid_gemm_tn.
@@ -673,18 +677,7 @@ template <int G>
 __global__ __launch_bounds__(512, 2) void lora_da_image_kernel(const DaParams p) {
     REID_T16_ENTER();
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int i0 = blockIdx.x * p.span, cnt = min(p.n_img - i0, p.span);
-    const uint64_t mods = span_mods(p.img_mod, i0, cnt);
-    for (int a = 0; a < cnt;) {                               // maximal runs of equal img_mod, as in lora_bwd_image_kernel
-        const int mu = span_mod(mods, a);
-        int b = a + 1;
-        while (b < cnt && span_mod(mods, b) == mu) ++b;
-        const int rbeg = (i0 + a) * p.rows_per_img;
-        const int rend = min(p.M, (i0 + b) * p.rows_per_img);
-        if (rbeg >= rend) break;
-        a = b;
-        lora_da_image_run<G>(p, smem, rbeg, rend, mu, a < cnt);
-    }
+    for_each_run(p, [=](int rbeg, int rend, int mu, bool more) { lora_da_image_run<G>(p, smem, rbeg, rend, mu, more); });
 }
 }  // namespace image
 
@@ -702,6 +695,10 @@ static int lora_span(int n_img) {
     return n_img >= reid_num_cus() ? 4 : 1;
 }
 
+// The shapes the image kernels take: an image spans at least one 32-row step, and a modality's mask_r adapter columns lie inside one
+// aligned 16-column window
+static bool lora_image_shape(int rows_per_img, int mask_r) { return rows_per_img >= image::R && mask_r <= 16 && 16 % mask_r == 0; }
+
 extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, int32_t ldt, const void* BT, int32_t ldbt, void* U,
                                    int32_t ldu, float* dB, int32_t lddb, const int32_t* img_mod, int32_t rows_per_img, int32_t mask_r,
                                    int32_t M, int32_t N, int32_t Rp, float scale, float* u_partial, int32_t u_mode, void* stream) {
@@ -715,7 +712,7 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
     fused::Params p{(const bf16_t*)dY, (const bf16_t*)T, (const bf16_t*)BT, (bf16_t*)U, dB, img_mod, lddy, ldt, ldbt, ldu, lddb, rows_per_img,
                     mask_r, M, 0, scale, u_partial, u_mode, 1, 0};
     // REID_LORA_IMPL: 1 = the slab kernel always; default: one image per workgroup where an image spans at least one 32-row step
-    const bool use_image = reid_knob(KNOB_LORA_IMPL) != 1 && rows_per_img >= image::R && mask_r <= 16 && 16 % mask_r == 0;
+    const bool use_image = reid_knob(KNOB_LORA_IMPL) != 1 && lora_image_shape(rows_per_img, mask_r);
     // the slab kernel exists for Rp = 32 only: the class-row form (rows_per_img < 32) of 64 adapter columns is reid_mer_gemm + reid_gemm_tn
     REID_CHECK_ARG(Rp == 32 || use_image, "reid_lora_bwd_fused: Rp=64 runs one image per workgroup only: rows_per_img=%d must be >= 32, mask_r=%d a "
                    "divisor of 16, and REID_LORA_IMPL not 1 (the slab kernel is built for Rp = 32)", rows_per_img, mask_r);
@@ -743,8 +740,8 @@ extern "C" int reid_lora_bwd_fused(const void* dY, int32_t lddy, const void* T, 
     int slabs = 64;
     p.slab_rows = ((M + slabs - 1) / slabs + fused::R - 1) / fused::R * fused::R;
     slabs = (M + p.slab_rows - 1) / p.slab_rows;
-    REID_MAX_LDS((fused::lora_bwd_fused_kernel<8>), fused::Geo<8>::LDS_BYTES);
-    hipLaunchKernelGGL(fused::lora_bwd_fused_kernel<8>, dim3(slabs), dim3(512), fused::Geo<8>::LDS_BYTES, (hipStream_t)stream, p);
+    REID_MAX_LDS(fused::lora_bwd_fused_kernel, fused::LDS_BYTES);
+    hipLaunchKernelGGL(fused::lora_bwd_fused_kernel, dim3(slabs), dim3(fused::NW * 64), fused::LDS_BYTES, (hipStream_t)stream, p);
     REID_CHECK_LAUNCH("reid_lora_bwd_fused");
     return REID_OK;
 }
@@ -753,7 +750,7 @@ extern "C" int reid_lora_da_fused(const void* X, int32_t ldx, const void* U, int
                                   int32_t rows_per_img, int32_t mask_r, int32_t M, int32_t K, int32_t Rp, int32_t n_groups, void* stream) {
     REID_CHECK_ARG(X && U && dA && img_mod, "reid_lora_da_fused: null pointer");
     REID_CHECK_ARG(M > 0 && K > 0 && K % 768 == 0 && (Rp == 32 || Rp == 64) && (n_groups == 1 || n_groups == 3), "reid_lora_da_fused: M=%d K=%d Rp=%d groups=%d (K a multiple of 768, Rp = 32 or 64, 1 or 3 groups)", M, K, Rp, n_groups);
-    REID_CHECK_ARG(rows_per_img >= image::R && mask_r > 0 && mask_r <= 16 && 16 % mask_r == 0, "reid_lora_da_fused: rows_per_img=%d (>= 32) mask_r=%d (a divisor of 16)", rows_per_img, mask_r);
+    REID_CHECK_ARG(mask_r > 0 && lora_image_shape(rows_per_img, mask_r), "reid_lora_da_fused: rows_per_img=%d (>= 32) mask_r=%d (a divisor of 16)", rows_per_img, mask_r);
     REID_CHECK_ARG(ldx % 8 == 0 && ldu % 8 == 0 && ldx >= K && ldu >= n_groups * Rp && ldda >= K, "reid_lora_da_fused: leading dimensions");
     REID_CHECK_ARG(((uintptr_t)X | (uintptr_t)U) % 16 == 0, "reid_lora_da_fused: operand alignment");
     const int n_img = (M + rows_per_img - 1) / rows_per_img;
