@@ -406,6 +406,53 @@ int reid_cross_triplet_bwd(const float* q, int32_t ldq, const float* g, int32_t 
                            int32_t lddq, float* dg, int32_t lddg, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Hetero-center triplet loss (Zhu et al., "Hetero-Center Loss", Neurocomputing 2020; Liu et al., "Parameter Sharing Exploration and
+ * Hetero-Center Triplet Loss", IEEE TMM 2020; the reference has no such loss): the triplet runs on the per-identity CENTRES of
+ * every modality inside the batch, each non-vis modality against vis.  All fp32.  Inputs as reid_cross_triplet_*: q [P*N, D] (ldq),
+ * g [Mg, D] (ldg), q_label [N] / g_label [Mg] int64, q_valid [P*N] / g_valid [Mg] uint8 or NULL.
+ *   1. Unit rows (normalize == 1): x^ exactly as reid_cross_triplet_fwd and reid_l2norm_rows evaluate it; normalize == 0: the rows as
+ *      they are.
+ *   2. Centres.  On one side (pair p's q rows, or the g rows) the leader of a valid row i is the lowest-index valid row of that side
+ *      with the same label.  The centres of a side are listed in ascending leader order, compacted: centre s belongs to the s-th
+ *      leader; every side has its own centre count S, which exists only on the device.  centre = (fp32 sum of the members' x^ in
+ *      ascending row order) / float(count), one division per element.  The g centres are computed once and shared by all pairs.
+ *      Saved: lead int32 [P*N + Mg] per ROW (q rows, then g rows) = the centre slot of the row within its side, -1 for an invalid row;
+ *      count int32 [P*N + Mg] per SLOT (pair p's q slots at p*N, the g slots at P*N) = members, 0 behind S; clabel int64 [P*N + Mg] =
+ *      the centre's label per slot (0 behind S).
+ *   3. Mining, per pair p, over the union U_p = [q centres of pair p | g centres] in the index space 0 .. N+Mg-1: q centre s -> s,
+ *      g centre t -> N + t.  Every centre is an anchor.  Its positive is the centre of the OTHER side with the same label (at most one:
+ *      labels are distinct within a side); its negative is the centre of U_p with another label and the smallest fp32 d2, from either
+ *      side, ties to the lowest index.  d2 in the difference form, d = sqrt(max(d2, 1e-12)); clamped, +inf and NaN distances follow the
+ *      rules of reid_triplet_hard_*.  An anchor is active when it has a positive and a negative; otherwise its indices are -1 and its
+ *      distances and loss 0 (so are the slots behind a side's S).  The two distances an active anchor keeps are re-evaluated from the
+ *      fp32 centres with an fp64 sum, rounded once and rooted in fp32, as reid_cross_triplet_fwd does.
+ *      Saved: d [2, P, N+Mg] = d_ap | d_an, idx [2, P, N+Mg] = idx_p | idx_n, both in the index space.
+ *   4. Loss.  l = max(0, d_ap - d_an + margin) for margin >= 0, softplus(d_ap - d_an) for margin < 0 (soft margin).
+ *      L_p = sum over the active anchors of l / max(1, n_q[p] + n_g[p]) (n_q / n_g: active anchors among the q / g centres), summed in
+ *      a fixed order in fp64; result [P, 4] = {L_p, flag_p, n_q, n_g} with flag_p = 1 iff n_q + n_g > 0.
+ *   5. bwd: dq [P*N, D] (lddq) and dg [Mg, D] (lddg) are OVERWRITTEN (invalid rows with zeros), gather form, no atomics.  The
+ *      centre-space gradient of a centre: its own two terms as an anchor, then the anchors of U_p that chose it in ascending index;
+ *      for a g centre this runs over p ascending.  A term is gscale[p] * l' / max(1, n_q + n_g) * (c_i - c_a) / d (nothing where the
+ *      saved d is the clamp value).  A valid row receives G_centre(lead) / float(count), then the projection through the normalisation
+ *      exactly as reid_cross_triplet_bwd, the |x| < eps branch included.  Two runs give the same bits in every output.
+ *   ws: reid_hc_triplet_ws_floats(P, N, Mg, D) floats, kept from fwd to bwd (bwd writes the centre gradients into it):
+ *     unit rows R D | centres P U D (compact per pair: S_q[p] q centres, then S_g g centres) | centre gradients R D | centre labels
+ *     P U int64 | compact distances 2 P U | compact indices 2 P U | anchor losses P U | 1 / max(|x|, eps) R | |x| R | leader rows R |
+ *     centre counts P + 1, with R = P N + Mg and U = N + Mg (a negative count = bad shape).
+ *   Nothing is allocated, synchronised or read back inside a call.
+ * Requirements and argument checks: those of reid_cross_triplet_* (REID_ERR_ARG before any launch).
+ * ------------------------------------------------------------------------------------------ */
+int64_t reid_hc_triplet_ws_floats(int32_t P, int32_t N, int32_t Mg, int32_t D);
+int reid_hc_triplet_fwd(const float* q, int32_t ldq, const float* g, int32_t ldg, const int64_t* q_label,
+                        const int64_t* g_label, const uint8_t* q_valid, const uint8_t* g_valid, int32_t P, int32_t N,
+                        int32_t Mg, int32_t D, float margin, int32_t normalize, float eps, int32_t* lead, int32_t* count,
+                        int64_t* clabel, float* d, int32_t* idx, float* ws, float* result, void* stream);
+int reid_hc_triplet_bwd(const float* q, int32_t ldq, const float* g, int32_t ldg, int32_t P, int32_t N, int32_t Mg, int32_t D,
+                        float margin, int32_t normalize, float eps, const int32_t* lead, const int32_t* count, float* ws,
+                        const float* result, const float* gscale, float* dq, int32_t lddq, float* dg, int32_t lddg,
+                        void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Retrieval (train.py:499 + :463; tools/eval_mm_protocol.py:50-53,401-423,622-625):
  *   sim = Q . G^T on L2-normalised rows, per-query top-k in (score desc, index asc) order.
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;

@@ -89,6 +89,10 @@ class TrainingConfig:
     cross_triplet_weight: float = 0.0
     cross_triplet_margin: Optional[float] = 0.3      # None: soft margin
     cross_triplet_normalize: bool = True             # distances between unit rows
+    # nor these: hetero-center triplet loss, the per-identity centres of every non-vis modality against those of vis
+    hc_triplet_weight: float = 0.0
+    hc_triplet_margin: Optional[float] = 0.3         # None: soft margin
+    hc_triplet_normalize: bool = True                # centres of unit rows
     sdm_semantic_dim: int = 512
     sdm_num_heads: int = 8
     sdm_dropout: float = 0.1   # not a reference config field: hard-coded in SemanticDisentanglementModule (models/model.py:35,43)

@@ -32,33 +32,14 @@ struct Ws {
     }
 };
 
-constexpr int MAXV = 4;                  // 16-byte chunks per lane: D <= 1024
-
-// rows [0, PN) are q rows, rows [PN, PN + Mg) are g rows
+// rows [0, PN) are q rows, rows [PN, PN + Mg) are g rows; one wave per row (triplet::unit_row)
 __global__ __launch_bounds__(256) void xt_unit_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ g, int ldg, int PN,
                                                       int Mg, int D, float eps, float* __restrict__ unit, float* __restrict__ inv_out,
                                                       float* __restrict__ norm_out) {
-    const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= PN + Mg) return;
-    const float* x = row < PN ? q + (size_t)row * ldq : g + (size_t)(row - PN) * ldg;
-    const int nv = D >> 2;
-    f32x4 v[MAXV];
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + i * 64;
-        v[i] = c < nv ? *(const f32x4*)(x + c * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-        s += v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2] + v[i][3] * v[i][3];
-    }
-    const float norm = sqrtf(wave_sum(s));
-    const float inv = 1.f / fmaxf(norm, eps);
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        const int c = lane + i * 64;
-        if (c < nv) *(f32x4*)(unit + (size_t)row * D + c * 4) = v[i] * inv;
-    }
-    if (lane == 0) { inv_out[row] = inv; norm_out[row] = norm; }
+    unit_row(row < PN ? q + (size_t)row * ldq : g + (size_t)(row - PN) * ldg, D, eps, unit + (size_t)row * D, inv_out + row, norm_out + row,
+             threadIdx.x & 63);
 }
 
 // the two sides as the kernels see them: unit rows in ws (normalize = 1) or the callers' rows
@@ -156,19 +137,6 @@ __global__ __launch_bounds__(256) void xt_finalize_kernel(const float* __restric
         result[4 * p + 1] = any ? 1.f : 0.f;
         result[4 * p + 2] = (float)c[0];
         result[4 * p + 3] = (float)c[1];
-    }
-}
-
-// the two terms of row `me` (its row xi in registers) as anchor `a` of a direction whose chosen rows live in xo (leading dimension ldo, no)
-__device__ __forceinline__ void add_own(f32x4 (&acc)[NV], const f32x4 (&xi)[NV], int a, const float* __restrict__ xo, int ldo, int no,
-                                        const int* __restrict__ idx_p, const int* __restrict__ idx_n, const float* __restrict__ d_ap,
-                                        const float* __restrict__ d_an, float cn, float margin, int lane, int D) {
-    const int jp = idx_p[a], jn = idx_n[a];
-    if (jp >= 0 && jp < no && jn >= 0 && jn < no) {
-        const float dp = d_ap[a], dn = d_an[a];
-        const float c = cn * row_dloss_of(dp - dn, margin);
-        add_term(acc, xi, xo + (size_t)jp * ldo, term_scale(c, dp), lane, D);
-        add_term(acc, xi, xo + (size_t)jn * ldo, -term_scale(c, dn), lane, D);
     }
 }
 

@@ -1,5 +1,6 @@
-// Batch-hard mining shared by the two triplet losses (triplet.hip: one set of rows against itself; cross_triplet.hip: one set against
-// another): the ONE copy of the mining loop, the row-loss forms and the pieces of the gather-form backward.  All fp32.
+// Batch-hard mining shared by the triplet losses (triplet.hip: one set of rows against itself; cross_triplet.hip: one set against
+// another; hc_triplet.hip: a set of per-identity centres against itself): the ONE copy of the mining loop, the unit-row pass, the
+// row-loss forms and the pieces of the gather-form backward.  All fp32.
 //
 //   d2(i,j) = sum_c (x_ic - y_jc)^2   -- the DIFFERENCE form on the vector ALU (the features are mostly a common
 //   mean, the Gram form loses more of d2 than the gap between the hardest and the second-hardest candidate).
@@ -164,6 +165,32 @@ __device__ __forceinline__ void mine_tile(const Rows A, const Rows C, int a0, in
     }
 }
 
+constexpr int MAXV = 4;                  // 16-byte chunks per lane of the unit-row pass: D <= 1024
+
+// One wave: the unit row x * (1 / max(|x|, eps)) of x [D] into unit [D], with 1 / max(|x|, eps) and |x| beside it -- the body of
+// rowops.hip's l2norm_kernel (per-lane partial sums in the same order, wave_sum, sqrtf, one division, one product), so bit-equal rows
+// give bit-equal unit rows.
+__device__ __forceinline__ void unit_row(const float* __restrict__ x, int D, float eps, float* __restrict__ unit, float* __restrict__ inv_out,
+                                         float* __restrict__ norm_out, int lane) {
+    const int nv = D >> 2;
+    f32x4 v[MAXV];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + i * 64;
+        v[i] = c < nv ? *(const f32x4*)(x + c * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        s += v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2] + v[i][3] * v[i][3];
+    }
+    const float norm = sqrtf(wave_sum(s));
+    const float inv = 1.f / fmaxf(norm, eps);
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int c = lane + i * 64;
+        if (c < nv) *(f32x4*)(unit + c * 4) = v[i] * inv;
+    }
+    if (lane == 0) { *inv_out = inv; *norm_out = norm; }
+}
+
 constexpr int NV = 4;                    // 16-byte column chunks per lane of the backward (one wave per row): D <= 256 NV
 
 // acc += s * (x_i - x_a) over this lane's columns
@@ -181,6 +208,20 @@ __device__ __forceinline__ void add_term(f32x4 (&acc)[NV], const f32x4 (&xi)[NV]
 
 // c_a / d of one saved distance; 0 for a clamped distance (d2 <= 1e-12: the saved d is the clamp value itself)
 __device__ __forceinline__ float term_scale(float c, float d) { return d > sqrtf(D2_MIN) ? c / d : 0.f; }
+
+// The two terms of row `me` (its row xi in registers) as anchor `a` of a direction whose chosen rows live in xo (leading dimension
+// ldo, no rows).  Called by a whole wave.
+__device__ __forceinline__ void add_own(f32x4 (&acc)[NV], const f32x4 (&xi)[NV], int a, const float* __restrict__ xo, int ldo, int no,
+                                        const int* __restrict__ idx_p, const int* __restrict__ idx_n, const float* __restrict__ d_ap,
+                                        const float* __restrict__ d_an, float cn, float margin, int lane, int D) {
+    const int jp = idx_p[a], jn = idx_n[a];
+    if (jp >= 0 && jp < no && jn >= 0 && jn < no) {
+        const float dp = d_ap[a], dn = d_an[a];
+        const float c = cn * row_dloss_of(dp - dn, margin);
+        add_term(acc, xi, xo + (size_t)jp * ldo, term_scale(c, dp), lane, D);
+        add_term(acc, xi, xo + (size_t)jn * ldo, -term_scale(c, dn), lane, D);
+    }
+}
 
 // The terms of the gather form that come from OTHER rows' choices: every anchor a of [0, n) in ascending order whose idx_p[a] or
 // idx_n[a] is `me` adds cn * l'(a) * (+-1 / d) * (x_me - x_a), x_a = row a of xa (leading dimension lda).  Called by a whole wave.

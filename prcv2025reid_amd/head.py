@@ -243,6 +243,84 @@ def cross_modal_triplet(q, g, q_labels, g_labels, q_valid=None, g_valid=None, ma
     return loss, flag, rows
 
 
+class HcTripletFn(torch.autograd.Function):
+    """(loss [P], flag [P], n_active [P, 2]) of the hetero-center triplet loss between P stacked modality feature sets q [P, N, D] and
+    the vis features g [Mg, D] (csrc/hc_triplet.hip; the reference has no such loss): unit rows, per-identity centres of every side,
+    the triplet on the centres of [pair p's q centres | g centres].  ``margin`` None: the soft-margin form.  n_active = active anchors
+    among the (q, g) centres as floats; nothing is read back to the host.  ``rows_out``: an optional trailing dict that receives COPIES
+    of the saved arrays (hetero_center_triplet); the call the model makes is
+    ``apply(q, g, q_label, g_label, q_valid, g_valid, margin, normalize)``."""
+    EPS = 1e-12                                               # F.normalize's default
+
+    @staticmethod
+    def forward(ctx, q, g, q_label, g_label, q_valid, g_valid, margin, normalize: bool, rows_out=None):
+        m = -1.0 if margin is None else float(margin)
+        if m < 0 and margin is not None:
+            raise ValueError('HcTripletFn: margin must be >= 0, or None for the soft-margin form')
+        P, N, D = q.shape
+        q2 = q.reshape(P * N, D).contiguous().float(); g = g.contiguous().float()
+        Mg, dev = g.shape[0], q.device
+        R, U = P * N + Mg, N + Mg
+        ws = torch.empty(ops.hc_triplet_ws_floats(P, N, Mg, D), device=dev)
+        ints = torch.empty(2, R, dtype=torch.int32, device=dev)                                  # lead | count
+        clabel = torch.empty(R, dtype=torch.int64, device=dev)
+        d = torch.empty(2, P, U, device=dev); idx = torch.empty(2, P, U, dtype=torch.int32, device=dev)
+        res = torch.empty(P, 4, device=dev)
+        qv = None if q_valid is None else q_valid.reshape(P * N).contiguous()
+        ops.hc_triplet_fwd(q2, g, q_label.contiguous(), g_label.contiguous(), qv, g_valid, m, normalize, HcTripletFn.EPS,
+                           ints[0], ints[1], clabel, d, idx, ws, res, P=P)
+        ctx.save_for_backward(q2, g, ints, ws, res)
+        ctx.margin, ctx.normalize, ctx.P = m, bool(normalize), P
+        loss, flag, n_active = res[:, 0].contiguous(), res[:, 1].contiguous(), res[:, 2:].contiguous()
+        ctx.mark_non_differentiable(flag, n_active)
+        if rows_out is not None:                              # copies: the saved arrays belong to the backward
+            for side, rows, slots in (('q', slice(0, P * N), slice(0, N)), ('g', slice(P * N, R), slice(N, U))):
+                shape = (P, N) if side == 'q' else (Mg,)
+                rows_out.update({f'{side}_lead': ints[0, rows].reshape(shape).clone(), f'{side}_count': ints[1, rows].reshape(shape).clone(),
+                                 f'{side}_label': clabel[rows].reshape(shape).clone(),
+                                 f'{side}_d_ap': d[0, :, slots].clone(), f'{side}_d_an': d[1, :, slots].clone(),
+                                 f'{side}_idx_p': idx[0, :, slots].clone(), f'{side}_idx_n': idx[1, :, slots].clone()})
+        return loss, flag, n_active
+
+    @staticmethod
+    def backward(ctx, dloss, _dflag, _dn):
+        q2, g, ints, ws, res = ctx.saved_tensors
+        P = ctx.P
+        dq = torch.empty_like(q2); dg = torch.empty_like(g)
+        gs = torch.empty(P, device=q2.device)                 # (a copy: the cotangent of L.sum() is an expanded scalar with stride 0)
+        gs.copy_(dloss.reshape(P))
+        ops.hc_triplet_bwd(q2, g, ctx.margin, ctx.normalize, HcTripletFn.EPS, ints[0], ints[1], ws, res, gs, dq, dg, P=P)
+        return dq.view(P, q2.shape[0] // P, q2.shape[1]), dg, None, None, None, None, None, None, None
+
+
+def hetero_center_triplet(q, g, q_labels, g_labels, q_valid=None, g_valid=None, margin=0.3, normalize=True):
+    """Hetero-center triplet loss (Zhu et al. 2020; Liu et al. 2020) for users with their own loop: ``q`` [P, N, D] (P query modalities
+    stacked; [N, D] = one) against the vis features ``g`` [Mg, D].  On every side the valid rows of one label are averaged into a centre
+    (of the unit rows; ``normalize`` False: of the rows as they are); per pair, every centre of [q centres | g centres] is an anchor, its
+    positive the centre of the other side with its label, its negative the nearest centre of another label from either side
+    (difference form, fp32, ties to the lowest index); L_p = mean over the active anchors.  ``q_valid`` [P, N] / ``g_valid`` [Mg]:
+    optional bool / uint8, rows that take part; ``margin`` None: soft margin.  Returns (losses [P], flags [P], rows): flag 1 where the
+    pair has an active anchor; rows = {'q_lead' [P, N], 'g_lead' [Mg]} (the centre slot of a row, -1: invalid), {'q_count', 'q_label'
+    [P, N], 'g_count', 'g_label' [Mg]} per centre slot (count 0 behind the side's centres), {'q_d_ap', 'q_d_an', 'q_idx_p', 'q_idx_n'}
+    [P, N] and {'g_d_ap', 'g_d_an', 'g_idx_p', 'g_idx_n'} [P, Mg] per centre slot, indices in 0..N+Mg-1 (q centre s = s, g centre t =
+    N + t), plus 'n_active' [P, 2]; the losses carry the gradient to ``q`` and ``g``."""
+    tensors = (q, g, q_labels, g_labels) + tuple(t for t in (q_valid, g_valid) if t is not None)
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.ReidHipError('hetero_center_triplet needs device tensors (there is no CPU path)')
+    if q.dim() == 2:
+        q = q.unsqueeze(0)
+    if q.dim() != 3 or g.dim() != 2 or g.shape[1] != q.shape[2] or q_labels.shape != q.shape[1:2] or g_labels.shape != g.shape[:1]:
+        raise ValueError('hetero_center_triplet: q [P, N, D] or [N, D], g [Mg, D], q_labels [N], g_labels [Mg]')
+    if q_valid is not None:
+        q_valid = q_valid.to(torch.uint8).reshape(q.shape[0], q.shape[1]).contiguous()
+    if g_valid is not None:
+        g_valid = g_valid.to(torch.uint8).contiguous()
+    rows = {}
+    loss, flag, n_active = HcTripletFn.apply(q, g, q_labels.long(), g_labels.long(), q_valid, g_valid, margin, bool(normalize), rows)
+    rows['n_active'] = n_active
+    return loss, flag, rows
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # Small fp32 pieces of SemanticDisentanglementModule (models/model.py:57-77) and FeatureFusion (:113-183)
 class AddFn(torch.autograd.Function):

@@ -37,7 +37,7 @@ from . import _lib, ops
 from .config import arch_of
 from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CrossEntropyLSFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn,
-                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn)
+                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn, HcTripletFn)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -96,6 +96,9 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.cross_triplet_weight = getattr(config, 'cross_triplet_weight', 0.0)      # cross-modal batch-hard triplet loss (not in the reference)
         self.cross_triplet_margin = getattr(config, 'cross_triplet_margin', 0.3)
         self.cross_triplet_normalize = getattr(config, 'cross_triplet_normalize', True)
+        self.hc_triplet_weight = getattr(config, 'hc_triplet_weight', 0.0)                # hetero-center triplet loss (not in the reference)
+        self.hc_triplet_margin = getattr(config, 'hc_triplet_margin', 0.3)
+        self.hc_triplet_normalize = getattr(config, 'hc_triplet_normalize', True)
         self.num_classes = None
         self.bn_neck = None
         self._ref: "OrderedDict[str, nn.Parameter]" = OrderedDict()
@@ -591,8 +594,9 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         use_sdm = (self.current_epoch >= self.config.sdm_weight_warmup_epochs) and (self.contrastive_weight > 0)
         raw = outputs.get('raw_modality_features', {})
         use_xt = self.cross_triplet_weight > 0
+        use_hc = self.hc_triplet_weight > 0
         q = None
-        if (use_sdm or use_xt) and 'vis' in raw and 'vis' in fm:
+        if (use_sdm or use_xt or use_hc) and 'vis' in raw and 'vis' in fm:
             gv = cent['gv']
             mods = [m for m in raw if m != 'vis' and m in fm]
             if mods:
@@ -622,6 +626,14 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             out['total_loss'] = out['total_loss'] + self.cross_triplet_weight * xt
             out['cross_triplet_loss'] = xt
             out['cross_triplet_active_cnt'] = LazyCount(n_act.sum())
+        if use_hc and q is not None:
+            # hetero-center triplet loss (csrc/hc_triplet.hip) on the same stack, not tied to the SDM warm-up epoch either; under
+            # DataParallel the centres are those of the global batch on every rank
+            L, flag, n_act = HcTripletFn.apply(q, raw['vis'], labels, labels, qv, gv, self.hc_triplet_margin, bool(self.hc_triplet_normalize))
+            hc = L.sum() / flag.sum().clamp_min(1.0)                                             # mean over the pairs with an active anchor
+            out['total_loss'] = out['total_loss'] + self.hc_triplet_weight * hc
+            out['hc_triplet_loss'] = hc
+            out['hc_triplet_active_cnt'] = LazyCount(n_act.sum())
         return out
 
     # ------------------------------------------------------------------ optimiser groups

@@ -392,6 +392,63 @@ def cross_triplet_bwd(q, g, q_valid, g_valid, margin, normalize, eps, q_d, q_idx
                                        ptr(dq), dq.stride(0), ptr(dg), dg.stride(0), stream_ptr()))
 
 
+def hc_triplet_ws_floats(P, N, Mg, D):
+    n = int(lib().reid_hc_triplet_ws_floats(P, N, Mg, D))
+    if n < 0:
+        check(n)
+    return n
+
+
+def _hc_triplet_shapes(who, q, g, lead, count, ws, result, P):
+    for n, t, d in (('q', q, torch.float32), ('g', g, torch.float32), ('lead', lead, torch.int32), ('count', count, torch.int32),
+                    ('ws', ws, torch.float32), ('result', result, torch.float32)):
+        L._req(t, d, n)
+    if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] % P or g.shape[1] != q.shape[1]:
+        raise ValueError(f'{who}: q [P*N, D], g [Mg, D]')
+    N, Mg = q.shape[0] // P, g.shape[0]
+    if min(lead.numel(), count.numel()) < P * N + Mg or result.numel() < 4 * P \
+            or not (lead.is_contiguous() and count.is_contiguous() and ws.is_contiguous() and result.is_contiguous()):
+        raise ValueError(f'{who}: lead / count [P*N + Mg], result [P, 4], all contiguous')
+    if ws.numel() < hc_triplet_ws_floats(P, N, Mg, q.shape[1]):
+        raise ValueError(f'{who}: ws holds fewer than hc_triplet_ws_floats(P, N, Mg, D) floats')
+    return N, Mg
+
+
+def hc_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, eps, lead, count, clabel, d, idx, ws, result, P=1):
+    """Hetero-center triplet loss: q [P*N, D] (P query sides stacked) against g [Mg, D], the triplet on the per-identity centres of
+    every side; margin < 0 selects the soft-margin form.  lead i32 [P*N + Mg] per row, count i32 / clabel i64 [P*N + Mg] per centre
+    slot; d f32 / idx i32 [2, P, N + Mg] = (d_ap | d_an), (idx_p | idx_n) in the index space (q centre s -> s, g centre t -> N + t);
+    result f32 [P, 4] = (L_p, flag_p, n_q, n_g); ws is kept for hc_triplet_bwd."""
+    N, Mg = _hc_triplet_shapes('hc_triplet_fwd', q, g, lead, count, ws, result, P)
+    for n, t, dt in (('q_label', q_label, torch.int64), ('g_label', g_label, torch.int64), ('clabel', clabel, torch.int64),
+                     ('d', d, torch.float32), ('idx', idx, torch.int32)):
+        L._req(t, dt, n)
+    if q_label.numel() != N or g_label.numel() != Mg:
+        raise ValueError('hc_triplet_fwd: q_label [N], g_label [Mg]')
+    for n, t, rows in (('q_valid', q_valid, P * N), ('g_valid', g_valid, Mg)):
+        if t is not None:
+            L._req(t, torch.uint8, n)
+            if t.numel() != rows:
+                raise ValueError(f'hc_triplet_fwd: {n} has {t.numel()} elements, not {rows}')
+    if clabel.numel() < P * N + Mg or min(d.numel(), idx.numel()) < 2 * P * (N + Mg) \
+            or not (clabel.is_contiguous() and d.is_contiguous() and idx.is_contiguous()):
+        raise ValueError('hc_triplet_fwd: clabel [P*N + Mg], d / idx [2, P, N + Mg], all contiguous')
+    check(lib().reid_hc_triplet_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_label), ptr(g_label), ptr(q_valid), ptr(g_valid),
+                                    P, N, Mg, q.shape[1], margin, int(normalize), eps, ptr(lead), ptr(count), ptr(clabel), ptr(d), ptr(idx),
+                                    ptr(ws), ptr(result), stream_ptr()))
+
+
+def hc_triplet_bwd(q, g, margin, normalize, eps, lead, count, ws, result, gscale, dq, dg, P=1):
+    """dq [P*N, D], dg [Mg, D] (both overwritten, two launches) from what hc_triplet_fwd saved; gscale f32 [P] on the device."""
+    N, Mg = _hc_triplet_shapes('hc_triplet_bwd', q, g, lead, count, ws, result, P)
+    L._req(gscale, torch.float32, 'gscale'); L._req(dq, torch.float32, 'dq'); L._req(dg, torch.float32, 'dg')
+    if dq.shape != q.shape or dg.shape != g.shape or gscale.numel() < P:
+        raise ValueError('hc_triplet_bwd: dq as q, dg as g, gscale [P]')
+    check(lib().reid_hc_triplet_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), P, N, Mg, q.shape[1], margin, int(normalize), eps,
+                                    ptr(lead), ptr(count), ptr(ws), ptr(result), ptr(gscale), ptr(dq), dq.stride(0), ptr(dg), dg.stride(0),
+                                    stream_ptr()))
+
+
 # ----------------------------------------------------------------------------------------- retrieval
 def topk_ws_bytes(Nq, Ng, k):
     return int(lib().reid_topk_ws_bytes(Nq, Ng, k))

@@ -1,0 +1,143 @@
+"""Hetero-center triplet loss (csrc/hc_triplet.hip): what it costs.
+
+    python tools/bench_hc_triplet.py kernels [reps] [rounds]
+                                               forward and backward alone at (P, N = Mg, D) = (4, 64, 512), (4, 256, 512) and
+                                               (4, 1024, 512) with K = 4 rows per identity, against the same loss written with torch
+                                               ops (normalise, one-hot centre means, cdist, masked min, autograd) and against the
+                                               cross-modal batch-hard loss of section 14 on the same rows, on the same GPU in the
+                                               same process
+    python tools/bench_hc_triplet.py step      the config-2 training step (P = 16, K = 4, rank 8: bench.py's headline, eager
+                                               StepDriver) with hc_triplet_weight 0 against 0.3, alternating blocks on one device
+
+Times are HIP events around windows that end in a synchronise; every line printed is one JSON record."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+import torch
+
+MARGIN = 0.3
+K = 4
+SHAPES = [(4, 64, 512), (4, 256, 512), (4, 1024, 512)]
+
+
+def torch_hc_triplet(q, g, ql, gl, margin=MARGIN):
+    """The hand-written version for data in which every row is valid and every identity is on both sides: L [P]."""
+    qh = torch.nn.functional.normalize(q, dim=-1); gh = torch.nn.functional.normalize(g, dim=-1)
+    uq, iq = torch.unique(ql, return_inverse=True)
+    ug, ig = torch.unique(gl, return_inverse=True)
+    oq = torch.nn.functional.one_hot(iq, uq.numel()).to(q.dtype); og = torch.nn.functional.one_hot(ig, ug.numel()).to(q.dtype)
+    cq = torch.matmul(oq.t(), qh) / oq.sum(0)[:, None]                              # [P, Sq, D]
+    cg = (og.t() @ gh) / og.sum(0)[:, None]
+    c = torch.cat([cq, cg[None].expand(q.shape[0], -1, -1)], dim=1)                 # [P, S, D]
+    lab = torch.cat([uq, ug])
+    side = torch.cat([torch.zeros_like(uq), torch.ones_like(ug)])
+    d = torch.cdist(c, c)
+    same = (lab[:, None] == lab[None, :])[None]
+    pos = same & (side[:, None] != side[None, :])[None]
+    d_ap = d.masked_fill(~pos, 0.0).sum(2)                                          # one positive per centre
+    d_an = d.masked_fill(same, float('inf')).min(2).values
+    return (d_ap - d_an + margin).clamp(min=0).mean(1)
+
+
+def window(fn, reps):
+    e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / reps * 1e3
+
+
+def make_calls(P, N, D, ratio=30.0):
+    import hc_triplet_ref as R
+    from prcv2025reid_amd.head import HcTripletFn, CrossTripletFn
+    q, g, ql, gl = R.make_case(P, N, N, D, ratio, seed=N, K=K, device='cuda')
+    one = torch.ones((), device='cuda')
+    leaves = {k: (q.clone().requires_grad_(True), g.clone().requires_grad_(True)) for k in ('hip', 'torch', 'xt')}
+    state = {}
+
+    def fwd(k, fn):
+        def run():
+            state[k] = fn(*leaves[k]).sum()
+        return run
+
+    def bwd(k):
+        def run():
+            leaves[k][0].grad = leaves[k][1].grad = None
+            state[k].backward(one, retain_graph=True)
+        return run
+
+    calls = dict(hip_fwd=fwd('hip', lambda a, b: HcTripletFn.apply(a, b, ql, gl, None, None, MARGIN, True)[0]), hip_bwd=bwd('hip'),
+                 torch_fwd=fwd('torch', lambda a, b: torch_hc_triplet(a, b, ql, gl)), torch_bwd=bwd('torch'),
+                 xt_fwd=fwd('xt', lambda a, b: CrossTripletFn.apply(a, b, ql, gl, None, None, MARGIN, True)[0]), xt_bwd=bwd('xt'))
+    return calls, state
+
+
+def kernels(reps=500, rounds=7):
+    for P, N, D in SHAPES:
+        calls, state = make_calls(P, N, D)
+        for fn in calls.values():
+            for _ in range(5):
+                fn()
+        torch.cuda.synchronize()
+        rec = dict(mode='kernels', P=P, N=N, Mg=N, D=D, K=K, margin=MARGIN, reps=reps, rounds=rounds)
+        samples = {k: [] for k in calls}
+        for _ in range(rounds):                              # alternating windows: drift hits every variant alike
+            for k, fn in calls.items():
+                samples[k].append(window(fn, reps))
+        for k, v in samples.items():
+            v.sort()
+            rec[k + '_us_median'] = round(v[len(v) // 2], 2); rec[k + '_us_min'] = round(v[0], 2)
+        rec['loss_sum_hip'] = float(state['hip'].detach()); rec['loss_sum_torch'] = float(state['torch'].detach())
+        print(json.dumps(rec), flush=True)
+
+
+def step(steps=10, rounds=6, warmup=3):
+    import argparse
+    import bench
+    from prcv2025reid_amd.parallel import DataParallel
+    from prcv2025reid_amd.synthetic import synthetic_batch
+    P, C = 16, 400
+    args = argparse.Namespace(optimizer='fused', accum=1, graph='off')
+    steppers = {}
+    for w in (0.0, 0.3):
+        torch.manual_seed(0)
+        model = bench.build_model(0, 8, 'bf16', C)
+        model.hc_triplet_weight = w
+        batch = synthetic_batch(P, K, model.arch, seed=1000, num_classes=C)
+        images = {m: t.cuda() for m, t in batch['images'].items()}
+        tok = model.tokenizer(batch['texts'], return_tensors='pt', padding=True, truncation=True, max_length=77)
+        tokens = {k: v.cuda() for k, v in tok.items()}
+        st, _, _ = bench.make_stepper(model, DataParallel(model), args, images, tokens, batch['modality_mask'], batch['person_id'].cuda(), 1)
+        steppers[w] = st
+        for _ in range(warmup):
+            L = st()
+        torch.cuda.synchronize()
+        print(json.dumps(dict(mode='step-warmup', hc_triplet_weight=w, keys=sorted(L), total_loss=float(L['total_loss'].detach()),
+                              hc_triplet_loss=float(L['hc_triplet_loss'].detach()) if 'hc_triplet_loss' in L else None,
+                              active=int(L['hc_triplet_active_cnt']) if 'hc_triplet_active_cnt' in L else None)), flush=True)
+    samples = {w: [] for w in steppers}
+    for _ in range(rounds):
+        for w, st in steppers.items():
+            samples[w].append(window(st, steps) / 1e3)
+    rec = dict(mode='step', P=P, K=K, rank=8, steps_per_window=steps, rounds=rounds)
+    for w, v in samples.items():
+        rec[f'ms_per_step_w{w}'] = [round(t, 3) for t in v]
+        s = sorted(v)
+        rec[f'median_ms_w{w}'] = round(s[len(s) // 2], 3)
+    rec['added_ms_median'] = round(rec['median_ms_w0.3'] - rec['median_ms_w0.0'], 3)
+    print(json.dumps(rec), flush=True)
+
+
+if __name__ == '__main__':
+    if not torch.cuda.is_available():
+        raise SystemExit('bench_hc_triplet.py needs the GPU: nothing is measured without one')
+    mode = sys.argv[1] if len(sys.argv) > 1 else 'kernels'
+    if mode == 'kernels':
+        kernels(*[int(v) for v in sys.argv[2:4]])
+    else:
+        step()
