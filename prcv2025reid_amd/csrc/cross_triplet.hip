@@ -2,14 +2,17 @@
 // shared vis side g [Mg, D], mined in both directions (Ye et al., AGW 2021; mining of Hermans et al. 2017).  The reference has no
 // such loss; include/reid_hip.h (reid_cross_triplet_*) and DESIGN.md section 14 are the definition.
 //
+// The kernels here decode indices and call the pieces of triplet_mine.h (shared with triplet.hip and hc_triplet.hip; the list of
+// pieces and callers is at its head); the entry points use its argument checks.
+//
 // Forward, launch 1 (xt_unit_kernel, normalize = 1 only): the unit rows x * (1 / max(|x|, eps)) of BOTH sides, once and not once per
-//   pair, into ws, with 1 / max(|x|, eps) and |x| beside them; one wave per row, the body of rowops.hip's l2norm_kernel (per-lane
-//   partial sums in the same order, wave_sum, sqrtf, one division, one product), so bit-equal rows give bit-equal unit rows.
+//   pair, into ws, with 1 / max(|x|, eps) and |x| beside them; one wave per row (triplet::unit_row).
 // Forward, launch 2 (xt_fwd_kernel): blockIdx = (pair, direction, tile of 4 anchors).  Direction q->g: anchors are q rows of pair p,
 //   candidates the g rows; g->q: the other way round, indices pair-local.  Both are ONE call of triplet::mine_tile (triplet_mine.h, the
 //   loop of csrc/triplet.hip) with the two sides swapped; nothing is excluded as "self" (row i of q and row i of g are one person in
 //   two modalities: a legitimate positive).
-// Forward, launch 3 (xt_refine_kernel): one wave per anchor re-evaluates the two distances it keeps with an fp64 sum (see there).
+// Forward, launch 3 (xt_refine_kernel): one wave per anchor re-evaluates the two distances it keeps with an fp64 sum
+//   (triplet::refine_anchor).
 // Forward, launch 4 (xt_finalize_kernel): one workgroup per pair adds the row losses of either direction in a fixed order in fp64
 //   -> result [P, 4] = {L_p, flag_p, n_qg, n_gq}.
 // Backward (xt_bwd_kernel): gather form, one wave per output row of dq and dg.  The unit-space gradient G of q row (p, i): its own two
@@ -32,7 +35,8 @@ struct Ws {
     }
 };
 
-// rows [0, PN) are q rows, rows [PN, PN + Mg) are g rows; one wave per row (triplet::unit_row)
+// rows [0, PN) are q rows, rows [PN, PN + Mg) are g rows; one wave per row (triplet::unit_row).  (The same body as hc_triplet.hip's
+// hc_unit_kernel.)
 __global__ __launch_bounds__(256) void xt_unit_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ g, int ldg, int PN,
                                                       int Mg, int D, float eps, float* __restrict__ unit, float* __restrict__ inv_out,
                                                       float* __restrict__ norm_out) {
@@ -41,12 +45,6 @@ __global__ __launch_bounds__(256) void xt_unit_kernel(const float* __restrict__ 
     unit_row(row < PN ? q + (size_t)row * ldq : g + (size_t)(row - PN) * ldg, D, eps, unit + (size_t)row * D, inv_out + row, norm_out + row,
              threadIdx.x & 63);
 }
-
-// the two sides as the kernels see them: unit rows in ws (normalize = 1) or the callers' rows
-struct Sides {
-    const float* q; int ldq;
-    const float* g; int ldg;
-};
 
 __global__ __launch_bounds__(256) void xt_fwd_kernel(Sides s, const int64_t* __restrict__ q_label, const int64_t* __restrict__ g_label,
                                                      const uint8_t* __restrict__ q_valid, const uint8_t* __restrict__ g_valid, int P, int N,
@@ -66,9 +64,7 @@ __global__ __launch_bounds__(256) void xt_fwd_kernel(Sides s, const int64_t* __r
 }
 
 // One wave per anchor of either direction: the two distances the anchor keeps, re-evaluated from the same rows with an fp64 sum and
-// rounded once, and its row loss from them.  Mining compares the fp32 d2 (a D-term sum: a few u on d); but l'(d_ap - d_an) of the
-// backward inherits the ABSOLUTE error of the saved distances, and with unnormalised rows at d = 40 those few u are already 1e-5 of
-// the soft margin's gradient.  (3 rows per anchor: next to nothing beside the mining.)
+// rounded once (triplet::refine_anchor: why), and its row loss from them.
 __global__ __launch_bounds__(256) void xt_refine_kernel(Sides s, int P, int N, int Mg, int D, float margin, float* __restrict__ q_d,
                                                         const int* __restrict__ q_idx, float* __restrict__ g_d,
                                                         const int* __restrict__ g_idx, float* __restrict__ loss_q,
@@ -86,29 +82,16 @@ __global__ __launch_bounds__(256) void xt_refine_kernel(Sides s, int P, int N, i
     const int* ix = qg ? q_idx : g_idx;
     const int jp = ix[r], jn = ix[P * n + r];
     if (jp < 0 || jp >= nc || jn < 0 || jn >= nc) return;                            // not active: the zeros stay
-    double sp = 0.0, sn = 0.0;
-#pragma unroll
-    for (int v = 0; v < MAXV; ++v) {
-        const int c = 4 * lane + 256 * v;
-        if (c < D) {
-            const f32x4 x = *(const f32x4*)(xa + c), yp = *(const f32x4*)(xc + (size_t)jp * ldc + c), yn = *(const f32x4*)(xc + (size_t)jn * ldc + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const double up = (double)x[e] - (double)yp[e], un = (double)x[e] - (double)yn[e];
-                sp = fma(up, up, sp); sn = fma(un, un, sn);
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); sn += __shfl_xor(sn, o, 64); }
+    float dp, dn;                                                                    // (lane 0's)
+    refine_anchor(xa, xc, ldc, jp, jn, D, lane, dp, dn);
     if (lane == 0) {
-        const float dp = sqrtf(fmaxf((float)sp, D2_MIN)), dn = sqrtf(fmaxf((float)sn, D2_MIN));
         d[r] = dp; d[P * n + r] = dn;
         (qg ? loss_q : loss_g)[r] = row_loss_of(dp - dn, margin);
     }
 }
 
-// one workgroup per pair: thread t adds rows t, t + 256, ... of a direction in fp64, the 256 sums are added in index order
+// one workgroup per pair: thread t adds rows t, t + 256, ... of a direction in fp64, the 256 sums are added in index order (the tail
+// of triplet_finalize_kernel and hc_finalize_kernel, with two sums and two counts)
 __global__ __launch_bounds__(256) void xt_finalize_kernel(const float* __restrict__ loss_q, const float* __restrict__ loss_g,
                                                           const int* __restrict__ q_idx, const int* __restrict__ g_idx, int N, int Mg,
                                                           float* __restrict__ result) {
@@ -158,12 +141,8 @@ __global__ __launch_bounds__(256) void xt_bwd_kernel(Sides s, const uint8_t* __r
     float* o = is_q ? dq + (size_t)row * lddq : dg + (size_t)me * lddg;
     const bool valid = is_q ? (!q_valid || q_valid[row]) : (!g_valid || g_valid[me]);
     f32x4 xi[NV], acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int c = 4 * lane + 256 * v;
-        xi[v] = c < D && valid ? *(const f32x4*)(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    load_row(xi, xr, lane, D, valid);
+    zero_acc(acc);
     if (valid) {                                                     // (an invalid row is no anchor and nobody's choice: zeros)
         for (int p = is_q ? row / N : 0; p < (is_q ? row / N + 1 : P); ++p) {
             // c = gscale[p] * 0.5 * l' / max(1, n) with n the active anchors of the ANCHOR's direction
@@ -179,8 +158,8 @@ __global__ __launch_bounds__(256) void xt_bwd_kernel(Sides s, const uint8_t* __r
         }
         if (normalize) {
             const int r = is_q ? row : PN + me;
-            if (norm[r] >= eps) {                                    // dx = (G - x^ (x^ . G)) / max(|x|, eps)
-                float dot = 0.f;
+            if (norm[r] >= eps) {                                    // dx = (G - x^ (x^ . G)) / max(|x|, eps); the same block as in
+                float dot = 0.f;                                     // hc_triplet.hip's hc_bwd_rows_kernel
 #pragma unroll
                 for (int v = 0; v < NV; ++v) dot += xi[v][0] * acc[v][0] + xi[v][1] * acc[v][1] + xi[v][2] * acc[v][2] + xi[v][3] * acc[v][3];
                 dot = wave_sum(dot);
@@ -193,36 +172,13 @@ __global__ __launch_bounds__(256) void xt_bwd_kernel(Sides s, const uint8_t* __r
             }
         }
     }
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int c = 4 * lane + 256 * v;
-        if (c < D) *(f32x4*)(o + c) = acc[v];
-    }
-}
-
-int xt_check_dims(const char* who, int32_t P, int32_t N, int32_t Mg, int32_t D) {
-    REID_CHECK_ARG(P >= 1 && P <= 8, "%s: P=%d (1..8)", who, P);
-    REID_CHECK_ARG(N >= 1 && N <= 8192, "%s: N=%d (1..8192)", who, N);
-    REID_CHECK_ARG(Mg >= 1 && Mg <= 8192, "%s: Mg=%d (1..8192)", who, Mg);
-    REID_CHECK_ARG(D % 4 == 0 && D >= 4 && D <= 1024, "%s: D=%d (a multiple of 4, 4..1024)", who, D);
-    return REID_OK;
-}
-int xt_check_ld(const char* who, int64_t rows, int32_t D, int32_t ld, const char* ld_name) {
-    REID_CHECK_ARG(ld >= D && ld % 4 == 0, "%s: %s=%d (a multiple of 4, >= D=%d)", who, ld_name, ld, D);
-    REID_CHECK_ARG(rows * ld < (1ll << 31), "%s: rows * %s beyond 2^31 elements", who, ld_name);
-    return REID_OK;
-}
-int xt_check_scalars(const char* who, float margin, int32_t normalize, float eps) {
-    REID_CHECK_ARG(margin == margin, "%s: margin is NaN", who);
-    REID_CHECK_ARG(normalize == 0 || normalize == 1, "%s: normalize=%d (0 or 1)", who, normalize);
-    REID_CHECK_ARG(eps >= 0.f, "%s: eps=%g (>= 0)", who, (double)eps);
-    return REID_OK;
+    store_row(o, acc, lane, D);
 }
 
 }  // namespace
 
 extern "C" int64_t reid_cross_triplet_ws_floats(int32_t P, int32_t N, int32_t Mg, int32_t D) {
-    if (int rc = xt_check_dims("reid_cross_triplet_ws_floats", P, N, Mg, D)) return rc;
+    if (int rc = check_dims("reid_cross_triplet_ws_floats", P, N, Mg, D)) return rc;
     return Ws(P, N, Mg, D).total;
 }
 
@@ -232,10 +188,10 @@ extern "C" int reid_cross_triplet_fwd(const float* q, int32_t ldq, const float* 
                                       float* g_d, int32_t* g_idx, float* ws, float* result, void* stream) {
     const char* who = "reid_cross_triplet_fwd";
     REID_CHECK_ARG(q && g && q_label && g_label && q_d && q_idx && g_d && g_idx && ws && result, "%s: null pointer", who);
-    if (int rc = xt_check_dims(who, P, N, Mg, D)) return rc;
-    if (int rc = xt_check_ld(who, (int64_t)P * N, D, ldq, "ldq")) return rc;
-    if (int rc = xt_check_ld(who, Mg, D, ldg, "ldg")) return rc;
-    if (int rc = xt_check_scalars(who, margin, normalize, eps)) return rc;
+    if (int rc = check_dims(who, P, N, Mg, D)) return rc;
+    if (int rc = check_ld(who, (int64_t)P * N, D, ldq, "ldq")) return rc;
+    if (int rc = check_ld(who, Mg, D, ldg, "ldg")) return rc;
+    if (int rc = check_scalars(who, margin, normalize, eps)) return rc;
     REID_CHECK_ARG(aligned16(q) && aligned16(g) && aligned16(ws), "%s: q, g or ws is not 16-byte aligned", who);
     const Ws w(P, N, Mg, D);
     hipStream_t s = (hipStream_t)stream;
@@ -266,12 +222,12 @@ extern "C" int reid_cross_triplet_bwd(const float* q, int32_t ldq, const float* 
                                       int32_t lddq, float* dg, int32_t lddg, void* stream) {
     const char* who = "reid_cross_triplet_bwd";
     REID_CHECK_ARG(q && g && q_d && q_idx && g_d && g_idx && ws && result && gscale && dq && dg, "%s: null pointer", who);
-    if (int rc = xt_check_dims(who, P, N, Mg, D)) return rc;
-    if (int rc = xt_check_ld(who, (int64_t)P * N, D, ldq, "ldq")) return rc;
-    if (int rc = xt_check_ld(who, Mg, D, ldg, "ldg")) return rc;
-    if (int rc = xt_check_ld(who, (int64_t)P * N, D, lddq, "lddq")) return rc;
-    if (int rc = xt_check_ld(who, Mg, D, lddg, "lddg")) return rc;
-    if (int rc = xt_check_scalars(who, margin, normalize, eps)) return rc;
+    if (int rc = check_dims(who, P, N, Mg, D)) return rc;
+    if (int rc = check_ld(who, (int64_t)P * N, D, ldq, "ldq")) return rc;
+    if (int rc = check_ld(who, Mg, D, ldg, "ldg")) return rc;
+    if (int rc = check_ld(who, (int64_t)P * N, D, lddq, "lddq")) return rc;
+    if (int rc = check_ld(who, Mg, D, lddg, "lddg")) return rc;
+    if (int rc = check_scalars(who, margin, normalize, eps)) return rc;
     REID_CHECK_ARG(aligned16(q) && aligned16(g) && aligned16(ws) && aligned16(dq) && aligned16(dg),
                    "%s: q, g, ws, dq or dg is not 16-byte aligned", who);
     const Ws w(P, N, Mg, D);

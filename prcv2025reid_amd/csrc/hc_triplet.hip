@@ -3,6 +3,9 @@
 // shared vis side g [Mg, D]; the triplet runs on the per-identity CENTRES of every side inside the batch.  The reference has no such
 // loss; include/reid_hip.h (reid_hc_triplet_*) and DESIGN.md section 15 are the definition.
 //
+// The kernels here decode indices and call the pieces of triplet_mine.h (shared with triplet.hip and cross_triplet.hip; the list of
+// pieces and callers is at its head); the entry points use its argument checks.
+//
 // Forward, launch 1 (hc_unit_kernel, normalize = 1 only): the unit rows of both sides (triplet::unit_row, as cross_triplet.hip).
 // Forward, launch 2 (hc_lead_kernel): one workgroup per side (P q sides, then g).  leader(i) = the lowest valid row with row i's label
 //   (an O(n^2) label compare, 64 candidates at a time per wave), the leaders numbered in ascending order by a workgroup scan -> lead [row] = centre slot or -1,
@@ -14,7 +17,7 @@
 //   triplet.hip) with A = C = U_p and self-exclusion, the row count S_q[p] + S_g read from ws.  The grid is sized for N + Mg centres;
 //   workgroups behind the count leave, and the candidates walked are the S_q + S_g used ones.
 // Forward, launch 5 (hc_refine_kernel): one wave per slot of the index space 0 .. N + Mg - 1 (q centre s -> s, g centre t -> N + t):
-//   the two distances an active anchor keeps re-evaluated with an fp64 sum (as xt_refine_kernel), its compact indices mapped to the
+//   the two distances an active anchor keeps re-evaluated with an fp64 sum (triplet::refine_anchor), its compact indices mapped to the
 //   index space; unused slots and inactive anchors get -1 / 0.
 // Forward, launch 6 (hc_finalize_kernel): one workgroup per pair adds the anchors' losses in a fixed order in fp64
 //   -> result [P, 4] = {L_p, flag_p, n_q, n_g}.
@@ -30,7 +33,7 @@ namespace {
 using namespace triplet;
 
 constexpr int LT = 1024;                 // threads of hc_lead_kernel
-constexpr int MAXN = 8192;               // rows per side (checked by hc_check_dims)
+constexpr int MAXN = MAX_ROWS;           // rows per side (checked by triplet::check_dims)
 
 inline int64_t up4(int64_t n) { return (n + 3) & ~(int64_t)3; }
 
@@ -47,13 +50,7 @@ struct Ws {
     }
 };
 
-// the two sides as the kernels see them: unit rows in ws (normalize = 1) or the callers' rows
-struct Sides {
-    const float* q; int ldq;
-    const float* g; int ldg;
-};
-
-// rows [0, PN) are q rows, rows [PN, PN + Mg) are g rows; one wave per row
+// rows [0, PN) are q rows, rows [PN, PN + Mg) are g rows; one wave per row.  (The same body as cross_triplet.hip's xt_unit_kernel.)
 __global__ __launch_bounds__(256) void hc_unit_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ g, int ldg, int PN,
                                                       int Mg, int D, float eps, float* __restrict__ unit, float* __restrict__ inv_out,
                                                       float* __restrict__ norm_out) {
@@ -149,8 +146,7 @@ __global__ __launch_bounds__(256) void hc_centre_kernel(Sides sd, const int64_t*
     const int ld = t.is_q ? sd.ldq : sd.ldg;
     const int r0 = srow[w];
     f32x4 acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     int cnt = 0;
     for (int b = r0 & ~63; b < t.n; b += 64) {                       // the members in ascending row order (the leader is the first)
         const int a = b + lane;
@@ -214,23 +210,9 @@ __global__ __launch_bounds__(256) void hc_refine_kernel(const float* __restrict_
     }
     const float* c = cen + (size_t)p * U * D;
     const float* xa = c + (size_t)k * D;
-    double sp = 0.0, sn = 0.0;
-#pragma unroll
-    for (int v = 0; v < MAXV; ++v) {
-        const int col = 4 * lane + 256 * v;
-        if (col < D) {
-            const f32x4 x = *(const f32x4*)(xa + col), yp = *(const f32x4*)(c + (size_t)jp * D + col), yn = *(const f32x4*)(c + (size_t)jn * D + col);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const double up = (double)x[e] - (double)yp[e], un = (double)x[e] - (double)yn[e];
-                sp = fma(up, up, sp); sn = fma(un, un, sn);
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); sn += __shfl_xor(sn, o, 64); }
+    float dp, dn;                                                    // (lane 0's)
+    refine_anchor(xa, c, D, jp, jn, D, lane, dp, dn);
     if (lane == 0) {
-        const float dp = sqrtf(fmaxf((float)sp, D2_MIN)), dn = sqrtf(fmaxf((float)sn, D2_MIN));
         cd[p * U + k] = dp; cd[PU + p * U + k] = dn;
         closs[p * U + k] = row_loss_of(dp - dn, margin);
         d[w] = dp; d[PU + w] = dn;
@@ -238,7 +220,8 @@ __global__ __launch_bounds__(256) void hc_refine_kernel(const float* __restrict_
     }
 }
 
-// one workgroup per pair: thread t adds anchors t, t + 256, ... in fp64, the 256 sums are added in index order
+// one workgroup per pair: thread t adds anchors t, t + 256, ... in fp64, the 256 sums are added in index order (the tail of
+// triplet_finalize_kernel and xt_finalize_kernel, with one sum and two counts)
 __global__ __launch_bounds__(256) void hc_finalize_kernel(const float* __restrict__ closs, const int* __restrict__ cidx,
                                                           const int* __restrict__ S, int P, int U, float* __restrict__ result) {
     __shared__ double s_sum[256];
@@ -275,15 +258,14 @@ __global__ __launch_bounds__(256) void hc_bwd_centre_kernel(const float* __restr
     if (t.s >= S[t.p]) return;                                       // nobody reads the gradient of an unused slot
     const int U = N + Mg, PU = P * U;
     f32x4 xi[NV], acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     for (int p = t.is_q ? t.p : 0; p < (t.is_q ? t.p + 1 : P); ++p) {
         const int sq = S[p], n = sq + S[P];
         const int k = t.is_q ? t.s : sq + t.s;
         const float* c = cen + (size_t)p * U * D;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {                                // (a g centre holds the same bits in every pair's block)
-            const int col = 4 * lane + 256 * v;
+            const int col = 4 * lane + 256 * v;                      // (triplet::load_row and store_row, written out in this kernel)
             xi[v] = col < D ? *(const f32x4*)(c + (size_t)k * D + col) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
         const float cn = gscale[p] / fmaxf(result[4 * p + 2] + result[4 * p + 3], 1.f);
@@ -313,8 +295,7 @@ __global__ __launch_bounds__(256) void hc_bwd_rows_kernel(Sides sd, int P, int N
     float* o = is_q ? dq + (size_t)row * lddq : dg + (size_t)(row - PN) * lddg;
     const int slot = lead[row];
     f32x4 acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     if (slot >= 0) {                                                 // (an invalid row belongs to no centre: zeros)
         const float fc = (float)count[off + slot];
 #pragma unroll
@@ -323,7 +304,8 @@ __global__ __launch_bounds__(256) void hc_bwd_rows_kernel(Sides sd, int P, int N
             if (c < D) acc[v] = *(const f32x4*)(grad + (size_t)(off + slot) * D + c) / fc;
         }
         if (normalize) {
-            if (norm[row] >= eps) {                                  // dx = (G - x^ (x^ . G)) / max(|x|, eps)
+            if (norm[row] >= eps) {                                  // dx = (G - x^ (x^ . G)) / max(|x|, eps); the same block as in
+                                                                     // cross_triplet.hip's xt_bwd_kernel, which has x^ in registers already
                 const float* xr = is_q ? sd.q + (size_t)row * sd.ldq : sd.g + (size_t)(row - PN) * sd.ldg;
                 f32x4 xi[NV];
                 float dot = 0.f;
@@ -343,36 +325,13 @@ __global__ __launch_bounds__(256) void hc_bwd_rows_kernel(Sides sd, int P, int N
             }
         }
     }
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int c = 4 * lane + 256 * v;
-        if (c < D) *(f32x4*)(o + c) = acc[v];
-    }
-}
-
-int hc_check_dims(const char* who, int32_t P, int32_t N, int32_t Mg, int32_t D) {
-    REID_CHECK_ARG(P >= 1 && P <= 8, "%s: P=%d (1..8)", who, P);
-    REID_CHECK_ARG(N >= 1 && N <= MAXN, "%s: N=%d (1..8192)", who, N);
-    REID_CHECK_ARG(Mg >= 1 && Mg <= MAXN, "%s: Mg=%d (1..8192)", who, Mg);
-    REID_CHECK_ARG(D % 4 == 0 && D >= 4 && D <= 1024, "%s: D=%d (a multiple of 4, 4..1024)", who, D);
-    return REID_OK;
-}
-int hc_check_ld(const char* who, int64_t rows, int32_t D, int32_t ld, const char* ld_name) {
-    REID_CHECK_ARG(ld >= D && ld % 4 == 0, "%s: %s=%d (a multiple of 4, >= D=%d)", who, ld_name, ld, D);
-    REID_CHECK_ARG(rows * ld < (1ll << 31), "%s: rows * %s beyond 2^31 elements", who, ld_name);
-    return REID_OK;
-}
-int hc_check_scalars(const char* who, float margin, int32_t normalize, float eps) {
-    REID_CHECK_ARG(margin == margin, "%s: margin is NaN", who);
-    REID_CHECK_ARG(normalize == 0 || normalize == 1, "%s: normalize=%d (0 or 1)", who, normalize);
-    REID_CHECK_ARG(eps >= 0.f, "%s: eps=%g (>= 0)", who, (double)eps);
-    return REID_OK;
+    store_row(o, acc, lane, D);
 }
 
 }  // namespace
 
 extern "C" int64_t reid_hc_triplet_ws_floats(int32_t P, int32_t N, int32_t Mg, int32_t D) {
-    if (int rc = hc_check_dims("reid_hc_triplet_ws_floats", P, N, Mg, D)) return rc;
+    if (int rc = check_dims("reid_hc_triplet_ws_floats", P, N, Mg, D)) return rc;
     return Ws(P, N, Mg, D).total;
 }
 
@@ -382,10 +341,10 @@ extern "C" int reid_hc_triplet_fwd(const float* q, int32_t ldq, const float* g, 
                                    int64_t* clabel, float* d, int32_t* idx, float* ws, float* result, void* stream) {
     const char* who = "reid_hc_triplet_fwd";
     REID_CHECK_ARG(q && g && q_label && g_label && lead && count && clabel && d && idx && ws && result, "%s: null pointer", who);
-    if (int rc = hc_check_dims(who, P, N, Mg, D)) return rc;
-    if (int rc = hc_check_ld(who, (int64_t)P * N, D, ldq, "ldq")) return rc;
-    if (int rc = hc_check_ld(who, Mg, D, ldg, "ldg")) return rc;
-    if (int rc = hc_check_scalars(who, margin, normalize, eps)) return rc;
+    if (int rc = check_dims(who, P, N, Mg, D)) return rc;
+    if (int rc = check_ld(who, (int64_t)P * N, D, ldq, "ldq")) return rc;
+    if (int rc = check_ld(who, Mg, D, ldg, "ldg")) return rc;
+    if (int rc = check_scalars(who, margin, normalize, eps)) return rc;
     REID_CHECK_ARG(aligned16(q) && aligned16(g) && aligned16(ws), "%s: q, g or ws is not 16-byte aligned", who);
     const Ws w(P, N, Mg, D);
     hipStream_t s = (hipStream_t)stream;
@@ -423,12 +382,12 @@ extern "C" int reid_hc_triplet_bwd(const float* q, int32_t ldq, const float* g, 
                                    void* stream) {
     const char* who = "reid_hc_triplet_bwd";
     REID_CHECK_ARG(q && g && lead && count && ws && result && gscale && dq && dg, "%s: null pointer", who);
-    if (int rc = hc_check_dims(who, P, N, Mg, D)) return rc;
-    if (int rc = hc_check_ld(who, (int64_t)P * N, D, ldq, "ldq")) return rc;
-    if (int rc = hc_check_ld(who, Mg, D, ldg, "ldg")) return rc;
-    if (int rc = hc_check_ld(who, (int64_t)P * N, D, lddq, "lddq")) return rc;
-    if (int rc = hc_check_ld(who, Mg, D, lddg, "lddg")) return rc;
-    if (int rc = hc_check_scalars(who, margin, normalize, eps)) return rc;
+    if (int rc = check_dims(who, P, N, Mg, D)) return rc;
+    if (int rc = check_ld(who, (int64_t)P * N, D, ldq, "ldq")) return rc;
+    if (int rc = check_ld(who, Mg, D, ldg, "ldg")) return rc;
+    if (int rc = check_ld(who, (int64_t)P * N, D, lddq, "lddq")) return rc;
+    if (int rc = check_ld(who, Mg, D, lddg, "lddg")) return rc;
+    if (int rc = check_scalars(who, margin, normalize, eps)) return rc;
     REID_CHECK_ARG(aligned16(q) && aligned16(g) && aligned16(ws) && aligned16(dq) && aligned16(dg),
                    "%s: q, g, ws, dq or dg is not 16-byte aligned", who);
     const Ws w(P, N, Mg, D);

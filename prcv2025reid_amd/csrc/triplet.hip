@@ -6,10 +6,12 @@
 //   The whole problem is 3 B^2 D flop (1.6 GFLOP at B = 1024): the matrix cores are not needed.
 //
 // Forward, launch 1 (triplet_fwd_kernel): a workgroup owns TA = 4 anchors and mines them against all rows with triplet::mine_tile
-//   (triplet_mine.h, shared with cross_triplet.hip: one candidate per lane, 256-row pieces staged through padded LDS rows).
+//   (triplet_mine.h: one candidate per lane, 256-row pieces staged through padded LDS rows).
 // Forward, launch 2 (triplet_finalize_kernel): ONE workgroup adds row_loss in a fixed order in fp64 -> result = {loss, n_active}.
 // Backward (triplet_bwd_kernel): gather form, one wave per output row i: its own two terms, then every anchor a in ascending order whose
 //   idx_p[a] or idx_n[a] is i.  No atomics anywhere: two runs give the same bits in every output.
+// triplet_mine.h is shared with cross_triplet.hip and hc_triplet.hip; from it come the mining loop, the row helpers and the two halves
+// of the gather form (add_own, add_chosen_by) of the kernels here, and the D / leading-dimension checks of the entry points.
 #include "triplet_mine.h"
 
 namespace {
@@ -25,7 +27,8 @@ __global__ __launch_bounds__(256) void triplet_fwd_kernel(const float* __restric
     mine_tile(all, all, a0, a0, D, margin, d_ap, d_an, idx_p, idx_n, row_loss);      // a row is no positive of itself
 }
 
-// one workgroup: thread t adds rows t, t + 256, ... in fp64, the 256 sums are added in index order
+// one workgroup: thread t adds rows t, t + 256, ... in fp64, the 256 sums are added in index order (the same tail, with more sums
+// and counts, ends xt_finalize_kernel and hc_finalize_kernel)
 __global__ __launch_bounds__(256) void triplet_finalize_kernel(const float* __restrict__ row_loss, const int* __restrict__ idx_p, int rows,
                                                                float* __restrict__ result) {
     __shared__ double s_sum[256];
@@ -58,34 +61,17 @@ __global__ __launch_bounds__(256) void triplet_bwd_kernel(const float* __restric
     const float g = dloss[0] / fmaxf(result[1], 1.f);
     const float* xr = x + (size_t)i * ldx;
     f32x4 xi[NV], acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int c = 4 * lane + 256 * v;
-        xi[v] = c < D ? *(const f32x4*)(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-        acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    const int jp = idx_p[i], jn = idx_n[i];
-    if (jp >= 0 && jp < rows && jn >= 0 && jn < rows) {              // i is an active anchor: its own two terms
-        const float dp = d_ap[i], dn = d_an[i];
-        const float c = g * row_dloss_of(dp - dn, margin);
-        add_term(acc, xi, x + (size_t)jp * ldx, term_scale(c, dp), lane, D);
-        add_term(acc, xi, x + (size_t)jn * ldx, -term_scale(c, dn), lane, D);
-    }
+    load_row(xi, xr, lane, D);
+    zero_acc(acc);
+    add_own(acc, xi, i, x, ldx, rows, idx_p, idx_n, d_ap, d_an, g, margin, lane, D);            // i as an active anchor: its own two terms
     add_chosen_by(acc, xi, i, x, ldx, rows, idx_p, idx_n, d_ap, d_an, g, margin, lane, D);      // anchors that chose i, in ascending order
-    float* o = dx + (size_t)i * lddx;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        const int c = 4 * lane + 256 * v;
-        if (c < D) *(f32x4*)(o + c) = acc[v];
-    }
+    store_row(dx + (size_t)i * lddx, acc, lane, D);
 }
 
 int triplet_check_shape(const char* who, int32_t rows, int32_t D, int32_t ld, const char* ld_name) {
-    REID_CHECK_ARG(D % 4 == 0 && D >= 4 && D <= 1024, "%s: D=%d (a multiple of 4, 4..1024)", who, D);
-    REID_CHECK_ARG(rows >= 1 && rows <= 8192, "%s: rows=%d (1..8192)", who, rows);
-    REID_CHECK_ARG(ld >= D && ld % 4 == 0, "%s: %s=%d (a multiple of 4, >= D=%d)", who, ld_name, ld, D);
-    REID_CHECK_ARG((int64_t)rows * ld < (1ll << 31), "%s: rows * %s beyond 2^31 elements", who, ld_name);
-    return REID_OK;
+    if (int rc = check_d(who, D)) return rc;
+    REID_CHECK_ARG(rows >= 1 && rows <= MAX_ROWS, "%s: rows=%d (1..8192)", who, rows);      // (its own: the message says "rows")
+    return check_ld(who, rows, D, ld, ld_name);
 }
 
 }  // namespace

@@ -1,6 +1,18 @@
-// Batch-hard mining shared by the triplet losses (triplet.hip: one set of rows against itself; cross_triplet.hip: one set against
-// another; hc_triplet.hip: a set of per-identity centres against itself): the ONE copy of the mining loop, the unit-row pass, the
-// row-loss forms and the pieces of the gather-form backward.  All fp32.
+// What the triplet losses share (triplet.hip: one set of rows against itself; cross_triplet.hip: one set against another;
+// hc_triplet.hip: a set of per-identity centres against itself) -- the ONE copy of each piece, all fp32 unless said; on the right, who
+// calls it:
+//   Rows, mine_tile                   the mining loop                              triplet_fwd_kernel, xt_fwd_kernel, hc_mine_kernel
+//   row_loss_of, row_dloss_of         the row-loss forms                           mine_tile, add_own, add_chosen_by, the refine kernels
+//   Sides                             the two sides as a kernel parameter          cross_triplet.hip, hc_triplet.hip
+//   unit_row                          the unit row of one row                      xt_unit_kernel, hc_unit_kernel
+//   refine_anchor                     the kept distances re-evaluated in fp64      xt_refine_kernel, hc_refine_kernel
+//   load_row, zero_acc, store_row     a row as NV 16-byte chunks per lane          triplet_bwd_kernel, xt_bwd_kernel, hc_centre_kernel,
+//                                                                                  hc_bwd_centre_kernel, hc_bwd_rows_kernel
+//   add_term, term_scale, add_own, add_chosen_by   the gather-form backward        triplet_bwd_kernel, xt_bwd_kernel, hc_bwd_centre_kernel
+//   check_d, check_dims, check_ld, check_scalars, aligned16   the argument checks  the extern "C" entry points of the three files
+// Shared forms of the four-line bodies of the unit kernels, of the projection through the normalisation (xt_bwd_kernel,
+// hc_bwd_rows_kernel) and of the finalize kernels' ordered fp64 tails changed the machine code of their callers, so those stay written
+// out in the .hip files, each copy naming the other (profiles/triplet_shared_isa_identity.md, "Left duplicated").
 //
 //   d2(i,j) = sum_c (x_ic - y_jc)^2   -- the DIFFERENCE form on the vector ALU (the features are mostly a common
 //   mean, the Gram form loses more of d2 than the gap between the hardest and the second-hardest candidate).
@@ -18,6 +30,18 @@
 #pragma once
 #include "rank.h"
 
+namespace {
+
+// The two sides of cross_triplet.hip and hc_triplet.hip as their kernels see them: unit rows in ws (normalize = 1) or the callers'
+// rows.  A kernel parameter type, so its namespace is part of those kernels' symbols: it stays in the unnamed one, where the two
+// files had it, and the symbols stay what they were.
+struct Sides {
+    const float* q; int ldq;
+    const float* g; int ldg;
+};
+
+}  // namespace
+
 namespace triplet {
 
 constexpr int TA = 4;                    // anchors per workgroup
@@ -29,6 +53,9 @@ constexpr float D2_MIN = 1e-12f;         // clamp(min=1e-12).sqrt()
 // negative) is still taken when it is the only one
 constexpr int NONE = 0x7fffffff;
 constexpr int NO_SELF = -0x40000000;     // mine_tile's excl0 when no candidate is the anchor itself
+constexpr int NV = 4;                    // 16-byte chunks per lane where one wave owns a row: D <= 64 * 4 * NV = 1024
+constexpr int MAX_D = 64 * 4 * NV;
+constexpr int MAX_ROWS = 8192;           // rows per side
 
 // l = max(0, z + margin) (margin >= 0) or softplus(z) (margin < 0), z = d_ap - d_an; dl = its derivative
 __device__ __forceinline__ float row_loss_of(float z, float margin) {
@@ -165,18 +192,16 @@ __device__ __forceinline__ void mine_tile(const Rows A, const Rows C, int a0, in
     }
 }
 
-constexpr int MAXV = 4;                  // 16-byte chunks per lane of the unit-row pass: D <= 1024
-
 // One wave: the unit row x * (1 / max(|x|, eps)) of x [D] into unit [D], with 1 / max(|x|, eps) and |x| beside it -- the body of
 // rowops.hip's l2norm_kernel (per-lane partial sums in the same order, wave_sum, sqrtf, one division, one product), so bit-equal rows
 // give bit-equal unit rows.
 __device__ __forceinline__ void unit_row(const float* __restrict__ x, int D, float eps, float* __restrict__ unit, float* __restrict__ inv_out,
                                          float* __restrict__ norm_out, int lane) {
     const int nv = D >> 2;
-    f32x4 v[MAXV];
+    f32x4 v[NV];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
+    for (int i = 0; i < NV; ++i) {
         const int c = lane + i * 64;
         v[i] = c < nv ? *(const f32x4*)(x + c * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
         s += v[i][0] * v[i][0] + v[i][1] * v[i][1] + v[i][2] * v[i][2] + v[i][3] * v[i][3];
@@ -184,14 +209,57 @@ __device__ __forceinline__ void unit_row(const float* __restrict__ x, int D, flo
     const float norm = sqrtf(wave_sum(s));
     const float inv = 1.f / fmaxf(norm, eps);
 #pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
+    for (int i = 0; i < NV; ++i) {
         const int c = lane + i * 64;
         if (c < nv) *(f32x4*)(unit + c * 4) = v[i] * inv;
     }
     if (lane == 0) { *inv_out = inv; *norm_out = norm; }
 }
 
-constexpr int NV = 4;                    // 16-byte column chunks per lane of the backward (one wave per row): D <= 256 NV
+// One wave: the two distances an anchor keeps -- from its row xa to rows jp and jn of xc (leading dimension ldc), D columns -- re-
+// evaluated with an fp64 sum, rounded once and clamped as the mining clamps; LANE 0 gets them, the other lanes' d_ap / d_an are left
+// alone.  Mining compares the fp32 d2 (a D-term sum: a few u on d); but l'(d_ap - d_an) of the backward inherits the ABSOLUTE error
+// of the saved distances, and with unnormalised rows at d = 40 those few u are already 1e-5 of the soft margin's gradient.  (3 rows
+// per anchor: next to nothing beside the mining.)
+__device__ __forceinline__ void refine_anchor(const float* xa, const float* xc, int ldc, int jp, int jn, int D, int lane, float& d_ap,
+                                              float& d_an) {
+    double sp = 0.0, sn = 0.0;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int c = 4 * lane + 256 * v;
+        if (c < D) {
+            const f32x4 x = *(const f32x4*)(xa + c), p = *(const f32x4*)(xc + (size_t)jp * ldc + c), n = *(const f32x4*)(xc + (size_t)jn * ldc + c);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double up = (double)x[e] - (double)p[e], un = (double)x[e] - (double)n[e];
+                sp = fma(up, up, sp); sn = fma(un, un, sn);
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { sp += __shfl_xor(sp, o, 64); sn += __shfl_xor(sn, o, 64); }
+    if (lane == 0) { d_ap = sqrtf(fmaxf((float)sp, D2_MIN)); d_an = sqrtf(fmaxf((float)sn, D2_MIN)); }
+}
+
+// A row of D columns held by one wave as NV 16-byte chunks per lane (zeros past D): load it (on = false: zeros), zero it, store it.
+__device__ __forceinline__ void load_row(f32x4 (&xi)[NV], const float* __restrict__ xr, int lane, int D, bool on = true) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int c = 4 * lane + 256 * v;
+        xi[v] = c < D && on ? *(const f32x4*)(xr + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[NV]) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+__device__ __forceinline__ void store_row(float* __restrict__ o, const f32x4 (&acc)[NV], int lane, int D) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        const int c = 4 * lane + 256 * v;
+        if (c < D) *(f32x4*)(o + c) = acc[v];
+    }
+}
 
 // acc += s * (x_i - x_a) over this lane's columns
 __device__ __forceinline__ void add_term(f32x4 (&acc)[NV], const f32x4 (&xi)[NV], const float* __restrict__ xa, float s, int lane, int D) {
@@ -244,6 +312,30 @@ __device__ __forceinline__ void add_chosen_by(f32x4 (&acc)[NV], const f32x4 (&xi
     }
 }
 
+// ---- host side: the argument checks of the extern "C" entry points (`who` = the entry point's name)
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+static_assert(MAX_D == 1024 && MAX_ROWS == 8192, "the limits are spelled out in the messages below");
+inline int check_d(const char* who, int32_t D) {
+    REID_CHECK_ARG(D % 4 == 0 && D >= 4 && D <= MAX_D, "%s: D=%d (a multiple of 4, 4..1024)", who, D);
+    return REID_OK;
+}
+inline int check_dims(const char* who, int32_t P, int32_t N, int32_t Mg, int32_t D) {
+    REID_CHECK_ARG(P >= 1 && P <= 8, "%s: P=%d (1..8)", who, P);
+    REID_CHECK_ARG(N >= 1 && N <= MAX_ROWS, "%s: N=%d (1..8192)", who, N);
+    REID_CHECK_ARG(Mg >= 1 && Mg <= MAX_ROWS, "%s: Mg=%d (1..8192)", who, Mg);
+    return check_d(who, D);
+}
+inline int check_ld(const char* who, int64_t rows, int32_t D, int32_t ld, const char* ld_name) {
+    REID_CHECK_ARG(ld >= D && ld % 4 == 0, "%s: %s=%d (a multiple of 4, >= D=%d)", who, ld_name, ld, D);
+    REID_CHECK_ARG(rows * ld < (1ll << 31), "%s: rows * %s beyond 2^31 elements", who, ld_name);
+    return REID_OK;
+}
+inline int check_scalars(const char* who, float margin, int32_t normalize, float eps) {
+    REID_CHECK_ARG(margin == margin, "%s: margin is NaN", who);
+    REID_CHECK_ARG(normalize == 0 || normalize == 1, "%s: normalize=%d (0 or 1)", who, normalize);
+    REID_CHECK_ARG(eps >= 0.f, "%s: eps=%g (>= 0)", who, (double)eps);
+    return REID_OK;
+}
 
 }  // namespace triplet

@@ -121,6 +121,47 @@ class SDMFn(torch.autograd.Function):
         return dq.view(P, q2.shape[0] // P, q2.shape[1]), dg, None, None, None, None, None
 
 
+EPS = 1e-12                                                   # of the triplet losses' unit rows: F.normalize's default
+
+
+def _margin_arg(fn, margin):
+    """The kernels' margin: None (the soft-margin form) -> -1.0."""
+    if margin is not None and float(margin) < 0:
+        raise ValueError(f'{fn.__name__}: margin must be >= 0, or None for the soft-margin form')
+    return -1.0 if margin is None else float(margin)
+
+
+def _two_sided_prepare(q, g, q_valid):
+    """q [P, N, D], g [Mg, D], q_valid [P, N] or None as the two-sided kernels take them: (q2 [P*N, D], g, qv [P*N], res [P, 4])."""
+    P, N, D = q.shape
+    q2 = q.reshape(P * N, D).contiguous().float()
+    return q2, g.contiguous().float(), None if q_valid is None else q_valid.reshape(P * N).contiguous(), torch.empty(P, 4, device=q.device)
+
+
+def _two_sided_results(ctx, res):
+    """(loss, flag, n_active) of res [P, 4]; only the loss is differentiable."""
+    loss, flag, n_active = res[:, 0].contiguous(), res[:, 1].contiguous(), res[:, 2:].contiguous()
+    ctx.mark_non_differentiable(flag, n_active)
+    return loss, flag, n_active
+
+
+def _gscale(dloss, P):                                        # (a copy: the cotangent of L.sum() is an expanded scalar with stride 0)
+    return torch.empty(P, device=dloss.device).copy_(dloss.reshape(P))
+
+
+def _two_sided_args(who, q, g, q_labels, g_labels, q_valid, g_valid):
+    """The public two-sided functions' argument checks; returns q as [P, N, D] and the validity vectors as the kernels take them."""
+    tensors = (q, g, q_labels, g_labels) + tuple(t for t in (q_valid, g_valid) if t is not None)
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.ReidHipError(f'{who} needs device tensors (there is no CPU path)')
+    if q.dim() == 2:
+        q = q.unsqueeze(0)
+    if q.dim() != 3 or g.dim() != 2 or g.shape[1] != q.shape[2] or q_labels.shape != q.shape[1:2] or g_labels.shape != g.shape[:1]:
+        raise ValueError(f'{who}: q [P, N, D] or [N, D], g [Mg, D], q_labels [N], g_labels [Mg]')
+    return (q, None if q_valid is None else q_valid.to(torch.uint8).reshape(q.shape[0], q.shape[1]).contiguous(),
+            None if g_valid is None else g_valid.to(torch.uint8).contiguous())
+
+
 class TripletHardFn(torch.autograd.Function):
     """(loss, n_active) of the batch-hard triplet loss of x [B, D] (csrc/triplet.hip; the reference has no such loss).  ``margin`` None:
     the soft-margin form softplus(d_ap - d_an).  n_active is a float tensor; nothing is read back to the host.  ``rows_out``: an optional
@@ -129,9 +170,7 @@ class TripletHardFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, labels, valid, margin, rows_out=None):
-        m = -1.0 if margin is None else float(margin)
-        if m < 0 and margin is not None:
-            raise ValueError('TripletHardFn: margin must be >= 0, or None for the soft-margin form')
+        m = _margin_arg(TripletHardFn, margin)
         x = x.contiguous().float()
         B, dev = x.shape[0], x.device
         fl = torch.empty(3, B, device=dev); ix = torch.empty(2, B, dtype=torch.int32, device=dev)      # d_ap | d_an | row_loss, idx_p | idx_n
@@ -179,27 +218,18 @@ class CrossTripletFn(torch.autograd.Function):
     soft-margin form.  n_active = (q->g, g->q) active anchors as floats; nothing is read back to the host.  ``rows_out``: an optional
     trailing dict that receives COPIES of the saved arrays (cross_modal_triplet); the call the model makes is
     ``apply(q, g, q_label, g_label, q_valid, g_valid, margin, normalize)``."""
-    EPS = 1e-12                                               # F.normalize's default
-
     @staticmethod
     def forward(ctx, q, g, q_label, g_label, q_valid, g_valid, margin, normalize: bool, rows_out=None):
-        m = -1.0 if margin is None else float(margin)
-        if m < 0 and margin is not None:
-            raise ValueError('CrossTripletFn: margin must be >= 0, or None for the soft-margin form')
-        P, N, D = q.shape
-        q2 = q.reshape(P * N, D).contiguous().float(); g = g.contiguous().float()
-        Mg, dev = g.shape[0], q.device
+        m = _margin_arg(CrossTripletFn, margin)
+        (P, N, D), Mg, dev = q.shape, g.shape[0], q.device
+        q2, g, qv, res = _two_sided_prepare(q, g, q_valid)
         ws = torch.empty(ops.cross_triplet_ws_floats(P, N, Mg, D), device=dev)
         qd = torch.empty(2, P * N, device=dev); qi = torch.empty(2, P * N, dtype=torch.int32, device=dev)
         gd = torch.empty(2, P * Mg, device=dev); gi = torch.empty(2, P * Mg, dtype=torch.int32, device=dev)
-        res = torch.empty(P, 4, device=dev)
-        qv = None if q_valid is None else q_valid.reshape(P * N).contiguous()
-        ops.cross_triplet_fwd(q2, g, q_label.contiguous(), g_label.contiguous(), qv, g_valid, m, normalize, CrossTripletFn.EPS,
-                              qd, qi, gd, gi, ws, res, P=P)
+        ops.cross_triplet_fwd(q2, g, q_label.contiguous(), g_label.contiguous(), qv, g_valid, m, normalize, EPS, qd, qi, gd, gi, ws, res, P=P)
         ctx.save_for_backward(q2, g, qv, g_valid, qd, qi, gd, gi, ws, res)
         ctx.margin, ctx.normalize, ctx.P = m, bool(normalize), P
-        loss, flag, n_active = res[:, 0].contiguous(), res[:, 1].contiguous(), res[:, 2:].contiguous()
-        ctx.mark_non_differentiable(flag, n_active)
+        loss, flag, n_active = _two_sided_results(ctx, res)
         if rows_out is not None:                              # copies: the saved arrays belong to the backward
             rows_out.update(q_d_ap=qd[0].view(P, N).clone(), q_d_an=qd[1].view(P, N).clone(), q_idx_p=qi[0].view(P, N).clone(),
                             q_idx_n=qi[1].view(P, N).clone(), g_d_ap=gd[0].view(P, Mg).clone(), g_d_an=gd[1].view(P, Mg).clone(),
@@ -211,9 +241,7 @@ class CrossTripletFn(torch.autograd.Function):
         q2, g, qv, gv, qd, qi, gd, gi, ws, res = ctx.saved_tensors
         P = ctx.P
         dq = torch.empty_like(q2); dg = torch.empty_like(g)
-        gs = torch.empty(P, device=q2.device)                 # (a copy: the cotangent of L.sum() is an expanded scalar with stride 0)
-        gs.copy_(dloss.reshape(P))
-        ops.cross_triplet_bwd(q2, g, qv, gv, ctx.margin, ctx.normalize, CrossTripletFn.EPS, qd, qi, gd, gi, ws, res, gs, dq, dg, P=P)
+        ops.cross_triplet_bwd(q2, g, qv, gv, ctx.margin, ctx.normalize, EPS, qd, qi, gd, gi, ws, res, _gscale(dloss, P), dq, dg, P=P)
         return dq.view(P, q2.shape[0] // P, q2.shape[1]), dg, None, None, None, None, None, None, None
 
 
@@ -226,17 +254,7 @@ def cross_modal_triplet(q, g, q_labels, g_labels, q_valid=None, g_valid=None, ma
     (losses [P], flags [P], rows): flag 1 where the pair has an active anchor, rows = {'q_d_ap', 'q_d_an', 'q_idx_p', 'q_idx_n'} [P, N]
     and {'g_d_ap', 'g_d_an', 'g_idx_p', 'g_idx_n'} [P, Mg] (g indices into 0..N-1) plus 'n_active' [P, 2]; the losses carry the
     gradient to ``q`` and ``g``."""
-    tensors = (q, g, q_labels, g_labels) + tuple(t for t in (q_valid, g_valid) if t is not None)
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.ReidHipError('cross_modal_triplet needs device tensors (there is no CPU path)')
-    if q.dim() == 2:
-        q = q.unsqueeze(0)
-    if q.dim() != 3 or g.dim() != 2 or g.shape[1] != q.shape[2] or q_labels.shape != q.shape[1:2] or g_labels.shape != g.shape[:1]:
-        raise ValueError('cross_modal_triplet: q [P, N, D] or [N, D], g [Mg, D], q_labels [N], g_labels [Mg]')
-    if q_valid is not None:
-        q_valid = q_valid.to(torch.uint8).reshape(q.shape[0], q.shape[1]).contiguous()
-    if g_valid is not None:
-        g_valid = g_valid.to(torch.uint8).contiguous()
+    q, q_valid, g_valid = _two_sided_args('cross_modal_triplet', q, g, q_labels, g_labels, q_valid, g_valid)
     rows = {}
     loss, flag, n_active = CrossTripletFn.apply(q, g, q_labels.long(), g_labels.long(), q_valid, g_valid, margin, bool(normalize), rows)
     rows['n_active'] = n_active
@@ -250,29 +268,21 @@ class HcTripletFn(torch.autograd.Function):
     among the (q, g) centres as floats; nothing is read back to the host.  ``rows_out``: an optional trailing dict that receives COPIES
     of the saved arrays (hetero_center_triplet); the call the model makes is
     ``apply(q, g, q_label, g_label, q_valid, g_valid, margin, normalize)``."""
-    EPS = 1e-12                                               # F.normalize's default
-
     @staticmethod
     def forward(ctx, q, g, q_label, g_label, q_valid, g_valid, margin, normalize: bool, rows_out=None):
-        m = -1.0 if margin is None else float(margin)
-        if m < 0 and margin is not None:
-            raise ValueError('HcTripletFn: margin must be >= 0, or None for the soft-margin form')
-        P, N, D = q.shape
-        q2 = q.reshape(P * N, D).contiguous().float(); g = g.contiguous().float()
-        Mg, dev = g.shape[0], q.device
+        m = _margin_arg(HcTripletFn, margin)
+        (P, N, D), Mg, dev = q.shape, g.shape[0], q.device
+        q2, g, qv, res = _two_sided_prepare(q, g, q_valid)
         R, U = P * N + Mg, N + Mg
         ws = torch.empty(ops.hc_triplet_ws_floats(P, N, Mg, D), device=dev)
         ints = torch.empty(2, R, dtype=torch.int32, device=dev)                                  # lead | count
         clabel = torch.empty(R, dtype=torch.int64, device=dev)
         d = torch.empty(2, P, U, device=dev); idx = torch.empty(2, P, U, dtype=torch.int32, device=dev)
-        res = torch.empty(P, 4, device=dev)
-        qv = None if q_valid is None else q_valid.reshape(P * N).contiguous()
-        ops.hc_triplet_fwd(q2, g, q_label.contiguous(), g_label.contiguous(), qv, g_valid, m, normalize, HcTripletFn.EPS,
+        ops.hc_triplet_fwd(q2, g, q_label.contiguous(), g_label.contiguous(), qv, g_valid, m, normalize, EPS,
                            ints[0], ints[1], clabel, d, idx, ws, res, P=P)
         ctx.save_for_backward(q2, g, ints, ws, res)
         ctx.margin, ctx.normalize, ctx.P = m, bool(normalize), P
-        loss, flag, n_active = res[:, 0].contiguous(), res[:, 1].contiguous(), res[:, 2:].contiguous()
-        ctx.mark_non_differentiable(flag, n_active)
+        loss, flag, n_active = _two_sided_results(ctx, res)
         if rows_out is not None:                              # copies: the saved arrays belong to the backward
             for side, rows, slots in (('q', slice(0, P * N), slice(0, N)), ('g', slice(P * N, R), slice(N, U))):
                 shape = (P, N) if side == 'q' else (Mg,)
@@ -287,9 +297,7 @@ class HcTripletFn(torch.autograd.Function):
         q2, g, ints, ws, res = ctx.saved_tensors
         P = ctx.P
         dq = torch.empty_like(q2); dg = torch.empty_like(g)
-        gs = torch.empty(P, device=q2.device)                 # (a copy: the cotangent of L.sum() is an expanded scalar with stride 0)
-        gs.copy_(dloss.reshape(P))
-        ops.hc_triplet_bwd(q2, g, ctx.margin, ctx.normalize, HcTripletFn.EPS, ints[0], ints[1], ws, res, gs, dq, dg, P=P)
+        ops.hc_triplet_bwd(q2, g, ctx.margin, ctx.normalize, EPS, ints[0], ints[1], ws, res, _gscale(dloss, P), dq, dg, P=P)
         return dq.view(P, q2.shape[0] // P, q2.shape[1]), dg, None, None, None, None, None, None, None
 
 
@@ -304,17 +312,7 @@ def hetero_center_triplet(q, g, q_labels, g_labels, q_valid=None, g_valid=None, 
     [P, N], 'g_count', 'g_label' [Mg]} per centre slot (count 0 behind the side's centres), {'q_d_ap', 'q_d_an', 'q_idx_p', 'q_idx_n'}
     [P, N] and {'g_d_ap', 'g_d_an', 'g_idx_p', 'g_idx_n'} [P, Mg] per centre slot, indices in 0..N+Mg-1 (q centre s = s, g centre t =
     N + t), plus 'n_active' [P, 2]; the losses carry the gradient to ``q`` and ``g``."""
-    tensors = (q, g, q_labels, g_labels) + tuple(t for t in (q_valid, g_valid) if t is not None)
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.ReidHipError('hetero_center_triplet needs device tensors (there is no CPU path)')
-    if q.dim() == 2:
-        q = q.unsqueeze(0)
-    if q.dim() != 3 or g.dim() != 2 or g.shape[1] != q.shape[2] or q_labels.shape != q.shape[1:2] or g_labels.shape != g.shape[:1]:
-        raise ValueError('hetero_center_triplet: q [P, N, D] or [N, D], g [Mg, D], q_labels [N], g_labels [Mg]')
-    if q_valid is not None:
-        q_valid = q_valid.to(torch.uint8).reshape(q.shape[0], q.shape[1]).contiguous()
-    if g_valid is not None:
-        g_valid = g_valid.to(torch.uint8).contiguous()
+    q, q_valid, g_valid = _two_sided_args('hetero_center_triplet', q, g, q_labels, g_labels, q_valid, g_valid)
     rows = {}
     loss, flag, n_active = HcTripletFn.apply(q, g, q_labels.long(), g_labels.long(), q_valid, g_valid, margin, bool(normalize), rows)
     rows['n_active'] = n_active

@@ -340,16 +340,26 @@ def triplet_hard_bwd(x, margin, d_ap, d_an, idx_p, idx_n, result, dloss, dx):
                                       ptr(result), ptr(dloss), ptr(dx), dx.stride(0), stream_ptr()))
 
 
-def cross_triplet_ws_floats(P, N, Mg, D):
-    n = int(lib().reid_cross_triplet_ws_floats(P, N, Mg, D))
+def _ws_floats(fn, P, N, Mg, D):
+    n = int(fn(P, N, Mg, D))
     if n < 0:
         check(n)
     return n
 
 
-def _cross_triplet_shapes(who, q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, ws, result, P):
-    for n, t, d in (('q', q, torch.float32), ('g', g, torch.float32), ('q_d', q_d, torch.float32), ('q_idx', q_idx, torch.int32),
-                    ('g_d', g_d, torch.float32), ('g_idx', g_idx, torch.int32), ('ws', ws, torch.float32), ('result', result, torch.float32)):
+def cross_triplet_ws_floats(P, N, Mg, D):
+    return _ws_floats(lib().reid_cross_triplet_ws_floats, P, N, Mg, D)
+
+
+def hc_triplet_ws_floats(P, N, Mg, D):
+    return _ws_floats(lib().reid_hc_triplet_ws_floats, P, N, Mg, D)
+
+
+def _two_sided_shapes(who, ws_floats, q, g, q_valid, g_valid, own, own_numel, own_text, ws, result, P):
+    """The checks the two-sided losses share: q [P*N, D] against g [Mg, D], the optional validity vectors, result [P, 4], ws of
+    ``ws_floats`` floats, and the loss's own saved arrays ``own`` = (name, tensor, dtype)s, each of at least ``own_numel(N, Mg)`` of
+    its elements (``own_text``: how the message describes them).  Returns (N, Mg)."""
+    for n, t, d in (('q', q, torch.float32), ('g', g, torch.float32)) + own + (('ws', ws, torch.float32), ('result', result, torch.float32)):
         L._req(t, d, n)
     if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] % P or g.shape[1] != q.shape[1]:
         raise ValueError(f'{who}: q [P*N, D], g [Mg, D]')
@@ -359,13 +369,19 @@ def _cross_triplet_shapes(who, q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, w
             L._req(t, torch.uint8, n)
             if t.numel() != rows:
                 raise ValueError(f'{who}: {n} has {t.numel()} elements, not {rows}')
-    if min(q_d.numel(), q_idx.numel()) < 2 * P * N or min(g_d.numel(), g_idx.numel()) < 2 * P * Mg or result.numel() < 4 * P \
-            or not (q_d.is_contiguous() and q_idx.is_contiguous() and g_d.is_contiguous() and g_idx.is_contiguous()
-                    and ws.is_contiguous() and result.is_contiguous()):
-        raise ValueError(f'{who}: q_d / q_idx [2, P*N], g_d / g_idx [2, P*Mg], result [P, 4], all contiguous')
-    if ws.numel() < cross_triplet_ws_floats(P, N, Mg, q.shape[1]):
-        raise ValueError(f'{who}: ws holds fewer than cross_triplet_ws_floats(P, N, Mg, D) floats')
+    if any(t.numel() < least for (_, t, _), least in zip(own, own_numel(N, Mg))) or result.numel() < 4 * P \
+            or not all(t.is_contiguous() for t in [t for _, t, _ in own] + [ws, result]):
+        raise ValueError(f'{who}: {own_text}, result [P, 4], all contiguous')
+    if ws.numel() < ws_floats(P, N, Mg, q.shape[1]):
+        raise ValueError(f'{who}: ws holds fewer than {ws_floats.__name__}(P, N, Mg, D) floats')
     return N, Mg
+
+
+def _cross_triplet_shapes(who, q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, ws, result, P):
+    own = (('q_d', q_d, torch.float32), ('q_idx', q_idx, torch.int32), ('g_d', g_d, torch.float32), ('g_idx', g_idx, torch.int32))
+    return _two_sided_shapes(who, cross_triplet_ws_floats, q, g, q_valid, g_valid, own,
+                             lambda N, Mg: (2 * P * N, 2 * P * N, 2 * P * Mg, 2 * P * Mg), 'q_d / q_idx [2, P*N], g_d / g_idx [2, P*Mg]',
+                             ws, result, P)
 
 
 def cross_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, g_d, g_idx, ws, result, P=1):
@@ -392,26 +408,10 @@ def cross_triplet_bwd(q, g, q_valid, g_valid, margin, normalize, eps, q_d, q_idx
                                        ptr(dq), dq.stride(0), ptr(dg), dg.stride(0), stream_ptr()))
 
 
-def hc_triplet_ws_floats(P, N, Mg, D):
-    n = int(lib().reid_hc_triplet_ws_floats(P, N, Mg, D))
-    if n < 0:
-        check(n)
-    return n
-
-
-def _hc_triplet_shapes(who, q, g, lead, count, ws, result, P):
-    for n, t, d in (('q', q, torch.float32), ('g', g, torch.float32), ('lead', lead, torch.int32), ('count', count, torch.int32),
-                    ('ws', ws, torch.float32), ('result', result, torch.float32)):
-        L._req(t, d, n)
-    if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] % P or g.shape[1] != q.shape[1]:
-        raise ValueError(f'{who}: q [P*N, D], g [Mg, D]')
-    N, Mg = q.shape[0] // P, g.shape[0]
-    if min(lead.numel(), count.numel()) < P * N + Mg or result.numel() < 4 * P \
-            or not (lead.is_contiguous() and count.is_contiguous() and ws.is_contiguous() and result.is_contiguous()):
-        raise ValueError(f'{who}: lead / count [P*N + Mg], result [P, 4], all contiguous')
-    if ws.numel() < hc_triplet_ws_floats(P, N, Mg, q.shape[1]):
-        raise ValueError(f'{who}: ws holds fewer than hc_triplet_ws_floats(P, N, Mg, D) floats')
-    return N, Mg
+def _hc_triplet_shapes(who, q, g, q_valid, g_valid, lead, count, ws, result, P):
+    own = (('lead', lead, torch.int32), ('count', count, torch.int32))
+    return _two_sided_shapes(who, hc_triplet_ws_floats, q, g, q_valid, g_valid, own, lambda N, Mg: (P * N + Mg, P * N + Mg),
+                             'lead / count [P*N + Mg]', ws, result, P)
 
 
 def hc_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, eps, lead, count, clabel, d, idx, ws, result, P=1):
@@ -419,17 +419,12 @@ def hc_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, 
     every side; margin < 0 selects the soft-margin form.  lead i32 [P*N + Mg] per row, count i32 / clabel i64 [P*N + Mg] per centre
     slot; d f32 / idx i32 [2, P, N + Mg] = (d_ap | d_an), (idx_p | idx_n) in the index space (q centre s -> s, g centre t -> N + t);
     result f32 [P, 4] = (L_p, flag_p, n_q, n_g); ws is kept for hc_triplet_bwd."""
-    N, Mg = _hc_triplet_shapes('hc_triplet_fwd', q, g, lead, count, ws, result, P)
+    N, Mg = _hc_triplet_shapes('hc_triplet_fwd', q, g, q_valid, g_valid, lead, count, ws, result, P)
     for n, t, dt in (('q_label', q_label, torch.int64), ('g_label', g_label, torch.int64), ('clabel', clabel, torch.int64),
                      ('d', d, torch.float32), ('idx', idx, torch.int32)):
         L._req(t, dt, n)
     if q_label.numel() != N or g_label.numel() != Mg:
         raise ValueError('hc_triplet_fwd: q_label [N], g_label [Mg]')
-    for n, t, rows in (('q_valid', q_valid, P * N), ('g_valid', g_valid, Mg)):
-        if t is not None:
-            L._req(t, torch.uint8, n)
-            if t.numel() != rows:
-                raise ValueError(f'hc_triplet_fwd: {n} has {t.numel()} elements, not {rows}')
     if clabel.numel() < P * N + Mg or min(d.numel(), idx.numel()) < 2 * P * (N + Mg) \
             or not (clabel.is_contiguous() and d.is_contiguous() and idx.is_contiguous()):
         raise ValueError('hc_triplet_fwd: clabel [P*N + Mg], d / idx [2, P, N + Mg], all contiguous')
@@ -440,7 +435,7 @@ def hc_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, 
 
 def hc_triplet_bwd(q, g, margin, normalize, eps, lead, count, ws, result, gscale, dq, dg, P=1):
     """dq [P*N, D], dg [Mg, D] (both overwritten, two launches) from what hc_triplet_fwd saved; gscale f32 [P] on the device."""
-    N, Mg = _hc_triplet_shapes('hc_triplet_bwd', q, g, lead, count, ws, result, P)
+    N, Mg = _hc_triplet_shapes('hc_triplet_bwd', q, g, None, None, lead, count, ws, result, P)
     L._req(gscale, torch.float32, 'gscale'); L._req(dq, torch.float32, 'dq'); L._req(dg, torch.float32, 'dg')
     if dq.shape != q.shape or dg.shape != g.shape or gscale.numel() < P:
         raise ValueError('hc_triplet_bwd: dq as q, dg as g, gscale [P]')
