@@ -453,6 +453,56 @@ int reid_hc_triplet_bwd(const float* q, int32_t ldq, const float* g, int32_t ldg
                         void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cross-batch memory for the cross-modal triplet loss (Wang et al., "Cross-Batch Memory for Embedding Learning", CVPR 2020; the
+ * reference has no such loss): the rows of the last batches stay in a ring on the device, and the anchors of the current batch mine
+ * their hardest positive / negative among ALL of the ring's rows, which are constants.  All fp32.
+ *   Sides: 0 = vis, 1 .. P = the P non-vis modalities (P <= 8).  The memory of capacity M (N <= M <= 8192) is
+ *     rows [P+1, M, D] f32 (contiguous) | mem_labels [M] int64 | mem_valid [P+1, M] uint8 | cursor int32 [2] = (next slot, rows ever
+ *     written; the count stops at 2^31 - 1), all on the device.  A fresh or reset memory: mem_valid = 0 everywhere, cursor = (0, 0).
+ *   A batch: q [P*N, D] (ldq) = the P non-vis sides stacked, g [N, D] (ldg) = the vis side, labels [N] int64, q_valid [P*N] / g_valid
+ *   [N] uint8 or NULL (all valid); row i of every side is the same instance.
+ *   reid_xbm_enqueue: row i of side s goes to slot (cursor[0] + i) mod M of side s (a batch may wrap; the oldest rows are overwritten),
+ *   as its unit row x * (1 / max(|x|, eps)) when normalize == 1 -- evaluated as reid_l2norm_rows evaluates it, bit for bit -- or as it
+ *   is; labels[i] and the sides' validity bytes go to the same slot (an invalid row is stored with mem_valid = 0).  Then the cursor
+ *   advances by N.  The cursor is read and written ON THE DEVICE (one launch for the rows, a one-thread launch behind it for the
+ *   cursor), so a captured graph that holds the call keeps filing rows where the last replay stopped.
+ *   reid_xbm_triplet_fwd mines the memory AS IT STANDS (call reid_xbm_enqueue first and the current batch is part of it, as in the
+ *   paper).  Per pair p, direction q->mem: every valid row of q's pair p is an anchor against the valid slots of side 0; direction
+ *   g->mem: every valid row of g is an anchor against the valid slots of side p + 1.  The rules are those of reid_cross_triplet_fwd:
+ *   hardest positive = same label at the largest d2, hardest negative = another label at the smallest d2; d2 in the difference form
+ *   in fp32; ties go to the lowest SLOT; no self-exclusion (an anchor never meets its own side); an anchor is active when it is valid
+ *   and has both, otherwise its indices are -1 and its distances and row loss 0; the two kept distances are re-evaluated with an fp64
+ *   sum, d = sqrt(max(d2, 1e-12)).  normalize == 1: the anchors are the unit rows of the batch (the ring is expected to hold unit rows
+ *   too).  Row loss l = max(0, d_ap - d_an + margin) for margin >= 0, softplus(d_ap - d_an) for margin < 0.
+ *   L_p = 0.5 * (sum over the active q anchors of l / max(1, n_q[p]) + sum over the active g anchors of l / max(1, n_g[p])), summed in a
+ *   fixed order in fp64; result [P, 4] = {L_p, flag_p, n_q[p], n_g[p]} with flag_p = 1 iff n_q + n_g > 0.
+ *   Saved: q_d [2, P*N] = d_ap | d_an, q_idx [2, P*N] = idx_p | idx_n (slots of side 0); g_d, g_idx [2, P*N] (slots of side p + 1);
+ *   ws (reid_xbm_ws_floats(P, N, M, D) floats, kept from fwd to bwd; a negative count = bad shape):
+ *     unit rows (P + 1) N D | COPIES of the two kept rows of every active anchor 2 P N x 2 D | 1 / max(|x|, eps) (P + 1) N | |x| (P + 1) N
+ *     | row losses 2 P N.
+ *   reid_xbm_triplet_bwd: dq [P*N, D] (lddq) and dg [N, D] (lddg) are OVERWRITTEN (invalid rows with zeros).  The memory's rows are
+ *   constants: an anchor gets only its own two terms, c ((x^ - m_p) / d_ap - (x^ - m_n) / d_an) with c = gscale[p] * 0.5 * l' /
+ *   max(1, n) (n of the anchor's direction; a term whose saved d is the clamp value is dropped); a g row adds its terms for p = 0 ..
+ *   P-1 in ascending order; then the projection through the normalisation exactly as reid_cross_triplet_bwd.  m_p and m_n are the
+ *   COPIES in ws: the backward never reads the ring, which later enqueues may have overwritten.
+ *   No atomics: two runs give the same bits in every output and in the ring.  Nothing is allocated, synchronised or read back.
+ * Requirements: those of reid_cross_triplet_* with Mg = N, and N <= M <= 8192; rows 16-byte aligned.  Anything else: REID_ERR_ARG
+ * before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int64_t reid_xbm_ws_floats(int32_t P, int32_t N, int32_t M, int32_t D);
+int reid_xbm_enqueue(const float* q, int32_t ldq, const float* g, int32_t ldg, const int64_t* labels, const uint8_t* q_valid,
+                     const uint8_t* g_valid, int32_t P, int32_t N, int32_t M, int32_t D, int32_t normalize, float eps,
+                     float* rows, int64_t* mem_labels, uint8_t* mem_valid, int32_t* cursor, void* stream);
+int reid_xbm_triplet_fwd(const float* q, int32_t ldq, const float* g, int32_t ldg, const int64_t* labels, const uint8_t* q_valid,
+                         const uint8_t* g_valid, int32_t P, int32_t N, int32_t M, int32_t D, float margin, int32_t normalize,
+                         float eps, const float* rows, const int64_t* mem_labels, const uint8_t* mem_valid, float* q_d,
+                         int32_t* q_idx, float* g_d, int32_t* g_idx, float* ws, float* result, void* stream);
+int reid_xbm_triplet_bwd(const float* q, int32_t ldq, const float* g, int32_t ldg, const uint8_t* q_valid, const uint8_t* g_valid,
+                         int32_t P, int32_t N, int32_t D, float margin, int32_t normalize, float eps, const float* q_d,
+                         const int32_t* q_idx, const float* g_d, const int32_t* g_idx, const float* ws, const float* result,
+                         const float* gscale, float* dq, int32_t lddq, float* dg, int32_t lddg, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Retrieval (train.py:499 + :463; tools/eval_mm_protocol.py:50-53,401-423,622-625):
  *   sim = Q . G^T on L2-normalised rows, per-query top-k in (score desc, index asc) order.
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;

@@ -97,6 +97,10 @@ SIGNATURES = {
     'reid_hc_triplet_ws_floats': (_I64, [_I, _I, _I, _I]),
     'reid_hc_triplet_fwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     'reid_hc_triplet_bwd': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _F, _I, _F, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    'reid_xbm_ws_floats': (_I64, [_I, _I, _I, _I]),
+    'reid_xbm_enqueue': (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    'reid_xbm_triplet_fwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    'reid_xbm_triplet_bwd': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
     'reid_topk_ws_bytes': (_I64, [_I, _I, _I]),
     'reid_topk_scan_ok': (_I, [_I, _I, _I, _I]),
     'reid_cosine_topk': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

@@ -93,6 +93,12 @@ class TrainingConfig:
     hc_triplet_weight: float = 0.0
     hc_triplet_margin: Optional[float] = 0.3         # None: soft margin
     hc_triplet_normalize: bool = True                # centres of unit rows
+    # nor these: cross-batch memory (XBM) for the cross-modal triplet loss, the anchors of a batch against the rows of the last batches
+    xbm_weight: float = 0.0
+    xbm_size: int = 4096                             # slots per side (batch size .. 8192)
+    xbm_margin: Optional[float] = 0.3                # None: soft margin
+    xbm_normalize: bool = True                       # the ring holds unit rows
+    xbm_start_epoch: int = 1                         # first epoch that enqueues and mines
     sdm_semantic_dim: int = 512
     sdm_num_heads: int = 8
     sdm_dropout: float = 0.1   # not a reference config field: hard-coded in SemanticDisentanglementModule (models/model.py:35,43)

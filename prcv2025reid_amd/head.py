@@ -319,6 +319,109 @@ def hetero_center_triplet(q, g, q_labels, g_labels, q_valid=None, g_valid=None, 
     return loss, flag, rows
 
 
+class CrossBatchMemory:
+    """The ring of xbm_cross_triplet (Wang et al., "Cross-Batch Memory for Embedding Learning", CVPR 2020; csrc/xbm.hip): the rows of
+    the last ``capacity`` instances of every side (side 0 = vis, 1 .. sides-1 = the non-vis modalities), their labels and validity
+    bytes, and a DEVICE-side cursor (next slot, rows ever written) that the enqueue kernels read and advance -- no host-side counter
+    takes part, so a captured graph keeps filing rows where its last replay stopped.  Plain tensors, not parameters or buffers: a
+    memory is not part of a state_dict, a resumed run refills it."""
+
+    def __init__(self, capacity, sides, dim, device='cuda'):
+        device = torch.device(device)
+        if device.type != 'cuda':
+            raise _lib.ReidHipError('CrossBatchMemory needs device tensors (there is no CPU path)')
+        if not (1 <= capacity <= 8192 and 2 <= sides <= 9 and dim % 4 == 0 and 4 <= dim <= 1024):
+            raise ValueError('CrossBatchMemory: capacity 1..8192, sides 2..9 (vis + 1..8 modalities), dim a multiple of 4 in 4..1024')
+        self.capacity, self.sides, self.dim = int(capacity), int(sides), int(dim)
+        self.rows = torch.zeros(sides, capacity, dim, device=device)
+        self.labels = torch.zeros(capacity, dtype=torch.int64, device=device)
+        self.valid = torch.zeros(sides, capacity, dtype=torch.uint8, device=device)
+        self.cursor = torch.zeros(2, dtype=torch.int32, device=device)
+
+    def reset(self):
+        """Empties the memory (device fills only)."""
+        for t in (self.rows, self.labels, self.valid, self.cursor):
+            t.zero_()
+
+    @property
+    def rows_written(self):
+        """Rows ever enqueued per side, read from the device when someone looks at it."""
+        from .model import LazyCount
+        return LazyCount(self.cursor[1])
+
+    @property
+    def filled(self):
+        """Slots that hold a row (valid or not), read from the device when someone looks at it."""
+        from .model import LazyCount
+        return LazyCount(self.cursor[1].clamp(max=self.capacity))
+
+
+class XbmTripletFn(torch.autograd.Function):
+    """(loss [P], flag [P], n_active [P, 2]) of the cross-modal batch-hard triplet loss with a cross-batch memory (csrc/xbm.hip; the
+    reference has no such loss): with ``enqueue`` the batch q [P, N, D], g [N, D] is first filed into ``memory`` (unit rows when
+    ``normalize``), then every valid q row of pair p mines the slots of memory side 0 and every valid g row the slots of side p + 1 by
+    the rules of CrossTripletFn; indices are slot numbers.  The memory's rows are constants: the gradient reaches the anchors only, from
+    copies of the kept rows the forward puts into its workspace (the ring may be overwritten before the backward runs).  ``rows_out``:
+    an optional trailing dict that receives COPIES of the saved arrays (xbm_cross_triplet); the call the model makes is
+    ``apply(q, g, labels, q_valid, g_valid, memory, margin, normalize, enqueue)``."""
+    @staticmethod
+    def forward(ctx, q, g, labels, q_valid, g_valid, memory, margin, normalize: bool, enqueue: bool, rows_out=None):
+        m = _margin_arg(XbmTripletFn, margin)
+        (P, N, D), dev = q.shape, q.device
+        if g.shape[0] != N or P + 1 != memory.sides:
+            raise ValueError(f'XbmTripletFn: q [P, N, D] and g [N, D] with P + 1 = {memory.sides} sides of the memory')
+        if N > memory.capacity:
+            raise ValueError(f'XbmTripletFn: a batch of N={N} rows does not fit a memory of {memory.capacity} slots')
+        if D != memory.dim:
+            raise _lib.ReidHipError(f'XbmTripletFn: the memory holds rows of D={memory.dim}, the batch has D={D}')
+        q2, g, qv, res = _two_sided_prepare(q, g, q_valid)
+        labels = labels.contiguous()
+        mem = (memory.rows, memory.labels, memory.valid)
+        if enqueue:
+            ops.xbm_enqueue(q2, g, labels, qv, g_valid, normalize, EPS, *mem, memory.cursor, P=P)
+        ws = torch.empty(ops.xbm_ws_floats(P, N, memory.capacity, D), device=dev)
+        qd = torch.empty(2, P * N, device=dev); qi = torch.empty(2, P * N, dtype=torch.int32, device=dev)
+        gd = torch.empty(2, P * N, device=dev); gi = torch.empty(2, P * N, dtype=torch.int32, device=dev)
+        ops.xbm_triplet_fwd(q2, g, labels, qv, g_valid, m, normalize, EPS, *mem, qd, qi, gd, gi, ws, res, P=P)
+        ctx.save_for_backward(q2, g, qv, g_valid, qd, qi, gd, gi, ws, res)
+        ctx.margin, ctx.normalize, ctx.P = m, bool(normalize), P
+        loss, flag, n_active = _two_sided_results(ctx, res)
+        if rows_out is not None:                              # copies: the saved arrays belong to the backward
+            for side, d, ix in (('q', qd, qi), ('g', gd, gi)):
+                rows_out.update({f'{side}_d_ap': d[0].view(P, N).clone(), f'{side}_d_an': d[1].view(P, N).clone(),
+                                 f'{side}_idx_p': ix[0].view(P, N).clone(), f'{side}_idx_n': ix[1].view(P, N).clone()})
+        return loss, flag, n_active
+
+    @staticmethod
+    def backward(ctx, dloss, _dflag, _dn):
+        q2, g, qv, gv, qd, qi, gd, gi, ws, res = ctx.saved_tensors
+        P = ctx.P
+        dq = torch.empty_like(q2); dg = torch.empty_like(g)
+        ops.xbm_triplet_bwd(q2, g, qv, gv, ctx.margin, ctx.normalize, EPS, qd, qi, gd, gi, ws, res, _gscale(dloss, P), dq, dg, P=P)
+        return dq.view(P, q2.shape[0] // P, q2.shape[1]), dg, None, None, None, None, None, None, None, None
+
+
+def xbm_cross_triplet(q, g, labels, memory, q_valid=None, g_valid=None, margin=0.3, normalize=True, enqueue=True):
+    """Cross-modal batch-hard triplet loss with a cross-batch memory, for users with their own loop: ``q`` [P, N, D] (P query
+    modalities stacked; [N, D] = one) and the vis features ``g`` [N, D] of the SAME N instances, ``labels`` [N], ``memory`` a
+    CrossBatchMemory(capacity >= N, P + 1, D).  With ``enqueue`` the batch is first filed into the memory at its cursor (the oldest
+    rows are overwritten), so it is part of what is mined; ``enqueue=False`` mines the memory as it stands and leaves it untouched.
+    Per pair, every valid q row mines its hardest positive / negative among the valid slots of memory side 0 (vis) and every valid g
+    row among those of side p + 1 (Euclidean distance of the unit rows, difference form, fp32; ties to the lowest slot);
+    L_p = 0.5 * (mean over the active q anchors + mean over the active g anchors).  The memory's rows are constants.  ``q_valid``
+    [P, N] / ``g_valid`` [N]: optional bool / uint8; ``margin`` None: soft margin; ``normalize`` False: the rows are used and stored
+    as they are.  Returns (losses [P], flags [P], rows): rows = {'q_d_ap', 'q_d_an', 'q_idx_p', 'q_idx_n', 'g_d_ap', 'g_d_an',
+    'g_idx_p', 'g_idx_n'} [P, N] (indices are slot numbers, -1 = inactive) plus 'n_active' [P, 2]; the losses carry the gradient to
+    ``q`` and ``g``."""
+    q, q_valid, g_valid = _two_sided_args('xbm_cross_triplet', q, g, labels, labels, q_valid, g_valid)
+    if not isinstance(memory, CrossBatchMemory):
+        raise TypeError('xbm_cross_triplet: memory must be a CrossBatchMemory')
+    rows = {}
+    loss, flag, n_active = XbmTripletFn.apply(q, g, labels.long(), q_valid, g_valid, memory, margin, bool(normalize), bool(enqueue), rows)
+    rows['n_active'] = n_active
+    return loss, flag, rows
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # Small fp32 pieces of SemanticDisentanglementModule (models/model.py:57-77) and FeatureFusion (:113-183)
 class AddFn(torch.autograd.Function):

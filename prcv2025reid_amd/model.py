@@ -37,7 +37,7 @@ from . import _lib, ops
 from .config import arch_of
 from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CrossEntropyLSFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn,
-                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn, HcTripletFn)
+                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn, HcTripletFn, XbmTripletFn, CrossBatchMemory)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -99,6 +99,13 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.hc_triplet_weight = getattr(config, 'hc_triplet_weight', 0.0)                # hetero-center triplet loss (not in the reference)
         self.hc_triplet_margin = getattr(config, 'hc_triplet_margin', 0.3)
         self.hc_triplet_normalize = getattr(config, 'hc_triplet_normalize', True)
+        self.xbm_weight = getattr(config, 'xbm_weight', 0.0)                              # cross-batch memory triplet loss (not in the reference)
+        self.xbm_size = getattr(config, 'xbm_size', 4096)
+        self.xbm_margin = getattr(config, 'xbm_margin', 0.3)
+        self.xbm_normalize = getattr(config, 'xbm_normalize', True)
+        self.xbm_start_epoch = getattr(config, 'xbm_start_epoch', 1)
+        self.xbm_memory = None               # a CrossBatchMemory made on first use; a plain attribute: not in state_dict()
+        self._xbm_sides = None               # the modality names of its sides 1 .. P
         self.num_classes = None
         self.bn_neck = None
         self._ref: "OrderedDict[str, nn.Parameter]" = OrderedDict()
@@ -595,8 +602,9 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         raw = outputs.get('raw_modality_features', {})
         use_xt = self.cross_triplet_weight > 0
         use_hc = self.hc_triplet_weight > 0
+        use_xbm = self.xbm_weight > 0 and self.current_epoch >= self.xbm_start_epoch
         q = None
-        if (use_sdm or use_xt or use_hc) and 'vis' in raw and 'vis' in fm:
+        if (use_sdm or use_xt or use_hc or use_xbm) and 'vis' in raw and 'vis' in fm:
             gv = cent['gv']
             mods = [m for m in raw if m != 'vis' and m in fm]
             if mods:
@@ -634,7 +642,28 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             out['total_loss'] = out['total_loss'] + self.hc_triplet_weight * hc
             out['hc_triplet_loss'] = hc
             out['hc_triplet_active_cnt'] = LazyCount(n_act.sum())
+        if use_xbm and q is not None:
+            # cross-batch memory (csrc/xbm.hip) on the same stack: the batch is filed into the ring (training with gradients only), then
+            # every anchor mines the ring; the ring's rows are constants.  Under DataParallel the raw features and labels are the global
+            # batch on every rank, so every rank keeps an identical memory and no collective is added
+            if self.xbm_memory is None:
+                self.xbm_memory = CrossBatchMemory(self.xbm_size, len(mods) + 1, q.shape[2], dev)
+                self._xbm_sides = tuple(mods)
+            elif self._xbm_sides != tuple(mods):
+                raise ValueError(f'the cross-batch memory was made for the modalities {self._xbm_sides}, this batch brings {tuple(mods)}: '
+                                 'set model.xbm_memory = None to start a new one')
+            L, flag, n_act = XbmTripletFn.apply(q, raw['vis'], labels, qv, gv, self.xbm_memory, self.xbm_margin, bool(self.xbm_normalize),
+                                                bool(self.training and torch.is_grad_enabled()))
+            xbm = L.sum() / flag.sum().clamp_min(1.0)                                            # mean over the pairs with an active anchor
+            out['total_loss'] = out['total_loss'] + self.xbm_weight * xbm
+            out['xbm_loss'] = xbm
+            out['xbm_active_cnt'] = LazyCount(n_act.sum())
         return out
+
+    def reset_xbm(self):
+        """Empties the cross-batch memory in place (device fills: a captured graph that holds it stays valid)."""
+        if self.xbm_memory is not None:
+            self.xbm_memory.reset()
 
     # ------------------------------------------------------------------ optimiser groups
     def get_learnable_params(self) -> List[Dict[str, Any]]:

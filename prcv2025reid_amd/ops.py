@@ -444,6 +444,95 @@ def hc_triplet_bwd(q, g, margin, normalize, eps, lead, count, ws, result, gscale
                                     stream_ptr()))
 
 
+def xbm_ws_floats(P, N, M, D):
+    return _ws_floats(lib().reid_xbm_ws_floats, P, N, M, D)
+
+
+def _xbm_memory_shapes(who, q, g, rows, mem_labels, mem_valid, P):
+    """The checks of a cross-batch memory against a batch: q [P*N, D], g [N, D]; rows f32 [P+1, M, D], mem_labels i64 [M], mem_valid
+    u8 [P+1, M], all contiguous.  Returns (N, M)."""
+    for n, t, d in (('q', q, torch.float32), ('g', g, torch.float32), ('rows', rows, torch.float32), ('mem_labels', mem_labels, torch.int64),
+                    ('mem_valid', mem_valid, torch.uint8)):
+        L._req(t, d, n)
+    if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] != P * g.shape[0] or g.shape[1] != q.shape[1]:
+        raise ValueError(f'{who}: q [P*N, D], g [N, D]')
+    N, D = g.shape
+    if rows.dim() != 3 or rows.shape[0] != P + 1 or rows.shape[2] != D:
+        raise L.ReidHipError(f'{who}: the memory holds rows {tuple(rows.shape)}, the batch needs [{P + 1}, M, {D}]')
+    M = rows.shape[1]
+    if mem_labels.shape != (M,) or mem_valid.shape != (P + 1, M) or not (rows.is_contiguous() and mem_labels.is_contiguous()
+                                                                         and mem_valid.is_contiguous()):
+        raise ValueError(f'{who}: rows [P+1, M, D], mem_labels [M], mem_valid [P+1, M], all contiguous')
+    if N > M:
+        raise ValueError(f'{who}: a batch of N={N} rows does not fit a memory of M={M} slots')
+    return N, M
+
+
+def _xbm_valid(who, q_valid, g_valid, P, N):
+    for n, t, rows in (('q_valid', q_valid, P * N), ('g_valid', g_valid, N)):
+        if t is not None:
+            L._req(t, torch.uint8, n)
+            if t.numel() != rows:
+                raise ValueError(f'{who}: {n} has {t.numel()} elements, not {rows}')
+
+
+def xbm_enqueue(q, g, labels, q_valid, g_valid, normalize, eps, rows, mem_labels, mem_valid, cursor, P=1):
+    """Files the batch q [P*N, D], g [N, D], labels [N] into the cross-batch memory (rows [P+1, M, D], mem_labels [M], mem_valid
+    [P+1, M], cursor i32 [2], side 0 = g) at the device-side cursor and advances it by N; unit rows when ``normalize``."""
+    N, M = _xbm_memory_shapes('xbm_enqueue', q, g, rows, mem_labels, mem_valid, P)
+    _xbm_valid('xbm_enqueue', q_valid, g_valid, P, N)
+    L._req(labels, torch.int64, 'labels'); L._req(cursor, torch.int32, 'cursor')
+    if labels.numel() != N or cursor.numel() != 2 or not cursor.is_contiguous():
+        raise ValueError('xbm_enqueue: labels [N], cursor [2]')
+    check(lib().reid_xbm_enqueue(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(labels), ptr(q_valid), ptr(g_valid), P, N, M, q.shape[1],
+                                 int(normalize), eps, ptr(rows), ptr(mem_labels), ptr(mem_valid), ptr(cursor), stream_ptr()))
+
+
+def _xbm_saved_shapes(who, q_d, q_idx, g_d, g_idx, ws, result, P, N, M, D):
+    for n, t, d in (('q_d', q_d, torch.float32), ('q_idx', q_idx, torch.int32), ('g_d', g_d, torch.float32), ('g_idx', g_idx, torch.int32),
+                    ('ws', ws, torch.float32), ('result', result, torch.float32)):
+        L._req(t, d, n)
+    if min(q_d.numel(), q_idx.numel(), g_d.numel(), g_idx.numel()) < 2 * P * N or result.numel() < 4 * P \
+            or not all(t.is_contiguous() for t in (q_d, q_idx, g_d, g_idx, ws, result)):
+        raise ValueError(f'{who}: q_d / q_idx / g_d / g_idx [2, P*N], result [P, 4], all contiguous')
+    if ws.numel() < xbm_ws_floats(P, N, M, D):
+        raise ValueError(f'{who}: ws holds fewer than xbm_ws_floats(P, N, M, D) floats')
+
+
+def xbm_triplet_fwd(q, g, labels, q_valid, g_valid, margin, normalize, eps, rows, mem_labels, mem_valid, q_d, q_idx, g_d, g_idx, ws,
+                    result, P=1):
+    """Cross-modal batch-hard triplet loss of the batch against the cross-batch memory as it stands: the q rows of pair p against the
+    slots of side 0, the g rows against the slots of side p + 1; margin < 0 selects the soft-margin form.  q_d / q_idx, g_d / g_idx
+    [2, P*N] = (d_ap | d_an), (idx_p | idx_n) as SLOT numbers; result f32 [P, 4] = (L_p, flag_p, n_q, n_g); ws is kept for
+    xbm_triplet_bwd, with copies of the kept rows."""
+    N, M = _xbm_memory_shapes('xbm_triplet_fwd', q, g, rows, mem_labels, mem_valid, P)
+    _xbm_valid('xbm_triplet_fwd', q_valid, g_valid, P, N)
+    _xbm_saved_shapes('xbm_triplet_fwd', q_d, q_idx, g_d, g_idx, ws, result, P, N, M, q.shape[1])
+    L._req(labels, torch.int64, 'labels')
+    if labels.numel() != N:
+        raise ValueError('xbm_triplet_fwd: labels [N]')
+    check(lib().reid_xbm_triplet_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(labels), ptr(q_valid), ptr(g_valid), P, N, M, q.shape[1],
+                                     margin, int(normalize), eps, ptr(rows), ptr(mem_labels), ptr(mem_valid), ptr(q_d), ptr(q_idx),
+                                     ptr(g_d), ptr(g_idx), ptr(ws), ptr(result), stream_ptr()))
+
+
+def xbm_triplet_bwd(q, g, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, g_d, g_idx, ws, result, gscale, dq, dg, P=1):
+    """dq [P*N, D], dg [N, D] (both overwritten, one launch) from what xbm_triplet_fwd saved -- the memory itself is not read;
+    gscale f32 [P] on the device."""
+    for n, t in (('q', q), ('g', g), ('gscale', gscale), ('dq', dq), ('dg', dg)):
+        L._req(t, torch.float32, n)
+    if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] != P * g.shape[0] or g.shape[1] != q.shape[1]:
+        raise ValueError('xbm_triplet_bwd: q [P*N, D], g [N, D]')
+    N, D = g.shape
+    _xbm_valid('xbm_triplet_bwd', q_valid, g_valid, P, N)
+    _xbm_saved_shapes('xbm_triplet_bwd', q_d, q_idx, g_d, g_idx, ws, result, P, N, N, D)
+    if dq.shape != q.shape or dg.shape != g.shape or gscale.numel() < P:
+        raise ValueError('xbm_triplet_bwd: dq as q, dg as g, gscale [P]')
+    check(lib().reid_xbm_triplet_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_valid), ptr(g_valid), P, N, D, margin, int(normalize),
+                                     eps, ptr(q_d), ptr(q_idx), ptr(g_d), ptr(g_idx), ptr(ws), ptr(result), ptr(gscale), ptr(dq),
+                                     dq.stride(0), ptr(dg), dg.stride(0), stream_ptr()))
+
+
 # ----------------------------------------------------------------------------------------- retrieval
 def topk_ws_bytes(Nq, Ng, k):
     return int(lib().reid_topk_ws_bytes(Nq, Ng, k))
