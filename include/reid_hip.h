@@ -614,6 +614,31 @@ int reid_opt_adamw(const void* table, int32_t n_entries, const float* coef, floa
                    int32_t step, int32_t zero_grad, float* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exponential moving average of the trainable weights (csrc/ema.hip): the model the evaluator scores and the best checkpoint is
+ * chosen on.  A DEVICE table of reid_ema_entry records of its own (parameter p, shadow s, both flat fp32 and 16-byte aligned, n
+ * elements), so buffers reid_opt_adamw never sees (BatchNorm running statistics) can be averaged by the same launch.
+ *   reid_ema_update  per element s := s + w * (p - s), the difference, the product and the sum each rounded once to fp32 (never
+ *                    contracted into a fused multiply-add: a float32 loop on the host reproduces the bits);
+ *                    w = (float)(1.0 - d_t), d_t = min((double)decay, (1 + t) / (10 + t)) when warmup != 0, else (double)decay,
+ *                    evaluated in double; t = 1-based number of the optimizer step just taken: step >= 1 gives it from the host,
+ *                    step == 0 reads it from state[16], the counter reid_opt_adamw(step == 0) has advanced on the same stream --
+ *                    the form a captured HIP graph replays.  state is only read, and only when step == 0.
+ *   reid_ema_swap    exchanges p[i] and s[i] IN PLACE as raw 32-bit words (NaN payloads, -0 and denormals survive): every pointer
+ *                    held elsewhere -- the optimizer table, a captured graph's kernel arguments, views of the parameters -- stays
+ *                    valid, and a second swap restores both sides exactly.
+ * Refused before any launch: decay outside (0, 1), a null table, n_entries < 1 (or > 65535, the grid's y extent), step < 0, step == 0
+ * without state.  No atomics, nothing is allocated, nothing is synchronised; grid = 128 x n_entries workgroups.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct reid_ema_entry {
+    float* p; float* s;
+    int64_t n;
+} reid_ema_entry;
+int32_t reid_ema_entry_bytes(void);
+int reid_ema_update(const void* table, int32_t n_entries, float decay, int32_t warmup, int32_t step, const float* state,
+                    void* stream);
+int reid_ema_swap(const void* table, int32_t n_entries, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * AP / CMC from fp32 similarity rows: the metric half of rank_and_metrics,
  * tools/eval_mm_protocol.py:401-469 (and _reid_map, train.py:450-479) without sorting the gallery.
  *   scores  f32 [nq, ld] (ld % 4 == 0, 16-byte aligned): cosine similarities of nq queries against Ng gallery rows

@@ -121,6 +121,9 @@ SIGNATURES = {
     'reid_opt_sumsq': (_I, [_P, _I, _P, _P]),
     'reid_opt_clip': (_I, [_P, _I, _P, _I, _F, _I, _P]),
     'reid_opt_adamw': (_I, [_P, _I, _P, _F, _F, _F, _I, _I, _P, _P]),
+    'reid_ema_entry_bytes': (_I, []),
+    'reid_ema_update': (_I, [_P, _I, _F, _I, _I, _P, _P]),
+    'reid_ema_swap': (_I, [_P, _I, _P]),
     'reid_rank_metrics': (_I, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     'reid_rows_topk': (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _P]),
     'reid_augment_ws_bytes': (_I64, [_I, _I]),

@@ -105,9 +105,21 @@ def full_state_dict(model, kept_dead: Optional[Dict[str, torch.Tensor]] = None) 
     return out
 
 
-def save_checkpoint(model, optimizer, scheduler_state, epoch: int, best_map: float, config, filename: str):
+def _has_ema(optimizer) -> bool:
+    return getattr(optimizer, 'ema_decay', None) is not None
+
+
+def save_checkpoint(model, optimizer, scheduler_state, epoch: int, best_map: float, config, filename: str, use_ema: bool = False):
     """train.py:1785-1796, same dictionary.  ``optimizer`` may be a FusedAdamW (its moments are written in
-    torch.optim.AdamW's state-dict layout) or any torch optimizer."""
+    torch.optim.AdamW's state-dict layout) or any torch optimizer.
+
+    An optimizer that keeps a weight EMA (``FusedAdamW(ema_decay=...)``) adds one key, ``ema_state_dict`` = its ``ema_state()``
+    (decay, warm-up flag, update count, shadows on the CPU); without an EMA the dictionary has exactly the reference's keys.
+    ``use_ema=True`` writes the AVERAGED weights as ``model_state_dict`` (swap, ``full_state_dict``, swap back), so the file
+    loads into the reference unchanged and evaluates as the average; the optimizer state and ``ema_state_dict`` are the same
+    either way."""
+    if use_ema and not _has_ema(optimizer):
+        raise ValueError('use_ema=True needs an optimizer that keeps an EMA (FusedAdamW(ema_decay=...))')
     os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
     if hasattr(optimizer, 'exp_avg'):        # prcv2025reid_amd.trainer.FusedAdamW
         state, groups, i = {}, [], 0
@@ -122,10 +134,17 @@ def save_checkpoint(model, optimizer, scheduler_state, epoch: int, best_map: flo
         opt_state = {'state': state, 'param_groups': groups}
     else:
         opt_state = optimizer.state_dict() if optimizer is not None else None
-    ckpt = {'epoch': epoch, 'model_state_dict': full_state_dict(model), 'optimizer_state_dict': opt_state,
+    if use_ema:
+        with optimizer.ema_weights():
+            model_state = full_state_dict(model)
+    else:
+        model_state = full_state_dict(model)
+    ckpt = {'epoch': epoch, 'model_state_dict': model_state, 'optimizer_state_dict': opt_state,
             'scheduler_state_dict': scheduler_state, 'best_map': best_map,
             'num_classes': getattr(config, 'num_classes', None) or model.num_classes,
             'config': dict(config.__dict__) if hasattr(config, '__dict__') else str(config)}
+    if _has_ema(optimizer):
+        ckpt['ema_state_dict'] = optimizer.ema_state()
     torch.save(ckpt, filename)
     return ckpt
 
@@ -147,7 +166,13 @@ def load_checkpoint(filename: str, model, optimizer=None, strict: bool = True) -
             if i in st:
                 optimizer.exp_avg[i].copy_(st[i]['exp_avg']); optimizer.exp_avg_sq[i].copy_(st[i]['exp_avg_sq'])
                 optimizer.step_count = int(st[i]['step'])
-    return {k: v for k, v in ckpt.items() if k not in ('model_state_dict', 'optimizer_state_dict')} if isinstance(ckpt, dict) else {}
+    if _has_ema(optimizer):                  # after step_count: the EMA's update count is kept relative to it
+        if isinstance(ckpt, dict) and ckpt.get('ema_state_dict'):
+            optimizer.load_ema_state(ckpt['ema_state_dict'])
+        else:                                # a checkpoint without an average: start it from the weights just loaded, not from
+            optimizer.reset_ema()            # the ones the optimizer was constructed on
+    return ({k: v for k, v in ckpt.items() if k not in ('model_state_dict', 'optimizer_state_dict', 'ema_state_dict')}
+            if isinstance(ckpt, dict) else {})
 
 
 # ------------------------------------------------------------------------------------------------------------------

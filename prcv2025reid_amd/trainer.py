@@ -5,7 +5,9 @@ reference's parameter groups, the warm-up + cosine LambdaLR -- without its host 
 The reference pays one ``.item()`` per parameter tensor for the gradient norm and one masked assignment per tensor for
 the sanitiser (~1.2 k tensors).  Here the trainable set is a few flat fp32 buffers (the LoRA arena is one tensor) held
 in a device table, and a step is three launches of libreid_hip (csrc/optim.hip); the adaptive rule's history and
-percentile live on the device, so nothing is read back unless the caller asks for the statistics.
+percentile live on the device, so nothing is read back unless the caller asks for the statistics.  An optional fourth
+launch (csrc/ema.hip, ``FusedAdamW(ema_decay=...)``) keeps an exponential moving average of the trainable weights for
+evaluation; the reference keeps none.
 
 Semantics kept from the reference (file:line):
   * gradients accumulate over ``accum_steps`` micro-batches with ``loss / accum_steps`` (train.py:833-834, 895, 975);
@@ -19,6 +21,7 @@ Semantics kept from the reference (file:line):
 One deliberate difference: a non-finite LOSS does not skip the backward pass through a host check
 (train.py:872-879 reads the loss with ``.item()``); its gradients are non-finite and are zeroed by the sanitiser.
 """
+import contextlib
 import ctypes as C
 import math
 from typing import Any, Dict, List, Optional
@@ -49,14 +52,28 @@ class _Entry(C.Structure):
                 ('lr', C.c_float), ('wd', C.c_float)]
 
 
+class _EmaEntry(C.Structure):
+    _fields_ = [('p', C.c_void_p), ('s', C.c_void_p), ('n', C.c_int64)]
+
+
 class FusedAdamW:
     """AdamW over ``param_groups`` (the list ``model.get_learnable_params()`` returns, filtered to ``requires_grad``).
 
     Gradients live in persistent buffers (``p.grad`` is created once and zeroed by the step kernel), so the device table
     is built once and only rewritten when a learning rate changes.
+
+    ``ema_decay`` (None = off: nothing is allocated, nothing is launched) keeps an exponential moving average of every trainable
+    parameter and of every tensor in ``ema_buffers`` (meant for the BN-neck's ``running_mean`` / ``running_var``, which the
+    forward updates in place) in shadow tensors that start equal to their sources: ``step`` launches ``reid_ema_update``
+    (csrc/ema.hip) right after the AdamW kernel, s += w (p - s) with w = 1 - min(decay, (1 + t) / (10 + t)) at optimizer step t
+    (``ema_warmup``; w = 1 - decay without it).  Frozen tensors are not averaged, buffers only when listed.  ``ema_weights()`` /
+    ``swap_ema()`` exchange parameters and shadows IN PLACE, so the optimizer table, a captured graph and the engine's views stay
+    valid.  Under ``parallel.DataParallel`` the parameters are identical on every rank after ``reduce_grads``, so the shadows are
+    too: no collective is added for them (listed buffers are averaged per rank, as the forward leaves them).
     """
 
-    def __init__(self, param_groups: List[Dict[str, Any]], weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8):
+    def __init__(self, param_groups: List[Dict[str, Any]], weight_decay: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, ema_buffers=()):
         self.param_groups = []
         for g in param_groups:
             ps = [p for p in g['params'] if p.requires_grad]
@@ -85,6 +102,22 @@ class FusedAdamW:
         self.state = torch.zeros(lib().reid_opt_state_floats(), device=dev)
         self._table = torch.empty(n * C.sizeof(_Entry), dtype=torch.uint8, device=dev)
         self._write_table()
+        self.ema_decay, self.ema_warmup, self.ema_buffers, self.ema_shadow = None, bool(ema_warmup), [], []
+        self._ema_swapped, self._ema_step0 = False, 0
+        if ema_decay is not None:
+            if not 0.0 < float(ema_decay) < 1.0:
+                raise ValueError('ema_decay must lie in (0, 1)')
+            self.ema_decay, self.ema_buffers = float(ema_decay), list(ema_buffers)
+            for b in self.ema_buffers:
+                if b.device != dev or b.dtype != torch.float32 or not b.is_contiguous() or b.data_ptr() % 16:
+                    raise ValueError('ema_buffers must be contiguous, 16-byte aligned fp32 tensors on the optimizer\'s device')
+            self.ema_shadow = [t.detach().clone() for t in self.ema_sources()]
+            assert lib().reid_ema_entry_bytes() == C.sizeof(_EmaEntry)
+            ents = (_EmaEntry * len(self.ema_shadow))(*[_EmaEntry(t.data_ptr(), s.data_ptr(), t.numel())
+                                                        for t, s in zip(self.ema_sources(), self.ema_shadow)])
+            self._ema_table = torch.frombuffer(bytearray(bytes(ents)), dtype=torch.uint8).to(dev)
+        elif len(ema_buffers):
+            raise ValueError('ema_buffers without ema_decay')
 
     def _write_table(self):
         ents = (_Entry * len(self.params))()
@@ -128,6 +161,8 @@ class FusedAdamW:
         ``device_counters``: the step number (bias correction) and the record-every-200 decision are taken from counters in
         the device state instead of host arguments, so the three launches can be captured once and replayed as a HIP graph
         (``record_norm`` is then the period, e.g. 200)."""
+        if self._ema_swapped:
+            raise RuntimeError('the parameters hold the averaged weights (swap_ema / ema_weights): swap back before stepping')
         if [p.grad.data_ptr() if p.grad is not None else 0 for p in self.params] != self._grad_ptrs:
             self._write_table()                              # someone replaced a .grad tensor
         n = len(self.params)
@@ -138,9 +173,75 @@ class FusedAdamW:
         coef = self.state.data_ptr() + 8                     # state[2]
         check(lib().reid_opt_adamw(ptr(self._table), n, coef, self.betas[0], self.betas[1], self.eps,
                                    0 if device_counters else self.step_count, int(zero_grad), ptr(self.state), stream_ptr()))
+        if self.ema_decay is not None:                       # t = the step just taken: state[16] after the tick, or the host's count
+            check(lib().reid_ema_update(ptr(self._ema_table), len(self.ema_shadow), self.ema_decay, int(self.ema_warmup),
+                                        0 if device_counters else self.step_count, ptr(self.state), stream_ptr()))
         # the kernel wrote through raw pointers: tell autograd / the engine's pack cache (engine.refresh keys on _version)
         for p in self.params:
             torch.autograd.graph.increment_version(p)
+
+    # ------------------------------------------------------------------------------------------------ weight EMA
+    def ema_sources(self) -> List[torch.Tensor]:
+        """The averaged tensors in table order: every trainable parameter, then ``ema_buffers``."""
+        return list(self.params) + list(self.ema_buffers)
+
+    @property
+    def ema_num_updates(self) -> int:
+        """EMA updates so far: one per optimizer step since the shadows were created, reset or loaded."""
+        return self.step_count - self._ema_step0 if self.ema_decay is not None else 0
+
+    def _need_ema(self, live: bool = True):
+        if self.ema_decay is None:
+            raise RuntimeError('this optimizer keeps no EMA (ema_decay=None)')
+        if live and self._ema_swapped:
+            raise RuntimeError('the parameters hold the averaged weights (swap_ema / ema_weights): swap back first')
+
+    def swap_ema(self):
+        """Exchange parameters (and listed buffers) with their shadows in place; a second call restores both, bit for bit."""
+        self._need_ema(live=False)
+        check(lib().reid_ema_swap(ptr(self._ema_table), len(self.ema_shadow), stream_ptr()))
+        self._ema_swapped = not self._ema_swapped
+        for t in self.ema_sources():                         # engine.refresh re-merges the LoRA weights and re-packs
+            torch.autograd.graph.increment_version(t)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with opt.ema_weights(): evaluate(model)`` -- the model computes with the averaged weights inside the block and has
+        its live ones back afterwards, also after an exception."""
+        self._need_ema()
+        self.swap_ema()
+        try:
+            yield self
+        finally:
+            if self._ema_swapped:
+                self.swap_ema()
+
+    def reset_ema(self):
+        """Shadows := the current parameters / buffers, update count := 0 (after loading weights that carry no average)."""
+        self._need_ema()
+        for t, s in zip(self.ema_sources(), self.ema_shadow):
+            s.copy_(t.detach())
+        self._ema_step0 = self.step_count
+
+    def ema_state(self) -> Dict[str, Any]:
+        """{'decay', 'warmup', 'num_updates', 'shadows': CPU copies in ``ema_sources()`` order} (synchronises)."""
+        self._need_ema()
+        return dict(decay=self.ema_decay, warmup=self.ema_warmup, num_updates=self.ema_num_updates,
+                    shadows=[s.detach().cpu() for s in self.ema_shadow])
+
+    def load_ema_state(self, state: Dict[str, Any]):
+        """Restore what ``ema_state`` returned; ``step_count`` must already hold its restored value (the update count is kept
+        relative to it)."""
+        self._need_ema()
+        sh = state['shadows']
+        if len(sh) != len(self.ema_shadow) or any(tuple(a.shape) != tuple(b.shape) for a, b in zip(sh, self.ema_shadow)):
+            raise ValueError('EMA state does not match this optimizer\'s averaged tensors')
+        if not 0.0 < float(state['decay']) < 1.0:
+            raise ValueError('ema_decay must lie in (0, 1)')
+        self.ema_decay, self.ema_warmup = float(state['decay']), bool(state['warmup'])
+        for a, b in zip(sh, self.ema_shadow):
+            b.copy_(a)
+        self._ema_step0 = self.step_count - int(state['num_updates'])
 
     def stats(self) -> Dict[str, float]:
         """Host copy of the last step's statistics (synchronises)."""
@@ -193,7 +294,8 @@ class GraphedStep:
     GPU per 52 ms step in eager mode).
 
     NOTE: construction runs ``warmup`` REAL optimizer steps on the sample batch (lazy initialisation, routing plan, allocator
-    pools) before the capture -- parameters, moments and the step count advance by that many steps.
+    pools) before the capture -- parameters, moments and the step count advance by that many steps, and so do the optimizer's
+    EMA shadows (``ema_decay``) and their update count: the update launch is part of ``FusedAdamW.step`` and is captured with it.
 
     Constraints of a captured step: single process (collectives are left to the eager path), ``accum_steps == 1``, static
     shapes -- the batch layout AND the modality-mask pattern are part of the graph (masked rows are compacted on the host
