@@ -727,6 +727,56 @@ int reid_expand_rows(const float* x, int64_t ldx, const float* table, int64_t ld
                      int32_t normalize, float eps, float* out, int64_t ldo, int32_t rows, int32_t D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cosine-margin identity heads with a fused label-smoothed CE (csrc/margin_ce.hip; the reference has none: its identity branch is
+ * a plain Linear followed by label-smoothed CE).  All fp32, no atomics (two runs give the same bits), nothing allocated, nothing
+ * read back.  No alignment or leading-dimension multiple is asked for; padding columns are neither read nor written.
+ *   x f32 [B, ldx >= D] (not assumed unit), W f32 [C, ldw >= D], scale s > 0, margin m, eps >= 0 (1e-12 = F.normalize's default).
+ *   rx_b = 1 / max(|x_b|, eps), rw_c = 1 / max(|W_c|, eps), cos_bc = (x_b . W_c) rx_b rw_c, logits l_bc = s cos_bc.
+ *   A row whose norm is below eps is divided by eps, and its gradient has no projection term (F.normalize).
+ * The dot products of this head cancel (a class centre against an unrelated row; a gradient that is orthogonal to its own row), so
+ * products and sums are formed in fp64 and every output is rounded to fp32 once.
+ * reid_cos_logits_fwd       rx f64 [B], rw f64 [C] (kept for the backward) and logits f32 [B, ldl >= C]; two launches (inverse
+ *       norms; 32 x 32 tiles of the products with the scaling as their epilogue).
+ * reid_cos_logits_bwd_prep  from g = dL/dl f32 [B, ldg >= C]: G f64 [B, D] = g (rw . W), G_b = sum_c g_bc rw_c W_c (NULL: dx is not
+ *       wanted; W and rw are then not read) and H f64 [C, D] = g^T (rx . x), H_c = sum_b g_bc rx_b x_b (NULL: dW is not wanted), each
+ *       summed in a fixed order; one launch.
+ * reid_cos_logits_bwd_fix   dx_b = s rx_b (G_b - xh_b (xh_b . G_b)), xh_b = x_b rx_b, and dW_c = s rw_c (H_c - wh_c (wh_c . H_c)),
+ *       wh_c = W_c rw_c: with dz = s g rx_b rw_c and tb_b = sum_c g_bc l_bc = s xh_b . G_b these are dz W - x_b rx_b^2 tb_b and
+ *       dz^T x - W_c rw_c^2 tc_c.  dx f32 [B, lddx >= D] or dW f32 [C, lddw >= D] may be NULL (with its inputs); one launch.
+ * Margin logits z' of a row with label y (kind: REID_MARGIN_*; cos = l / s):
+ *   COSINE   z' = l (margin ignored)
+ *   COSFACE  z'_y = l_y - s m (0 <= m < 1)
+ *   ARCFACE  t = clamp(cos_y, -1 + 2^-23, 1 - 2^-23); phi = t cos(m) - sqrt(1 - t^2) sin(m) where t > cos(pi - m), else
+ *            t - m sin(pi - m); z'_y = s phi (0 <= m < pi/2).  dphi/dt = cos(m) + t sin(m) / sqrt(1 - t^2), 1 in the fallback, and
+ *            0 where the clamp acted (torch.clamp).
+ *   CIRCLE   alpha_p = max(1 + m - cos_y, 0), alpha_n = max(cos_c + m, 0), constants of the gradient; z'_y = s alpha_p (cos_y - (1 - m)),
+ *            z'_c = s alpha_n (cos_c - m) for c != y (0 <= m < 1)
+ *   every other class: z'_c = l_c.
+ * Row loss = (1 - e)(lse(z') - z'_y) + e (lse(z') - mean_c z'_c), e = smoothing in [0, 1]; rows with valid == 0 (valid u8 [rows],
+ * NULL: all) or a label outside [0, C) are unused: loss 0, gradient 0.
+ * reid_margin_ce_fwd   row_loss f32 [rows]; result f32 [3] = (sum of the used rows' losses, their count, the mean = sum /
+ *       max(count, 1)), added in fp64 in a fixed order; two launches; z' is never written to memory.
+ * reid_margin_ce_bwd   dlogits f32 [rows, lddl >= C] = gs (p - e / C - (1 - e)[c == y]) dz'_c/dl_c, p = softmax(z'),
+ *       gs = dloss[0] / max(result[1], 1) (dloss: a device scalar, the cotangent of the mean); unused rows are written as zeros.
+ * ------------------------------------------------------------------------------------------ */
+#define REID_MARGIN_COSINE 0
+#define REID_MARGIN_COSFACE 1
+#define REID_MARGIN_ARCFACE 2
+#define REID_MARGIN_CIRCLE 3
+int reid_cos_logits_fwd(const float* x, int32_t ldx, const float* W, int32_t ldw, int32_t B, int32_t C, int32_t D, float scale,
+                        float eps, double* rx, double* rw, float* logits, int32_t ldl, void* stream);
+int reid_cos_logits_bwd_prep(const float* g, int32_t ldg, const float* x, int32_t ldx, const float* W, int32_t ldw, const double* rx,
+                             const double* rw, int32_t B, int32_t C, int32_t D, double* G, double* H, void* stream);
+int reid_cos_logits_bwd_fix(const float* x, int32_t ldx, const double* rx, const double* G, float* dx, int32_t lddx, const float* W,
+                            int32_t ldw, const double* rw, const double* H, float* dW, int32_t lddw, int32_t B, int32_t C, int32_t D,
+                            float scale, float eps, void* stream);
+int reid_margin_ce_fwd(const float* logits, int32_t ld, const int64_t* labels, const uint8_t* valid, int32_t rows, int32_t C,
+                       int32_t kind, float scale, float margin, float smoothing, float* row_loss, float* result, void* stream);
+int reid_margin_ce_bwd(const float* logits, int32_t ld, const int64_t* labels, const uint8_t* valid, int32_t rows, int32_t C,
+                       int32_t kind, float scale, float margin, float smoothing, const float* result, const float* dloss,
+                       float* dlogits, int32_t lddl, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * k-reciprocal re-ranking (Zhong et al., CVPR 2017) of pooled unit rows X = [Q; G], N = Nq + Ng <= 65 536, dense; the
  * definition is DESIGN.md "k-reciprocal re-ranking" (the reference has none).  kh = round-half-to-even(k1 / 2).
  *   nbr   i32 [N, ldn >= k1 + 1]: row i of the pooled ranking (score descending, index ascending; i itself is an entry)

@@ -33,6 +33,7 @@ def t16() -> torch.dtype:
 ABI_VERSION = 201                 # REID_ABI_VERSION of include/reid_hip.h: a library that reports anything else is a stale build
 BF16, F32, F16 = 0, 1, 2          # reid_dtype: BF16 = the flavor's 16-bit format, F16 = IEEE half whatever the flavor
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU, ACT_DGELU, ACT_DQUICK_GELU, ACT_DRELU, ACT_MUL_AUX, ACT_GELU_DSAVE = range(9)
+MARGIN_KINDS = {'cosine': 0, 'cosface': 1, 'arcface': 2, 'circle': 3}      # REID_MARGIN_*
 
 
 class GemmArgs(C.Structure):
@@ -129,6 +130,11 @@ SIGNATURES = {
     'reid_augment_ws_bytes': (_I64, [_I, _I]),
     'reid_augment_images': (_I, [_P, _I64, _P, _P, _I, _I, _P, _P, _I64, _P, _P]),
     'reid_expand_rows': (_I, [_P, _I64, _P, _I64, _I, _P, _P, _I, _I, _I, _I, _I64, _I, _F, _P, _I64, _I, _I, _P]),
+    'reid_cos_logits_fwd': (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _F, _P, _P, _P, _I, _P]),
+    'reid_cos_logits_bwd_prep': (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    'reid_cos_logits_bwd_fix': (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
+    'reid_margin_ce_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P]),
+    'reid_margin_ce_bwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _I, _P]),
     'reid_rerank_weights_sparse': (_I, [_P, _I, _P, _I, _P, _P, _P, _I64, _I, _I, _I, _P]),
     'reid_rerank_expand_count': (_I, [_P, _P, _P, _I64, _P, _I, _P, _I, _I, _I, _P]),
     'reid_rerank_expand_sparse': (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _I, _I, _I, _P]),

@@ -99,6 +99,11 @@ class TrainingConfig:
     xbm_margin: Optional[float] = 0.3                # None: soft margin
     xbm_normalize: bool = True                       # the ring holds unit rows
     xbm_start_epoch: int = 1                         # first epoch that enqueues and mines
+    # nor these: the identity head.  'linear' = the reference's Linear + label-smoothed CE; 'cosine' (NormFace), 'cosface', 'arcface' and
+    # 'circle' = a normalised-weight classifier on the same bn_neck.classifier.weight, logits = id_scale * cos, with that margin in the CE
+    id_head: str = 'linear'
+    id_scale: Optional[float] = None                 # None: the kind's default (30; circle 64)
+    id_margin: Optional[float] = None                # None: the kind's default (cosine 0, cosface 0.35, arcface 0.5, circle 0.35)
     sdm_semantic_dim: int = 512
     sdm_num_heads: int = 8
     sdm_dropout: float = 0.1   # not a reference config field: hard-coded in SemanticDisentanglementModule (models/model.py:35,43)

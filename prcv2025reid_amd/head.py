@@ -1,9 +1,11 @@
 """Autograd boundaries of the head kernels: BN-neck, classifier, label-smoothed CE, SDM loss, batch-hard triplet loss, cross-modal
-batch-hard triplet loss.
+batch-hard triplet loss, cosine-margin identity heads.
 
 Reference: BNNeck.forward models/model.py:208-224; compute_loss :512-659; sdm_loss_stable
 models/sdm_loss.py:13-149.  All arithmetic is in libreid_hip.so (fp32); torch only carries the tensors.
 """
+import math
+
 import torch
 
 from . import _lib, ops
@@ -420,6 +422,109 @@ def xbm_cross_triplet(q, g, labels, memory, q_valid=None, g_valid=None, margin=0
     loss, flag, n_active = XbmTripletFn.apply(q, g, labels.long(), q_valid, g_valid, memory, margin, bool(normalize), bool(enqueue), rows)
     rows['n_active'] = n_active
     return loss, flag, rows
+
+
+MARGIN_KINDS = ('cosine', 'cosface', 'arcface', 'circle')
+# (scale, margin) a kind takes when the caller leaves them open (TrainingConfig.id_scale / id_margin = None)
+MARGIN_DEFAULTS = {'cosine': (30.0, 0.0), 'cosface': (30.0, 0.35), 'arcface': (30.0, 0.5), 'circle': (64.0, 0.35)}
+
+
+def margin_args(who, kind, scale, margin):
+    """The checked (kind, scale, margin) of a cosine-margin head; None for scale or margin = the kind's default."""
+    if kind not in MARGIN_KINDS:
+        raise ValueError(f'{who}: kind must be one of {MARGIN_KINDS}, not {kind!r}')
+    scale = MARGIN_DEFAULTS[kind][0] if scale is None else float(scale)
+    margin = MARGIN_DEFAULTS[kind][1] if margin is None else float(margin)
+    if not (scale > 0 and math.isfinite(scale)):
+        raise ValueError(f'{who}: scale must be > 0 and finite, not {scale}')
+    if kind == 'cosine':
+        return kind, scale, 0.0                               # the margin is ignored
+    limit, text = (math.pi / 2, 'pi/2 for arcface') if kind == 'arcface' else (1.0, f'1 for {kind}')
+    if not 0 <= margin < limit:
+        raise ValueError(f'{who}: margin must be in [0, {text}), not {margin}')
+    return kind, scale, margin
+
+
+class CosineLinearFn(torch.autograd.Function):
+    """logits [B, C] = scale * cos(x_b, W_c) of x [B, D] (not assumed unit) and W [C, D] (csrc/margin_ce.hip; the reference has no
+    such head): rows divided by max(|row|, EPS) as F.normalize does.  The margin-free logits of the cosine-margin heads."""
+
+    @staticmethod
+    def forward(ctx, x, W, scale: float):
+        x = x.contiguous().float(); W = W.detach().contiguous().float()
+        (B, D), C, dev = x.shape, W.shape[0], x.device
+        rx = torch.empty(B, device=dev, dtype=torch.float64); rw = torch.empty(C, device=dev, dtype=torch.float64)
+        logits = torch.empty(B, C, device=dev)
+        ops.cos_logits_fwd(x, W, float(scale), EPS, rx, rw, logits)
+        ctx.save_for_backward(x, W, rx, rw)
+        ctx.scale = float(scale)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        x, W, rx, rw = ctx.saved_tensors
+        want_x, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_x or want_w):                            # only what autograd asks for, as LinearF32Fn
+            return None, None, None
+        g = g.contiguous().float()
+        dev = x.device
+        G = torch.empty(x.shape, device=dev, dtype=torch.float64) if want_x else None          # fp64 products, rounded once in the fix
+        H = torch.empty(W.shape, device=dev, dtype=torch.float64) if want_w else None
+        ops.cos_logits_bwd_prep(g, x, W, rx, rw, G, H)
+        dx = torch.empty_like(x) if want_x else None
+        dW = torch.empty_like(W) if want_w else None
+        ops.cos_logits_bwd_fix(x, rx, G, dx, W, rw, H, dW, ctx.scale, EPS)
+        return dx, dW, None
+
+
+class MarginCEFn(torch.autograd.Function):
+    """(loss, count) of the label-smoothed CE of the margin logits of ``kind`` (cosine | cosface | arcface | circle; include/reid_hip.h
+    has the definitions) of logits = scale * cos (CosineLinearFn's): the mean over the rows with valid != 0 and a label in [0, C).
+    count is a float tensor; nothing is read back to the host."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, valid, smoothing: float, kind: str, scale: float, margin: float):
+        kind, scale, margin = margin_args('MarginCEFn', kind, scale, margin)
+        logits = logits.contiguous().float()
+        labels = labels.contiguous()
+        row_loss = torch.empty(logits.shape[0], device=logits.device)
+        res = torch.empty(3, device=logits.device)
+        ops.margin_ce_fwd(logits, labels, valid, kind, scale, margin, float(smoothing), row_loss, res)
+        ctx.save_for_backward(logits, labels, valid, res)
+        ctx.args = (kind, scale, margin, float(smoothing))
+        loss, cnt = res[2], res[1]
+        ctx.mark_non_differentiable(cnt)
+        return loss, cnt
+
+    @staticmethod
+    def backward(ctx, dloss, _dcnt):
+        logits, labels, valid, res = ctx.saved_tensors
+        dl = torch.empty_like(logits)
+        ops.margin_ce_bwd(logits, labels, valid, *ctx.args, res, dloss.reshape(1).float().contiguous(), dl)
+        return dl, None, None, None, None, None, None
+
+
+def margin_cross_entropy(features, weight, labels, valid=None, kind='cosface', scale=30.0, margin=0.35, smoothing=0.1):
+    """Cosine-margin identity loss for users with their own loop: ``features`` [B, D] (not assumed unit) against the class weights
+    ``weight`` [C, D], both L2-normalised inside; logits = scale * cos; ``kind`` 'cosine' (NormFace, margin ignored), 'cosface'
+    (cos_y - m), 'arcface' (cos(theta_y + m) with the hard fallback below cos(pi - m)) or 'circle' (Sun et al. 2020, self-paced
+    weights that carry no gradient); label-smoothed CE of the margin logits, mean over the rows that take part.  ``valid``: optional
+    bool / uint8 [B]; rows with a label outside [0, C) take no part either.  Returns (loss, LazyCount(count), logits): the loss
+    carries the gradient to ``features`` and ``weight``, logits are the margin-free scale * cos."""
+    from .model import LazyCount
+    kind, scale, margin = margin_args('margin_cross_entropy', kind, scale, margin)
+    if not 0 <= smoothing <= 1:
+        raise ValueError(f'margin_cross_entropy: smoothing must be in [0, 1], not {smoothing}')
+    if not (features.is_cuda and weight.is_cuda and labels.is_cuda and (valid is None or valid.is_cuda)):
+        raise _lib.ReidHipError('margin_cross_entropy needs device tensors (there is no CPU path)')
+    if features.dim() != 2 or weight.dim() != 2 or weight.shape[1] != features.shape[1] or labels.shape != features.shape[:1] \
+            or (valid is not None and valid.shape != labels.shape):
+        raise ValueError('margin_cross_entropy: features [B, D], weight [C, D], labels [B], valid [B]')
+    if valid is not None:
+        valid = valid.to(torch.uint8).contiguous()
+    logits = CosineLinearFn.apply(features, weight, scale)
+    loss, cnt = MarginCEFn.apply(logits, labels.long(), valid, float(smoothing), kind, scale, margin)
+    return loss, LazyCount(cnt), logits
 
 
 # ----------------------------------------------------------------------------------------------------------------

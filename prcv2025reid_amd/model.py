@@ -37,7 +37,8 @@ from . import _lib, ops
 from .config import arch_of
 from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CrossEntropyLSFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn,
-                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn, HcTripletFn, XbmTripletFn, CrossBatchMemory)
+                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn, HcTripletFn, XbmTripletFn, CrossBatchMemory,
+                   CosineLinearFn, MarginCEFn, margin_args)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -104,6 +105,15 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.xbm_margin = getattr(config, 'xbm_margin', 0.3)
         self.xbm_normalize = getattr(config, 'xbm_normalize', True)
         self.xbm_start_epoch = getattr(config, 'xbm_start_epoch', 1)
+        # identity head (not in the reference): 'linear' = the reference's Linear + label-smoothed CE; cosine | cosface | arcface | circle = a
+        # normalised-weight classifier on bn_neck.classifier.weight with that margin (csrc/margin_ce.hip); scale / margin None: the kind's default
+        self.id_head = getattr(config, 'id_head', 'linear')
+        self.id_scale = self.id_margin = None
+        if self.id_head != 'linear':
+            if self.id_head not in ('cosine', 'cosface', 'arcface', 'circle'):
+                raise ValueError(f"TrainingConfig.id_head must be 'linear', 'cosine', 'cosface', 'arcface' or 'circle', not {self.id_head!r}")
+            self.id_head, self.id_scale, self.id_margin = margin_args('TrainingConfig.id_head', self.id_head, getattr(config, 'id_scale', None),
+                                                                      getattr(config, 'id_margin', None))
         self.xbm_memory = None               # a CrossBatchMemory made on first use; a plain attribute: not in state_dict()
         self._xbm_sides = None               # the modality names of its sides 1 .. P
         self.num_classes = None
@@ -564,7 +574,10 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             bnf = BNNeckFn.apply(fused, P['bn_neck.bn.weight'], P['bn_neck.bn.bias'], self._bufs['bn_neck.bn.running_mean'],
                                  self._bufs['bn_neck.bn.running_var'], self.training, 0.1, 1e-5)
             out['bn_features'] = bnf
-            out['logits'] = LinearF32Fn.apply(self._dropout(bnf, self.dropout_rate), P['bn_neck.classifier.weight'], None)
+            if self.id_head == 'linear':
+                out['logits'] = LinearF32Fn.apply(self._dropout(bnf, self.dropout_rate), P['bn_neck.classifier.weight'], None)
+            else:                      # the margin-free s * cos, in training and in eval; the margin enters in compute_loss
+                out['logits'] = CosineLinearFn.apply(self._dropout(bnf, self.dropout_rate), P['bn_neck.classifier.weight'], self.id_scale)
         if return_features:
             out['intermediate_features'] = {'raw_modality': raw, 'semantic_modality': sem, 'fused': fused}
         out['feature_masks'] = fmask
@@ -595,7 +608,10 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
                 self._loss_cache.clear()
             self._loss_cache[ckey] = cent
         valid = cent['valid']
-        ce, cnt = CrossEntropyLSFn.apply(logits, labels, valid, 0.1)
+        if self.id_head == 'linear':
+            ce, cnt = CrossEntropyLSFn.apply(logits, labels, valid, 0.1)
+        else:
+            ce, cnt = MarginCEFn.apply(logits, labels, valid, 0.1, self.id_head, self.id_scale, self.id_margin)
         zero = torch.zeros((), device=dev)
         sdm = zero
         use_sdm = (self.current_epoch >= self.config.sdm_weight_warmup_epochs) and (self.contrastive_weight > 0)

@@ -533,6 +533,99 @@ def xbm_triplet_bwd(q, g, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, 
                                      dq.stride(0), ptr(dg), dg.stride(0), stream_ptr()))
 
 
+def _f32_matrices(who, text, *named):
+    """Every (name, tensor, shape) of ``named``: a 2-d fp32 device tensor of that shape with unit column stride."""
+    for n, t, shape in named:
+        L._req(t, torch.float32, n)
+        if t.dim() != 2 or tuple(t.shape) != tuple(shape):
+            raise ValueError(f'{who}: {text}')
+
+
+def _vectors(who, text, dtype, *named):
+    """Every (name, tensor, numel) of ``named``: a contiguous device tensor of ``dtype`` with at least that many elements."""
+    for n, t, least in named:
+        L._req(t, dtype, n)
+        if t.numel() < least or not t.is_contiguous():
+            raise ValueError(f'{who}: {text}')
+
+
+def cos_logits_fwd(x, W, scale, eps, rx, rw, logits):
+    """logits [B, C] = scale * cos(x_b, W_c) of x [B, D], W [C, D] (fp32, any leading dimension); rx f64 [B], rw f64 [C] receive the
+    inverse norms 1 / max(|row|, eps) and are kept for the backward.  Two launches."""
+    text = 'x [B, D], W [C, D], logits [B, C] fp32; rx [B], rw [C] fp64'
+    if x.dim() != 2 or W.dim() != 2:
+        raise ValueError(f'cos_logits_fwd: {text}')
+    (B, D), C = x.shape, W.shape[0]
+    _f32_matrices('cos_logits_fwd', text, ('x', x, (B, D)), ('W', W, (C, D)), ('logits', logits, (B, C)))
+    _vectors('cos_logits_fwd', text, torch.float64, ('rx', rx, B), ('rw', rw, C))
+    check(lib().reid_cos_logits_fwd(ptr(x), x.stride(0), ptr(W), W.stride(0), B, C, D, scale, eps, ptr(rx), ptr(rw), ptr(logits),
+                                    logits.stride(0), stream_ptr()))
+
+
+def cos_logits_bwd_prep(g, x, W, rx, rw, G, H):
+    """From g = dL/dlogits [B, C]: G f64 [B, D] = sum_c g_bc rw_c W_c (None: dx is not wanted) and H f64 [C, D] = sum_b g_bc rx_b x_b
+    (None: dW is not wanted), fp64 sums in a fixed order.  One launch."""
+    text = 'g [B, C], x [B, D], W [C, D] fp32; rx [B], rw [C], G [B, D], H [C, D] fp64, contiguous; G or H'
+    if g.dim() != 2 or x.dim() != 2 or W.dim() != 2 or (G is None and H is None):
+        raise ValueError(f'cos_logits_bwd_prep: {text}')
+    (B, C), D = g.shape, x.shape[1]
+    _f32_matrices('cos_logits_bwd_prep', text, ('g', g, (B, C)), ('x', x, (B, D)), ('W', W, (C, D)))
+    _vectors('cos_logits_bwd_prep', text, torch.float64, ('rx', rx, B), ('rw', rw, C), *([('G', G, B * D)] if G is not None else []),
+             *([('H', H, C * D)] if H is not None else []))
+    check(lib().reid_cos_logits_bwd_prep(ptr(g), g.stride(0), ptr(x), x.stride(0), ptr(W), W.stride(0), ptr(rx), ptr(rw), B, C, D, ptr(G),
+                                         ptr(H), stream_ptr()))
+
+
+def cos_logits_bwd_fix(x, rx, G, dx, W, rw, H, dW, scale, eps):
+    """dx [B, D] = scale * rx_b * (G_b - xh_b (xh_b . G_b)) and dW [C, D] = scale * rw_c * (H_c - wh_c (wh_c . H_c)): the products of
+    cos_logits_bwd_prep projected through the two normalisations (rows below eps have no projection); dx or dW may be None (its
+    inputs are then not looked at).  One launch."""
+    text = 'x and dx [B, D], W and dW [C, D] fp32; rx [B], G [B, D], rw [C], H [C, D] fp64, contiguous; dx or dW'
+    if x.dim() != 2 or W.dim() != 2 or (dx is None and dW is None):
+        raise ValueError(f'cos_logits_bwd_fix: {text}')
+    (B, D), C = x.shape, W.shape[0]
+    _f32_matrices('cos_logits_bwd_fix', text, ('x', x, (B, D)), ('W', W, (C, D)))
+    if dx is not None:
+        _f32_matrices('cos_logits_bwd_fix', text, ('dx', dx, (B, D)))
+        _vectors('cos_logits_bwd_fix', text, torch.float64, ('rx', rx, B), ('G', G, B * D))
+    if dW is not None:
+        _f32_matrices('cos_logits_bwd_fix', text, ('dW', dW, (C, D)))
+        _vectors('cos_logits_bwd_fix', text, torch.float64, ('rw', rw, C), ('H', H, C * D))
+    no = dx is None, dW is None
+    check(lib().reid_cos_logits_bwd_fix(ptr(x), x.stride(0), None if no[0] else ptr(rx), None if no[0] else ptr(G), ptr(dx),
+                                        0 if no[0] else dx.stride(0), ptr(W), W.stride(0), None if no[1] else ptr(rw),
+                                        None if no[1] else ptr(H), ptr(dW), 0 if no[1] else dW.stride(0), B, C, D, scale, eps, stream_ptr()))
+
+
+def _margin_ce_shapes(who, logits, labels, valid):
+    L._req(logits, torch.float32, 'logits'); L._req(labels, torch.int64, 'labels')
+    if logits.dim() != 2 or labels.numel() != logits.shape[0] or not labels.is_contiguous():
+        raise ValueError(f'{who}: logits [rows, C], labels [rows]')
+    if valid is not None:
+        L._req(valid, torch.uint8, 'valid')
+        if valid.numel() != logits.shape[0] or not valid.is_contiguous():
+            raise ValueError(f'{who}: valid [rows]')
+    return logits.shape
+
+
+def margin_ce_fwd(logits, labels, valid, kind, scale, margin, smoothing, row_loss, result):
+    """Label-smoothed CE of the margin logits of ``kind`` ('cosine' | 'cosface' | 'arcface' | 'circle') of logits [rows, C] =
+    scale * cos: row_loss f32 [rows], result f32 [3] = (sum over the used rows, their count, the mean).  Two launches."""
+    rows, C = _margin_ce_shapes('margin_ce_fwd', logits, labels, valid)
+    _vectors('margin_ce_fwd', 'row_loss [rows], result [3]', torch.float32, ('row_loss', row_loss, rows), ('result', result, 3))
+    check(lib().reid_margin_ce_fwd(ptr(logits), logits.stride(0), ptr(labels), ptr(valid), rows, C, L.MARGIN_KINDS[kind], scale, margin,
+                                   smoothing, ptr(row_loss), ptr(result), stream_ptr()))
+
+
+def margin_ce_bwd(logits, labels, valid, kind, scale, margin, smoothing, result, dloss, dlogits):
+    """dlogits [rows, C] (overwritten, one launch) of the mean margin_ce_fwd returned; dloss a device scalar."""
+    rows, C = _margin_ce_shapes('margin_ce_bwd', logits, labels, valid)
+    _f32_matrices('margin_ce_bwd', 'dlogits [rows, C]', ('dlogits', dlogits, (rows, C)))
+    _vectors('margin_ce_bwd', 'result [3], dloss [1]', torch.float32, ('result', result, 3), ('dloss', dloss, 1))
+    check(lib().reid_margin_ce_bwd(ptr(logits), logits.stride(0), ptr(labels), ptr(valid), rows, C, L.MARGIN_KINDS[kind], scale, margin,
+                                   smoothing, ptr(result), ptr(dloss), ptr(dlogits), dlogits.stride(0), stream_ptr()))
+
+
 # ----------------------------------------------------------------------------------------- retrieval
 def topk_ws_bytes(Nq, Ng, k):
     return int(lib().reid_topk_ws_bytes(Nq, Ng, k))
