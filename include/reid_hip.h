@@ -503,6 +503,38 @@ int reid_xbm_triplet_bwd(const float* q, int32_t ldq, const float* g, int32_t ld
                          const float* gscale, float* dq, int32_t lddq, float* dg, int32_t lddg, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Center loss (Wen et al., "A Discriminative Feature Learning Approach for Deep Face Recognition", ECCV 2016; the reference has no
+ * such loss; csrc/center.hip): one centre per identity in a table on the device, every used row pulled towards the centre of its
+ * label, and Wen's update (eq. 4) of the centres the forward has just used.  All fp32, every operation rounded on its own (no fused
+ * multiply-add), so a float32 loop on the host reproduces diff, the updated centres and dx bit for bit.
+ *   x [S*N, D] (ldx): S sides stacked, row s*N + i = instance i of side s; labels [N] int64, shared by the sides; valid [S*N] uint8 or
+ *   NULL (all valid); centers [C, D] f32, contiguous.  A row is USED when it is valid and 0 <= labels[i] < C.
+ *   ws: reid_center_ws_floats(S, N, D) floats kept from fwd to bwd (a negative count = bad shape): diff S N D | used flags S N.
+ *   reid_center_fwd: diff[r, c] = x[r, c] - centers[y_r, c] (unused rows: zeros; they read no centre); d2[r] = sum_c diff^2 in fp32
+ *   (per-lane partial sums, then a butterfly over the wave; unused rows 0); a one-workgroup launch behind it writes
+ *   result[0] = 0.5 * sum over the used rows of d2 / max(1, n_used), added in ascending row order in fp64 and rounded once, and
+ *   result[1] = n_used as a float.  Neither is read back.
+ *   reid_center_update (with the labels / valid the forward had): a row CONTRIBUTES when it is used and its d2 is finite (a NaN or inf
+ *   feature makes the loss non-finite, which the step driver skips; it must not reach a centre).  For every class j with n_j >= 1
+ *   contributing rows: acc = 0; for those rows r ascending: acc = acc + (-diff[r, c]); delta = acc / float(1 + n_j);
+ *   centers[j, c] = centers[j, c] - alpha * delta.  Gather form: the wave of the lowest contributing row of a label does its centre
+ *   row, every other wave leaves; rows of classes not in the batch keep their bits.
+ *   reid_center_bwd: coef = dloss[0] / max(1.0f, result[1]) (one fp32 division); dx[r, c] = coef * diff[r, c]; dx [S*N, D] (lddx) is
+ *   OVERWRITTEN (unused rows with zeros, padding columns untouched).  It reads ws and result only, never centers: an update between
+ *   the forward and the backward does not change the gradient (the rule of reid_xbm_triplet_bwd).
+ *   No atomics: two runs give the same bits in every output and in the table.  Nothing is allocated, synchronised or read back.
+ * Requirements: 1 <= S <= 9, 1 <= N <= 8192, C >= 1, D % 4 == 0, 4 <= D <= 1024, ldx / lddx multiples of 4 and >= D, S*N*ld < 2^31,
+ * C*D < 2^31, x, centers, ws and dx 16-byte aligned, alpha finite.  Anything else: REID_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int64_t reid_center_ws_floats(int32_t S, int32_t N, int32_t D);
+int reid_center_fwd(const float* x, int32_t ldx, const int64_t* labels, const uint8_t* valid, int32_t S, int32_t N, int32_t D,
+                    const float* centers, int32_t C, float* ws, float* d2, float* result, void* stream);
+int reid_center_update(const int64_t* labels, const uint8_t* valid, int32_t S, int32_t N, int32_t D, const float* d2,
+                       const float* ws, float* centers, int32_t C, float alpha, void* stream);
+int reid_center_bwd(int32_t S, int32_t N, int32_t D, const float* ws, const float* result, const float* dloss, float* dx,
+                    int32_t lddx, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Retrieval (train.py:499 + :463; tools/eval_mm_protocol.py:50-53,401-423,622-625):
  *   sim = Q . G^T on L2-normalised rows, per-query top-k in (score desc, index asc) order.
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;

@@ -102,6 +102,10 @@ SIGNATURES = {
     'reid_xbm_enqueue': (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     'reid_xbm_triplet_fwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     'reid_xbm_triplet_bwd': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _F, _I, _F, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    'reid_center_ws_floats': (_I64, [_I, _I, _I]),
+    'reid_center_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    'reid_center_update': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _F, _P]),
+    'reid_center_bwd': (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
     'reid_topk_ws_bytes': (_I64, [_I, _I, _I]),
     'reid_topk_scan_ok': (_I, [_I, _I, _I, _I]),
     'reid_cosine_topk': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

@@ -117,7 +117,10 @@ def save_checkpoint(model, optimizer, scheduler_state, epoch: int, best_map: flo
     (decay, warm-up flag, update count, shadows on the CPU); without an EMA the dictionary has exactly the reference's keys.
     ``use_ema=True`` writes the AVERAGED weights as ``model_state_dict`` (swap, ``full_state_dict``, swap back), so the file
     loads into the reference unchanged and evaluates as the average; the optimizer state and ``ema_state_dict`` are the same
-    either way."""
+    either way.
+
+    A model that holds class centres of the center loss (``model.centers``) adds ``center_state_dict`` = the table on the CPU plus the
+    ``center_source`` it was trained on; ``load_checkpoint`` restores it, creating the table when the model has none yet."""
     if use_ema and not _has_ema(optimizer):
         raise ValueError('use_ema=True needs an optimizer that keeps an EMA (FusedAdamW(ema_decay=...))')
     os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
@@ -145,6 +148,8 @@ def save_checkpoint(model, optimizer, scheduler_state, epoch: int, best_map: flo
             'config': dict(config.__dict__) if hasattr(config, '__dict__') else str(config)}
     if _has_ema(optimizer):
         ckpt['ema_state_dict'] = optimizer.ema_state()
+    if getattr(model, 'centers', None) is not None:
+        ckpt['center_state_dict'] = dict(model.centers.state(), center_source=getattr(model, 'center_source', 'fused'))
     torch.save(ckpt, filename)
     return ckpt
 
@@ -171,7 +176,14 @@ def load_checkpoint(filename: str, model, optimizer=None, strict: bool = True) -
             optimizer.load_ema_state(ckpt['ema_state_dict'])
         else:                                # a checkpoint without an average: start it from the weights just loaded, not from
             optimizer.reset_ema()            # the ones the optimizer was constructed on
-    return ({k: v for k, v in ckpt.items() if k not in ('model_state_dict', 'optimizer_state_dict', 'ema_state_dict')}
+    if isinstance(ckpt, dict) and ckpt.get('center_state_dict'):      # after set_num_classes: that drops a table of another size
+        st = ckpt['center_state_dict']
+        if getattr(model, 'centers', None) is None:
+            from .head import ClassCenters
+            C, D = st['centers'].shape
+            model.centers = ClassCenters(C, D, getattr(model, 'device', 'cpu'))
+        model.centers.load_state(st)
+    return ({k: v for k, v in ckpt.items() if k not in ('model_state_dict', 'optimizer_state_dict', 'ema_state_dict', 'center_state_dict')}
             if isinstance(ckpt, dict) else {})
 
 

@@ -99,6 +99,11 @@ class TrainingConfig:
     xbm_margin: Optional[float] = 0.3                # None: soft margin
     xbm_normalize: bool = True                       # the ring holds unit rows
     xbm_start_epoch: int = 1                         # first epoch that enqueues and mines
+    # nor these: center loss (Wen et al. 2016), one centre per identity kept on the device and moved by its own update rule, not by
+    # the optimizer.  "Bag of Tricks" (Luo et al. 2019) uses center_weight = 5e-4 with center_alpha = 0.5
+    center_weight: float = 0.0
+    center_alpha: float = 0.5                        # step of the centre update
+    center_source: str = 'fused'                     # 'fused': the fused feature; 'modalities': every modality's raw feature, ONE shared table
     # nor these: the identity head.  'linear' = the reference's Linear + label-smoothed CE; 'cosine' (NormFace), 'cosface', 'arcface' and
     # 'circle' = a normalised-weight classifier on the same bn_neck.classifier.weight, logits = id_scale * cos, with that margin in the CE
     id_head: str = 'linear'

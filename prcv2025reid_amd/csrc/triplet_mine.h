@@ -7,7 +7,7 @@
 //   unit_row                          the unit row of one row                      xt_unit_kernel, hc_unit_kernel
 //   refine_anchor                     the kept distances re-evaluated in fp64      xt_refine_kernel, hc_refine_kernel
 //   load_row, zero_acc, store_row     a row as NV 16-byte chunks per lane          triplet_bwd_kernel, xt_bwd_kernel, hc_centre_kernel,
-//                                                                                  hc_bwd_centre_kernel, hc_bwd_rows_kernel
+//                                                                                  hc_bwd_centre_kernel, hc_bwd_rows_kernel; center.hip
 //   add_term, term_scale, add_own, add_chosen_by   the gather-form backward        triplet_bwd_kernel, xt_bwd_kernel, hc_bwd_centre_kernel
 //   check_d, check_dims, check_ld, check_scalars, aligned16   the argument checks  the extern "C" entry points of the three files
 // Shared forms of the four-line bodies of the unit kernels, of the projection through the normalisation (xt_bwd_kernel,

@@ -1,5 +1,5 @@
 """Autograd boundaries of the head kernels: BN-neck, classifier, label-smoothed CE, SDM loss, batch-hard triplet loss, cross-modal
-batch-hard triplet loss, cosine-margin identity heads.
+batch-hard triplet loss, cosine-margin identity heads, center loss.
 
 Reference: BNNeck.forward models/model.py:208-224; compute_loss :512-659; sdm_loss_stable
 models/sdm_loss.py:13-149.  All arithmetic is in libreid_hip.so (fp32); torch only carries the tensors.
@@ -422,6 +422,101 @@ def xbm_cross_triplet(q, g, labels, memory, q_valid=None, g_valid=None, margin=0
     loss, flag, n_active = XbmTripletFn.apply(q, g, labels.long(), q_valid, g_valid, memory, margin, bool(normalize), bool(enqueue), rows)
     rows['n_active'] = n_active
     return loss, flag, rows
+
+
+class ClassCenters:
+    """The table of center_loss (Wen et al., ECCV 2016; csrc/center.hip): one centre per identity, ``centers`` f32 [num_classes, dim],
+    zero at the start and moved by the update kernel only -- not by the optimizer.  A plain tensor, not a parameter or buffer: the
+    table is not part of a state_dict; ``state()`` / ``load_state()`` carry it through a checkpoint (``center_state_dict``).  It may be
+    constructed on the CPU for that; the kernels need the device."""
+
+    def __init__(self, num_classes, dim, device='cuda'):
+        if not (num_classes >= 1 and dim % 4 == 0 and 4 <= dim <= 1024 and num_classes * dim < 2 ** 31):
+            raise ValueError('ClassCenters: num_classes >= 1, dim a multiple of 4 in 4..1024, num_classes * dim < 2^31')
+        self.num_classes, self.dim = int(num_classes), int(dim)
+        self.centers = torch.zeros(self.num_classes, self.dim, dtype=torch.float32, device=torch.device(device))
+
+    def reset(self):
+        """Zeroes the table in place (a device fill: a captured graph that holds it stays valid)."""
+        self.centers.zero_()
+
+    def state(self):
+        return {'centers': self.centers.detach().cpu().clone()}
+
+    def load_state(self, state):
+        """Copies ``state['centers']`` into the table in place; a table of another shape is refused."""
+        c = state['centers']
+        if tuple(c.shape) != (self.num_classes, self.dim):
+            raise ValueError(f'ClassCenters: the state holds centres {tuple(c.shape)}, this table is [{self.num_classes}, {self.dim}]')
+        self.centers.copy_(c.to(torch.float32))
+
+
+class CenterLossFn(torch.autograd.Function):
+    """(loss, n_used) of the center loss of x [S, N, D] (S sides stacked, ``labels`` [N] shared) against the table ``centers``
+    (csrc/center.hip; the reference has no such loss): loss = 0.5 * mean over the used rows of |x - c_y|^2, a row used when it is valid
+    and its label lies in the table.  With ``update`` the centres the forward used are then moved by Wen's rule with step ``alpha``.
+    The centres are constants of the loss: the gradient reaches x only, from the differences the forward left in its workspace (the
+    table may have moved before the backward runs).  n_used is a float tensor; nothing is read back to the host.  ``rows_out``: an
+    optional trailing dict that receives a COPY of ``d2`` (center_loss); the call the model makes is
+    ``apply(x, labels, valid, centers, alpha, update)``."""
+    @staticmethod
+    def forward(ctx, x, labels, valid, centers, alpha: float, update: bool, rows_out=None):
+        (S, N, D), dev = x.shape, x.device
+        if D != centers.dim:
+            raise _lib.ReidHipError(f'CenterLossFn: the table holds centres of D={centers.dim}, the batch has D={D}')
+        x2 = x.reshape(S * N, D).contiguous().float()
+        labels = labels.contiguous()
+        vv = None if valid is None else valid.reshape(S * N).contiguous()
+        ws = torch.empty(ops.center_ws_floats(S, N, D), device=dev)
+        d2 = torch.empty(S * N, device=dev); res = torch.empty(2, device=dev)
+        ops.center_fwd(x2, labels, vv, centers.centers, ws, d2, res, S=S)
+        if update:
+            ops.center_update(labels, vv, d2, ws, centers.centers, alpha, S=S)
+        ctx.save_for_backward(ws, res)
+        ctx.shape = (S, N, D)
+        loss, n_used = res[0], res[1]
+        ctx.mark_non_differentiable(n_used)
+        if rows_out is not None:
+            rows_out.update(d2=d2.view(S, N).clone())
+        return loss, n_used
+
+    @staticmethod
+    def backward(ctx, dloss, _dn):
+        ws, res = ctx.saved_tensors
+        S, N, D = ctx.shape
+        dx = torch.empty(S * N, D, device=ws.device)
+        ops.center_bwd(ws, res, dloss.reshape(1).float().contiguous(), dx, S=S)
+        return dx.view(S, N, D), None, None, None, None, None, None
+
+
+def center_loss(x, labels, centers, valid=None, alpha=0.5, update=True):
+    """Center loss (Wen et al., ECCV 2016) for users with their own loop: ``x`` [S, N, D] (S sides stacked, e.g. the raw features of
+    every modality; [N, D] = one side) of the N instances with ``labels`` [N], ``centers`` a ClassCenters(C, D).  A row is used when it
+    is valid (``valid`` [S, N] or [N] for one side: optional bool / uint8) and its label lies in 0..C-1; loss = 0.5 * mean over the used
+    rows of |x - c_y|^2 (fp32 differences, the mean in fp64).  With ``update`` the centres of the classes in the batch then move:
+    c_j -= alpha * sum over its rows of (c_j - x) / (1 + n_j), rows with a non-finite distance left out; ``update=False`` leaves the
+    table as it is.  Returns (loss, LazyCount(n_used), rows) with rows = {'d2' [S, N]} (a copy); the loss carries the gradient to ``x``."""
+    from .model import LazyCount
+    if not (x.is_cuda and labels.is_cuda and (valid is None or valid.is_cuda)):
+        raise _lib.ReidHipError('center_loss needs device tensors (there is no CPU path)')
+    if not isinstance(centers, ClassCenters):
+        raise TypeError('center_loss: centers must be a ClassCenters')
+    if not centers.centers.is_cuda:
+        raise _lib.ReidHipError('center_loss needs the table on the device (there is no CPU path)')
+    flat = x.dim() == 2
+    if flat:
+        x = x.unsqueeze(0)
+    if x.dim() != 3 or labels.shape != x.shape[1:2]:
+        raise ValueError('center_loss: x [S, N, D] or [N, D], labels [N]')
+    if valid is not None:
+        valid = valid.to(torch.uint8).reshape(x.shape[0], x.shape[1]).contiguous()
+    if not math.isfinite(float(alpha)):
+        raise ValueError(f'center_loss: alpha must be finite, not {alpha}')
+    rows = {}
+    loss, n_used = CenterLossFn.apply(x, labels.long(), valid, centers, float(alpha), bool(update), rows)
+    if flat:
+        rows['d2'] = rows['d2'][0]
+    return loss, LazyCount(n_used), rows
 
 
 MARGIN_KINDS = ('cosine', 'cosface', 'arcface', 'circle')

@@ -38,7 +38,7 @@ from .config import arch_of
 from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CrossEntropyLSFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn,
                    NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn, HcTripletFn, XbmTripletFn, CrossBatchMemory,
-                   CosineLinearFn, MarginCEFn, margin_args)
+                   CosineLinearFn, MarginCEFn, margin_args, CenterLossFn, ClassCenters)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -105,6 +105,11 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.xbm_margin = getattr(config, 'xbm_margin', 0.3)
         self.xbm_normalize = getattr(config, 'xbm_normalize', True)
         self.xbm_start_epoch = getattr(config, 'xbm_start_epoch', 1)
+        self.center_weight = getattr(config, 'center_weight', 0.0)                        # center loss (not in the reference)
+        self.center_alpha = getattr(config, 'center_alpha', 0.5)
+        self.center_source = getattr(config, 'center_source', 'fused')
+        if self.center_source not in ('fused', 'modalities'):
+            raise ValueError(f"TrainingConfig.center_source must be 'fused' or 'modalities', not {self.center_source!r}")
         # identity head (not in the reference): 'linear' = the reference's Linear + label-smoothed CE; cosine | cosface | arcface | circle = a
         # normalised-weight classifier on bn_neck.classifier.weight with that margin (csrc/margin_ce.hip); scale / margin None: the kind's default
         self.id_head = getattr(config, 'id_head', 'linear')
@@ -116,6 +121,7 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
                                                                       getattr(config, 'id_margin', None))
         self.xbm_memory = None               # a CrossBatchMemory made on first use; a plain attribute: not in state_dict()
         self._xbm_sides = None               # the modality names of its sides 1 .. P
+        self.centers = None                  # the ClassCenters of the center loss, made on first use; a plain attribute: not in state_dict()
         self.num_classes = None
         self.bn_neck = None
         self._ref: "OrderedDict[str, nn.Parameter]" = OrderedDict()
@@ -223,6 +229,8 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
 
     def set_num_classes(self, num_classes: int):
         """models/model.py:310-319: create the BN-neck for ``num_classes`` identities."""
+        if self.centers is not None and self.centers.num_classes != num_classes:
+            self.centers = None              # a table for another number of identities: the next compute_loss makes a new one
         self.num_classes = num_classes
         dev = torch.device(self.device)
         for k, shp in param_spec(self.arch, num_classes).items():
@@ -674,7 +682,36 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             out['total_loss'] = out['total_loss'] + self.xbm_weight * xbm
             out['xbm_loss'] = xbm
             out['xbm_active_cnt'] = LazyCount(n_act.sum())
+        if self.center_weight > 0:
+            # center loss (csrc/center.hip): 'fused' = the fused feature in front of the BN-neck with the CE branch's validity;
+            # 'modalities' = the raw feature of every modality that has a mask (vis first), stacked, against ONE shared table -- every
+            # modality of a person is pulled to the same point.  The centres move once per forward in training with gradients, so once
+            # per micro-batch under gradient accumulation; eval() and no_grad() leave them alone.  Under DataParallel features and labels
+            # are the global batch on every rank, so every rank keeps an identical table and no collective is added
+            if self.center_source == 'fused':
+                x, xv = outputs['features'].unsqueeze(0), valid
+            else:
+                cm = [m for m in raw if m in fm]
+                cm = [m for m in cm if m == 'vis'] + [m for m in cm if m != 'vis']
+                if not cm:
+                    raise ValueError("center_source='modalities' needs raw_modality_features with feature_masks")
+                x = torch.stack([raw[m] for m in cm], dim=0)                                     # [S, B, D]
+                xv = cent.get(('cv', tuple(cm)))
+                if xv is None:
+                    xv = cent[('cv', tuple(cm))] = torch.stack([(fm[m].to(dev) > 0) for m in cm], dim=0).to(torch.uint8).contiguous()
+            if self.centers is None:
+                self.centers = ClassCenters(self.num_classes, x.shape[2], dev)
+            ctr, n_used = CenterLossFn.apply(x, labels, xv, self.centers, float(self.center_alpha),
+                                             bool(self.training and torch.is_grad_enabled()))
+            out['total_loss'] = out['total_loss'] + self.center_weight * ctr
+            out['center_loss'] = ctr
+            out['center_valid_cnt'] = LazyCount(n_used)
         return out
+
+    def reset_centers(self):
+        """Zeroes the class centres of the center loss in place (a device fill: a captured graph that holds the table stays valid)."""
+        if self.centers is not None:
+            self.centers.reset()
 
     def reset_xbm(self):
         """Empties the cross-batch memory in place (device fills: a captured graph that holds it stays valid)."""

@@ -533,6 +533,80 @@ def xbm_triplet_bwd(q, g, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, 
                                      dq.stride(0), ptr(dg), dg.stride(0), stream_ptr()))
 
 
+def center_ws_floats(S, N, D):
+    n = int(lib().reid_center_ws_floats(S, N, D))
+    if n < 0:
+        check(n)
+    return n
+
+
+def _center_rows(who, x, name, S):
+    """x [S*N, D] fp32 on the device (any leading dimension); returns (N, D)."""
+    L._req(x, torch.float32, name)
+    if x.dim() != 2 or S < 1 or x.shape[0] % S:
+        raise ValueError(f'{who}: {name} [S*N, D]')
+    return x.shape[0] // S, x.shape[1]
+
+
+def _center_batch(who, labels, valid, S, N):
+    L._req(labels, torch.int64, 'labels')
+    if labels.numel() != N or not labels.is_contiguous():
+        raise ValueError(f'{who}: labels [N], contiguous')
+    if valid is not None:
+        L._req(valid, torch.uint8, 'valid')
+        if valid.numel() != S * N or not valid.is_contiguous():
+            raise ValueError(f'{who}: valid has {valid.numel()} elements, not {S * N}')
+
+
+def _center_table(who, centers, D):
+    L._req(centers, torch.float32, 'centers')
+    if centers.dim() != 2 or not centers.is_contiguous():
+        raise ValueError(f'{who}: centers [C, D], contiguous')
+    if centers.shape[1] != D:
+        raise L.ReidHipError(f'{who}: the table holds centres of D={centers.shape[1]}, the batch has D={D}')
+
+
+def _center_saved(who, ws, S, N, D, **vectors):
+    """ws of center_ws_floats(S, N, D) floats and the named fp32 vectors (name -> (tensor, least numel)), all contiguous."""
+    for n, (t, least) in dict(vectors, ws=(ws, center_ws_floats(S, N, D))).items():
+        L._req(t, torch.float32, n)
+        if t.numel() < least or not t.is_contiguous():
+            raise ValueError(f'{who}: {n} holds fewer than {least} floats or is not contiguous')
+
+
+def center_fwd(x, labels, valid, centers, ws, d2, result, S=1):
+    """Center loss of x [S*N, D] (S sides stacked, labels [N] shared) against the table centers [C, D]: ws receives diff = x - c_y (kept
+    for center_update and center_bwd), d2 [S*N] the squared distances, result f32 [2] = (0.5 * mean d2 over the used rows, n_used)."""
+    N, D = _center_rows('center_fwd', x, 'x', S)
+    _center_batch('center_fwd', labels, valid, S, N)
+    _center_table('center_fwd', centers, D)
+    _center_saved('center_fwd', ws, S, N, D, d2=(d2, S * N), result=(result, 2))
+    check(lib().reid_center_fwd(ptr(x), x.stride(0), ptr(labels), ptr(valid), S, N, D, ptr(centers), centers.shape[0], ptr(ws), ptr(d2),
+                                ptr(result), stream_ptr()))
+
+
+def center_update(labels, valid, d2, ws, centers, alpha, S=1):
+    """Wen's update of the centres center_fwd has just used, in place: c_j -= alpha * sum(c_j - x_r) / (1 + n_j) over the rows of class
+    j that are used and have a finite d2 (one launch, no atomics); rows of classes not in the batch keep their bits."""
+    N = labels.numel()
+    _center_batch('center_update', labels, valid, S, N)
+    if centers.dim() != 2:
+        raise ValueError('center_update: centers [C, D], contiguous')
+    D = centers.shape[1]
+    _center_table('center_update', centers, D)
+    _center_saved('center_update', ws, S, N, D, d2=(d2, S * N))
+    check(lib().reid_center_update(ptr(labels), ptr(valid), S, N, D, ptr(d2), ptr(ws), ptr(centers), centers.shape[0], float(alpha),
+                                   stream_ptr()))
+
+
+def center_bwd(ws, result, dloss, dx, S=1):
+    """dx [S*N, D] = dloss / max(1, n_used) * diff from what center_fwd saved (overwritten, one launch) -- the table itself is not read;
+    dloss a device scalar."""
+    N, D = _center_rows('center_bwd', dx, 'dx', S)
+    _center_saved('center_bwd', ws, S, N, D, result=(result, 2), dloss=(dloss, 1))
+    check(lib().reid_center_bwd(S, N, D, ptr(ws), ptr(result), ptr(dloss), ptr(dx), dx.stride(0), stream_ptr()))
+
+
 def _f32_matrices(who, text, *named):
     """Every (name, tensor, shape) of ``named``: a 2-d fp32 device tensor of that shape with unit column stride."""
     for n, t, shape in named:
