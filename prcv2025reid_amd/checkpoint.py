@@ -179,7 +179,7 @@ def load_checkpoint(filename: str, model, optimizer=None, strict: bool = True) -
     if isinstance(ckpt, dict) and ckpt.get('center_state_dict'):      # after set_num_classes: that drops a table of another size
         st = ckpt['center_state_dict']
         if getattr(model, 'centers', None) is None:
-            from .head import ClassCenters
+            from .losses import ClassCenters
             C, D = st['centers'].shape
             model.centers = ClassCenters(C, D, getattr(model, 'device', 'cpu'))
         model.centers.load_state(st)

@@ -1,15 +1,24 @@
 // What the triplet losses share (triplet.hip: one set of rows against itself; cross_triplet.hip: one set against another;
-// hc_triplet.hip: a set of per-identity centres against itself) -- the ONE copy of each piece, all fp32 unless said; on the right, who
-// calls it:
-//   Rows, mine_tile                   the mining loop                              triplet_fwd_kernel, xt_fwd_kernel, hc_mine_kernel
-//   row_loss_of, row_dloss_of         the row-loss forms                           mine_tile, add_own, add_chosen_by, the refine kernels
-//   Sides                             the two sides as a kernel parameter          cross_triplet.hip, hc_triplet.hip
-//   unit_row                          the unit row of one row                      xt_unit_kernel, hc_unit_kernel
-//   refine_anchor                     the kept distances re-evaluated in fp64      xt_refine_kernel, hc_refine_kernel
+// hc_triplet.hip: a set of per-identity centres against itself; xbm.hip: one set against the slots of a cross-batch memory) and what
+// center.hip takes of it -- the ONE copy of each piece, all fp32 unless said; on the right, who calls it:
+//   Rows, mine_tile                   the mining loop                              triplet_fwd_kernel, xt_fwd_kernel, hc_mine_kernel,
+//                                                                                  xbm_mine_kernel
+//   row_loss_of, row_dloss_of         the row-loss forms                           mine_tile, add_own, add_chosen_by, the refine kernels,
+//                                                                                  xbm_bwd_kernel
+//   Sides                             the two sides as a kernel parameter          cross_triplet.hip, hc_triplet.hip, xbm.hip
+//   unit_row                          the unit row of one row                      xt_unit_kernel, hc_unit_kernel, xbm_unit_kernel,
+//                                                                                  xbm_enqueue_kernel
+//   refine_anchor                     the kept distances re-evaluated in fp64      xt_refine_kernel, hc_refine_kernel, xbm_refine_kernel
 //   load_row, zero_acc, store_row     a row as NV 16-byte chunks per lane          triplet_bwd_kernel, xt_bwd_kernel, hc_centre_kernel,
-//                                                                                  hc_bwd_centre_kernel, hc_bwd_rows_kernel; center.hip
-//   add_term, term_scale, add_own, add_chosen_by   the gather-form backward        triplet_bwd_kernel, xt_bwd_kernel, hc_bwd_centre_kernel
-//   check_d, check_dims, check_ld, check_scalars, aligned16   the argument checks  the extern "C" entry points of the three files
+//                                                                                  hc_bwd_centre_kernel, hc_bwd_rows_kernel; xbm_enqueue_kernel,
+//                                                                                  xbm_refine_kernel, xbm_bwd_kernel; center_fwd_kernel,
+//                                                                                  center_update_kernel, center_bwd_kernel
+//   add_term, term_scale              the gather-form backward, one term           add_own, add_chosen_by; xbm_bwd_kernel (its chosen rows
+//                                                                                  are the two copies its forward kept, not rows by index)
+//   add_own, add_chosen_by            the gather-form backward, an anchor's terms  triplet_bwd_kernel, xt_bwd_kernel, hc_bwd_centre_kernel
+//   check_d, check_dims, check_ld, check_scalars, aligned16   the argument checks  the extern "C" entry points of triplet.hip,
+//                                                                                  cross_triplet.hip, hc_triplet.hip and xbm.hip;
+//                                                                                  center.hip's take check_d, check_ld and aligned16
 // Shared forms of the four-line bodies of the unit kernels, of the projection through the normalisation (xt_bwd_kernel,
 // hc_bwd_rows_kernel) and of the finalize kernels' ordered fp64 tails changed the machine code of their callers, so those stay written
 // out in the .hip files, each copy naming the other (profiles/triplet_shared_isa_identity.md, "Left duplicated").

@@ -4,7 +4,7 @@ Same constructor (``config`` object read with getattr), same ``forward(images, t
 return_features)`` / ``compute_loss(outputs, labels)`` / ``set_num_classes`` / ``set_epoch`` /
 ``get_learnable_params`` surface, same output-dict keys and the same ``state_dict`` key names for every
 tensor the hot path uses (reference: models/model.py:227-737).  Underneath, the
-encoders run on the HIP executor in engine.py and the BN-neck / CE / SDM kernels in head.py.  There is
+encoders run on the HIP executor in engine.py, the BN-neck kernels in head.py and the loss kernels in losses.py.  There is
 no CPU path: constructing the model needs a gfx950 device and libreid_hip.so.
 
 Deliberate differences (documented in DESIGN.md):
@@ -34,11 +34,12 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .config import arch_of
+from .config import TrainingConfig, arch_of
 from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
-from .head import (MulFn, ActFn, AddFn, BNNeckFn, CrossEntropyLSFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn,
-                   NanToNumFn, SDMFn, SmallAttnFn, TripletHardFn, CrossTripletFn, HcTripletFn, XbmTripletFn, CrossBatchMemory,
-                   CosineLinearFn, MarginCEFn, margin_args, CenterLossFn, ClassCenters)
+from .head import (MulFn, ActFn, AddFn, BNNeckFn, CosineLinearFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn, NanToNumFn,
+                   SmallAttnFn)
+from .losses import (CenterLossFn, ClassCenters, CrossBatchMemory, CrossEntropyLSFn, CrossTripletFn, HcTripletFn, LazyCount, MarginCEFn,
+                     SDMFn, TripletHardFn, XbmTripletFn, margin_args)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -46,26 +47,23 @@ logger = logging.getLogger(__name__)
 
 LORA_PARAM_NAME = 'clip_encoder.vision_layers.loras.arena'
 
+# The loss settings the model takes from its config as plain attributes of the same name (assignable after construction).  A config
+# that lacks one -- the reference's has ce_weight and sdm_temperature only -- gets the default of TrainingConfig's own field.
+LOSS_FIELDS = ('sdm_temperature', 'ce_weight',
+               'triplet_weight', 'triplet_margin',                                               # batch-hard triplet loss; margin None: soft
+               'cross_triplet_weight', 'cross_triplet_margin', 'cross_triplet_normalize',         # cross-modal batch-hard triplet loss
+               'hc_triplet_weight', 'hc_triplet_margin', 'hc_triplet_normalize',                  # hetero-center triplet loss
+               'xbm_weight', 'xbm_size', 'xbm_margin', 'xbm_normalize', 'xbm_start_epoch',        # cross-batch memory triplet loss
+               'center_weight', 'center_alpha', 'center_source')                                  # center loss
+# The auxiliary terms of compute_loss in the order they are added to total_loss: (name, the key of its count).  Term ``name`` has the
+# weight ``<name>_weight``, the method ``_<name>_term`` and the key ``<name>_loss``.
+AUX_TERMS = (('triplet', 'triplet_active_cnt'), ('cross_triplet', 'cross_triplet_active_cnt'), ('hc_triplet', 'hc_triplet_active_cnt'),
+             ('xbm', 'xbm_active_cnt'), ('center', 'center_valid_cnt'))
 
-class LazyCount:
-    """Integer that lives on the device until someone looks at it (keeps compute_loss free of host syncs)."""
 
-    def __init__(self, t):
-        self._t = t
-
-    def __int__(self):
-        return int(self._t.item())
-
-    __index__ = __int__
-
-    def __eq__(self, o):
-        return int(self) == o
-
-    def __gt__(self, o):
-        return int(self) > o
-
-    def __repr__(self):
-        return str(int(self))
+def _pair_mean(L, flag):
+    """Mean of the per-pair losses L [P] over the pairs whose flag is set (model.py:617-622), 0 when none is."""
+    return L.sum() / flag.sum().clamp_min(1.0)
 
 
 class _NS:
@@ -89,36 +87,7 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.vision_modalities = [m for m in self.modalities if m != 'text']
         self.fusion_dim = self.arch['fusion_dim']
         self.vision_hidden_dim = self.arch['vision_hidden_dim']
-        self.sdm_temperature = getattr(config, 'sdm_temperature', 0.2)
-        self.ce_weight = getattr(config, 'ce_weight', 1.0)
-        self.contrastive_weight = getattr(config, 'contrastive_weight', 0.1)
-        self.triplet_weight = getattr(config, 'triplet_weight', 0.0)          # batch-hard triplet loss (not in the reference): off by default
-        self.triplet_margin = getattr(config, 'triplet_margin', 0.3)          # None: soft margin
-        self.cross_triplet_weight = getattr(config, 'cross_triplet_weight', 0.0)      # cross-modal batch-hard triplet loss (not in the reference)
-        self.cross_triplet_margin = getattr(config, 'cross_triplet_margin', 0.3)
-        self.cross_triplet_normalize = getattr(config, 'cross_triplet_normalize', True)
-        self.hc_triplet_weight = getattr(config, 'hc_triplet_weight', 0.0)                # hetero-center triplet loss (not in the reference)
-        self.hc_triplet_margin = getattr(config, 'hc_triplet_margin', 0.3)
-        self.hc_triplet_normalize = getattr(config, 'hc_triplet_normalize', True)
-        self.xbm_weight = getattr(config, 'xbm_weight', 0.0)                              # cross-batch memory triplet loss (not in the reference)
-        self.xbm_size = getattr(config, 'xbm_size', 4096)
-        self.xbm_margin = getattr(config, 'xbm_margin', 0.3)
-        self.xbm_normalize = getattr(config, 'xbm_normalize', True)
-        self.xbm_start_epoch = getattr(config, 'xbm_start_epoch', 1)
-        self.center_weight = getattr(config, 'center_weight', 0.0)                        # center loss (not in the reference)
-        self.center_alpha = getattr(config, 'center_alpha', 0.5)
-        self.center_source = getattr(config, 'center_source', 'fused')
-        if self.center_source not in ('fused', 'modalities'):
-            raise ValueError(f"TrainingConfig.center_source must be 'fused' or 'modalities', not {self.center_source!r}")
-        # identity head (not in the reference): 'linear' = the reference's Linear + label-smoothed CE; cosine | cosface | arcface | circle = a
-        # normalised-weight classifier on bn_neck.classifier.weight with that margin (csrc/margin_ce.hip); scale / margin None: the kind's default
-        self.id_head = getattr(config, 'id_head', 'linear')
-        self.id_scale = self.id_margin = None
-        if self.id_head != 'linear':
-            if self.id_head not in ('cosine', 'cosface', 'arcface', 'circle'):
-                raise ValueError(f"TrainingConfig.id_head must be 'linear', 'cosine', 'cosface', 'arcface' or 'circle', not {self.id_head!r}")
-            self.id_head, self.id_scale, self.id_margin = margin_args('TrainingConfig.id_head', self.id_head, getattr(config, 'id_scale', None),
-                                                                      getattr(config, 'id_margin', None))
+        self._read_loss_settings(config)
         self.xbm_memory = None               # a CrossBatchMemory made on first use; a plain attribute: not in state_dict()
         self._xbm_sides = None               # the modality names of its sides 1 .. P
         self.centers = None                  # the ClassCenters of the center loss, made on first use; a plain attribute: not in state_dict()
@@ -174,6 +143,24 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.clip_encoder.tokenizer = self.tokenizer
         self.feature_fusion = self._fusion
         self.sdm_module = self._sdm_module
+
+    def _read_loss_settings(self, config):
+        """The loss settings of ``config`` as attributes (no device is needed for this part of the constructor)."""
+        defaults = TrainingConfig()
+        for name in LOSS_FIELDS:
+            setattr(self, name, getattr(config, name, getattr(defaults, name)))
+        self.contrastive_weight = getattr(config, 'contrastive_weight', 0.1)          # the reference's own fallback (TrainingConfig: 0.0)
+        if self.center_source not in ('fused', 'modalities'):
+            raise ValueError(f"TrainingConfig.center_source must be 'fused' or 'modalities', not {self.center_source!r}")
+        # identity head (not in the reference): 'linear' = the reference's Linear + label-smoothed CE; cosine | cosface | arcface | circle = a
+        # normalised-weight classifier on bn_neck.classifier.weight with that margin (csrc/margin_ce.hip); scale / margin None: the kind's default
+        self.id_head = getattr(config, 'id_head', defaults.id_head)
+        self.id_scale = self.id_margin = None
+        if self.id_head != 'linear':
+            if self.id_head not in ('cosine', 'cosface', 'arcface', 'circle'):
+                raise ValueError(f"TrainingConfig.id_head must be 'linear', 'cosine', 'cosface', 'arcface' or 'circle', not {self.id_head!r}")
+            self.id_head, self.id_scale, self.id_margin = margin_args('TrainingConfig.id_head', self.id_head, getattr(config, 'id_scale', None),
+                                                                      getattr(config, 'id_margin', None))
 
     # ------------------------------------------------------------------ parameter plumbing
     def _add_param(self, ref_name: str, value: torch.Tensor, buffer: bool = False):
@@ -620,93 +607,91 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             ce, cnt = CrossEntropyLSFn.apply(logits, labels, valid, 0.1)
         else:
             ce, cnt = MarginCEFn.apply(logits, labels, valid, 0.1, self.id_head, self.id_scale, self.id_margin)
-        zero = torch.zeros((), device=dev)
-        sdm = zero
+        sdm = torch.zeros((), device=dev)
         use_sdm = (self.current_epoch >= self.config.sdm_weight_warmup_epochs) and (self.contrastive_weight > 0)
         raw = outputs.get('raw_modality_features', {})
-        use_xt = self.cross_triplet_weight > 0
-        use_hc = self.hc_triplet_weight > 0
         use_xbm = self.xbm_weight > 0 and self.current_epoch >= self.xbm_start_epoch
-        q = None
-        if (use_sdm or use_xt or use_hc or use_xbm) and 'vis' in raw and 'vis' in fm:
-            gv = cent['gv']
+        pairs = None
+        if (use_sdm or self.cross_triplet_weight > 0 or self.hc_triplet_weight > 0 or use_xbm) and 'vis' in raw and 'vis' in fm:
             mods = [m for m in raw if m != 'vis' and m in fm]
             if mods:
-                # every non-vis modality against vis in ONE fused launch per loss: the query sides are stacked (built once for both)
+                # every non-vis modality against vis in ONE fused launch per loss: the query sides are stacked (built once for all)
                 q = torch.stack([raw[m] for m in mods], dim=0)                                   # [P, B, D]
                 qv = cent.get(('qv', tuple(mods)))
                 if qv is None:
                     qv = cent[('qv', tuple(mods))] = torch.stack([(fm[m] > 0) for m in mods], dim=0).to(torch.uint8).contiguous()
-        if use_sdm and q is not None:
-            L, flag = SDMFn.apply(q, raw['vis'], labels, labels, qv, gv, float(self.sdm_temperature))   # csrc/sdm.hip
-            sdm = L.sum() / flag.sum().clamp_min(1.0)                                            # mean over the pairs that contribute (model.py:617-622)
+                pairs = (q, raw['vis'], qv, cent['gv'], tuple(mods))
+        if use_sdm and pairs is not None:
+            sdm = _pair_mean(*SDMFn.apply(q, raw['vis'], labels, labels, qv, cent['gv'], float(self.sdm_temperature)))   # csrc/sdm.hip
         total = self.ce_weight * ce + self.contrastive_weight * sdm
         out = {'total_loss': total, 'ce_loss': ce, 'sdm_loss': sdm, 'contrastive_loss': sdm, 'ce_valid_cnt': LazyCount(cnt)}
-        if self.triplet_weight > 0:
-            # batch-hard triplet loss on the fused feature in front of the BN-neck (csrc/triplet.hip); under DataParallel features and
-            # labels are the global batch, so mining is global on every rank
-            tri, n_act = TripletHardFn.apply(outputs['features'], labels, valid, self.triplet_margin)
-            out['total_loss'] = total + self.triplet_weight * tri
-            out['triplet_loss'] = tri
-            out['triplet_active_cnt'] = LazyCount(n_act)
-        if use_xt and q is not None:
-            # cross-modal batch-hard triplet loss (csrc/cross_triplet.hip) on the stack the SDM branch uses, not tied to its warm-up epoch;
-            # under DataParallel the raw features and labels are the global batch (the path SDM takes), so mining is global on every rank
-            L, flag, n_act = CrossTripletFn.apply(q, raw['vis'], labels, labels, qv, gv, self.cross_triplet_margin,
-                                                  bool(self.cross_triplet_normalize))
-            xt = L.sum() / flag.sum().clamp_min(1.0)                                             # mean over the pairs with an active anchor
-            out['total_loss'] = out['total_loss'] + self.cross_triplet_weight * xt
-            out['cross_triplet_loss'] = xt
-            out['cross_triplet_active_cnt'] = LazyCount(n_act.sum())
-        if use_hc and q is not None:
-            # hetero-center triplet loss (csrc/hc_triplet.hip) on the same stack, not tied to the SDM warm-up epoch either; under
-            # DataParallel the centres are those of the global batch on every rank
-            L, flag, n_act = HcTripletFn.apply(q, raw['vis'], labels, labels, qv, gv, self.hc_triplet_margin, bool(self.hc_triplet_normalize))
-            hc = L.sum() / flag.sum().clamp_min(1.0)                                             # mean over the pairs with an active anchor
-            out['total_loss'] = out['total_loss'] + self.hc_triplet_weight * hc
-            out['hc_triplet_loss'] = hc
-            out['hc_triplet_active_cnt'] = LazyCount(n_act.sum())
-        if use_xbm and q is not None:
-            # cross-batch memory (csrc/xbm.hip) on the same stack: the batch is filed into the ring (training with gradients only), then
-            # every anchor mines the ring; the ring's rows are constants.  Under DataParallel the raw features and labels are the global
-            # batch on every rank, so every rank keeps an identical memory and no collective is added
-            if self.xbm_memory is None:
-                self.xbm_memory = CrossBatchMemory(self.xbm_size, len(mods) + 1, q.shape[2], dev)
-                self._xbm_sides = tuple(mods)
-            elif self._xbm_sides != tuple(mods):
-                raise ValueError(f'the cross-batch memory was made for the modalities {self._xbm_sides}, this batch brings {tuple(mods)}: '
-                                 'set model.xbm_memory = None to start a new one')
-            L, flag, n_act = XbmTripletFn.apply(q, raw['vis'], labels, qv, gv, self.xbm_memory, self.xbm_margin, bool(self.xbm_normalize),
-                                                bool(self.training and torch.is_grad_enabled()))
-            xbm = L.sum() / flag.sum().clamp_min(1.0)                                            # mean over the pairs with an active anchor
-            out['total_loss'] = out['total_loss'] + self.xbm_weight * xbm
-            out['xbm_loss'] = xbm
-            out['xbm_active_cnt'] = LazyCount(n_act.sum())
-        if self.center_weight > 0:
-            # center loss (csrc/center.hip): 'fused' = the fused feature in front of the BN-neck with the CE branch's validity;
-            # 'modalities' = the raw feature of every modality that has a mask (vis first), stacked, against ONE shared table -- every
-            # modality of a person is pulled to the same point.  The centres move once per forward in training with gradients, so once
-            # per micro-batch under gradient accumulation; eval() and no_grad() leave them alone.  Under DataParallel features and labels
-            # are the global batch on every rank, so every rank keeps an identical table and no collective is added
-            if self.center_source == 'fused':
-                x, xv = outputs['features'].unsqueeze(0), valid
-            else:
-                cm = [m for m in raw if m in fm]
-                cm = [m for m in cm if m == 'vis'] + [m for m in cm if m != 'vis']
-                if not cm:
-                    raise ValueError("center_source='modalities' needs raw_modality_features with feature_masks")
-                x = torch.stack([raw[m] for m in cm], dim=0)                                     # [S, B, D]
-                xv = cent.get(('cv', tuple(cm)))
-                if xv is None:
-                    xv = cent[('cv', tuple(cm))] = torch.stack([(fm[m].to(dev) > 0) for m in cm], dim=0).to(torch.uint8).contiguous()
-            if self.centers is None:
-                self.centers = ClassCenters(self.num_classes, x.shape[2], dev)
-            ctr, n_used = CenterLossFn.apply(x, labels, xv, self.centers, float(self.center_alpha),
-                                             bool(self.training and torch.is_grad_enabled()))
-            out['total_loss'] = out['total_loss'] + self.center_weight * ctr
-            out['center_loss'] = ctr
-            out['center_valid_cnt'] = LazyCount(n_used)
+        for name, count_key in AUX_TERMS:
+            weight = getattr(self, name + '_weight')
+            term = getattr(self, f'_{name}_term')(outputs, labels, cent, pairs) if weight > 0 else None
+            if term is not None:
+                out['total_loss'] = out['total_loss'] + weight * term[0]
+                out[name + '_loss'] = term[0]
+                out[count_key] = LazyCount(term[1])
         return out
+
+    # The auxiliary terms (AUX_TERMS; none is in the reference): (loss, count) of one term from compute_loss's outputs, labels, cached
+    # validity vectors ``cent`` and ``pairs`` = (q [P, B, D], vis features, q_valid, g_valid, the modalities of q) or None; None when
+    # the term does not apply to this batch.  Under DataParallel features and labels are the global batch on every rank, so mining
+    # is global, every rank keeps an identical memory / table, and no collective is added.
+    def _triplet_term(self, outputs, labels, cent, pairs):
+        """Batch-hard triplet loss on the fused feature in front of the BN-neck (csrc/triplet.hip)."""
+        return TripletHardFn.apply(outputs['features'], labels, cent['valid'], self.triplet_margin)
+
+    def _cross_triplet_term(self, outputs, labels, cent, pairs):
+        """Cross-modal batch-hard triplet loss (csrc/cross_triplet.hip) on the stack the SDM branch uses, not tied to its warm-up epoch;
+        the mean over the pairs with an active anchor."""
+        if pairs is not None:
+            q, g, qv, gv, _ = pairs
+            L, flag, n_act = CrossTripletFn.apply(q, g, labels, labels, qv, gv, self.cross_triplet_margin, bool(self.cross_triplet_normalize))
+            return _pair_mean(L, flag), n_act.sum()
+
+    def _hc_triplet_term(self, outputs, labels, cent, pairs):
+        """Hetero-center triplet loss (csrc/hc_triplet.hip) on the same stack, not tied to the SDM warm-up epoch either."""
+        if pairs is not None:
+            q, g, qv, gv, _ = pairs
+            L, flag, n_act = HcTripletFn.apply(q, g, labels, labels, qv, gv, self.hc_triplet_margin, bool(self.hc_triplet_normalize))
+            return _pair_mean(L, flag), n_act.sum()
+
+    def _xbm_term(self, outputs, labels, cent, pairs):
+        """Cross-batch memory (csrc/xbm.hip) on the same stack from epoch xbm_start_epoch: the batch is filed into the ring (training
+        with gradients only), then every anchor mines the ring; the ring's rows are constants."""
+        if pairs is not None and self.current_epoch >= self.xbm_start_epoch:
+            q, g, qv, gv, mods = pairs
+            if self.xbm_memory is None:
+                self.xbm_memory = CrossBatchMemory(self.xbm_size, len(mods) + 1, q.shape[2], q.device)
+                self._xbm_sides = mods
+            elif self._xbm_sides != mods:
+                raise ValueError(f'the cross-batch memory was made for the modalities {self._xbm_sides}, this batch brings {mods}: '
+                                 'set model.xbm_memory = None to start a new one')
+            L, flag, n_act = XbmTripletFn.apply(q, g, labels, qv, gv, self.xbm_memory, self.xbm_margin, bool(self.xbm_normalize),
+                                                bool(self.training and torch.is_grad_enabled()))
+            return _pair_mean(L, flag), n_act.sum()
+
+    def _center_term(self, outputs, labels, cent, pairs):
+        """Center loss (csrc/center.hip): 'fused' = the fused feature in front of the BN-neck with the CE branch's validity; 'modalities'
+        = the raw feature of every modality that has a mask (vis first), stacked, against ONE shared table -- every modality of a person
+        is pulled to the same point.  The centres move once per forward in training with gradients, so once per micro-batch under
+        gradient accumulation; eval() and no_grad() leave them alone."""
+        if self.center_source == 'fused':
+            x, xv = outputs['features'].unsqueeze(0), cent['valid']
+        else:
+            raw, fm = outputs.get('raw_modality_features', {}), outputs.get('feature_masks', {})
+            cm = [m for m in raw if m in fm]
+            cm = [m for m in cm if m == 'vis'] + [m for m in cm if m != 'vis']
+            if not cm:
+                raise ValueError("center_source='modalities' needs raw_modality_features with feature_masks")
+            x = torch.stack([raw[m] for m in cm], dim=0)                                     # [S, B, D]
+            xv = cent.get(('cv', tuple(cm)))
+            if xv is None:
+                xv = cent[('cv', tuple(cm))] = torch.stack([(fm[m].to(x.device) > 0) for m in cm], dim=0).to(torch.uint8).contiguous()
+        if self.centers is None:
+            self.centers = ClassCenters(self.num_classes, x.shape[2], x.device)
+        return CenterLossFn.apply(x, labels, xv, self.centers, float(self.center_alpha), bool(self.training and torch.is_grad_enabled()))
 
     def reset_centers(self):
         """Zeroes the class centres of the center loss in place (a device fill: a captured graph that holds the table stays valid)."""

@@ -309,42 +309,90 @@ def sdm_bwd(q, g, q_label, g_label, q_valid, g_valid, tau, ws, gscale, dq, dg, P
                              ptr(dg), dg.stride(0), stream_ptr()))
 
 
+# ----------------------------------------------------------------------------------------- losses
+# What the C side cannot see of a tensor (dtype, numel, contiguity) every wrapper below checks with these helpers.
+f32, f64, i32, i64, u8 = torch.float32, torch.float64, torch.int32, torch.int64, torch.uint8
+
+
+def _f32_matrices(who, text, *named):
+    """Every (name, tensor, shape) of ``named``: a 2-d fp32 device tensor of that shape (None: any extent) with unit column stride."""
+    for n, t, shape in named:
+        L._req(t, f32, n)
+        if t.dim() != 2 or any(want is not None and want != got for want, got in zip(shape, t.shape)):
+            raise ValueError(f'{who}: {text}')
+
+
+def _stacked_rows(who, text, name, t, S):
+    """(N, D) of the fp32 matrix ``t`` [S*N, D] of S stacked sides."""
+    _f32_matrices(who, text, (name, t, (None, None)))
+    if S < 1 or t.shape[0] % S:
+        raise ValueError(f'{who}: {text}')
+    return t.shape[0] // S, t.shape[1]
+
+
+def _vectors(who, text, *named, exact=False):
+    """Every (name, tensor, dtype, numel) of ``named``: a contiguous device tensor of ``dtype`` with at least (``exact``: exactly)
+    that many elements."""
+    for n, t, dtype, count in named:
+        L._req(t, dtype, n)
+        if (t.numel() != count if exact else t.numel() < count) or not t.is_contiguous():
+            raise ValueError(f'{who}: {text}')
+
+
+def _valid_bytes(who, name, t, n):
+    """An optional validity vector: None, or contiguous uint8 of exactly ``n`` elements."""
+    if t is not None:
+        _vectors(who, f'{name} has {t.numel()} elements where {n} contiguous ones are expected', (name, t, u8, n), exact=True)
+
+
+def _ws_floats(fn, *dims):
+    n = int(fn(*dims))
+    if n < 0:
+        check(n)
+    return n
+
+
+def _pair_grads(who, q, g, gscale, dq, dg, P):
+    """What the two-sided backwards write: dq as q, dg as g, from gscale f32 [P]."""
+    text = 'dq as q, dg as g, gscale [P]'
+    _f32_matrices(who, text, ('dq', dq, q.shape), ('dg', dg, g.shape))
+    _vectors(who, text, ('gscale', gscale, f32, P))
+
+
+def _mined_saved(who, q_d, q_idx, g_d, g_idx, ws, result, P, N, Mg, ws_floats):
+    """What a mining forward leaves for its backward: (d_ap | d_an), (idx_p | idx_n) of the q and of the g anchors, result [P, 4] and
+    ws of the ``ws_floats`` floats the loss's *_ws_floats function asks."""
+    _vectors(who, 'q_d / q_idx [2, P*N], g_d / g_idx [2, P*Mg], result [P, 4], all contiguous', ('q_d', q_d, f32, 2 * P * N),
+             ('q_idx', q_idx, i32, 2 * P * N), ('g_d', g_d, f32, 2 * P * Mg), ('g_idx', g_idx, i32, 2 * P * Mg), ('result', result, f32, 4 * P))
+    _vectors(who, f'ws holds fewer than the {ws_floats} floats of its *_ws_floats', ('ws', ws, f32, ws_floats))
+
+
+def _triplet_hard_checks(who, text, x, d_ap, d_an, idx_p, idx_n, result):
+    _f32_matrices(who, text, ('x', x, (None, None)))
+    B = x.shape[0]
+    _vectors(who, text, ('d_ap', d_ap, f32, B), ('d_an', d_an, f32, B), ('idx_p', idx_p, i32, B), ('idx_n', idx_n, i32, B), ('result', result, f32, 2))
+    return B
+
+
 def triplet_hard_fwd(x, labels, valid, margin, d_ap, d_an, idx_p, idx_n, row_loss, result):
     """Batch-hard triplet loss of x [B, D] f32; margin < 0 selects the soft-margin form; result f32 [2] = (loss, n_active)."""
-    L._req(x, torch.float32, 'x'); L._req(labels, torch.int64, 'labels')
-    for n, t, d in (('d_ap', d_ap, torch.float32), ('d_an', d_an, torch.float32), ('idx_p', idx_p, torch.int32),
-                    ('idx_n', idx_n, torch.int32), ('row_loss', row_loss, torch.float32), ('result', result, torch.float32)):
-        L._req(t, d, n)
-    B = x.shape[0]
-    if x.dim() != 2 or labels.numel() != B or min(d_ap.numel(), d_an.numel(), idx_p.numel(), idx_n.numel(), row_loss.numel()) < B \
-            or result.numel() < 2:
-        raise ValueError('triplet_hard_fwd: x [B, D], labels [B], per-row outputs [B], result [2]')
-    if valid is not None:
-        L._req(valid, torch.uint8, 'valid')
-        if valid.numel() != B:
-            raise ValueError('triplet_hard_fwd: valid [B]')
+    who, text = 'triplet_hard_fwd', 'x [B, D], labels [B], per-row outputs [B], result [2]'
+    B = _triplet_hard_checks(who, text, x, d_ap, d_an, idx_p, idx_n, result)
+    _vectors(who, text, ('labels', labels, i64, B), exact=True)
+    _vectors(who, text, ('row_loss', row_loss, f32, B))
+    _valid_bytes(who, 'valid', valid, B)
     check(lib().reid_triplet_hard_fwd(ptr(x), x.stride(0), ptr(labels), ptr(valid), B, x.shape[1], margin, ptr(d_ap), ptr(d_an),
                                       ptr(idx_p), ptr(idx_n), ptr(row_loss), ptr(result), stream_ptr()))
 
 
 def triplet_hard_bwd(x, margin, d_ap, d_an, idx_p, idx_n, result, dloss, dx):
     """dx [B, D] = dloss * d loss / dx from the arrays triplet_hard_fwd saved (overwritten, one launch); dloss a device scalar."""
-    L._req(x, torch.float32, 'x'); L._req(dx, torch.float32, 'dx'); L._req(dloss, torch.float32, 'dloss'); L._req(result, torch.float32, 'result')
-    for n, t, d in (('d_ap', d_ap, torch.float32), ('d_an', d_an, torch.float32), ('idx_p', idx_p, torch.int32), ('idx_n', idx_n, torch.int32)):
-        L._req(t, d, n)
-    B = x.shape[0]
-    if x.dim() != 2 or dx.shape != x.shape or min(d_ap.numel(), d_an.numel(), idx_p.numel(), idx_n.numel()) < B or result.numel() < 2 \
-            or dloss.numel() < 1:
-        raise ValueError('triplet_hard_bwd: x and dx [B, D], per-row arrays [B], result [2], dloss [1]')
+    who, text = 'triplet_hard_bwd', 'x and dx [B, D], per-row arrays [B], result [2], dloss [1]'
+    B = _triplet_hard_checks(who, text, x, d_ap, d_an, idx_p, idx_n, result)
+    _f32_matrices(who, text, ('dx', dx, x.shape))
+    _vectors(who, text, ('dloss', dloss, f32, 1))
     check(lib().reid_triplet_hard_bwd(ptr(x), x.stride(0), B, x.shape[1], margin, ptr(d_ap), ptr(d_an), ptr(idx_p), ptr(idx_n),
                                       ptr(result), ptr(dloss), ptr(dx), dx.stride(0), stream_ptr()))
-
-
-def _ws_floats(fn, P, N, Mg, D):
-    n = int(fn(P, N, Mg, D))
-    if n < 0:
-        check(n)
-    return n
 
 
 def cross_triplet_ws_floats(P, N, Mg, D):
@@ -355,63 +403,41 @@ def hc_triplet_ws_floats(P, N, Mg, D):
     return _ws_floats(lib().reid_hc_triplet_ws_floats, P, N, Mg, D)
 
 
-def _two_sided_shapes(who, ws_floats, q, g, q_valid, g_valid, own, own_numel, own_text, ws, result, P):
-    """The checks the two-sided losses share: q [P*N, D] against g [Mg, D], the optional validity vectors, result [P, 4], ws of
-    ``ws_floats`` floats, and the loss's own saved arrays ``own`` = (name, tensor, dtype)s, each of at least ``own_numel(N, Mg)`` of
-    its elements (``own_text``: how the message describes them).  Returns (N, Mg)."""
-    for n, t, d in (('q', q, torch.float32), ('g', g, torch.float32)) + own + (('ws', ws, torch.float32), ('result', result, torch.float32)):
-        L._req(t, d, n)
-    if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] % P or g.shape[1] != q.shape[1]:
-        raise ValueError(f'{who}: q [P*N, D], g [Mg, D]')
-    N, Mg = q.shape[0] // P, g.shape[0]
-    for n, t, rows in (('q_valid', q_valid, P * N), ('g_valid', g_valid, Mg)):
-        if t is not None:
-            L._req(t, torch.uint8, n)
-            if t.numel() != rows:
-                raise ValueError(f'{who}: {n} has {t.numel()} elements, not {rows}')
-    if any(t.numel() < least for (_, t, _), least in zip(own, own_numel(N, Mg))) or result.numel() < 4 * P \
-            or not all(t.is_contiguous() for t in [t for _, t, _ in own] + [ws, result]):
-        raise ValueError(f'{who}: {own_text}, result [P, 4], all contiguous')
-    if ws.numel() < ws_floats(P, N, Mg, q.shape[1]):
-        raise ValueError(f'{who}: ws holds fewer than {ws_floats.__name__}(P, N, Mg, D) floats')
-    return N, Mg
-
-
-def _cross_triplet_shapes(who, q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, ws, result, P):
-    own = (('q_d', q_d, torch.float32), ('q_idx', q_idx, torch.int32), ('g_d', g_d, torch.float32), ('g_idx', g_idx, torch.int32))
-    return _two_sided_shapes(who, cross_triplet_ws_floats, q, g, q_valid, g_valid, own,
-                             lambda N, Mg: (2 * P * N, 2 * P * N, 2 * P * Mg, 2 * P * Mg), 'q_d / q_idx [2, P*N], g_d / g_idx [2, P*Mg]',
-                             ws, result, P)
+def _pair_batch(who, q, g, q_valid, g_valid, P):
+    """q [P*N, D] (P query sides stacked) against g [Mg, D] with their optional validity vectors; returns (N, Mg, D)."""
+    text = 'q [P*N, D], g [Mg, D]'
+    N, D = _stacked_rows(who, text, 'q', q, P)
+    _f32_matrices(who, text, ('g', g, (None, D)))
+    _valid_bytes(who, 'q_valid', q_valid, P * N); _valid_bytes(who, 'g_valid', g_valid, g.shape[0])
+    return N, g.shape[0], D
 
 
 def cross_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, g_d, g_idx, ws, result, P=1):
     """Cross-modal batch-hard triplet loss: q [P*N, D] (P query sides stacked) against g [Mg, D], mined in both directions; margin < 0
     selects the soft-margin form.  q_d / q_idx [2, P*N] = (d_ap | d_an), (idx_p | idx_n) of the q anchors, g_d / g_idx [2, P*Mg] of the
     g anchors (indices pair-local); result f32 [P, 4] = (L_p, flag_p, n_qg, n_gq); ws is kept for cross_triplet_bwd."""
-    N, Mg = _cross_triplet_shapes('cross_triplet_fwd', q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, ws, result, P)
-    L._req(q_label, torch.int64, 'q_label'); L._req(g_label, torch.int64, 'g_label')
-    if q_label.numel() != N or g_label.numel() != Mg:
-        raise ValueError('cross_triplet_fwd: q_label [N], g_label [Mg]')
+    N, Mg, D = _pair_batch('cross_triplet_fwd', q, g, q_valid, g_valid, P)
+    _mined_saved('cross_triplet_fwd', q_d, q_idx, g_d, g_idx, ws, result, P, N, Mg, cross_triplet_ws_floats(P, N, Mg, D))
+    _vectors('cross_triplet_fwd', 'q_label [N], g_label [Mg]', ('q_label', q_label, i64, N), ('g_label', g_label, i64, Mg), exact=True)
     check(lib().reid_cross_triplet_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_label), ptr(g_label), ptr(q_valid), ptr(g_valid),
-                                       P, N, Mg, q.shape[1], margin, int(normalize), eps, ptr(q_d), ptr(q_idx), ptr(g_d), ptr(g_idx),
+                                       P, N, Mg, D, margin, int(normalize), eps, ptr(q_d), ptr(q_idx), ptr(g_d), ptr(g_idx),
                                        ptr(ws), ptr(result), stream_ptr()))
 
 
 def cross_triplet_bwd(q, g, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, g_d, g_idx, ws, result, gscale, dq, dg, P=1):
     """dq [P*N, D], dg [Mg, D] (both overwritten, one launch) from what cross_triplet_fwd saved; gscale f32 [P] on the device."""
-    N, Mg = _cross_triplet_shapes('cross_triplet_bwd', q, g, q_valid, g_valid, q_d, q_idx, g_d, g_idx, ws, result, P)
-    L._req(gscale, torch.float32, 'gscale'); L._req(dq, torch.float32, 'dq'); L._req(dg, torch.float32, 'dg')
-    if dq.shape != q.shape or dg.shape != g.shape or gscale.numel() < P:
-        raise ValueError('cross_triplet_bwd: dq as q, dg as g, gscale [P]')
-    check(lib().reid_cross_triplet_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_valid), ptr(g_valid), P, N, Mg, q.shape[1], margin,
+    N, Mg, D = _pair_batch('cross_triplet_bwd', q, g, q_valid, g_valid, P)
+    _mined_saved('cross_triplet_bwd', q_d, q_idx, g_d, g_idx, ws, result, P, N, Mg, cross_triplet_ws_floats(P, N, Mg, D))
+    _pair_grads('cross_triplet_bwd', q, g, gscale, dq, dg, P)
+    check(lib().reid_cross_triplet_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_valid), ptr(g_valid), P, N, Mg, D, margin,
                                        int(normalize), eps, ptr(q_d), ptr(q_idx), ptr(g_d), ptr(g_idx), ptr(ws), ptr(result), ptr(gscale),
                                        ptr(dq), dq.stride(0), ptr(dg), dg.stride(0), stream_ptr()))
 
 
-def _hc_triplet_shapes(who, q, g, q_valid, g_valid, lead, count, ws, result, P):
-    own = (('lead', lead, torch.int32), ('count', count, torch.int32))
-    return _two_sided_shapes(who, hc_triplet_ws_floats, q, g, q_valid, g_valid, own, lambda N, Mg: (P * N + Mg, P * N + Mg),
-                             'lead / count [P*N + Mg]', ws, result, P)
+def _hc_triplet_saved(who, lead, count, ws, result, P, N, Mg, D):
+    _vectors(who, 'lead / count [P*N + Mg], result [P, 4], all contiguous', ('lead', lead, i32, P * N + Mg), ('count', count, i32, P * N + Mg),
+             ('result', result, f32, 4 * P))
+    _vectors(who, 'ws holds fewer than hc_triplet_ws_floats(P, N, Mg, D) floats', ('ws', ws, f32, hc_triplet_ws_floats(P, N, Mg, D)))
 
 
 def hc_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, eps, lead, count, clabel, d, idx, ws, result, P=1):
@@ -419,27 +445,22 @@ def hc_triplet_fwd(q, g, q_label, g_label, q_valid, g_valid, margin, normalize, 
     every side; margin < 0 selects the soft-margin form.  lead i32 [P*N + Mg] per row, count i32 / clabel i64 [P*N + Mg] per centre
     slot; d f32 / idx i32 [2, P, N + Mg] = (d_ap | d_an), (idx_p | idx_n) in the index space (q centre s -> s, g centre t -> N + t);
     result f32 [P, 4] = (L_p, flag_p, n_q, n_g); ws is kept for hc_triplet_bwd."""
-    N, Mg = _hc_triplet_shapes('hc_triplet_fwd', q, g, q_valid, g_valid, lead, count, ws, result, P)
-    for n, t, dt in (('q_label', q_label, torch.int64), ('g_label', g_label, torch.int64), ('clabel', clabel, torch.int64),
-                     ('d', d, torch.float32), ('idx', idx, torch.int32)):
-        L._req(t, dt, n)
-    if q_label.numel() != N or g_label.numel() != Mg:
-        raise ValueError('hc_triplet_fwd: q_label [N], g_label [Mg]')
-    if clabel.numel() < P * N + Mg or min(d.numel(), idx.numel()) < 2 * P * (N + Mg) \
-            or not (clabel.is_contiguous() and d.is_contiguous() and idx.is_contiguous()):
-        raise ValueError('hc_triplet_fwd: clabel [P*N + Mg], d / idx [2, P, N + Mg], all contiguous')
+    N, Mg, D = _pair_batch('hc_triplet_fwd', q, g, q_valid, g_valid, P)
+    _hc_triplet_saved('hc_triplet_fwd', lead, count, ws, result, P, N, Mg, D)
+    _vectors('hc_triplet_fwd', 'q_label [N], g_label [Mg]', ('q_label', q_label, i64, N), ('g_label', g_label, i64, Mg), exact=True)
+    _vectors('hc_triplet_fwd', 'clabel [P*N + Mg], d / idx [2, P, N + Mg], all contiguous', ('clabel', clabel, i64, P * N + Mg),
+             ('d', d, f32, 2 * P * (N + Mg)), ('idx', idx, i32, 2 * P * (N + Mg)))
     check(lib().reid_hc_triplet_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_label), ptr(g_label), ptr(q_valid), ptr(g_valid),
-                                    P, N, Mg, q.shape[1], margin, int(normalize), eps, ptr(lead), ptr(count), ptr(clabel), ptr(d), ptr(idx),
+                                    P, N, Mg, D, margin, int(normalize), eps, ptr(lead), ptr(count), ptr(clabel), ptr(d), ptr(idx),
                                     ptr(ws), ptr(result), stream_ptr()))
 
 
 def hc_triplet_bwd(q, g, margin, normalize, eps, lead, count, ws, result, gscale, dq, dg, P=1):
     """dq [P*N, D], dg [Mg, D] (both overwritten, two launches) from what hc_triplet_fwd saved; gscale f32 [P] on the device."""
-    N, Mg = _hc_triplet_shapes('hc_triplet_bwd', q, g, None, None, lead, count, ws, result, P)
-    L._req(gscale, torch.float32, 'gscale'); L._req(dq, torch.float32, 'dq'); L._req(dg, torch.float32, 'dg')
-    if dq.shape != q.shape or dg.shape != g.shape or gscale.numel() < P:
-        raise ValueError('hc_triplet_bwd: dq as q, dg as g, gscale [P]')
-    check(lib().reid_hc_triplet_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), P, N, Mg, q.shape[1], margin, int(normalize), eps,
+    N, Mg, D = _pair_batch('hc_triplet_bwd', q, g, None, None, P)
+    _hc_triplet_saved('hc_triplet_bwd', lead, count, ws, result, P, N, Mg, D)
+    _pair_grads('hc_triplet_bwd', q, g, gscale, dq, dg, P)
+    check(lib().reid_hc_triplet_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), P, N, Mg, D, margin, int(normalize), eps,
                                     ptr(lead), ptr(count), ptr(ws), ptr(result), ptr(gscale), ptr(dq), dq.stride(0), ptr(dg), dg.stride(0),
                                     stream_ptr()))
 
@@ -448,55 +469,37 @@ def xbm_ws_floats(P, N, M, D):
     return _ws_floats(lib().reid_xbm_ws_floats, P, N, M, D)
 
 
-def _xbm_memory_shapes(who, q, g, rows, mem_labels, mem_valid, P):
-    """The checks of a cross-batch memory against a batch: q [P*N, D], g [N, D]; rows f32 [P+1, M, D], mem_labels i64 [M], mem_valid
-    u8 [P+1, M], all contiguous.  Returns (N, M)."""
-    for n, t, d in (('q', q, torch.float32), ('g', g, torch.float32), ('rows', rows, torch.float32), ('mem_labels', mem_labels, torch.int64),
-                    ('mem_valid', mem_valid, torch.uint8)):
-        L._req(t, d, n)
-    if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] != P * g.shape[0] or g.shape[1] != q.shape[1]:
+def _xbm_batch(who, q, g, q_valid, g_valid, P):
+    """q [P*N, D] against g [N, D], the SAME N instances, with their optional validity vectors; returns (N, D)."""
+    N, Mg, D = _pair_batch(who, q, g, q_valid, g_valid, P)
+    if N != Mg:
         raise ValueError(f'{who}: q [P*N, D], g [N, D]')
-    N, D = g.shape
+    return N, D
+
+
+def _xbm_memory(who, rows, mem_labels, mem_valid, P, N, D):
+    """A cross-batch memory against a batch: rows f32 [P+1, M, D], mem_labels i64 [M], mem_valid u8 [P+1, M], all contiguous, with
+    room for the N rows.  Returns M."""
+    L._req(rows, f32, 'rows')
     if rows.dim() != 3 or rows.shape[0] != P + 1 or rows.shape[2] != D:
         raise L.ReidHipError(f'{who}: the memory holds rows {tuple(rows.shape)}, the batch needs [{P + 1}, M, {D}]')
-    M = rows.shape[1]
-    if mem_labels.shape != (M,) or mem_valid.shape != (P + 1, M) or not (rows.is_contiguous() and mem_labels.is_contiguous()
-                                                                         and mem_valid.is_contiguous()):
-        raise ValueError(f'{who}: rows [P+1, M, D], mem_labels [M], mem_valid [P+1, M], all contiguous')
+    M, text = rows.shape[1], 'rows [P+1, M, D], mem_labels [M], mem_valid [P+1, M], all contiguous'
+    _vectors(who, text, ('rows', rows, f32, 0), ('mem_labels', mem_labels, i64, M), ('mem_valid', mem_valid, u8, (P + 1) * M))
+    if mem_labels.shape != (M,) or mem_valid.shape != (P + 1, M):
+        raise ValueError(f'{who}: {text}')
     if N > M:
         raise ValueError(f'{who}: a batch of N={N} rows does not fit a memory of M={M} slots')
-    return N, M
-
-
-def _xbm_valid(who, q_valid, g_valid, P, N):
-    for n, t, rows in (('q_valid', q_valid, P * N), ('g_valid', g_valid, N)):
-        if t is not None:
-            L._req(t, torch.uint8, n)
-            if t.numel() != rows:
-                raise ValueError(f'{who}: {n} has {t.numel()} elements, not {rows}')
+    return M
 
 
 def xbm_enqueue(q, g, labels, q_valid, g_valid, normalize, eps, rows, mem_labels, mem_valid, cursor, P=1):
     """Files the batch q [P*N, D], g [N, D], labels [N] into the cross-batch memory (rows [P+1, M, D], mem_labels [M], mem_valid
     [P+1, M], cursor i32 [2], side 0 = g) at the device-side cursor and advances it by N; unit rows when ``normalize``."""
-    N, M = _xbm_memory_shapes('xbm_enqueue', q, g, rows, mem_labels, mem_valid, P)
-    _xbm_valid('xbm_enqueue', q_valid, g_valid, P, N)
-    L._req(labels, torch.int64, 'labels'); L._req(cursor, torch.int32, 'cursor')
-    if labels.numel() != N or cursor.numel() != 2 or not cursor.is_contiguous():
-        raise ValueError('xbm_enqueue: labels [N], cursor [2]')
-    check(lib().reid_xbm_enqueue(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(labels), ptr(q_valid), ptr(g_valid), P, N, M, q.shape[1],
+    N, D = _xbm_batch('xbm_enqueue', q, g, q_valid, g_valid, P)
+    M = _xbm_memory('xbm_enqueue', rows, mem_labels, mem_valid, P, N, D)
+    _vectors('xbm_enqueue', 'labels [N], cursor [2]', ('labels', labels, i64, N), ('cursor', cursor, i32, 2), exact=True)
+    check(lib().reid_xbm_enqueue(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(labels), ptr(q_valid), ptr(g_valid), P, N, M, D,
                                  int(normalize), eps, ptr(rows), ptr(mem_labels), ptr(mem_valid), ptr(cursor), stream_ptr()))
-
-
-def _xbm_saved_shapes(who, q_d, q_idx, g_d, g_idx, ws, result, P, N, M, D):
-    for n, t, d in (('q_d', q_d, torch.float32), ('q_idx', q_idx, torch.int32), ('g_d', g_d, torch.float32), ('g_idx', g_idx, torch.int32),
-                    ('ws', ws, torch.float32), ('result', result, torch.float32)):
-        L._req(t, d, n)
-    if min(q_d.numel(), q_idx.numel(), g_d.numel(), g_idx.numel()) < 2 * P * N or result.numel() < 4 * P \
-            or not all(t.is_contiguous() for t in (q_d, q_idx, g_d, g_idx, ws, result)):
-        raise ValueError(f'{who}: q_d / q_idx / g_d / g_idx [2, P*N], result [P, 4], all contiguous')
-    if ws.numel() < xbm_ws_floats(P, N, M, D):
-        raise ValueError(f'{who}: ws holds fewer than xbm_ws_floats(P, N, M, D) floats')
 
 
 def xbm_triplet_fwd(q, g, labels, q_valid, g_valid, margin, normalize, eps, rows, mem_labels, mem_valid, q_d, q_idx, g_d, g_idx, ws,
@@ -505,13 +508,11 @@ def xbm_triplet_fwd(q, g, labels, q_valid, g_valid, margin, normalize, eps, rows
     slots of side 0, the g rows against the slots of side p + 1; margin < 0 selects the soft-margin form.  q_d / q_idx, g_d / g_idx
     [2, P*N] = (d_ap | d_an), (idx_p | idx_n) as SLOT numbers; result f32 [P, 4] = (L_p, flag_p, n_q, n_g); ws is kept for
     xbm_triplet_bwd, with copies of the kept rows."""
-    N, M = _xbm_memory_shapes('xbm_triplet_fwd', q, g, rows, mem_labels, mem_valid, P)
-    _xbm_valid('xbm_triplet_fwd', q_valid, g_valid, P, N)
-    _xbm_saved_shapes('xbm_triplet_fwd', q_d, q_idx, g_d, g_idx, ws, result, P, N, M, q.shape[1])
-    L._req(labels, torch.int64, 'labels')
-    if labels.numel() != N:
-        raise ValueError('xbm_triplet_fwd: labels [N]')
-    check(lib().reid_xbm_triplet_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(labels), ptr(q_valid), ptr(g_valid), P, N, M, q.shape[1],
+    N, D = _xbm_batch('xbm_triplet_fwd', q, g, q_valid, g_valid, P)
+    M = _xbm_memory('xbm_triplet_fwd', rows, mem_labels, mem_valid, P, N, D)
+    _mined_saved('xbm_triplet_fwd', q_d, q_idx, g_d, g_idx, ws, result, P, N, N, xbm_ws_floats(P, N, M, D))
+    _vectors('xbm_triplet_fwd', 'labels [N]', ('labels', labels, i64, N), exact=True)
+    check(lib().reid_xbm_triplet_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(labels), ptr(q_valid), ptr(g_valid), P, N, M, D,
                                      margin, int(normalize), eps, ptr(rows), ptr(mem_labels), ptr(mem_valid), ptr(q_d), ptr(q_idx),
                                      ptr(g_d), ptr(g_idx), ptr(ws), ptr(result), stream_ptr()))
 
@@ -519,68 +520,41 @@ def xbm_triplet_fwd(q, g, labels, q_valid, g_valid, margin, normalize, eps, rows
 def xbm_triplet_bwd(q, g, q_valid, g_valid, margin, normalize, eps, q_d, q_idx, g_d, g_idx, ws, result, gscale, dq, dg, P=1):
     """dq [P*N, D], dg [N, D] (both overwritten, one launch) from what xbm_triplet_fwd saved -- the memory itself is not read;
     gscale f32 [P] on the device."""
-    for n, t in (('q', q), ('g', g), ('gscale', gscale), ('dq', dq), ('dg', dg)):
-        L._req(t, torch.float32, n)
-    if q.dim() != 2 or g.dim() != 2 or P < 1 or q.shape[0] != P * g.shape[0] or g.shape[1] != q.shape[1]:
-        raise ValueError('xbm_triplet_bwd: q [P*N, D], g [N, D]')
-    N, D = g.shape
-    _xbm_valid('xbm_triplet_bwd', q_valid, g_valid, P, N)
-    _xbm_saved_shapes('xbm_triplet_bwd', q_d, q_idx, g_d, g_idx, ws, result, P, N, N, D)
-    if dq.shape != q.shape or dg.shape != g.shape or gscale.numel() < P:
-        raise ValueError('xbm_triplet_bwd: dq as q, dg as g, gscale [P]')
+    N, D = _xbm_batch('xbm_triplet_bwd', q, g, q_valid, g_valid, P)
+    _mined_saved('xbm_triplet_bwd', q_d, q_idx, g_d, g_idx, ws, result, P, N, N, xbm_ws_floats(P, N, N, D))
+    _pair_grads('xbm_triplet_bwd', q, g, gscale, dq, dg, P)
     check(lib().reid_xbm_triplet_bwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_valid), ptr(g_valid), P, N, D, margin, int(normalize),
                                      eps, ptr(q_d), ptr(q_idx), ptr(g_d), ptr(g_idx), ptr(ws), ptr(result), ptr(gscale), ptr(dq),
                                      dq.stride(0), ptr(dg), dg.stride(0), stream_ptr()))
 
 
 def center_ws_floats(S, N, D):
-    n = int(lib().reid_center_ws_floats(S, N, D))
-    if n < 0:
-        check(n)
-    return n
-
-
-def _center_rows(who, x, name, S):
-    """x [S*N, D] fp32 on the device (any leading dimension); returns (N, D)."""
-    L._req(x, torch.float32, name)
-    if x.dim() != 2 or S < 1 or x.shape[0] % S:
-        raise ValueError(f'{who}: {name} [S*N, D]')
-    return x.shape[0] // S, x.shape[1]
+    return _ws_floats(lib().reid_center_ws_floats, S, N, D)
 
 
 def _center_batch(who, labels, valid, S, N):
-    L._req(labels, torch.int64, 'labels')
-    if labels.numel() != N or not labels.is_contiguous():
-        raise ValueError(f'{who}: labels [N], contiguous')
-    if valid is not None:
-        L._req(valid, torch.uint8, 'valid')
-        if valid.numel() != S * N or not valid.is_contiguous():
-            raise ValueError(f'{who}: valid has {valid.numel()} elements, not {S * N}')
+    _vectors(who, 'labels [N], contiguous', ('labels', labels, i64, N), exact=True)
+    _valid_bytes(who, 'valid', valid, S * N)
 
 
-def _center_table(who, centers, D):
-    L._req(centers, torch.float32, 'centers')
-    if centers.dim() != 2 or not centers.is_contiguous():
-        raise ValueError(f'{who}: centers [C, D], contiguous')
-    if centers.shape[1] != D:
+def _center_table(who, centers, D=None):
+    """centers f32 [C, D], contiguous; a table of another D than the batch's is refused.  Returns its D."""
+    text = 'centers [C, D], contiguous'
+    _f32_matrices(who, text, ('centers', centers, (None, None)))
+    _vectors(who, text, ('centers', centers, f32, 0))
+    if D is not None and centers.shape[1] != D:
         raise L.ReidHipError(f'{who}: the table holds centres of D={centers.shape[1]}, the batch has D={D}')
-
-
-def _center_saved(who, ws, S, N, D, **vectors):
-    """ws of center_ws_floats(S, N, D) floats and the named fp32 vectors (name -> (tensor, least numel)), all contiguous."""
-    for n, (t, least) in dict(vectors, ws=(ws, center_ws_floats(S, N, D))).items():
-        L._req(t, torch.float32, n)
-        if t.numel() < least or not t.is_contiguous():
-            raise ValueError(f'{who}: {n} holds fewer than {least} floats or is not contiguous')
+    return centers.shape[1]
 
 
 def center_fwd(x, labels, valid, centers, ws, d2, result, S=1):
     """Center loss of x [S*N, D] (S sides stacked, labels [N] shared) against the table centers [C, D]: ws receives diff = x - c_y (kept
     for center_update and center_bwd), d2 [S*N] the squared distances, result f32 [2] = (0.5 * mean d2 over the used rows, n_used)."""
-    N, D = _center_rows('center_fwd', x, 'x', S)
+    N, D = _stacked_rows('center_fwd', 'x [S*N, D]', 'x', x, S)
     _center_batch('center_fwd', labels, valid, S, N)
     _center_table('center_fwd', centers, D)
-    _center_saved('center_fwd', ws, S, N, D, d2=(d2, S * N), result=(result, 2))
+    _vectors('center_fwd', 'ws [center_ws_floats(S, N, D)], d2 [S*N], result [2], all contiguous', ('ws', ws, f32, center_ws_floats(S, N, D)),
+             ('d2', d2, f32, S * N), ('result', result, f32, 2))
     check(lib().reid_center_fwd(ptr(x), x.stride(0), ptr(labels), ptr(valid), S, N, D, ptr(centers), centers.shape[0], ptr(ws), ptr(d2),
                                 ptr(result), stream_ptr()))
 
@@ -590,11 +564,8 @@ def center_update(labels, valid, d2, ws, centers, alpha, S=1):
     j that are used and have a finite d2 (one launch, no atomics); rows of classes not in the batch keep their bits."""
     N = labels.numel()
     _center_batch('center_update', labels, valid, S, N)
-    if centers.dim() != 2:
-        raise ValueError('center_update: centers [C, D], contiguous')
-    D = centers.shape[1]
-    _center_table('center_update', centers, D)
-    _center_saved('center_update', ws, S, N, D, d2=(d2, S * N))
+    D = _center_table('center_update', centers)
+    _vectors('center_update', 'ws [center_ws_floats(S, N, D)], d2 [S*N], all contiguous', ('ws', ws, f32, center_ws_floats(S, N, D)), ('d2', d2, f32, S * N))
     check(lib().reid_center_update(ptr(labels), ptr(valid), S, N, D, ptr(d2), ptr(ws), ptr(centers), centers.shape[0], float(alpha),
                                    stream_ptr()))
 
@@ -602,25 +573,10 @@ def center_update(labels, valid, d2, ws, centers, alpha, S=1):
 def center_bwd(ws, result, dloss, dx, S=1):
     """dx [S*N, D] = dloss / max(1, n_used) * diff from what center_fwd saved (overwritten, one launch) -- the table itself is not read;
     dloss a device scalar."""
-    N, D = _center_rows('center_bwd', dx, 'dx', S)
-    _center_saved('center_bwd', ws, S, N, D, result=(result, 2), dloss=(dloss, 1))
+    N, D = _stacked_rows('center_bwd', 'dx [S*N, D]', 'dx', dx, S)
+    _vectors('center_bwd', 'ws [center_ws_floats(S, N, D)], result [2], dloss [1], all contiguous', ('ws', ws, f32, center_ws_floats(S, N, D)),
+             ('result', result, f32, 2), ('dloss', dloss, f32, 1))
     check(lib().reid_center_bwd(S, N, D, ptr(ws), ptr(result), ptr(dloss), ptr(dx), dx.stride(0), stream_ptr()))
-
-
-def _f32_matrices(who, text, *named):
-    """Every (name, tensor, shape) of ``named``: a 2-d fp32 device tensor of that shape with unit column stride."""
-    for n, t, shape in named:
-        L._req(t, torch.float32, n)
-        if t.dim() != 2 or tuple(t.shape) != tuple(shape):
-            raise ValueError(f'{who}: {text}')
-
-
-def _vectors(who, text, dtype, *named):
-    """Every (name, tensor, numel) of ``named``: a contiguous device tensor of ``dtype`` with at least that many elements."""
-    for n, t, least in named:
-        L._req(t, dtype, n)
-        if t.numel() < least or not t.is_contiguous():
-            raise ValueError(f'{who}: {text}')
 
 
 def cos_logits_fwd(x, W, scale, eps, rx, rw, logits):
@@ -631,7 +587,7 @@ def cos_logits_fwd(x, W, scale, eps, rx, rw, logits):
         raise ValueError(f'cos_logits_fwd: {text}')
     (B, D), C = x.shape, W.shape[0]
     _f32_matrices('cos_logits_fwd', text, ('x', x, (B, D)), ('W', W, (C, D)), ('logits', logits, (B, C)))
-    _vectors('cos_logits_fwd', text, torch.float64, ('rx', rx, B), ('rw', rw, C))
+    _vectors('cos_logits_fwd', text, ('rx', rx, f64, B), ('rw', rw, f64, C))
     check(lib().reid_cos_logits_fwd(ptr(x), x.stride(0), ptr(W), W.stride(0), B, C, D, scale, eps, ptr(rx), ptr(rw), ptr(logits),
                                     logits.stride(0), stream_ptr()))
 
@@ -644,8 +600,8 @@ def cos_logits_bwd_prep(g, x, W, rx, rw, G, H):
         raise ValueError(f'cos_logits_bwd_prep: {text}')
     (B, C), D = g.shape, x.shape[1]
     _f32_matrices('cos_logits_bwd_prep', text, ('g', g, (B, C)), ('x', x, (B, D)), ('W', W, (C, D)))
-    _vectors('cos_logits_bwd_prep', text, torch.float64, ('rx', rx, B), ('rw', rw, C), *([('G', G, B * D)] if G is not None else []),
-             *([('H', H, C * D)] if H is not None else []))
+    _vectors('cos_logits_bwd_prep', text, ('rx', rx, f64, B), ('rw', rw, f64, C), *([('G', G, f64, B * D)] if G is not None else []),
+             *([('H', H, f64, C * D)] if H is not None else []))
     check(lib().reid_cos_logits_bwd_prep(ptr(g), g.stride(0), ptr(x), x.stride(0), ptr(W), W.stride(0), ptr(rx), ptr(rw), B, C, D, ptr(G),
                                          ptr(H), stream_ptr()))
 
@@ -661,10 +617,10 @@ def cos_logits_bwd_fix(x, rx, G, dx, W, rw, H, dW, scale, eps):
     _f32_matrices('cos_logits_bwd_fix', text, ('x', x, (B, D)), ('W', W, (C, D)))
     if dx is not None:
         _f32_matrices('cos_logits_bwd_fix', text, ('dx', dx, (B, D)))
-        _vectors('cos_logits_bwd_fix', text, torch.float64, ('rx', rx, B), ('G', G, B * D))
+        _vectors('cos_logits_bwd_fix', text, ('rx', rx, f64, B), ('G', G, f64, B * D))
     if dW is not None:
         _f32_matrices('cos_logits_bwd_fix', text, ('dW', dW, (C, D)))
-        _vectors('cos_logits_bwd_fix', text, torch.float64, ('rw', rw, C), ('H', H, C * D))
+        _vectors('cos_logits_bwd_fix', text, ('rw', rw, f64, C), ('H', H, f64, C * D))
     no = dx is None, dW is None
     check(lib().reid_cos_logits_bwd_fix(ptr(x), x.stride(0), None if no[0] else ptr(rx), None if no[0] else ptr(G), ptr(dx),
                                         0 if no[0] else dx.stride(0), ptr(W), W.stride(0), None if no[1] else ptr(rw),
@@ -672,13 +628,9 @@ def cos_logits_bwd_fix(x, rx, G, dx, W, rw, H, dW, scale, eps):
 
 
 def _margin_ce_shapes(who, logits, labels, valid):
-    L._req(logits, torch.float32, 'logits'); L._req(labels, torch.int64, 'labels')
-    if logits.dim() != 2 or labels.numel() != logits.shape[0] or not labels.is_contiguous():
-        raise ValueError(f'{who}: logits [rows, C], labels [rows]')
-    if valid is not None:
-        L._req(valid, torch.uint8, 'valid')
-        if valid.numel() != logits.shape[0] or not valid.is_contiguous():
-            raise ValueError(f'{who}: valid [rows]')
+    _f32_matrices(who, 'logits [rows, C], labels [rows]', ('logits', logits, (None, None)))
+    _vectors(who, 'logits [rows, C], labels [rows]', ('labels', labels, i64, logits.shape[0]), exact=True)
+    _valid_bytes(who, 'valid', valid, logits.shape[0])
     return logits.shape
 
 
@@ -686,7 +638,7 @@ def margin_ce_fwd(logits, labels, valid, kind, scale, margin, smoothing, row_los
     """Label-smoothed CE of the margin logits of ``kind`` ('cosine' | 'cosface' | 'arcface' | 'circle') of logits [rows, C] =
     scale * cos: row_loss f32 [rows], result f32 [3] = (sum over the used rows, their count, the mean).  Two launches."""
     rows, C = _margin_ce_shapes('margin_ce_fwd', logits, labels, valid)
-    _vectors('margin_ce_fwd', 'row_loss [rows], result [3]', torch.float32, ('row_loss', row_loss, rows), ('result', result, 3))
+    _vectors('margin_ce_fwd', 'row_loss [rows], result [3]', ('row_loss', row_loss, f32, rows), ('result', result, f32, 3))
     check(lib().reid_margin_ce_fwd(ptr(logits), logits.stride(0), ptr(labels), ptr(valid), rows, C, L.MARGIN_KINDS[kind], scale, margin,
                                    smoothing, ptr(row_loss), ptr(result), stream_ptr()))
 
@@ -695,7 +647,7 @@ def margin_ce_bwd(logits, labels, valid, kind, scale, margin, smoothing, result,
     """dlogits [rows, C] (overwritten, one launch) of the mean margin_ce_fwd returned; dloss a device scalar."""
     rows, C = _margin_ce_shapes('margin_ce_bwd', logits, labels, valid)
     _f32_matrices('margin_ce_bwd', 'dlogits [rows, C]', ('dlogits', dlogits, (rows, C)))
-    _vectors('margin_ce_bwd', 'result [3], dloss [1]', torch.float32, ('result', result, 3), ('dloss', dloss, 1))
+    _vectors('margin_ce_bwd', 'result [3], dloss [1]', ('result', result, f32, 3), ('dloss', dloss, f32, 1))
     check(lib().reid_margin_ce_bwd(ptr(logits), logits.stride(0), ptr(labels), ptr(valid), rows, C, L.MARGIN_KINDS[kind], scale, margin,
                                    smoothing, ptr(result), ptr(dloss), ptr(dlogits), dlogits.stride(0), stream_ptr()))
 

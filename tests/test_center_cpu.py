@@ -64,19 +64,19 @@ def test_config_defaults():
 
 
 def test_cpu_tensors_are_refused():
-    from prcv2025reid_amd import head, _lib
+    from prcv2025reid_amd import losses, _lib
     x, labels, valid, _ = R.make_case(2, 5, 8, 4, 1)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.center_loss(x, labels, head.ClassCenters(4, 8, 'cpu'))
+        losses.center_loss(x, labels, losses.ClassCenters(4, 8, 'cpu'))
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.center_loss(x[0], labels, None, valid=valid[0])
+        losses.center_loss(x[0], labels, None, valid=valid[0])
     with pytest.raises(_lib.ReidHipError):
         from prcv2025reid_amd import ops
         ops.center_fwd(x[0], labels, None, torch.zeros(4, 8), torch.zeros(64), torch.zeros(5), torch.zeros(2))
 
 
 def test_class_centers_state_round_trip():
-    from prcv2025reid_amd.head import ClassCenters
+    from prcv2025reid_amd.losses import ClassCenters
     a = ClassCenters(6, 12, 'cpu')
     assert a.centers.shape == (6, 12) and a.centers.dtype == torch.float32 and float(a.centers.abs().max()) == 0.0
     a.centers.copy_(torch.randn(6, 12, generator=torch.Generator().manual_seed(1)))
@@ -125,7 +125,7 @@ class _Centers:
 
 def test_checkpoint_round_trips_center_state(tmp_path):
     from prcv2025reid_amd import checkpoint as ck
-    from prcv2025reid_amd.head import ClassCenters
+    from prcv2025reid_amd.losses import ClassCenters
     cfg, arch, sd = _tiny()
     m = _Model(arch, {k: v.clone() for k, v in sd.items()}, 5)
     table = torch.randn(5, 16, generator=torch.Generator().manual_seed(2))

@@ -274,14 +274,14 @@ def test_violated_requirements_are_refused_and_write_nothing(ops):
 # ---------------------------------------------------------------------------------------------------------------- 5. public call
 @pytest.mark.parametrize('flat', [True, False])
 def test_public_call_against_autograd(ops, flat):
-    from prcv2025reid_amd import head, _lib
+    from prcv2025reid_amd import losses, _lib
     S, N, D, C, _ = (1, 16, 512, 6, 0) if flat else R.SHAPES[4]
     x, labels, valid, centers = R.make_case(S, N, D, C, 21)
     xin, vin = (x[0], valid[0]) if flat else (x, valid)
-    table = head.ClassCenters(C, D, 'cuda')
+    table = losses.ClassCenters(C, D, 'cuda')
     table.load_state({'centers': centers})
     xa = xin.cuda().requires_grad_(True)
-    loss, n_used, rows = head.center_loss(xa, labels.cuda(), table, valid=vin.cuda() != 0, alpha=0.25)
+    loss, n_used, rows = losses.center_loss(xa, labels.cuda(), table, valid=vin.cuda() != 0, alpha=0.25)
     x64 = x.double().requires_grad_(True)
     L64, n64, d64 = R.ref64_loss(x64, labels, valid, centers)
     assert int(n_used) == n64 > 0 and rows['d2'].shape == xin.shape[:-1]
@@ -299,17 +299,17 @@ def test_public_call_against_autograd(ops, flat):
     assert not torch.equal(table.centers.cpu(), centers)
     # update=False leaves the table as it is
     before = bits(table.centers)
-    loss2, _, _ = head.center_loss(xin.cuda(), labels.cuda(), table, valid=vin.cuda(), update=False)
+    loss2, _, _ = losses.center_loss(xin.cuda(), labels.cuda(), table, valid=vin.cuda(), update=False)
     torch.cuda.synchronize()
     assert torch.equal(bits(table.centers), before) and float(loss2) != float(loss.detach())
     with pytest.raises(_lib.ReidHipError, match='D='):
-        head.center_loss(xin.cuda()[..., :8], labels.cuda(), table)
+        losses.center_loss(xin.cuda()[..., :8], labels.cuda(), table)
     with pytest.raises(TypeError, match='ClassCenters'):
-        head.center_loss(xin.cuda(), labels.cuda(), table.centers)
+        losses.center_loss(xin.cuda(), labels.cuda(), table.centers)
     with pytest.raises(ValueError, match='alpha'):
-        head.center_loss(xin.cuda(), labels.cuda(), table, alpha=float('nan'))
+        losses.center_loss(xin.cuda(), labels.cuda(), table, alpha=float('nan'))
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.center_loss(xin, labels, table)
+        losses.center_loss(xin, labels, table)
     assert torch.equal(bits(table.centers), before)              # a refused call moves nothing
 
 

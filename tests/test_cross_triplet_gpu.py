@@ -384,14 +384,14 @@ def test_two_runs_give_the_same_bits(ops, normalize):
 
 def test_public_call_and_autograd(ops):
     """The autograd boundary by value, with upstream factors that are not 1, and q [N, D] as P = 1."""
-    from prcv2025reid_amd import head, _lib
+    from prcv2025reid_amd import losses, _lib
     shape = R.SHAPES[3]
     P, N, Mg, D, _ = shape
     q, g, ql, gl = R.fixture(shape, 30.0, 'cuda')
     qv = torch.ones(P, N, dtype=torch.bool, device='cuda'); qv[1, 3] = False
     for margin, normalize in ((0.3, True), (None, False)):
         qa, ga = q.clone().requires_grad_(True), g.clone().requires_grad_(True)
-        L, flag, rows = head.cross_modal_triplet(qa, ga, ql, gl, q_valid=qv, margin=margin, normalize=normalize)
+        L, flag, rows = losses.cross_modal_triplet(qa, ga, ql, gl, q_valid=qv, margin=margin, normalize=normalize)
         assert L.shape == (P,) and flag.tolist() == [1.0] * P and set(rows) == {'q_d_ap', 'q_d_an', 'q_idx_p', 'q_idx_n', 'g_d_ap', 'g_d_an',
                                                                                 'g_idx_p', 'g_idx_n', 'n_active'}
         assert rows['q_idx_p'].shape == (P, N) and rows['g_idx_n'].shape == (P, Mg) and rows['n_active'].shape == (P, 2)
@@ -411,18 +411,18 @@ def test_public_call_and_autograd(ops):
     # L.sum().backward() = the direct backward call with gscale 1; q [N, D] = P = 1
     q1 = q[2].clone().requires_grad_(True)
     g1 = g.clone().requires_grad_(True)
-    L1, flag1, rows1 = head.cross_modal_triplet(q1, g1, ql, gl)
+    L1, flag1, rows1 = losses.cross_modal_triplet(q1, g1, ql, gl)
     L1.sum().backward()
     o1 = run_fwd(ops, q[2:3], g, ql, gl, None, None, 0.3, True)
     dq1, dg1 = run_bwd(ops, o1, [1.0], pad=0)
     assert L1.shape == (1,) and torch.equal(L1.detach(), o1['res'][:, 0]) and rows1['q_idx_p'].shape == (1, N)
     assert torch.equal(q1.grad, dq1) and torch.equal(g1.grad, dg1) and float(dq1.abs().max()) > 0
     with pytest.raises(ValueError, match='margin'):
-        head.cross_modal_triplet(q, g, ql, gl, margin=-1.0)
+        losses.cross_modal_triplet(q, g, ql, gl, margin=-1.0)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.cross_modal_triplet(q.cpu(), g.cpu(), ql.cpu(), gl.cpu())
+        losses.cross_modal_triplet(q.cpu(), g.cpu(), ql.cpu(), gl.cpu())
     with pytest.raises(_lib.ReidHipError, match='D='):
-        head.cross_modal_triplet(q[:, :, :6], g[:, :6], ql, gl)
+        losses.cross_modal_triplet(q[:, :, :6], g[:, :6], ql, gl)
 
 
 # ---------------------------------------------------------------------------------------------------------------- model level

@@ -145,10 +145,10 @@ def test_entry_points_check_their_arguments_without_a_device(libs, flavor):
 
 
 def test_config_and_head_expose_the_loss():
-    from prcv2025reid_amd import _lib, head
+    from prcv2025reid_amd import _lib, losses
     from prcv2025reid_amd.config import TrainingConfig
     cfg = TrainingConfig()
     assert cfg.hc_triplet_weight == 0.0 and cfg.hc_triplet_margin == 0.3 and cfg.hc_triplet_normalize is True
     z = torch.zeros(4, 8)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.hetero_center_triplet(z, z, torch.zeros(4, dtype=torch.int64), torch.zeros(4, dtype=torch.int64))
+        losses.hetero_center_triplet(z, z, torch.zeros(4, dtype=torch.int64), torch.zeros(4, dtype=torch.int64))

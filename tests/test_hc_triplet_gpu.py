@@ -373,7 +373,7 @@ def test_two_runs_give_the_same_bits(ops, normalize):
 
 def test_public_call_and_autograd(ops):
     """The autograd boundary by value, with upstream factors that are not 1, and q [N, D] as P = 1."""
-    from prcv2025reid_amd import head, _lib
+    from prcv2025reid_amd import losses, _lib
     shape = R.SHAPES[2]
     P, N, Mg, D, _ = shape
     q, g, ql, gl = R.fixture(shape, 30.0, 'cuda')
@@ -381,7 +381,7 @@ def test_public_call_and_autograd(ops):
     names = {f'{s}_{k}' for s in 'qg' for k in ('lead', 'count', 'label', 'd_ap', 'd_an', 'idx_p', 'idx_n')} | {'n_active'}
     for margin, normalize in ((0.3, True), (None, False)):
         qa, ga = q.clone().requires_grad_(True), g.clone().requires_grad_(True)
-        L, flag, rows = head.hetero_center_triplet(qa, ga, ql, gl, q_valid=qv, margin=margin, normalize=normalize)
+        L, flag, rows = losses.hetero_center_triplet(qa, ga, ql, gl, q_valid=qv, margin=margin, normalize=normalize)
         assert L.shape == (P,) and flag.tolist() == [1.0] * P and set(rows) == names
         assert rows['q_lead'].shape == (P, N) and rows['g_count'].shape == (Mg,) and rows['q_idx_p'].shape == (P, N) \
             and rows['g_idx_n'].shape == (P, Mg) and rows['n_active'].shape == (P, 2)
@@ -402,18 +402,18 @@ def test_public_call_and_autograd(ops):
     # L.sum().backward() = the direct backward call with gscale 1; q [N, D] = P = 1
     q1 = q[2].clone().requires_grad_(True)
     g1 = g.clone().requires_grad_(True)
-    L1, flag1, rows1 = head.hetero_center_triplet(q1, g1, ql, gl)
+    L1, flag1, rows1 = losses.hetero_center_triplet(q1, g1, ql, gl)
     L1.sum().backward()
     o1 = run_fwd(ops, q[2:3], g, ql, gl, None, None, 0.3, True)
     dq1, dg1 = run_bwd(ops, o1, [1.0], pad=0)
     assert L1.shape == (1,) and torch.equal(L1.detach(), o1['res'][:, 0]) and rows1['q_idx_p'].shape == (1, N)
     assert torch.equal(q1.grad, dq1) and torch.equal(g1.grad, dg1) and float(dq1.abs().max()) > 0
     with pytest.raises(ValueError, match='margin'):
-        head.hetero_center_triplet(q, g, ql, gl, margin=-1.0)
+        losses.hetero_center_triplet(q, g, ql, gl, margin=-1.0)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.hetero_center_triplet(q.cpu(), g.cpu(), ql.cpu(), gl.cpu())
+        losses.hetero_center_triplet(q.cpu(), g.cpu(), ql.cpu(), gl.cpu())
     with pytest.raises(_lib.ReidHipError, match='D='):
-        head.hetero_center_triplet(q[:, :, :6], g[:, :6], ql, gl)
+        losses.hetero_center_triplet(q[:, :, :6], g[:, :6], ql, gl)
 
 
 # ---------------------------------------------------------------------------------------------------------------- model level

@@ -319,7 +319,7 @@ def test_ce_label_smoothing_elementwise(ops, C, scale):
 
 
 def test_ce_wrapper(ops):
-    from prcv2025reid_amd.head import CrossEntropyLSFn
+    from prcv2025reid_amd.losses import CrossEntropyLSFn
     g = torch.Generator().manual_seed(8)
     rows, C = 67, 400
     z = (torch.randn(rows, C, generator=g) * 30).float(); lab = torch.randint(0, C, (rows,), generator=g); lab[2] = -1; lab[3] = C
@@ -429,7 +429,7 @@ def test_sdm_elementwise(ops, P, N, Mg, D, tau, pad, zero_rows):
 
 
 def test_sdm_wrapper(ops):
-    from prcv2025reid_amd.head import SDMFn
+    from prcv2025reid_amd.losses import SDMFn
     g = torch.Generator().manual_seed(21)
     P, N, Mg, D = 2, 48, 40, 512
     q = torch.randn(P * N, D, generator=g); gal = torch.randn(Mg, D, generator=g)

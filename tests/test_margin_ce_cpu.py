@@ -119,19 +119,19 @@ def test_floor_is_the_same_function_in_fp32():
 
 
 def test_argument_checks_raise():
-    from prcv2025reid_amd import head
-    assert head.MARGIN_DEFAULTS == R.DEFAULTS and head.MARGIN_KINDS == R.KINDS and head.EPS == R.EPS
-    assert head.margin_args('t', 'circle', None, None) == ('circle', 64.0, 0.35)
-    assert head.margin_args('t', 'cosine', None, 5.0) == ('cosine', 30.0, 0.0)              # ignored
-    assert head.margin_args('t', 'arcface', 16, 1.5) == ('arcface', 16.0, 1.5)
+    from prcv2025reid_amd import losses
+    assert losses.MARGIN_DEFAULTS == R.DEFAULTS and losses.MARGIN_KINDS == R.KINDS and losses.EPS == R.EPS
+    assert losses.margin_args('t', 'circle', None, None) == ('circle', 64.0, 0.35)
+    assert losses.margin_args('t', 'cosine', None, 5.0) == ('cosine', 30.0, 0.0)              # ignored
+    assert losses.margin_args('t', 'arcface', 16, 1.5) == ('arcface', 16.0, 1.5)
     x, W, lab = torch.zeros(4, 8), torch.zeros(3, 8), torch.zeros(4, dtype=torch.long)
     for kw in (dict(kind='softmax'), dict(scale=0.0), dict(scale=-1.0), dict(scale=float('inf')), dict(margin=-0.1),
                dict(kind='cosface', margin=1.0), dict(kind='circle', margin=1.0), dict(kind='arcface', margin=1.6), dict(smoothing=1.5)):
         with pytest.raises(ValueError):
-            head.margin_cross_entropy(x, W, lab, **kw)
+            losses.margin_cross_entropy(x, W, lab, **kw)
     from prcv2025reid_amd import _lib
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.margin_cross_entropy(x, W, lab)
+        losses.margin_cross_entropy(x, W, lab)
 
 
 def test_config_defaults_to_the_linear_head():

@@ -225,16 +225,16 @@ def test_full_size_rows_every_scale_and_mask(ops, kind):
 # ---- autograd boundary ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('kind', R.KINDS)
 def test_public_call_equals_the_entry_points_and_is_deterministic(ops, kind):
-    """head.margin_cross_entropy (CosineLinearFn + MarginCEFn) gives the bits of the entry points called by hand (which the tests
+    """losses.margin_cross_entropy (CosineLinearFn + MarginCEFn) gives the bits of the entry points called by hand (which the tests
     above hold against the reference); two runs of forward + backward give identical bits; a frozen weight gets no gradient."""
-    from prcv2025reid_amd import head
+    from prcv2025reid_amd import losses
     rows, C, D = 67, 400, 96
     x, W, lab, valid, m = make_case(rows, C, D, kind, 'mixed', 5)
     s = F32(R.DEFAULTS[kind][0])
     runs = []
     for _ in range(2):
         xa, Wa = x.cuda().requires_grad_(True), W.cuda().requires_grad_(True)
-        loss, cnt, logits = head.margin_cross_entropy(xa, Wa, lab.cuda(), valid.cuda().bool(), kind=kind, scale=s, margin=m, smoothing=F32(0.1))
+        loss, cnt, logits = losses.margin_cross_entropy(xa, Wa, lab.cuda(), valid.cuda().bool(), kind=kind, scale=s, margin=m, smoothing=F32(0.1))
         (loss * 0.7).backward()
         runs.append((loss.detach().clone(), logits.detach().clone(), xa.grad.clone(), Wa.grad.clone()))
         assert int(cnt) == int(((lab >= 0) & (lab < C) & valid.bool()).sum())
@@ -253,13 +253,13 @@ def test_public_call_equals_the_entry_points_and_is_deterministic(ops, kind):
     assert torch.equal(runs[0][0], res[2]) and torch.equal(runs[0][1], lg) and torch.equal(runs[0][2], dx) and torch.equal(runs[0][3], dW)
     # only what autograd asks for: a frozen weight costs nothing and the gradient of x keeps its bits
     xa = x.cuda().requires_grad_(True); Wf = W.cuda()
-    loss, _, _ = head.margin_cross_entropy(xa, Wf, labd, vd, kind=kind, scale=s, margin=m, smoothing=F32(0.1))
+    loss, _, _ = losses.margin_cross_entropy(xa, Wf, labd, vd, kind=kind, scale=s, margin=m, smoothing=F32(0.1))
     (loss * 0.7).backward()
     assert Wf.grad is None and torch.equal(xa.grad, dx)
 
 
 def test_entry_points_refuse_bad_arguments(ops):
-    from prcv2025reid_amd import _lib, head
+    from prcv2025reid_amd import _lib, losses
     x, W = torch.zeros(4, 8, device='cuda'), torch.ones(3, 8, device='cuda')
     lab = torch.zeros(4, dtype=torch.long, device='cuda')
     l, rl, res = torch.zeros(4, 3, device='cuda'), torch.zeros(4, device='cuda'), torch.zeros(3, device='cuda')
@@ -273,9 +273,9 @@ def test_entry_points_refuse_bad_arguments(ops):
     with pytest.raises(ValueError, match='rx'):
         ops.cos_logits_fwd(x, W, 30.0, R.EPS, torch.zeros(3, device='cuda', dtype=torch.float64), torch.zeros(3, device='cuda', dtype=torch.float64), l)
     with pytest.raises(ValueError, match='features'):
-        head.margin_cross_entropy(x, W[:, :4], lab)
+        losses.margin_cross_entropy(x, W[:, :4], lab)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.margin_cross_entropy(x.cpu(), W.cpu(), lab.cpu())
+        losses.margin_cross_entropy(x.cpu(), W.cpu(), lab.cpu())
 
 
 # ---- model level ---------------------------------------------------------------------------------------------------------------------
@@ -288,7 +288,8 @@ def _inputs(batch):
 
 
 def test_default_config_is_the_linear_head_bit_for_bit():
-    from prcv2025reid_amd.head import CrossEntropyLSFn, LinearF32Fn
+    from prcv2025reid_amd.head import LinearF32Fn
+    from prcv2025reid_amd.losses import CrossEntropyLSFn
     from test_triplet_gpu import _tiny
     meta, state, batch, make = _tiny()
     images, masks, labels = _inputs(batch)

@@ -100,9 +100,9 @@ def test_entry_points_check_their_arguments_without_a_device(libs, flavor):
 
 
 def test_config_and_head_expose_the_loss():
-    from prcv2025reid_amd import _lib, head
+    from prcv2025reid_amd import _lib, losses
     from prcv2025reid_amd.config import TrainingConfig
     cfg = TrainingConfig()
     assert cfg.triplet_weight == 0.0 and cfg.triplet_margin == 0.3
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.batch_hard_triplet(torch.zeros(4, 8), torch.zeros(4, dtype=torch.int64))
+        losses.batch_hard_triplet(torch.zeros(4, 8), torch.zeros(4, dtype=torch.int64))

@@ -341,12 +341,12 @@ def test_two_runs_give_the_same_bits(ops):
 
 def test_public_call_and_autograd(ops):
     """The autograd boundary by value: open hinges (margin 4: a mix; margin None) and an upstream factor that is not 1."""
-    from prcv2025reid_amd import head, _lib
+    from prcv2025reid_amd import losses, _lib
     from prcv2025reid_amd.model import LazyCount
     for margin, up in ((4.0, 2.0), (None, -0.7)):
         x, labels, ref = case(16, 4, 512, 100.0, margin)
         f = x.clone().requires_grad_(True)
-        loss, n, rows = head.batch_hard_triplet(f, labels, margin=margin)
+        loss, n, rows = losses.batch_hard_triplet(f, labels, margin=margin)
         assert isinstance(n, LazyCount) and int(n) == ref['n_active'] == 64 and set(rows) == {'d_ap', 'd_an', 'idx_p', 'idx_n'}
         assert torch.equal(rows['idx_p'].long(), ref['idx_p']) and torch.equal(rows['idx_n'].long(), ref['idx_n'])
         saved = {k: v.clone() for k, v in rows.items()}
@@ -359,9 +359,9 @@ def test_public_call_and_autograd(ops):
         tol = 4 * U * (1 + ref['loss']) + 0.5 * 512 * U * float((ref['d_ap'] + ref['d_an']).mean())
         assert abs(float(loss.detach()) - ref['loss']) <= tol
     with pytest.raises(ValueError, match='margin'):
-        head.batch_hard_triplet(x, labels, margin=-1.0)
+        losses.batch_hard_triplet(x, labels, margin=-1.0)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.batch_hard_triplet(x.cpu(), labels.cpu())
+        losses.batch_hard_triplet(x.cpu(), labels.cpu())
     with pytest.raises(_lib.ReidHipError):
         ops.triplet_hard_fwd(x[:, :6], labels, None, 0.3, saved['d_ap'], saved['d_an'], saved['idx_p'], saved['idx_n'], saved['d_ap'].clone(),
                              torch.empty(2, device='cuda'))

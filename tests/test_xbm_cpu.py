@@ -77,12 +77,12 @@ def test_config_defaults():
 
 
 def test_cpu_tensors_are_refused():
-    from prcv2025reid_amd import head, _lib
+    from prcv2025reid_amd import losses, _lib
     q, g, lab = X.stream_step(2, 8, 12, 0.0, 1)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.xbm_cross_triplet(q, g, lab, None)
+        losses.xbm_cross_triplet(q, g, lab, None)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.CrossBatchMemory(32, 3, 12, 'cpu')
+        losses.CrossBatchMemory(32, 3, 12, 'cpu')
 
 
 @pytest.mark.parametrize('normalize', [True, False])

@@ -571,17 +571,17 @@ def test_two_runs_give_the_same_bits(ops, normalize):
 # ---------------------------------------------------------------------------------------------------------------- 7. public call
 def test_public_call_and_autograd(ops):
     """The autograd boundary by value, with upstream factors that are not 1; enqueue=False; the argument errors."""
-    from prcv2025reid_amd import head, _lib
+    from prcv2025reid_amd import losses, _lib
     P, N, D, M, _ = X.SHAPES[2]
     qv = torch.ones(P, N, dtype=torch.bool, device='cuda'); qv[1, 3] = False
     for margin, normalize in ((0.3, True), (None, False)):
-        memory = head.CrossBatchMemory(M, P + 1, D, 'cuda')
+        memory = losses.CrossBatchMemory(M, P + 1, D, 'cuda')
         mem = Mem(P, M, D)
         assert int(memory.rows_written) == 0 == int(memory.filled) and memory.cursor.tolist() == [0, 0] and not bool(memory.valid.any())
         for s in (1, 2, 3):                                     # the third batch wraps
             q, g, lab = batch(P, N, D, 30.0, s)
             qa, ga = q.clone().requires_grad_(True), g.clone().requires_grad_(True)
-            L, flag, rows = head.xbm_cross_triplet(qa, ga, lab, memory, q_valid=qv, margin=margin, normalize=normalize)
+            L, flag, rows = losses.xbm_cross_triplet(qa, ga, lab, memory, q_valid=qv, margin=margin, normalize=normalize)
             run_enqueue(ops, mem, q, g, lab, qv, None, normalize)
             o = run_fwd(ops, mem, q, g, lab, qv, None, margin, normalize)
             assert int(memory.rows_written) == s * N and int(memory.filled) == min(M, s * N)
@@ -605,22 +605,22 @@ def test_public_call_and_autograd(ops):
         # enqueue=False: the memory as it stands, ring and cursor untouched; the batch is not in it, so other rows are chosen
         before = [t.clone() for t in (memory.rows, memory.labels, memory.valid, memory.cursor)]
         q4, g4, lab4 = batch(P, N, D, 30.0, 4)
-        L4, _, rows4 = head.xbm_cross_triplet(q4, g4, lab4, memory, margin=margin, normalize=normalize, enqueue=False)
+        L4, _, rows4 = losses.xbm_cross_triplet(q4, g4, lab4, memory, margin=margin, normalize=normalize, enqueue=False)
         o4 = run_fwd(ops, mem, q4, g4, lab4, None, None, margin, normalize)
         assert [torch.equal(a, b) for a, b in zip(before, (memory.rows, memory.labels, memory.valid, memory.cursor))] == [True] * 4
         assert torch.equal(L4, o4['res'][:, 0]) and torch.equal(rows4['g_idx_n'].long(), o4['sel']['g_idx_n']) and float(L4.max()) > 0
         memory.reset()
         assert memory.cursor.tolist() == [0, 0] and not bool(memory.valid.any()) and int(memory.filled) == 0
     q, g, lab = batch(P, N, D, 30.0, 1)
-    memory = head.CrossBatchMemory(M, P + 1, D, 'cuda')
+    memory = losses.CrossBatchMemory(M, P + 1, D, 'cuda')
     with pytest.raises(ValueError, match='margin'):
-        head.xbm_cross_triplet(q, g, lab, memory, margin=-1.0)
+        losses.xbm_cross_triplet(q, g, lab, memory, margin=-1.0)
     with pytest.raises(ValueError, match='does not fit'):
-        head.xbm_cross_triplet(q, g, lab, head.CrossBatchMemory(N - 1, P + 1, D, 'cuda'))
+        losses.xbm_cross_triplet(q, g, lab, losses.CrossBatchMemory(N - 1, P + 1, D, 'cuda'))
     with pytest.raises(_lib.ReidHipError, match='D='):
-        head.xbm_cross_triplet(q[:, :, :8], g[:, :8], lab, memory)
+        losses.xbm_cross_triplet(q[:, :, :8], g[:, :8], lab, memory)
     with pytest.raises(_lib.ReidHipError, match='no CPU path'):
-        head.xbm_cross_triplet(q.cpu(), g.cpu(), lab.cpu(), memory)
+        losses.xbm_cross_triplet(q.cpu(), g.cpu(), lab.cpu(), memory)
     assert memory.cursor.tolist() == [0, 0]                      # a refused call files nothing
 
 

@@ -42,7 +42,7 @@ def window(fn, reps):
 
 def make_calls(P, N, D, ratio=30.0):
     import cross_triplet_ref as R
-    from prcv2025reid_amd.head import CrossTripletFn
+    from prcv2025reid_amd.losses import CrossTripletFn
     q, g, ql, gl = R.make_case(P, N, N, D, ratio, seed=N, device='cuda')
     one = torch.ones((), device='cuda')
     qa, ga = q.clone().requires_grad_(True), g.clone().requires_grad_(True)

@@ -54,7 +54,7 @@ def window(fn, reps):
 
 def make_calls(P, N, D, ratio=30.0):
     import hc_triplet_ref as R
-    from prcv2025reid_amd.head import HcTripletFn, CrossTripletFn
+    from prcv2025reid_amd.losses import HcTripletFn, CrossTripletFn
     q, g, ql, gl = R.make_case(P, N, N, D, ratio, seed=N, K=K, device='cuda')
     one = torch.ones((), device='cuda')
     leaves = {k: (q.clone().requires_grad_(True), g.clone().requires_grad_(True)) for k in ('hip', 'torch', 'xt')}

@@ -42,7 +42,7 @@ def window(fn, reps):
 
 def make_calls(B, D=512, ratio=30.0):
     import triplet_ref as R
-    from prcv2025reid_amd.head import TripletHardFn
+    from prcv2025reid_amd.losses import TripletHardFn
     x, labels = R.make_rows(B // 4, 4, D, ratio, seed=B, device='cuda')
     one = torch.ones((), device='cuda')
     xa = x.clone().requires_grad_(True); xb = x.clone().requires_grad_(True)

@@ -1,6 +1,6 @@
 """Center loss (csrc/center.hip): what it costs.
 
-    python tools/center_times.py launch   forward + centre update + backward through head.CenterLossFn at N = 64, D = 512, C = 1000 for
+    python tools/center_times.py launch   forward + centre update + backward through losses.CenterLossFn at N = 64, D = 512, C = 1000 for
                                           S = 1 and S = 5, against the same arithmetic written with torch ops (index_select for the
                                           centres, index_add_ for the per-class sums and counts) through autograd, alternating windows
                                           in one process
@@ -52,7 +52,7 @@ def torch_center(x, labels, valid, centers, alpha):
 
 
 def launch(reps=300, rounds=7):
-    from prcv2025reid_amd.head import CenterLossFn, ClassCenters
+    from prcv2025reid_amd.losses import CenterLossFn, ClassCenters
     rec = dict(mode='launch', N=N, D=D, C=CLASSES, alpha=ALPHA, reps=reps, rounds=rounds)
     for S in (1, 5):
         g = torch.Generator().manual_seed(S)

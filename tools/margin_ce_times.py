@@ -60,7 +60,8 @@ def torch_margin(x, W, y, kind, s, m):
 
 
 def head(out, reps=100, rounds=7):
-    from prcv2025reid_amd.head import CosineLinearFn, CrossEntropyLSFn, LinearF32Fn, MarginCEFn, MARGIN_DEFAULTS
+    from prcv2025reid_amd.head import CosineLinearFn, LinearF32Fn
+    from prcv2025reid_amd.losses import CrossEntropyLSFn, MarginCEFn, MARGIN_DEFAULTS
     rows = []
     for B in (64, 256):
         g = torch.Generator(device='cuda').manual_seed(B)
@@ -108,7 +109,7 @@ def step(out, steps=10, rounds=5, warmup=3):
     from prcv2025reid_amd.parallel import DataParallel
     from prcv2025reid_amd.synthetic import synthetic_batch
     from prcv2025reid_amd.trainer import FusedAdamW, StepDriver
-    from prcv2025reid_amd.head import margin_args
+    from prcv2025reid_amd.losses import margin_args
     inputs, steppers, last = None, {}, {}
     for kind in ('linear', 'cosface'):
         torch.manual_seed(0)

@@ -48,7 +48,7 @@ def window(fn, reps):
 def make_calls(M):
     import xbm_ref as X
     from prcv2025reid_amd import ops
-    from prcv2025reid_amd.head import CrossBatchMemory, XbmTripletFn, EPS
+    from prcv2025reid_amd.losses import CrossBatchMemory, XbmTripletFn, EPS
     memory = CrossBatchMemory(M, P + 1, D, 'cuda')
     for s in range(1, M // N + 1):                            # a full ring of unit rows, the last batch the one that is mined
         q, g, lab = X.stream_step(P, N, D, 0.0, s, 'cuda')
