@@ -630,6 +630,12 @@ int reid_l2norm_rows(const float* x, int32_t ldx, float* y, void* y_bf16, int32_
  *                   reid_opt_clip's record < 0 means "record when (device batch counter state[19]) % (-record) == 0" -- the
  *                   forms a captured HIP graph replays;
  *                   zero_grad != 0 clears g in the same pass (optimizer.zero_grad at the next accumulation window)
+ * An entry with g == NULL is skipped by every kernel: its p, exp_avg and exp_avg_sq are not touched, and reid_opt_sumsq writes
+ * zeros for its partials (ws never keeps stale values).  The squares are summed in fp32 within a workgroup (as clip_grad_norm_
+ * does on fp32 tensors): a g * g that overflows fp32 gives ||g|| = inf and a clip coefficient of 0.
+ * Refused before any launch: a null table (sumsq, adamw), ws (sumsq, clip) or state (clip), n_entries < 1 (or > 65535, the grid's y
+ * extent), fixed_max_norm that is not > 0 (NaN included), beta1 or beta2 outside [0, 1), eps that is not > 0, step < 0, step == 0
+ * without state.  No atomics, nothing is allocated, nothing is synchronised; grid = 128 x n_entries workgroups.
  * ------------------------------------------------------------------------------------------ */
 typedef struct reid_opt_entry {
     float* p; float* g; float* exp_avg; float* exp_avg_sq;

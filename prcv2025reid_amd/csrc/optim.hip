@@ -166,7 +166,7 @@ extern "C" int32_t reid_opt_ws_floats(int32_t n_entries) { return 2 * OPT_BLOCKS
 extern "C" int32_t reid_opt_state_floats(void) { return ST_FLOATS; }
 
 extern "C" int reid_opt_sumsq(const void* table, int32_t n_entries, float* ws, void* stream) {
-    REID_CHECK_ARG(table && ws && n_entries > 0, "reid_opt_sumsq: bad args");
+    REID_CHECK_ARG(table && ws && n_entries >= 1 && n_entries <= 65535, "reid_opt_sumsq: bad args (table, ws, 1 <= n_entries <= 65535)");
     hipLaunchKernelGGL(opt_sumsq_kernel, dim3(OPT_BLOCKS, n_entries), dim3(256), 0, (hipStream_t)stream, (const OptEntry*)table, ws,
                        ws + OPT_BLOCKS * n_entries);
     REID_CHECK_LAUNCH("reid_opt_sumsq");
@@ -175,7 +175,7 @@ extern "C" int reid_opt_sumsq(const void* table, int32_t n_entries, float* ws, v
 
 extern "C" int reid_opt_clip(const float* ws, int32_t n_entries, float* state, int32_t adaptive, float fixed_max_norm,
                              int32_t record, void* stream) {
-    REID_CHECK_ARG(ws && state && n_entries > 0, "reid_opt_clip: bad args");
+    REID_CHECK_ARG(ws && state && n_entries >= 1 && n_entries <= 65535, "reid_opt_clip: bad args (ws, state, 1 <= n_entries <= 65535)");
     REID_CHECK_ARG(fixed_max_norm > 0.f, "reid_opt_clip: max_norm must be positive");
     hipLaunchKernelGGL(opt_clip_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ws, ws + OPT_BLOCKS * n_entries,
                        OPT_BLOCKS * n_entries, state, adaptive, fixed_max_norm, record);
@@ -185,7 +185,8 @@ extern "C" int reid_opt_clip(const float* ws, int32_t n_entries, float* state, i
 
 extern "C" int reid_opt_adamw(const void* table, int32_t n_entries, const float* coef, float beta1, float beta2, float eps,
                               int32_t step, int32_t zero_grad, float* state, void* stream) {
-    REID_CHECK_ARG(table && n_entries > 0 && (step >= 1 || (step == 0 && state)), "reid_opt_adamw: bad args (step counts from 1; 0 = device counter in state)");
+    REID_CHECK_ARG(table && n_entries >= 1 && n_entries <= 65535, "reid_opt_adamw: bad args (table, 1 <= n_entries <= 65535)");
+    REID_CHECK_ARG(step >= 1 || (step == 0 && state), "reid_opt_adamw: bad args (step counts from 1; 0 = device counter in state)");
     REID_CHECK_ARG(beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps > 0.f, "reid_opt_adamw: betas/eps");
     AdamHp h;
     h.beta1 = beta1; h.beta2 = beta2; h.eps = eps;

@@ -44,8 +44,11 @@ def test_fused_adamw_vs_oracle(adaptive):
         for p, o in zip(dev_p, orc.params):
             assert torch.allclose(p.detach().cpu(), o, rtol=5e-6, atol=1e-7), step
             assert float(p.grad.abs().max()) == 0.0                  # cleared by the step kernel
+        for j, i in enumerate(order):                                # both moments too: they are checkpointed state
+            assert opt.exp_avg[j].shape == orc.m[i].shape
+            assert torch.allclose(opt.exp_avg[j].cpu(), orc.m[i], rtol=5e-6, atol=1e-7), (step, i)
+            assert torch.allclose(opt.exp_avg_sq[j].cpu(), orc.v[i], rtol=5e-6, atol=1e-7), (step, i)
     assert orc.history and len(orc.history) == 14 if adaptive else True
-    del order
 
 
 def test_step_driver_tiny_model():
