@@ -695,6 +695,35 @@ int reid_rank_metrics(const float* scores, int64_t ld, const int32_t* g_pid, con
                       int32_t* npos, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cutoff metrics: what mAP@K, CMC@K and mINP are made of (reference: compute_map / compute_cmc, train.py:101-138, the metric the
+ * competition ranks by at K = 100; mINP: Ye et al., TPAMI 2021).  Definitions, for one query: let
+ *   rank_0 < rank_1 < ... < rank_{np-1}
+ * be the ranks (1-based) of its np unmasked positives in the ranking of reid_rank_metrics -- score descending, gallery index
+ * ascending on ties, same-image rows removed.  For a cutoff K >= 1:
+ *   hits_K    = #{r : rank_r <= K}
+ *   sum_K     = sum over {r : rank_r <= K} of (r + 1) / rank_r, formed in fp64
+ *   rank_last = rank_{np-1}
+ *   AP@K, norm 'hits' = sum_K / hits_K, a query with hits_K == 0 left out of the mean (compute_map of the reference)
+ *   AP@K, norm 'min'  = sum_K / min(K, np) over every query with np > 0 (the usual truncated AP)
+ *   CMC@K = (rank_0 <= K);  INP = np / rank_last, mINP its mean over the queries with np > 0.
+ * The divisions and means are the caller's (evaluate.cutoff_summary); the kernels return hits, sum and the ranks.
+ *
+ * reid_rank_metrics_at: reid_rank_metrics with cutoffs -- the same one-pass kernel, the same arguments, plus
+ *   cutoffs   i32 [n_cut] ON THE HOST, 1 <= n_cut <= REID_METRICS_MAX_CUTOFFS, each >= 1, strictly ascending; a cutoff above Ng is
+ *             allowed.  They travel by value in the kernel's parameters: the array may be reused as soon as the call returns.
+ *   rank_last i32 [nq], hits i32 [nq, n_cut], sum_at f64 [nq, n_cut], contiguous
+ * ap, rank1 and npos are bit for bit those of reid_rank_metrics on the same rows.  A query without a positive (npos = 0) or with more
+ * than 8192 (npos = -1) writes zeros to the three new outputs.  The new sums are reduced in the fixed order of ap (lane shuffles,
+ * then the four wave partials): deterministic; no atomics beyond the integer LDS counters of reid_rank_metrics.
+ * ------------------------------------------------------------------------------------------ */
+#define REID_METRICS_MAX_CUTOFFS 8
+int reid_rank_metrics_at(const float* scores, int64_t ld, const int32_t* g_pid, const int32_t* g_img,
+                         const int32_t* q_pid, const int32_t* q_slot, const int32_t* q_excl, const int32_t* csr_off,
+                         const int32_t* csr_idx, int32_t nq, int32_t Ng, int32_t max_pos, const int32_t* cutoffs,
+                         int32_t n_cut, double* ap, int32_t* rank1, int32_t* npos, int32_t* rank_last, int32_t* hits,
+                         double* sum_at, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Exact top-k lists of fp32 score rows (csrc/select.hip): the ranked lists of the rows reid_rank_metrics scores, without a sort
  * of the row.
  *   scores  f32 [nq, ld], ld >= n, ld % 4 == 0, base 16-byte aligned (what reid_rank_metrics accepts and the re-ranking kernels
@@ -713,6 +742,37 @@ int reid_rank_metrics(const float* scores, int64_t ld, const int32_t* g_pid, con
 #define REID_ROWS_TOPK_MAX_K 1024
 int reid_rows_topk(const float* scores, int64_t ld, int32_t nq, int32_t n, int32_t k, const int32_t* g_img,
                    const int32_t* q_excl, int32_t* out_idx, float* out_score, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Cutoff metrics of ranked lists (csrc/list_metrics.hip): hits and sum of the definitions above from the first k gallery rows of a
+ * ranking -- the lists of reid_rows_topk / reid_cosine_topk*, or of a submission file -- instead of from score rows.
+ *   idx     i32 [nq, k], contiguous, 1 <= k <= REID_ROWS_TOPK_MAX_K: position t of row q is the gallery row ranked (t + 1)-th;
+ *           -1 = no entry, allowed only behind the last entry
+ *   g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx: as in reid_rank_metrics; Ng = number of gallery rows
+ *   cutoffs i32 [n_cut] ON THE HOST (by value in the kernel's parameters): 1 <= n_cut <= REID_METRICS_MAX_CUTOFFS, each >= 1,
+ *           strictly ascending and <= k -- a list of k entries says nothing about a rank beyond k; refused before the launch
+ * outputs per query:
+ *   npos    i32 [nq]: the unmasked positives IN THE GALLERY, counted from the CSR under the exclusion (what norm 'min' divides by)
+ *   rank1   i32 [nq]: the position of the first hit, 0 when the list holds none
+ *   hits    i32 [nq, n_cut], sum_at f64 [nq, n_cut]
+ *   status  i32 [nq]: 0, or a sum of REID_LIST_BAD_* -- the query's other outputs are then all zero
+ * Positions: an entry whose gallery row the query excludes (g_img / q_excl) is SKIPPED and the positions behind it move up by one,
+ * so a list is scored as the ranking with the same-image rows removed.  Lists of reid_rows_topk under the same exclusion hold no
+ * such entry; a foreign list may.
+ * Malformed lists: an index below -1 (REID_LIST_BAD_NEGATIVE), an index >= Ng (REID_LIST_BAD_RANGE), an entry behind a -1
+ * (REID_LIST_BAD_ORDER).  Every index is checked before g_pid / g_img are read: nothing is read out of bounds.  A gallery row
+ * listed twice is NOT detected here (ProtocolEvaluator.score_lists checks it with a sort).
+ * One wave per query; 64 positions at a time: ballots of the counted entries and of the hits, positions by popcount, running
+ * carries across the chunks; fp64 sums in a fixed shuffle order per chunk, chunks added in order: deterministic.  No atomics, no LDS,
+ * nothing is allocated, nothing is synchronised or read back.
+ * ------------------------------------------------------------------------------------------ */
+#define REID_LIST_BAD_NEGATIVE 1
+#define REID_LIST_BAD_RANGE 2
+#define REID_LIST_BAD_ORDER 4
+int reid_list_metrics(const int32_t* idx, int32_t nq, int32_t k, const int32_t* g_pid, const int32_t* g_img,
+                      const int32_t* q_pid, const int32_t* q_slot, const int32_t* q_excl, const int32_t* csr_off,
+                      const int32_t* csr_idx, int32_t Ng, const int32_t* cutoffs, int32_t n_cut, int32_t* npos,
+                      int32_t* rank1, int32_t* hits, double* sum_at, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Image transforms of the training input (datasets/dataset.py:284-307, train.py:1634-1641; eval: dataset.py:300-307,

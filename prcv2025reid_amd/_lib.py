@@ -130,7 +130,9 @@ SIGNATURES = {
     'reid_ema_update': (_I, [_P, _I, _F, _I, _I, _P, _P]),
     'reid_ema_swap': (_I, [_P, _I, _P]),
     'reid_rank_metrics': (_I, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    'reid_rank_metrics_at': (_I, [_P, _I64, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     'reid_rows_topk': (_I, [_P, _I64, _I, _I, _I, _P, _P, _P, _P, _P]),
+    'reid_list_metrics': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     'reid_augment_ws_bytes': (_I64, [_I, _I]),
     'reid_augment_images': (_I, [_P, _I64, _P, _P, _I, _I, _P, _P, _I64, _P, _P]),
     'reid_expand_rows': (_I, [_P, _I64, _P, _I64, _I, _P, _P, _I, _I, _I, _I, _I64, _I, _F, _P, _I64, _I, _I, _P]),

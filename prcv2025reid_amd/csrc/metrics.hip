@@ -12,6 +12,8 @@
 //      in an LDS histogram;
 //   3. prefix sum of the histogram -> rank of the r-th positive = 1 + r + #non-positives before it;
 //      AP = mean_r (r + 1) / rank_r (double), first-positive rank for CMC@k.
+// reid_rank_metrics_at (mAP@K of compute_map, train.py:101-126; mINP) is the same kernel with a flag: step 3 also keeps, per cutoff
+// K, the number of positives of rank <= K and the sum of their terms, and the rank of the last positive.
 // HBM-bound: 4 bytes of score + 8 bytes of L2-resident pid / image id per gallery entry per query.
 #include "rank.h"
 
@@ -21,6 +23,7 @@ using namespace ranking;
 
 constexpr int NBUCKET = 2048;      // score buckets between the weakest and the strongest positive of a query
 constexpr int MAXP_LIMIT = 8192;    // positives per query held in LDS (12 bytes each; more -> npos = -1, not evaluated)
+constexpr int MAX_CUT = REID_METRICS_MAX_CUTOFFS;
 
 struct MetricParams {
     const float* S; long long lds_;            // scores [nq, lds_]
@@ -30,8 +33,14 @@ struct MetricParams {
     const int32_t* csr_off; const int32_t* csr_idx;
     double* ap; int32_t* rank1; int32_t* npos;
     int nq, Ng, cap;                           // cap: power of two >= the longest CSR row, LDS capacity of this launch
+    // reid_rank_metrics_at only (AT below): the cutoffs by value, ascending, and the per-cutoff outputs
+    int32_t* rank_last; int32_t* hits; double* sum_at;   // [nq], [nq, n_cut], [nq, n_cut]
+    int n_cut; int cut[MAX_CUT];
 };
 
+// AT = false: reid_rank_metrics.  AT = true: the same pass also keeps, per cutoff K, the number of positives of rank <= K and the sum
+// of their (r + 1) / rank_r -- the terms of `ap`, masked -- and the rank of the last positive.
+template <bool AT>
 __global__ __launch_bounds__(256) void rank_metrics_kernel(const MetricParams p) {
     extern __shared__ __attribute__((aligned(16))) char dyn[];
     float* ps = (float*)dyn;
@@ -59,6 +68,10 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const MetricParams p)
     const int np = cnt;
     if (np == 0 || np > MAXP) {
         if (tid == 0) { p.ap[q] = 0.0; p.rank1[q] = 0; p.npos[q] = np == 0 ? 0 : -1; }
+        if constexpr (AT) {
+            if (tid == 0) p.rank_last[q] = 0;
+            if (tid < p.n_cut) { p.hits[(long long)q * p.n_cut + tid] = 0; p.sum_at[(long long)q * p.n_cut + tid] = 0.0; }
+        }
         return;
     }
     int n2 = 1;
@@ -137,20 +150,64 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const MetricParams p)
     }
     __syncthreads();
     double acc = 0.0;
+    double acc_at[AT ? MAX_CUT : 1] = {};
+    int hit_at[AT ? MAX_CUT : 1] = {};
     {
         int run = part[tid];
         for (int t = tid * per; t < min(np, (tid + 1) * per); ++t) {
             run += hist[t];
             const int rank = 1 + t + run;
-            acc += (double)(t + 1) / (double)rank;
+            const double term = (double)(t + 1) / (double)rank;
+            acc += term;
             if (t == 0) p.rank1[q] = rank;
+            if constexpr (AT) {
+                if (t == np - 1) p.rank_last[q] = rank;
+#pragma unroll
+                for (int c = 0; c < MAX_CUT; ++c)
+                    if (c < p.n_cut && rank <= p.cut[c]) { acc_at[c] += term; ++hit_at[c]; }
+            }
         }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
+    if constexpr (AT) {                                         // the same fixed order as `ap`: lane shuffles, then the four wave partials
+        __shared__ double red_at[MAX_CUT][4];
+        __shared__ int red_hit[MAX_CUT][4];
+#pragma unroll
+        for (int c = 0; c < MAX_CUT; ++c) {
+            if (c < p.n_cut) {                                  // (n_cut is uniform: whole waves take the shuffles or skip them)
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) { acc_at[c] += __shfl_xor(acc_at[c], o, 64); hit_at[c] += __shfl_xor(hit_at[c], o, 64); }
+                if ((tid & 63) == 0) { red_at[c][tid >> 6] = acc_at[c]; red_hit[c][tid >> 6] = hit_at[c]; }
+            }
+        }
+        __syncthreads();
+        if (tid < p.n_cut) {
+            p.sum_at[(long long)q * p.n_cut + tid] = (red_at[tid][0] + red_at[tid][1]) + (red_at[tid][2] + red_at[tid][3]);
+            p.hits[(long long)q * p.n_cut + tid] = (red_hit[tid][0] + red_hit[tid][1]) + (red_hit[tid][2] + red_hit[tid][3]);
+        }
+    } else {
+        __syncthreads();
+    }
     if (tid == 0) { p.ap[q] = ((red[0] + red[1]) + (red[2] + red[3])) / (double)np; p.npos[q] = np; }
+}
+
+// argument checks and the launch shared by both entry points
+template <bool AT>
+int launch_rank_metrics(const char* name, MetricParams p, int64_t ld, int32_t max_pos, void* stream) {
+    REID_CHECK_ARG(p.S && p.g_pid && p.q_pid && p.q_slot && p.csr_off && p.csr_idx && p.ap && p.rank1 && p.npos, "%s: null pointer", name);
+    REID_CHECK_ARG(p.nq > 0 && p.Ng > 0 && ld >= p.Ng && ld % 4 == 0, "%s: nq=%d Ng=%d ld=%lld (ld %% 4 == 0)", name, p.nq, p.Ng, (long long)ld);
+    REID_CHECK_ARG(((uintptr_t)p.S & 15) == 0, "%s: scores must be 16-byte aligned", name);
+    REID_CHECK_ARG(max_pos >= 1, "%s: max_pos", name);
+    int cap = 64;
+    while (cap < max_pos && cap < MAXP_LIMIT) cap <<= 1;
+    p.cap = cap;
+    const int lds = 12 * cap + 16;
+    REID_MAX_LDS((rank_metrics_kernel<AT>), 12 * MAXP_LIMIT + 16);
+    hipLaunchKernelGGL(rank_metrics_kernel<AT>, dim3(p.nq), dim3(256), lds, (hipStream_t)stream, p);
+    REID_CHECK_LAUNCH(name);
+    return REID_OK;
 }
 
 }  // namespace
@@ -159,16 +216,23 @@ extern "C" int reid_rank_metrics(const float* scores, int64_t ld, const int32_t*
                                  const int32_t* q_pid, const int32_t* q_slot, const int32_t* q_excl, const int32_t* csr_off,
                                  const int32_t* csr_idx, int32_t nq, int32_t Ng, int32_t max_pos, double* ap, int32_t* rank1,
                                  int32_t* npos, void* stream) {
-    REID_CHECK_ARG(scores && g_pid && q_pid && q_slot && csr_off && csr_idx && ap && rank1 && npos, "reid_rank_metrics: null pointer");
-    REID_CHECK_ARG(nq > 0 && Ng > 0 && ld >= Ng && ld % 4 == 0, "reid_rank_metrics: nq=%d Ng=%d ld=%lld (ld %% 4 == 0)", nq, Ng, (long long)ld);
-    REID_CHECK_ARG(((uintptr_t)scores & 15) == 0, "reid_rank_metrics: scores must be 16-byte aligned");
-    REID_CHECK_ARG(max_pos >= 1, "reid_rank_metrics: max_pos");
-    int cap = 64;
-    while (cap < max_pos && cap < MAXP_LIMIT) cap <<= 1;
-    MetricParams p{scores, (long long)ld, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, ap, rank1, npos, nq, Ng, cap};
-    const int lds = 12 * cap + 16;
-    REID_MAX_LDS((rank_metrics_kernel), 12 * MAXP_LIMIT + 16);
-    hipLaunchKernelGGL(rank_metrics_kernel, dim3(nq), dim3(256), lds, (hipStream_t)stream, p);
-    REID_CHECK_LAUNCH("reid_rank_metrics");
-    return REID_OK;
+    MetricParams p{scores, (long long)ld, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, ap, rank1, npos, nq, Ng, 0,
+                   nullptr, nullptr, nullptr, 0, {}};
+    return launch_rank_metrics<false>("reid_rank_metrics", p, ld, max_pos, stream);
+}
+
+extern "C" int reid_rank_metrics_at(const float* scores, int64_t ld, const int32_t* g_pid, const int32_t* g_img,
+                                    const int32_t* q_pid, const int32_t* q_slot, const int32_t* q_excl, const int32_t* csr_off,
+                                    const int32_t* csr_idx, int32_t nq, int32_t Ng, int32_t max_pos, const int32_t* cutoffs,
+                                    int32_t n_cut, double* ap, int32_t* rank1, int32_t* npos, int32_t* rank_last, int32_t* hits,
+                                    double* sum_at, void* stream) {
+    REID_CHECK_ARG(cutoffs && rank_last && hits && sum_at, "reid_rank_metrics_at: null pointer");
+    REID_CHECK_ARG(n_cut >= 1 && n_cut <= MAX_CUT, "reid_rank_metrics_at: n_cut=%d outside 1..%d", n_cut, MAX_CUT);
+    MetricParams p{scores, (long long)ld, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, ap, rank1, npos, nq, Ng, 0,
+                   rank_last, hits, sum_at, n_cut, {}};
+    for (int c = 0; c < n_cut; ++c) {
+        REID_CHECK_ARG(cutoffs[c] >= 1 && (c == 0 || cutoffs[c] > cutoffs[c - 1]), "reid_rank_metrics_at: cutoffs must be >= 1 and strictly ascending (cutoffs[%d]=%d)", c, cutoffs[c]);
+        p.cut[c] = cutoffs[c];
+    }
+    return launch_rank_metrics<true>("reid_rank_metrics_at", p, ld, max_pos, stream);
 }

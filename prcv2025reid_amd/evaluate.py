@@ -8,10 +8,13 @@ The reference scores one query at a time, argsorts the whole gallery row and wal
     pieces (2 for the f16 flavor, 3 for bf16) and the significant cross products are laid side by side along K, so one
     ``reid_mer_gemm`` call returns fp32-grade similarities (error <= ~2e-7 for unit vectors, i.e. fp32 rounding level)
     at matrix-core speed;
-  * AP / CMC come from ``reid_rank_metrics`` (csrc/metrics.hip): ranks of the positives only, no sort of the gallery.
+  * AP / CMC come from ``reid_rank_metrics`` (csrc/metrics.hip): ranks of the positives only, no sort of the gallery;
+  * mAP@K / CMC@K / mINP (``compute_map(k=100)`` / ``compute_cmc``, train.py:101-138: the competition's metric) come from the same pass
+    with cutoffs, ``reid_rank_metrics_at``, or from ranked lists, ``reid_list_metrics`` (csrc/list_metrics.hip); ``cutoff_summary``
+    forms the means.
 Nothing here falls back to the CPU; the pure-Python oracle lives in oracle/reid_oracle.py and is used by tests only.
 """
-from typing import TYPE_CHECKING, Dict, List, Optional, Sequence
+from typing import TYPE_CHECKING, Dict, List, Mapping, Optional, Sequence, Tuple
 
 import torch
 
@@ -143,24 +146,57 @@ class ProtocolEvaluator:
         re-ranked similarity s* (rerank.py) instead of the cosine; the same-image exclusion is the same.  ``expand``: an
         ``ExpansionParams`` first replaces the queries by their expansion (``_expanded``); with ``rerank`` as well, the expanded queries
         are what the re-ranker receives."""
-        if expand is not None:
-            q_feats, normalized = self._expanded(q_feats, expand, q_img_ids, ignore_same_img, chunk, normalized), True
-        Nq = q_feats.shape[0]
-        qp = q_pids.to(self.dev).long()
-        pos = torch.searchsorted(self._uniq, qp).clamp(max=self._uniq.numel() - 1)
-        slot = torch.where(self._uniq[pos] == qp, pos, torch.full_like(pos, -1)).to(torch.int32).contiguous()
-        qp32 = qp.to(torch.int32).contiguous()
-        excl = self._exclusions(q_img_ids, ignore_same_img)
+        Nq, qp32, slot, blocks = self._scored_blocks(q_feats, q_pids, q_img_ids, ignore_same_img, chunk, normalized, rerank, expand)
         ap = torch.zeros(Nq, dtype=torch.float64, device=self.dev)
         rank1 = torch.zeros(Nq, dtype=torch.int32, device=self.dev)
         npos = torch.zeros(Nq, dtype=torch.int32, device=self.dev)
-        rr = None if rerank is None else self._reranker(q_feats, rerank, normalized)
-        for a in range(0, Nq, chunk):
-            b = min(Nq, a + chunk)
-            S = self.scores(q_feats[a:b], normalized) if rr is None else rr.rows(a, b)
-            ops.rank_metrics(S, self.g_pid, self.g_img, qp32[a:b], slot[a:b], None if excl is None else excl[a:b].contiguous(),
+        for a, b, S, excl in blocks():
+            ops.rank_metrics(S, self.g_pid, self.g_img, qp32[a:b], slot[a:b], excl,
                              self.csr_off, self.csr_idx, self.Ng, self.max_pos, ap[a:b], rank1[a:b], npos[a:b])
         return ap, rank1, npos
+
+    def _query_ids(self, q_pids: torch.Tensor):
+        """(q_pid i32 [Nq], q_slot i32 [Nq]) on the device: the CSR row of every query's pid, -1 for a pid without a gallery row."""
+        qp = q_pids.to(self.dev).long()
+        pos = torch.searchsorted(self._uniq, qp).clamp(max=self._uniq.numel() - 1)
+        slot = torch.where(self._uniq[pos] == qp, pos, torch.full_like(pos, -1)).to(torch.int32).contiguous()
+        return qp.to(torch.int32).contiguous(), slot
+
+    def _scored_blocks(self, q_feats, q_pids, q_img_ids, ignore_same_img, chunk, normalized, rerank, expand):
+        """The prologue ``per_query`` and ``per_query_at`` share: (Nq, q_pid, q_slot, blocks), where ``blocks()`` yields, per chunk of
+        queries, (a, b, score rows of queries a..b, their exclusion rows or None) -- cosine rows, or s* rows with ``rerank``, of the
+        expanded queries with ``expand``."""
+        if expand is not None:
+            q_feats, normalized = self._expanded(q_feats, expand, q_img_ids, ignore_same_img, chunk, normalized), True
+        Nq = q_feats.shape[0]
+        qp32, slot = self._query_ids(q_pids)
+        excl = self._exclusions(q_img_ids, ignore_same_img)
+        rr = None if rerank is None else self._reranker(q_feats, rerank, normalized)
+
+        def blocks():
+            for a in range(0, Nq, chunk):
+                b = min(Nq, a + chunk)
+                S = self.scores(q_feats[a:b], normalized) if rr is None else rr.rows(a, b)
+                yield a, b, S, None if excl is None else excl[a:b].contiguous()
+        return Nq, qp32, slot, blocks
+
+    def per_query_at(self, q_feats: torch.Tensor, q_pids: torch.Tensor, ks: Sequence[int] = (100,), q_img_ids: Optional[Sequence] = None,
+                     ignore_same_img: bool = True, chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None,
+                     expand: Optional['ExpansionParams'] = None) -> Dict[str, torch.Tensor]:
+        """``per_query`` with cutoffs ``ks`` (ascending, at most 8): a dictionary of device tensors -- 'ap' f64, 'rank1', 'npos',
+        'rank_last' i32 [Nq], 'hits' i32 and 'sum_at' f64 [Nq, len(ks)] (include/reid_hip.h, reid_rank_metrics_at; the definitions are
+        DESIGN.md section 21) -- of the same rows, re-ranker and expansion; 'ap', 'rank1' and 'npos' are ``per_query``'s bit for bit.
+        ``cutoff_summary`` turns them into mAP@K / R@K / mINP."""
+        ops.check_cutoffs(ks)
+        Nq, qp32, slot, blocks = self._scored_blocks(q_feats, q_pids, q_img_ids, ignore_same_img, chunk, normalized, rerank, expand)
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        out = {'ap': torch.zeros(Nq, dtype=torch.float64, device=self.dev), 'rank1': torch.zeros(Nq, **i32), 'npos': torch.zeros(Nq, **i32),
+               'rank_last': torch.zeros(Nq, **i32), 'hits': torch.zeros(Nq, len(ks), **i32),
+               'sum_at': torch.zeros(Nq, len(ks), dtype=torch.float64, device=self.dev)}
+        for a, b, S, excl in blocks():
+            ops.rank_metrics_at(S, self.g_pid, self.g_img, qp32[a:b], slot[a:b], excl, self.csr_off, self.csr_idx, self.Ng, self.max_pos,
+                                ks, *(out[n][a:b] for n in ('ap', 'rank1', 'npos', 'rank_last', 'hits', 'sum_at')))
+        return out
 
     def ranked_lists(self, q_feats: torch.Tensor, k: int = 100, q_img_ids: Optional[Sequence] = None, ignore_same_img: bool = True,
                      chunk: int = 1024, normalized: bool = False, rerank: Optional['RerankParams'] = None,
@@ -187,25 +223,97 @@ class ProtocolEvaluator:
         return idx, score
 
     def rank_and_metrics(self, q_feats, q_pids, q_img_ids=None, ignore_same_img: bool = True, chunk: int = 1024,
-                         rerank: Optional['RerankParams'] = None, expand: Optional['ExpansionParams'] = None) -> Dict[str, float]:
-        """Same dictionary as eval_mm_protocol.py:455-469: queries without an (unmasked) positive are skipped."""
-        ap, rank1, npos = self.per_query(q_feats, q_pids, q_img_ids, ignore_same_img, chunk, rerank=rerank, expand=expand)
+                         rerank: Optional['RerankParams'] = None, expand: Optional['ExpansionParams'] = None,
+                         ks: Optional[Sequence[int]] = None, norm: str = 'hits') -> Dict[str, float]:
+        """Same dictionary as eval_mm_protocol.py:455-469: queries without an (unmasked) positive are skipped.  ``ks``: cutoffs add the
+        keys of ``cutoff_summary`` (mAP@K, R@K, num_queries@K, mINP) from the same pass; None returns the dictionary above alone."""
+        at = None
+        if ks is None:
+            ap, rank1, npos = self.per_query(q_feats, q_pids, q_img_ids, ignore_same_img, chunk, rerank=rerank, expand=expand)
+        else:
+            at = self.per_query_at(q_feats, q_pids, ks, q_img_ids, ignore_same_img, chunk, rerank=rerank, expand=expand)
+            ap, rank1, npos = at['ap'], at['rank1'], at['npos']
         if bool((npos < 0).any()):
             raise _lib.ReidHipError('a query has more than 8192 positives in the gallery: not supported by reid_rank_metrics')
         valid = npos > 0
         n = int(valid.sum())
         if n == 0:
-            return {'mAP': 0.0, 'R@1': 0.0, 'R@5': 0.0, 'R@10': 0.0, 'num_queries': 0}
-        r = rank1[valid]
-        return {'mAP': float(ap[valid].mean()), 'R@1': float((r <= 1).double().mean()), 'R@5': float((r <= 5).double().mean()),
-                'R@10': float((r <= 10).double().mean()), 'num_queries': n}
+            res = {'mAP': 0.0, 'R@1': 0.0, 'R@5': 0.0, 'R@10': 0.0, 'num_queries': 0}
+        else:
+            r = rank1[valid]
+            res = {'mAP': float(ap[valid].mean()), 'R@1': float((r <= 1).double().mean()), 'R@5': float((r <= 5).double().mean()),
+                   'R@10': float((r <= 10).double().mean()), 'num_queries': n}
+        if at is not None:
+            res.update(cutoff_summary(at['sum_at'], at['hits'], rank1, at['rank_last'], npos, ks, norm))
+        return res
 
-    def reid_map(self, q_feats, q_pids):
-        """(mAP, top-1) of _reid_map (train.py:450-479): mAP over queries with a positive, top-1 over ALL queries."""
-        ap, rank1, npos = self.per_query(q_feats, q_pids, None, False)
+    def reid_map(self, q_feats, q_pids, k: Optional[int] = None):
+        """(mAP, top-1) of _reid_map (train.py:450-479): mAP over queries with a positive, top-1 over ALL queries.  ``k``: a cutoff
+        returns (mAP@k in the 'hits' form -- compute_map(k), train.py:101-126 --, the same top-1)."""
+        if k is None:
+            ap, rank1, npos = self.per_query(q_feats, q_pids, None, False)
+        else:
+            at = self.per_query_at(q_feats, q_pids, (k,), None, False)
+            ap, rank1, npos = at['ap'], at['rank1'], at['npos']
         valid = npos > 0
         n = max(1, int(valid.sum()))
-        return float(ap[valid].sum() / n), float(((rank1 == 1) & valid).double().sum() / q_feats.shape[0])
+        top1 = float(((rank1 == 1) & valid).double().sum() / q_feats.shape[0])
+        if k is None:
+            return float(ap[valid].sum() / n), top1
+        return cutoff_summary(at['sum_at'], at['hits'], rank1, None, npos, (k,), 'hits')[f'mAP@{k}'], top1
+
+    # ---------------------------------------------------------------------------------------------------------
+    def per_query_lists(self, idx: torch.Tensor, q_pids: torch.Tensor, ks: Sequence[int] = (100,), q_img_ids: Optional[Sequence] = None,
+                        ignore_same_img: bool = True, check_duplicates: bool = True) -> Dict[str, torch.Tensor]:
+        """The per-query tensors of ``score_lists``: 'npos', 'rank1' i32 [Nq], 'hits' i32 and 'sum_at' f64 [Nq, len(ks)] of ranked
+        lists ``idx`` [Nq, k] (gallery rows, best first, -1 = no entry, trailing only; reid_list_metrics, include/reid_hip.h).  'npos'
+        counts the positives of the GALLERY, not of the list.  Raises ValueError for a cutoff above k (before any launch), for a
+        gallery row listed twice (``check_duplicates``: a sort of the lists on the device) and for an index outside -1 .. Ng - 1."""
+        idx = idx.to(self.dev)
+        if idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f'idx: expected an integer tensor [Nq, k], got {idx.dtype} {tuple(idx.shape)}')
+        if idx.shape[0] != len(q_pids):
+            raise ValueError(f'idx: {idx.shape[0]} lists for {len(q_pids)} query pids')
+        ops.check_cutoffs(ks, limit=idx.shape[1])
+        if idx.dtype != torch.int32:                      # (an int64 index beyond int32 is out of range whatever Ng is)
+            idx = idx.clamp(min=-2, max=2 ** 31 - 1)
+        idx = idx.to(torch.int32).contiguous()
+        if check_duplicates and idx.shape[1] > 1:
+            srt = torch.sort(idx, dim=1)[0]
+            twice = ((srt[:, 1:] == srt[:, :-1]) & (srt[:, 1:] >= 0)).any(1)
+            if bool(twice.any()):
+                raise ValueError(f'ranked lists: a gallery row occurs twice in the list of query {int(twice.nonzero()[0])}')
+        qp32, slot = self._query_ids(q_pids)
+        npos, rank1, hits, sum_at, status = ops.list_metrics(idx, self.g_pid, self.g_img, qp32, slot, self._exclusions(q_img_ids, ignore_same_img),
+                                                             self.csr_off, self.csr_idx, self.Ng, ks)
+        if bool(status.any()):
+            q = int(status.nonzero()[0])
+            raise ValueError(f'ranked lists: query {q} holds an index outside -1 .. {self.Ng - 1} or an entry behind a -1 '
+                             f'(reid_list_metrics status {int(status[q])})')
+        return {'npos': npos, 'rank1': rank1, 'hits': hits, 'sum_at': sum_at}
+
+    def score_lists(self, idx: torch.Tensor, q_pids: torch.Tensor, ks: Sequence[int] = (100,), q_img_ids: Optional[Sequence] = None,
+                    ignore_same_img: bool = True, norm: str = 'hits', check_duplicates: bool = True) -> Dict[str, float]:
+        """mAP@K / R@K / num_queries@K (``cutoff_summary``; no mINP: a list does not hold the last positive) of ranked lists, e.g. of
+        ``ranked_lists`` or ``GalleryIndex.topk``: see ``per_query_lists``.  A gallery row the query excludes is skipped and the
+        positions behind it move up, so a list is scored as the ranking without the same-image rows."""
+        t = self.per_query_lists(idx, q_pids, ks, q_img_ids, ignore_same_img, check_duplicates)
+        return cutoff_summary(t['sum_at'], t['hits'], t['rank1'], None, t['npos'], ks, norm)
+
+    def score_submission_csv(self, path: str, query_pids: Mapping[str, int], gallery_img_names: Sequence, ks: Sequence[int] = (100,),
+                             norm: str = 'hits') -> Dict[str, float]:
+        """``score_lists`` of the file ``export_submission_csv`` writes: one row per query, ``query_key,ranked_gallery_ids`` with the
+        gallery image names separated by blanks.  ``query_pids`` maps every query key to its pid; ``gallery_img_names`` are the names
+        the export was given (row i of the gallery <-> name i).  Unmasked, like the export's ranking.  A list shorter than the
+        largest cutoff counts as holding nothing further.  ValueError with the file's line number for an unknown query key or
+        gallery name."""
+        ops.check_cutoffs(ks)
+        rows, pids = parse_submission_csv(path, query_pids, gallery_img_names)
+        k = max(max(len(r) for r in rows), max(int(x) for x in ks))
+        if k > ops.ROWS_TOPK_MAX_K:
+            raise ValueError(f'{path}: lists of up to {k} entries, at most {ops.ROWS_TOPK_MAX_K} can be scored')
+        idx = torch.tensor([r + [-1] * (k - len(r)) for r in rows], dtype=torch.int32)
+        return self.score_lists(idx, torch.tensor(pids, dtype=torch.long), ks, None, False, norm)
 
     # ---------------------------------------------------------------------------------------------------------
     def export_submission_csv(self, q_feats, query_keys: Sequence[str], gallery_img_names: Sequence, output_path: str,
@@ -237,11 +345,87 @@ class ProtocolEvaluator:
                 w.writerow([key, ' '.join(str(gallery_img_names[i]) for i in row if i >= 0 and gallery_img_names[i] is not None)])
 
 
-def competition_metrics(all_metrics: Dict[str, Dict[str, float]]) -> Dict[str, float]:
-    """train.py:578-602: mean of the four single-modality mAPs, the four-modality mAP and their average."""
+def cutoff_summary(sum_at: torch.Tensor, hits: torch.Tensor, rank1: torch.Tensor, rank_last: Optional[torch.Tensor], npos: torch.Tensor,
+                   ks: Sequence[int], norm: str = 'hits') -> Dict[str, float]:
+    """mAP@K, R@K and num_queries@K for every K of ``ks`` (and mINP when ``rank_last`` is given) from the per-query tensors of
+    ``per_query_at`` / ``per_query_lists``: sum_at f64 and hits [Nq, len(ks)], rank1, rank_last, npos [Nq].  Plain torch on the
+    tensors' device, CPU included.  Definitions: include/reid_hip.h, DESIGN.md section 21.
+      norm 'hits': AP@K = sum_K / hits_K over the queries with hits_K > 0 -- compute_map(k) of the reference (train.py:101-126);
+      norm 'min':  AP@K = sum_K / min(K, npos) over the queries with npos > 0 -- the usual truncated AP.
+    R@K (CMC@K) is the share of the queries with npos > 0 whose first positive ranks <= K (rank1 = 0: no positive in the list);
+    num_queries@K is the number of queries in the mAP@K mean; mINP is the mean of npos / rank_last over the queries with npos > 0.
+    A mean over no query is 0."""
+    if norm not in ('hits', 'min'):
+        raise ValueError(f"norm: expected 'hits' or 'min', got {norm!r}")
+    ks = list(ops.check_cutoffs(ks))
+    if tuple(sum_at.shape) != (npos.shape[0], len(ks)) or tuple(hits.shape) != tuple(sum_at.shape):
+        raise ValueError(f'sum_at, hits: expected [{npos.shape[0]}, {len(ks)}], got {tuple(sum_at.shape)}, {tuple(hits.shape)}')
+    has_pos = npos > 0
+    n_pos = has_pos.sum().double()
+
+    def mean(x, use, n):                                  # of x over the queries of `use`, n of them; 0 for none
+        return torch.where(use, x, torch.zeros_like(x)).sum() / n.clamp(min=1.0)
+    vals = [(npos < 0).any().double()]
+    for c, K in enumerate(ks):
+        if norm == 'hits':
+            use, den = hits[:, c] > 0, hits[:, c]
+        else:
+            use, den = has_pos, npos.clamp(max=K)
+        n = use.sum().double()
+        vals += [mean(sum_at[:, c].double() / den.clamp(min=1).double(), use, n),
+                 mean(((rank1 >= 1) & (rank1 <= K)).double(), has_pos, n_pos), n]
+    if rank_last is not None:
+        vals.append(mean(npos.double() / rank_last.clamp(min=1).double(), has_pos, n_pos))
+    vals = torch.stack(vals).tolist()                     # one read-back for the whole dictionary
+    if vals[0]:
+        raise _lib.ReidHipError('a query has more than 8192 positives in the gallery: not evaluated by reid_rank_metrics_at')
+    out: Dict[str, float] = {}
+    for c, K in enumerate(ks):
+        out[f'mAP@{K}'], out[f'R@{K}'], out[f'num_queries@{K}'] = vals[1 + 3 * c], vals[2 + 3 * c], int(vals[3 + 3 * c])
+    if rank_last is not None:
+        out['mINP'] = vals[-1]
+    return out
+
+
+def parse_submission_csv(path: str, query_pids: Mapping[str, int], gallery_img_names: Sequence) -> Tuple[List[List[int]], List[int]]:
+    """(gallery rows per query, pid per query) of a file ``export_submission_csv`` wrote, in the file's order.  ValueError naming the
+    file's line for a query key ``query_pids`` lacks or a gallery name that is not one of ``gallery_img_names`` (compared as str,
+    the form the export writes; of rows that share a name the first one is meant)."""
+    import csv
+    row_of: Dict[str, int] = {}
+    for i, name in enumerate(gallery_img_names):
+        if name is not None:
+            row_of.setdefault(str(name), i)
+    rows, pids = [], []
+    with open(path, newline='') as f:
+        reader = csv.reader(f)
+        if next(reader, None) != ['query_key', 'ranked_gallery_ids']:
+            raise ValueError(f'{path}:1: expected the header query_key,ranked_gallery_ids')
+        for rec in reader:
+            line = reader.line_num
+            if not rec:
+                continue
+            if len(rec) != 2:
+                raise ValueError(f'{path}:{line}: expected 2 fields, got {len(rec)}')
+            key, names = rec[0], rec[1].split()
+            if key not in query_pids:
+                raise ValueError(f'{path}:{line}: unknown query key {key!r}')
+            unknown = [x for x in names if x not in row_of]
+            if unknown:
+                raise ValueError(f'{path}:{line}: unknown gallery image {unknown[0]!r}')
+            rows.append([row_of[x] for x in names])
+            pids.append(int(query_pids[key]))
+    if not rows:
+        raise ValueError(f'{path}: no query rows')
+    return rows, pids
+
+
+def competition_metrics(all_metrics: Dict[str, Dict[str, float]], key: Optional[str] = None) -> Dict[str, float]:
+    """train.py:578-602: mean of the four single-modality mAPs, the four-modality mAP and their average.  ``key``: the entry of every
+    metrics dictionary to average instead of the first of mAP / map / mAP_mean / map_mean -- 'mAP@100' for the competition's metric."""
     def _get_map(m):
         if isinstance(m, dict):
-            for k in ('mAP', 'map', 'mAP_mean', 'map_mean'):
+            for k in ('mAP', 'map', 'mAP_mean', 'map_mean') if key is None else (key,):
                 if k in m:
                     return float(m[k])
         if isinstance(m, (int, float)):

@@ -722,6 +722,86 @@ def rank_metrics(scores, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, 
 
 
 ROWS_TOPK_MAX_K = 1024        # REID_ROWS_TOPK_MAX_K: the longest list reid_rows_topk writes
+METRICS_MAX_CUTOFFS = 8       # REID_METRICS_MAX_CUTOFFS
+LIST_BAD_NEGATIVE, LIST_BAD_RANGE, LIST_BAD_ORDER = 1, 2, 4      # REID_LIST_BAD_*: bits of reid_list_metrics' status word
+
+
+def check_cutoffs(ks, limit=None):
+    """The cutoffs as a ctypes i32 array for the host side of a call: 1 .. METRICS_MAX_CUTOFFS integers >= 1, strictly ascending
+    (and <= ``limit`` when one is given); anything else raises ValueError before a launch."""
+    try:
+        ks = [int(k) for k in ks]
+    except TypeError:
+        raise ValueError(f'cutoffs: expected a sequence of integers, got {ks!r}') from None
+    if not 1 <= len(ks) <= METRICS_MAX_CUTOFFS:
+        raise ValueError(f'cutoffs: {len(ks)} given, 1..{METRICS_MAX_CUTOFFS} supported')
+    if ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f'cutoffs: expected integers >= 1 in strictly ascending order, got {tuple(ks)}')
+    if limit is not None and ks[-1] > limit:
+        raise ValueError(f'cutoffs: {ks[-1]} is beyond the list length {limit}')
+    return (C.c_int32 * len(ks))(*ks)
+
+
+def _req_ids(nq, Ng, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx):
+    """The id tensors ``rank_metrics_at`` and ``list_metrics`` share: i32, contiguous, of the lengths the kernels index."""
+    for name, t, n in (('g_pid', g_pid, Ng), ('g_img', g_img, Ng), ('q_pid', q_pid, nq), ('q_slot', q_slot, nq), ('csr_idx', csr_idx, Ng),
+                       ('csr_off', csr_off, 2)):
+        if t is None and name == 'g_img':
+            continue
+        L._req(t, torch.int32, name)
+        if t.dim() != 1 or t.numel() < n or not t.is_contiguous():
+            raise ValueError(f'{name}: expected contiguous [>= {n}], got {tuple(t.shape)}')
+    if q_excl is not None:
+        L._req(q_excl, torch.int32, 'q_excl')
+        if tuple(q_excl.shape) != (nq, 4) or not q_excl.is_contiguous():
+            raise ValueError(f'q_excl: expected contiguous [{nq}, 4], got {tuple(q_excl.shape)}')
+
+
+def _req_out(t, dtype, shape, name):
+    L._req(t, dtype, name)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f'{name}: expected contiguous {list(shape)}, got {tuple(t.shape)}')
+
+
+def rank_metrics_at(scores, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, Ng, max_pos, ks, ap, rank1, npos, rank_last, hits,
+                    sum_at):
+    """``rank_metrics`` with cutoffs ``ks`` (reid_rank_metrics_at, include/reid_hip.h): also writes rank_last i32 [nq], hits i32
+    [nq, len(ks)] and sum_at f64 [nq, len(ks)]; ap, rank1 and npos are those of ``rank_metrics`` bit for bit."""
+    cut = check_cutoffs(ks)
+    L._req(scores, torch.float32, 'scores')
+    if scores.dim() != 2 or Ng > scores.shape[1]:
+        raise ValueError(f'scores: expected [nq, ld >= {Ng}], got {tuple(scores.shape)}')
+    nq = scores.shape[0]
+    _req_ids(nq, Ng, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx)
+    _req_out(ap, torch.float64, (nq,), 'ap'); _req_out(rank1, torch.int32, (nq,), 'rank1'); _req_out(npos, torch.int32, (nq,), 'npos')
+    _req_out(rank_last, torch.int32, (nq,), 'rank_last')
+    _req_out(hits, torch.int32, (nq, len(cut)), 'hits'); _req_out(sum_at, torch.float64, (nq, len(cut)), 'sum_at')
+    check(lib().reid_rank_metrics_at(ptr(scores), scores.stride(0), ptr(g_pid), ptr(g_img), ptr(q_pid), ptr(q_slot), ptr(q_excl),
+                                     ptr(csr_off), ptr(csr_idx), nq, Ng, max_pos, C.addressof(cut), len(cut), ptr(ap), ptr(rank1),
+                                     ptr(npos), ptr(rank_last), ptr(hits), ptr(sum_at), stream_ptr()))
+
+
+def list_metrics(idx, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx, Ng, ks, out=None):
+    """(npos i32 [nq], rank1 i32 [nq], hits i32 [nq, len(ks)], sum_at f64 [nq, len(ks)], status i32 [nq]) of ranked lists ``idx``
+    i32 [nq, k] (reid_list_metrics, include/reid_hip.h): -1 = no entry (trailing only); an excluded gallery row is skipped and the
+    positions behind it move up.  Every cutoff must be <= k.  ``out``: the five tensors to write into."""
+    L._req(idx, torch.int32, 'idx')
+    if idx.dim() != 2 or not idx.is_contiguous() or not 1 <= idx.shape[1] <= ROWS_TOPK_MAX_K or idx.shape[0] < 1:
+        raise ValueError(f'idx: expected contiguous [nq >= 1, 1 <= k <= {ROWS_TOPK_MAX_K}], got {tuple(idx.shape)}')
+    nq, k = idx.shape
+    cut = check_cutoffs(ks, limit=k)
+    _req_ids(nq, Ng, g_pid, g_img, q_pid, q_slot, q_excl, csr_off, csr_idx)
+    if out is None:
+        i32 = dict(dtype=torch.int32, device=idx.device)
+        out = (torch.empty(nq, **i32), torch.empty(nq, **i32), torch.empty(nq, len(cut), **i32),
+               torch.empty(nq, len(cut), dtype=torch.float64, device=idx.device), torch.empty(nq, **i32))
+    npos, rank1, hits, sum_at, status = out
+    _req_out(npos, torch.int32, (nq,), 'npos'); _req_out(rank1, torch.int32, (nq,), 'rank1'); _req_out(status, torch.int32, (nq,), 'status')
+    _req_out(hits, torch.int32, (nq, len(cut)), 'hits'); _req_out(sum_at, torch.float64, (nq, len(cut)), 'sum_at')
+    check(lib().reid_list_metrics(ptr(idx), nq, k, ptr(g_pid), ptr(g_img), ptr(q_pid), ptr(q_slot), ptr(q_excl), ptr(csr_off),
+                                  ptr(csr_idx), Ng, C.addressof(cut), len(cut), ptr(npos), ptr(rank1), ptr(hits), ptr(sum_at),
+                                  ptr(status), stream_ptr()))
+    return npos, rank1, hits, sum_at, status
 
 
 def rows_topk(scores, n, k, g_img=None, q_excl=None, out=None):
