@@ -540,12 +540,17 @@ int reid_center_bwd(int32_t S, int32_t N, int32_t D, const float* ws, const floa
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;
  *   survivors are re-scored in fp32 from Qf/Gf so the order equals the fp32 oracle's.
  *   exclude_q/exclude_g (int32 ids, or NULL): entries with equal non-negative id get -1e9
- *   (same-image mask, eval_mm_protocol.py:421-422).
- *   out_idx int32 [Nq, k], out_score f32 [Nq, k].  ws: reid_topk_ws_bytes().
- *   Nq <= 128 with k <= 16, D = 256 or 512 and a gallery of at least 256 k rows: the candidate filter is ONE pass of a query-resident
+ *   (same-image mask, eval_mm_protocol.py:421-422) and STAY in the ranking, as in the reference's masked_fill + argsort: a query
+ *   with fewer than k other rows gets them behind those, in index order, with score -1e9; an id of -1 on either side excludes nothing.
+ *   k <= Ng, so a complete list holds k gallery indices >= 0 (never -1).
+ *   out_idx int32 [Nq, k], out_score f32 [Nq, k], contiguous (row q at element q k).  ws: reid_topk_ws_bytes(); scratch, may hold anything.
+ *   Nq <= 128 with k <= 16, D = 256 or 512, at least 4 k 64-row chunks of gallery (Ng > 256 k - 64; and 4 k <= compute units) and
+ *   Nq min(Ng, 8192) >= 6144 (the scan's counters live in the workspace's sample area): the candidate filter is ONE pass of a query-resident
  *   scan kernel (the 16-bit gallery streamed once, the queries as MFMA operands in registers, the bar of each query taken from the
  *   scan's own running maxima) instead of the sample / threshold / tiled filter launches -- same candidate lists contract, same
- *   results, same workspace.  A query whose candidate list overflows is marked out_idx[q, 0] = -2 for reid_cosine_topk_exact(_slots).
+ *   results, same workspace.  A query whose candidate list overflows (more than 6 k ceil(Ng / 8192) + 64 candidates, clamped to
+ *   256 .. 8192; for k <= 32 also more than 512 rows within the filter margin of the k-th score, e.g. a tie group) is marked
+ *   out_idx[q, 0] = -2 (the rest of its row is not written) for reid_cosine_topk_exact(_slots).
  * ------------------------------------------------------------------------------------------ */
 int64_t reid_topk_ws_bytes(int32_t Nq, int32_t Ng, int32_t k);
 /* 1 when reid_cosine_topk takes the query-resident scan for this shape (then also the faster form for 2-4 queries). */
@@ -568,9 +573,9 @@ int reid_cosine_topk_exact_slots(const float* Qf, const float* Gf, int32_t Nq, i
 /* The reference's one-query-at-a-time form (tools/eval_mm_protocol.py:401-455: sim = q @ G.T; argsort) for a handful of
  * queries: ONE pass over the fp32 gallery (Ng*D*4 bytes, HBM-bound) instead of the batched pipeline's launch chain.  Same
  * fp32 scores and the same (score desc, index asc) lists as reid_cosine_topk.  Allowed when reid_topk_stream_ok() returns 1
- * (Nq <= 4, k <= 32, D a multiple of 256 up to 1024).  ws: reid_topk_stream_ws_bytes(k) bytes owned by this entry point: ZERO before the
- * first call and not written by anyone else between calls (its last 256 bytes hold the arrival counter of the one-query form, in which
- * the workgroup whose partial list arrives last merges all lists -- one launch per call; every call leaves the counter at zero). */
+ * (Nq <= 4, k <= 32, D a multiple of 256 up to 1024).  ws: reid_topk_stream_ws_bytes(k) bytes of scratch for the call: the scan kernel
+ * writes every per-workgroup list entry the merge kernel then reads, so the buffer may hold anything on entry (its last 256 bytes are
+ * not used: they held the arrival counter of an earlier one-launch form and stay part of the size).  No query is ever flagged. */
 int32_t reid_topk_stream_ok(int32_t Nq, int32_t Ng, int32_t D, int32_t k);
 int64_t reid_topk_stream_ws_bytes(int32_t k);
 int reid_cosine_topk_stream(const float* Qf, const float* Gf, int32_t Nq, int32_t Ng, int32_t D, int32_t k,

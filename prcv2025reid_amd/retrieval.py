@@ -43,7 +43,8 @@ class GalleryIndex:
         """(indices int32 [Nq, k], scores f32 [Nq, k]); entries whose img id equals the query's are excluded
         (same-image mask of eval_mm_protocol.py:421-422) when both id vectors are given.  ``stream``: force the one-pass
         form for a few queries (True) or the batched MFMA pipeline (False); default: whichever fits the shape.
-        Index -1 = no entry (fewer than k gallery rows); no other negative value is ever returned."""
+        Excluded entries stay in the ranking with score -1e9 (the reference's masked_fill + argsort): a query with fewer than k other
+        rows gets them last, in index order.  k <= gallery rows; no negative index is ever returned."""
         Qf = queries.contiguous().float()
         if not normalized:
             Qf = l2_normalize(Qf)
