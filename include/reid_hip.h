@@ -880,6 +880,43 @@ int reid_margin_ce_bwd(const float* logits, int32_t ld, const int64_t* labels, c
                        float* dlogits, int32_t lddl, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * DBSCAN over fp32 similarity rows (csrc/cluster.hip); the definition is DESIGN.md §22 (the reference has no clustering).
+ * Given n rows, a similarity s(i, j) (larger = closer), a threshold thr and min_samples >= 1:
+ *   N(i) = {i} + {j < n : s(i, j) >= thr}, compared in fp32 on the bits of row i alone: NaN is never a neighbour, +inf is, and the
+ *   row's own column always counts, once.  core(i) <=> |N(i)| >= min_samples.  Cores i, j are joined iff j in N(i) or i in N(j);
+ *   clusters are the connected components, named by their smallest core row (the root).  A non-core j takes the smallest root
+ *   among the cores i with j in N(i); a row no core reaches is noise.
+ * The rows arrive in chunks and are not kept; each chunk becomes its slice of the neighbour CSR:
+ *   scores  f32 [nr, ld], ld >= n, ld % 4 == 0, base 16-byte aligned (what reid_rows_topk accepts and the re-ranking kernels write);
+ *           columns >= n are never candidates and may hold any bits.  Row r of the chunk is row row0 + r of the matrix:
+ *           0 <= row0, row0 + nr <= n.  thr must not be NaN.
+ *   reid_dbscan_count   count i32 [nr] = |N(row0 + r)|, core u8 [nr] = (count >= min_samples).
+ *   reid_dbscan_fill    rowptr i64 [nr + 1]: offsets into cols i32 [cap] (the caller's exclusive prefix sum of count); writes the
+ *           columns of N(row0 + r) strictly ascending from rowptr[r]; never writes at or past rowptr[r + 1] or cap.
+ * Components and labels on the CSR of all N rows (rowptr i64 [N + 1], cols i32 [nnz], core u8 [N]); a column outside 0 .. N - 1 is
+ * skipped, offsets are clipped to 0 .. nnz:
+ *   parent i32 [N], set to parent[i] = i by the caller.  Invariant: parent[x] <= x, and a parent only decreases.
+ *   reid_dbscan_hook      for each directed edge (i, j) between two cores with parent[i] != parent[j]:
+ *           atomicMin(parent[max(pi, pj)], min(pi, pj)); *changed (i32) grows by one per wave that saw such an edge, and stays
+ *           as it is when there was none.
+ *   reid_dbscan_compress  parent[x] = the fixed point of x -> parent[x] (at most x steps).
+ *           The caller alternates the two until a hook pass leaves *changed untouched: parent[i] is then the root of core i.
+ *   reid_dbscan_border    label i32 [N]: atomicMin(label[j], parent[i]) for each core i and each non-core j in N(i); the caller
+ *           fills label beforehand (INT32_MAX = noise).
+ * Integer atomicMin / atomicAdd only: every output is the same bits in every run.  No kernel waits for another workgroup.  Nothing is
+ * allocated, nothing is synchronised or read back.  Anything outside the limits above is refused before a launch.
+ * ------------------------------------------------------------------------------------------ */
+int reid_dbscan_count(const float* scores, int64_t ld, int32_t nr, int32_t n, int64_t row0, float thr, int32_t min_samples,
+                      int32_t* count, uint8_t* core, void* stream);
+int reid_dbscan_fill(const float* scores, int64_t ld, int32_t nr, int32_t n, int64_t row0, float thr, const int64_t* rowptr,
+                     int32_t* cols, int64_t cap, void* stream);
+int reid_dbscan_hook(const int64_t* rowptr, const int32_t* cols, int64_t nnz, const uint8_t* core, int32_t* parent, int32_t N,
+                     int32_t* changed, void* stream);
+int reid_dbscan_compress(int32_t* parent, int32_t N, void* stream);
+int reid_dbscan_border(const int64_t* rowptr, const int32_t* cols, int64_t nnz, const uint8_t* core, const int32_t* parent,
+                       int32_t* label, int32_t N, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * k-reciprocal re-ranking (Zhong et al., CVPR 2017) of pooled unit rows X = [Q; G], N = Nq + Ng <= 65 536, dense; the
  * definition is DESIGN.md "k-reciprocal re-ranking" (the reference has none).  kh = round-half-to-even(k1 / 2).
  *   nbr   i32 [N, ldn >= k1 + 1]: row i of the pooled ranking (score descending, index ascending; i itself is an entry)

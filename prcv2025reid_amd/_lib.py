@@ -141,6 +141,11 @@ SIGNATURES = {
     'reid_cos_logits_bwd_fix': (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _F, _F, _P]),
     'reid_margin_ce_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P]),
     'reid_margin_ce_bwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _F, _F, _P, _P, _P, _I, _P]),
+    'reid_dbscan_count': (_I, [_P, _I64, _I, _I, _I64, _F, _I, _P, _P, _P]),
+    'reid_dbscan_fill': (_I, [_P, _I64, _I, _I, _I64, _F, _P, _P, _I64, _P]),
+    'reid_dbscan_hook': (_I, [_P, _P, _I64, _P, _P, _I, _P, _P]),
+    'reid_dbscan_compress': (_I, [_P, _I, _P]),
+    'reid_dbscan_border': (_I, [_P, _P, _I64, _P, _P, _P, _I, _P]),
     'reid_rerank_weights_sparse': (_I, [_P, _I, _P, _I, _P, _P, _P, _I64, _I, _I, _I, _P]),
     'reid_rerank_expand_count': (_I, [_P, _P, _P, _I64, _P, _I, _P, _I, _I, _I, _P]),
     'reid_rerank_expand_sparse': (_I, [_P, _P, _P, _I64, _P, _I, _P, _P, _P, _I, _I, _I, _P]),

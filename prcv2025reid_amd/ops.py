@@ -904,6 +904,73 @@ def rerank_jaccard_sparse(rowptr, cols, vals, colptr, rows, cvals, cos, out, Ng,
                                            lambda_value, stream_ptr()))
 
 
+def _req_sim_rows(scores, n, row0):
+    """The similarity-row chunk ``dbscan_count`` and ``dbscan_fill`` share: f32 [nr >= 1, >= n], rows row0 .. row0 + nr - 1 of n."""
+    L._req(scores, torch.float32, 'scores')
+    if scores.dim() != 2 or scores.shape[0] < 1:
+        raise ValueError(f'scores: expected [nr >= 1, ld], got {tuple(scores.shape)}')
+    nr = scores.shape[0]
+    if n > scores.shape[1]:
+        raise ValueError(f'scores: n={n} columns asked of a [{nr}, {scores.shape[1]}] tensor')
+    if row0 < 0 or row0 + nr > n:
+        raise ValueError(f'scores: rows {row0}..{row0 + nr - 1} are not rows of an [{n}, {n}] matrix')
+    return nr
+
+
+def dbscan_count(scores, n, row0, thr, min_samples, count, core):
+    """count[r] = |N(row0 + r)| = the columns j < n of row r with scores[r, j] >= thr, the row's own column row0 + r always among them,
+    and core[r] = count[r] >= min_samples (reid_dbscan_count, include/reid_hip.h).  ``count`` i32 [nr], ``core`` u8 [nr]."""
+    nr = _req_sim_rows(scores, n, row0)
+    _req_out(count, torch.int32, (nr,), 'count'); _req_out(core, torch.uint8, (nr,), 'core')
+    check(lib().reid_dbscan_count(ptr(scores), scores.stride(0), nr, n, row0, thr, min_samples, ptr(count), ptr(core), stream_ptr()))
+
+
+def dbscan_fill(scores, n, row0, thr, rowptr, cols):
+    """cols[rowptr[r] : rowptr[r + 1]] = the columns of N(row0 + r), ascending (reid_dbscan_fill); ``rowptr`` i64 [nr + 1] is the
+    exclusive prefix sum of ``dbscan_count``'s counts for the same rows and threshold, ``cols`` i32 [>= rowptr[nr]]."""
+    nr = _req_sim_rows(scores, n, row0)
+    _req_out(rowptr, torch.int64, (nr + 1,), 'rowptr')
+    L._req(cols, torch.int32, 'cols')
+    if cols.dim() != 1 or not cols.is_contiguous():
+        raise ValueError(f'cols: expected a contiguous vector, got {tuple(cols.shape)}')
+    check(lib().reid_dbscan_fill(ptr(scores), scores.stride(0), nr, n, row0, thr, ptr(rowptr), ptr(cols), cols.shape[0], stream_ptr()))
+
+
+def _req_csr(rowptr, cols, core):
+    """The neighbour CSR of N rows and their core flags, as the component passes read them; returns N."""
+    L._req(rowptr, torch.int64, 'rowptr'); L._req(cols, torch.int32, 'cols'); L._req(core, torch.uint8, 'core')
+    N = core.shape[0]
+    if core.dim() != 1 or N < 1 or tuple(rowptr.shape) != (N + 1,) or cols.dim() != 1 or not (rowptr.is_contiguous() and cols.is_contiguous()
+                                                                                               and core.is_contiguous()):
+        raise ValueError(f'expected contiguous core [N >= 1], rowptr [N + 1], cols [nnz], got {tuple(core.shape)}, {tuple(rowptr.shape)}, '
+                         f'{tuple(cols.shape)}')
+    return N
+
+
+def dbscan_hook(rowptr, cols, core, parent, changed):
+    """One hook pass over the directed core-core edges of the CSR: atomicMin(parent[max(pi, pj)], min(pi, pj)); ``changed`` (an i32
+    scalar on the device) grows when, and only when, an edge saw two different parents (reid_dbscan_hook)."""
+    N = _req_csr(rowptr, cols, core)
+    _req_out(parent, torch.int32, (N,), 'parent')
+    L._req(changed, torch.int32, 'changed')
+    if changed.numel() != 1:
+        raise ValueError(f'changed: expected one i32, got {tuple(changed.shape)}')
+    check(lib().reid_dbscan_hook(ptr(rowptr), ptr(cols), cols.shape[0], ptr(core), ptr(parent), N, ptr(changed), stream_ptr()))
+
+
+def dbscan_compress(parent):
+    """parent[x] = the root of x's pointer chain (reid_dbscan_compress)."""
+    _req_out(parent, torch.int32, (parent.shape[0],), 'parent')
+    check(lib().reid_dbscan_compress(ptr(parent), parent.shape[0], stream_ptr()))
+
+
+def dbscan_border(rowptr, cols, core, parent, label):
+    """label[j] = min(label[j], parent[i]) over the cores i with the non-core j in N(i) (reid_dbscan_border); ``label`` i32 [N]."""
+    N = _req_csr(rowptr, cols, core)
+    _req_out(parent, torch.int32, (N,), 'parent'); _req_out(label, torch.int32, (N,), 'label')
+    check(lib().reid_dbscan_border(ptr(rowptr), ptr(cols), cols.shape[0], ptr(core), ptr(parent), ptr(label), N, stream_ptr()))
+
+
 def gather_rows(src, index, dst):
     """dst[r] = src[index[r]] (f32 rows, cols % 4 == 0; int32 index)."""
     check(lib().reid_gather_rows_f32(ptr(src), src.stride(0), ptr(index), ptr(dst), dst.stride(0), index.shape[0], dst.shape[1],

@@ -16,6 +16,10 @@ non-zeros only (layout: include/reid_hip.h), no limit on N other than int32 row 
                                 to CSC with torch ops (bincount, cumsum, one stable sort): a cold step
   4. s* rows per query chunk    reid_rerank_jaccard_sparse: one workgroup per s* row, m accumulated in the row itself
 
+The pooled-only form (``Reranker.for_pool(X, params)``, ``SparseReranker.for_pool``): the pool is X alone (Nq = 0, Ng = N), every row is
+both query and gallery column, ``rows(a, b)`` = s* of pool rows a..b-1 against all N columns.  Same steps, same kernels; it is what
+``cluster.jaccard_dbscan`` draws its Jaccard rows from.
+
 Ranked lists of either form (``topk``, ``rerank_topk``): reid_rows_topk on the s* rows, an exact top-k select in the order of a stable
 descending sort, without the sort.
 """
@@ -49,14 +53,24 @@ def list_width(k1: int) -> int:
 
 def check_shapes(Nq: int, Ng: int, params: RerankParams):
     """Refuses, before anything touches the device, what the kernels would refuse or what would not fit."""
-    N = Nq + Ng
     if Nq < 1 or Ng < 1:
         raise _lib.ReidHipError(f're-ranking needs at least one query and one gallery row (Nq={Nq}, Ng={Ng})')
+    _check_pooled(Nq + Ng, f'{Nq} + {Ng} = {Nq + Ng}', params)
+
+
+def check_pool(N: int, params: RerankParams):
+    """``check_shapes`` for the pooled-only form (``for_pool``): one set of N rows, every row both query and gallery column."""
+    if N < 1:
+        raise _lib.ReidHipError(f're-ranking needs at least one pooled row (N={N})')
+    _check_pooled(N, f'{N}', params)
+
+
+def _check_pooled(N: int, shown: str, params: RerankParams):
     if N > MAX_ROWS and not params.sparse:
-        raise _lib.ReidHipError(f're-ranking pools queries and gallery into dense [N, N] fp32 matrices: N = {Nq} + {Ng} = {N} exceeds '
+        raise _lib.ReidHipError(f're-ranking pools queries and gallery into dense [N, N] fp32 matrices: N = {shown} exceeds '
                                 f'{MAX_ROWS} rows (RerankParams(sparse=True) has no row limit)')
     if N > 2 ** 31 - 1:
-        raise _lib.ReidHipError(f're-ranking: N = {Nq} + {Ng} = {N} pooled rows do not fit int32 row indices')
+        raise _lib.ReidHipError(f're-ranking: N = {shown} pooled rows do not fit int32 row indices')
     if not 1 <= params.k1 <= MAX_K1:
         raise _lib.ReidHipError(f're-ranking: k1={params.k1} outside 1..{MAX_K1}')
     if params.k1 + 1 > N:
@@ -71,7 +85,26 @@ def check_shapes(Nq: int, Ng: int, params: RerankParams):
 
 
 class _RankedRows:
-    """What both forms share once ``rows(a, b)`` exists."""
+    """What both forms share: the two constructors in front of ``_build`` (steps 1-3), and the lists once ``rows(a, b)`` exists."""
+
+    def __init__(self, Qf: torch.Tensor, Gf: torch.Tensor, params: RerankParams, Gcat: Optional[torch.Tensor] = None):
+        """Qf, Gf: L2-normalised fp32 device rows; Gcat: the gallery's split operand (``split_gallery(Gf)``) if the caller has it."""
+        check_shapes(Qf.shape[0], Gf.shape[0], params)
+        if not (Qf.is_cuda and Gf.is_cuda):
+            raise _lib.ReidHipError('re-ranking needs device tensors (there is no CPU path)')
+        self._build(torch.cat([Qf, Gf], 0).contiguous(), Qf.shape[0], params, split_gallery(Gf) if Gcat is None else Gcat)
+
+    @classmethod
+    def for_pool(cls, X: torch.Tensor, params: RerankParams):
+        """The pooled-only form: the pool is X alone (L2-normalised fp32 device rows; Nq = 0, Ng = N), every row both query and gallery
+        column; ``rows(a, b)`` returns the s* rows of pool rows a..b-1 against all N columns."""
+        check_pool(X.shape[0], params)
+        if not X.is_cuda:
+            raise _lib.ReidHipError('re-ranking needs device tensors (there is no CPU path)')
+        self = cls.__new__(cls)
+        X = X.contiguous()
+        self._build(X, 0, params, split_gallery(X))
+        return self
 
     def topk(self, a: int, b: int, k: int, g_img: Optional[torch.Tensor] = None, q_excl: Optional[torch.Tensor] = None):
         """(idx i32 [b - a, k], s* f32 [b - a, k]): the first k gallery rows of queries a..b-1 by s* descending, gallery index ascending
@@ -82,16 +115,11 @@ class _RankedRows:
 class Reranker(_RankedRows):
     """Steps 1-3 for one (query set, gallery) pair, built once; ``rows(a, b)`` then returns the s* rows of queries a..b-1."""
 
-    def __init__(self, Qf: torch.Tensor, Gf: torch.Tensor, params: RerankParams, Gcat: Optional[torch.Tensor] = None):
-        """Qf, Gf: L2-normalised fp32 device rows; Gcat: the gallery's split operand (``split_gallery(Gf)``) if the caller has it."""
-        check_shapes(Qf.shape[0], Gf.shape[0], params)
-        if not (Qf.is_cuda and Gf.is_cuda):
-            raise _lib.ReidHipError('re-ranking needs device tensors (there is no CPU path)')
+    def _build(self, X: torch.Tensor, Nq: int, params: RerankParams, Gcat: torch.Tensor):
         self.params = params
-        self.Nq, self.Ng = Qf.shape[0], Gf.shape[0]
-        self.N = self.Nq + self.Ng
-        self.X = torch.cat([Qf, Gf], 0).contiguous()
-        self.Gcat = split_gallery(Gf) if Gcat is None else Gcat
+        self.Nq, self.Ng = Nq, X.shape[0] - Nq
+        self.N = X.shape[0]
+        self.X, self.Gcat = X, Gcat
         self.nbr, _ = GalleryIndex(self.X, normalized=True).topk(self.X, k=params.k1 + 1, normalized=True)
         ld = (self.N + 3) // 4 * 4
         V = torch.empty(self.N, ld, device=self.X.device)
@@ -111,16 +139,12 @@ class SparseReranker(_RankedRows):
     """``Reranker`` on the sparse form: the same ``rows(a, b)``, V2 as CSR (``rowptr``, ``cols``, ``vals``) and its gallery rows as
     CSC (``colptr``, ``grows``, ``cvals``).  Building it synchronises once, to size the arrays of non-zeros."""
 
-    def __init__(self, Qf: torch.Tensor, Gf: torch.Tensor, params: RerankParams, Gcat: Optional[torch.Tensor] = None):
-        check_shapes(Qf.shape[0], Gf.shape[0], params)
-        if not (Qf.is_cuda and Gf.is_cuda):
-            raise _lib.ReidHipError('re-ranking needs device tensors (there is no CPU path)')
+    def _build(self, X: torch.Tensor, Nq: int, params: RerankParams, Gcat: torch.Tensor):
         self.params = params
-        self.Nq, self.Ng = Qf.shape[0], Gf.shape[0]
-        self.N = N = self.Nq + self.Ng
-        dev = Qf.device
-        self.X = torch.cat([Qf, Gf], 0).contiguous()
-        self.Gcat = split_gallery(Gf) if Gcat is None else Gcat
+        self.Nq, self.Ng = Nq, X.shape[0] - Nq
+        self.N = N = X.shape[0]
+        dev = X.device
+        self.X, self.Gcat = X, Gcat
         index = GalleryIndex(self.X, normalized=True)
         index.exact_scratch_bytes = 2 << 30       # the pooled call is drawn in query chunks: no [N, N] scratch is kept
         self.nbr, _ = index.topk(self.X, k=params.k1 + 1, normalized=True)
