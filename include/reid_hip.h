@@ -120,6 +120,26 @@ typedef struct {
 } reid_gemm_args;
 int reid_mer_gemm(const reid_gemm_args* host_args, void* stream);
 
+/* The launch reid_mer_gemm chooses, as data: the one host-side statement of the dispatch (csrc/gemm.hip make_plan), which the
+ * launcher executes and the tests query. */
+typedef enum { REID_GEMM_TILED = 0, REID_GEMM_PP = 1, REID_GEMM_PPS = 2 } reid_gemm_kernel;
+typedef enum {
+    REID_EPI_GENERIC = 0,   /* every option evaluated at run time */
+    REID_EPI_PLAIN16 = 1, REID_EPI_RES32 = 2, REID_EPI_GELU2 = 3, REID_EPI_DGELU = 4, REID_EPI_GELU2D = 5, REID_EPI_MULAUX = 6,
+    REID_EPI_PLAIN16H = 7   /* the plain 16-bit store in IEEE half (bf16 flavor only) */
+} reid_gemm_epilogue;
+typedef struct reid_gemm_plan {
+    int32_t kernel;            /* REID_GEMM_TILED: one tile per workgroup (mer_gemm_kernel); REID_GEMM_PP: ping-pong tile; REID_GEMM_PPS: persistent ping-pong */
+    int32_t bm, bn;            /* tile */
+    int32_t epilogue;          /* REID_EPI_* */
+    int32_t tiles_m, tiles_n;  /* row tiles (summed over row groups) and column tiles */
+    int32_t grid;              /* workgroups launched */
+} reid_gemm_plan;
+/* What reid_mer_gemm would launch for *a on a device of `cus` compute units with GEMM_TILE = tile_knob (<= 0: not set).
+ * Checks the arguments exactly as reid_mer_gemm does (same return codes and messages), launches nothing, touches no device.
+ * cus <= 0: the current device's count. */
+int reid_mer_gemm_plan(const reid_gemm_args* a, int32_t cus, int32_t tile_knob, reid_gemm_plan* out);
+
 /* ------------------------------------------------------------------------------------------
  * Reduce-over-rows GEMM:  C[P, Q] = beta*C + alpha * X[M, P]^T . Y[M, Q]   (fp32 out)
  * Weight-gradient products of the backward pass: dB = dY^T T and dA = U^T X for LoRA

@@ -53,10 +53,19 @@ class GemmArgs(C.Structure):
                 ('b_group_stride', C.c_int64)]
 
 
+GEMM_KERNELS = ('tiled', 'pp', 'pps')                                                               # REID_GEMM_*
+GEMM_EPILOGUES = ('generic', 'plain16', 'res32', 'gelu2', 'dgelu', 'gelu2d', 'mulaux', 'plain16h')  # REID_EPI_*
+
+
+class GemmPlan(C.Structure):
+    _fields_ = [('kernel', C.c_int32), ('bm', C.c_int32), ('bn', C.c_int32), ('epilogue', C.c_int32),
+                ('tiles_m', C.c_int32), ('tiles_n', C.c_int32), ('grid', C.c_int32)]
+
+
 # Every entry point of include/reid_hip.h in header order, name -> (restype, argtypes): ctypes then refuses a call with too few
 # arguments and converts each plain Python value (int or None for a pointer, int for an integer, float for a float) itself.
 _P, _I, _I64, _F, _S = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_char_p   # T*; int, int32_t, enum; int64_t; float; const char*
-_GEMM = C.POINTER(GemmArgs)
+_GEMM, _PLAN = C.POINTER(GemmArgs), C.POINTER(GemmPlan)
 SIGNATURES = {
     'reid_last_error': (_S, []),
     'reid_version': (_I, []),
@@ -64,6 +73,7 @@ SIGNATURES = {
     'reid_check_device': (_I, [_I]),
     'reid_set_knob': (_I, [_S, _I]),
     'reid_mer_gemm': (_I, [_GEMM, _P]),
+    'reid_mer_gemm_plan': (_I, [_GEMM, _I, _I, _PLAN]),
     'reid_gemm_tn': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _P]),
     'reid_layernorm_fwd': (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _F, _P]),
     'reid_add_layernorm_fwd': (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _F, _P]),

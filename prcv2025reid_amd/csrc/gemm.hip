@@ -54,12 +54,18 @@ struct GemmParams {
 // two waves per SIMD: ~12 us per 256 x 256 tile, tools/exp_epilogue_scale.py at 13e2fd7).
 // PLAIN16H (r04, bf16 flavor only): the plain 16-bit store in IEEE half (REID_F16 output) -- the residual-branch outputs (out-projection,
 // fc2) are consumed by the add + LayerNorm kernel, never by an MFMA, so they can carry half's 11 significant bits instead of bf16's 8.
-enum { EPI_GENERIC = 0, EPI_PLAIN16 = 1, EPI_RES32 = 2, EPI_GELU2 = 3, EPI_DGELU = 4, EPI_GELU2D = 5, EPI_MULAUX = 6, EPI_PLAIN16H = 7 };
+enum { EPI_GENERIC = REID_EPI_GENERIC, EPI_PLAIN16 = REID_EPI_PLAIN16, EPI_RES32 = REID_EPI_RES32, EPI_GELU2 = REID_EPI_GELU2, EPI_DGELU = REID_EPI_DGELU,
+       EPI_GELU2D = REID_EPI_GELU2D, EPI_MULAUX = REID_EPI_MULAUX, EPI_PLAIN16H = REID_EPI_PLAIN16H };
 
 using namespace gemmcore;
 
-// first row, row limit and weight matrix of global row tile `tm` (tile height BM)
-__device__ __forceinline__ void tile_rows(const GemmParams& p, int tm, int BM, int& m0, int& m_end, const bf16_t*& B) {
+// Geometry of tile `v` of `n` in the XCD-aware, L2-aware tile order (gemm_core.h): first row and row limit of its row tile (which never
+// leaves its row group), first column, the row group's weight matrix and the low-rank operand of the column group.
+template <int BM, int BN>
+__device__ __forceinline__ void tile_of(const GemmParams& p, int v, int n, int& m0, int& m_end, int& n0, const bf16_t*& B, const bf16_t*& A2) {
+    const int lin = xcd_linear_block(v, n);
+    int tm, tn;
+    tile_coords(lin, p.tiles_m, p.tiles_n, tm, tn, p.group_m);
     B = p.B;
     if (p.n_groups > 0) {
         int g = 0;
@@ -73,6 +79,9 @@ __device__ __forceinline__ void tile_rows(const GemmParams& p, int tm, int BM, i
         m0 = tm * BM;
         m_end = p.M;
     }
+    n0 = tn * BN;
+    const int g = (p.k2_group_n > 0) ? (n0 / p.k2_group_n) : 0;
+    A2 = p.A2 ? p.A2 + (size_t)g * p.K2 : nullptr;
 }
 
 // Epilogue of one wave's [TM*16 x TN*16] sub-tile whose first element is C[m_base][n_base], straight from the
@@ -142,9 +151,10 @@ __device__ __forceinline__ void init_acc_m(const GemmParams& p, f32x4 (&acc)[TN]
         for (int i = 0; i < TM; ++i) acc[j][i] = b;
     }
 }
-template <int TM, int TN>
-__device__ __forceinline__ void init_acc(const GemmParams& p, f32x4 (&acc)[TN][TM], int n_base, int lane) {
-    if (p.c_dtype != REID_F32 && p.perm_b) init_acc_m<TM, TN, 1>(p, acc, n_base, lane);
+// in the column layout of the epilogue EPI: the 16-bit lean kinds use the perm32 staging, RES32 the natural one, GENERIC what the launch has
+template <int TM, int TN, int EPI>
+__device__ __forceinline__ void init_acc_e(const GemmParams& p, f32x4 (&acc)[TN][TM], int n_base, int lane) {
+    if (EPI == EPI_GENERIC ? p.c_dtype != REID_F32 && p.perm_b : EPI != EPI_RES32) init_acc_m<TM, TN, 1>(p, acc, n_base, lane);
     else init_acc_m<TM, TN, 0>(p, acc, n_base, lane);
 }
 
@@ -356,17 +366,6 @@ __device__ __forceinline__ void store_tile_fast(const GemmParams& p, f32x4 (&acc
     }
 }
 
-// host side: number of row tiles of height bm (per row group when groups are on) and, with `fill`, the tile index ranges of the groups
-static int row_tiles(GemmParams& p, int bm, bool fill) {
-    if (p.n_groups <= 0) return (p.M + bm - 1) / bm;
-    int t = 0;
-    for (int g = 0; g < p.n_groups; ++g) {
-        if (fill) p.grp_tile0[g] = t;
-        t += (p.grp_row_end[g] - p.grp_row0[g] + bm - 1) / bm;
-    }
-    return t;
-}
-
 // host side: which lean epilogue (if any) covers this launch
 static int pick_epilogue(const GemmParams& p, int BN) {
     if (p.alpha != 1.f || p.mask_r > 0 || p.c_group > 0 || p.r_period > 0 || p.N % BN != 0) return EPI_GENERIC;
@@ -409,21 +408,12 @@ __global__ __launch_bounds__(WM* WN * 64, 2) void mer_gemm_kernel(const GemmPara
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / WN, wn = wave % WN;
 
-    // XCD-aware, L2-aware tile order (gemm_core.h)
-    const int lin = xcd_linear_block(blockIdx.x, gridDim.x);
-    int tm, tn;
-    tile_coords(lin, p.tiles_m, p.tiles_n, tm, tn, p.group_m);
-    int m0, m_end;
-    const bf16_t* Bw;
-    tile_rows(p, tm, BM, m0, m_end, Bw);
-    const int n0 = tn * BN;
-    const int g = (p.k2_group_n > 0) ? (n0 / p.k2_group_n) : 0;
-    const bf16_t* A2 = p.A2 ? p.A2 + (size_t)g * p.K2 : nullptr;
+    int m0, m_end, n0;
+    const bf16_t *Bw, *A2;
+    tile_of<BM, BN>(p, blockIdx.x, gridDim.x, m0, m_end, n0, Bw, A2);
 
     f32x4 acc[C::TN][C::TM];
-    if constexpr (EPI == EPI_GENERIC) init_acc<C::TM, C::TN>(p, acc, n0 + wn * (BN / WN), lane);
-    else if constexpr (EPI == EPI_RES32) init_acc_m<C::TM, C::TN, 0>(p, acc, n0 + wn * (BN / WN), lane);
-    else init_acc_m<C::TM, C::TN, 1>(p, acc, n0 + wn * (BN / WN), lane);
+    init_acc_e<C::TM, C::TN, EPI>(p, acc, n0 + wn * (BN / WN), lane);
     mainloop<BM, BN, WM, WN>(p.A, p.lda, Bw, p.ldb, A2, p.lda2, p.B2, p.ldb2, m_end, p.N, p.K, p.K2, m0, n0, smem, acc,
                              p.perm_b != 0);
 
@@ -452,19 +442,11 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pp_kernel(const GemmParams p)
 #define GEMM_TRACE(slot) do { } while (0)
 #endif
     GEMM_TRACE(0);
-    const int lin = xcd_linear_block(blockIdx.x, gridDim.x);
-    int tm, tn;
-    tile_coords(lin, p.tiles_m, p.tiles_n, tm, tn, p.group_m);
-    int m0, m_end;
-    const bf16_t* Bw;
-    tile_rows(p, tm, BM, m0, m_end, Bw);
-    const int n0 = tn * 256;
-    const int g = (p.k2_group_n > 0) ? (n0 / p.k2_group_n) : 0;
-    const bf16_t* A2 = p.A2 ? p.A2 + (size_t)g * p.K2 : nullptr;
+    int m0, m_end, n0;
+    const bf16_t *Bw, *A2;
+    tile_of<BM, 256>(p, blockIdx.x, gridDim.x, m0, m_end, n0, Bw, A2);
     f32x4 acc[4][TM];
-    if constexpr (EPI == EPI_GENERIC) init_acc<TM, 4>(p, acc, n0 + wn * 64, lane);
-    else if constexpr (EPI == EPI_RES32) init_acc_m<TM, 4, 0>(p, acc, n0 + wn * 64, lane);
-    else init_acc_m<TM, 4, 1>(p, acc, n0 + wn * 64, lane);
+    init_acc_e<TM, 4, EPI>(p, acc, n0 + wn * 64, lane);
     // multiply-by-derivative epilogue on the 256-row tile: the aux tile is staged by the K loop's last two steps (gemm_core.h AUXPRE)
     constexpr bool AUX_IN_LOOP = EPI == EPI_MULAUX && BM == 256;
     const bool aux_staged = AUX_IN_LOOP && p.K2 == 0 && (p.K >> 6) >= 2;
@@ -472,41 +454,26 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pp_kernel(const GemmParams p)
                                       aux_staged ? (const bf16_t*)p.aux : nullptr, p.ldaux);
     GEMM_TRACE(1);
     if constexpr (EPI == EPI_MULAUX) {
-        if (aux_staged) {
-            wait_vm<0>();
-            __syncthreads();
-            store_tile_fast<TM, 4, EPI>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end, smem, wm * RW, wn * 8);
-            GEMM_TRACE(2);
-#ifdef REID_GEMM_TRACE
-            wait_vm<0>();
-            GEMM_TRACE(3);
-#endif
-            return;
-        }
-        // The saved-derivative tile (256 rows x 512 B) comes in through LDS, which the K loop has just left: 128 LDS-DMA instructions
-        // of two 512-byte row segments each, instead of 128 register loads of sixteen 64-byte row segments -- the register-direct form
-        // kept a workgroup 8.5 us in this epilogue (per-workgroup trace, tools/exp_gemm_trace.py), most of it waiting for those reads.
-        __syncthreads();                                     // every wave has left the K loop's last fragment reads
+        // The saved-derivative tile (256 rows x 512 B) comes in through LDS -- staged by the K loop's last two steps or, failing that, here,
+        // once the K loop has left the LDS: 128 LDS-DMA instructions of two 512-byte row segments each, instead of 128 register loads
+        // of sixteen 64-byte row segments -- the register-direct form kept a workgroup 8.5 us in this epilogue (per-workgroup trace,
+        // tools/exp_gemm_trace.py), most of it waiting for those reads.
+        if (!aux_staged) {
+            __syncthreads();                                 // every wave has left the K loop's last fragment reads
 #pragma unroll
-        for (int q = 0; q < BM / 16; ++q) {
-            const int rp = q * 8 + wave;                     // row pair
-            const int row = 2 * rp + (lane >> 5);
-            const int c = lane & 31;                         // destination chunk position; it holds source chunk c ^ (row & 15)
-            const int gm = m0 + row < m_end ? m0 + row : m_end - 1;
-            const char* src = (const char*)p.aux + ((size_t)gm * p.ldaux + n0) * 2 + (swz512(row, c) << 4);
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + rp * 1024), 16, 0, 0);
+            for (int q = 0; q < BM / 16; ++q) {
+                const int rp = q * 8 + wave;                 // row pair
+                const int row = 2 * rp + (lane >> 5);
+                const int c = lane & 31;                     // destination chunk position; it holds source chunk c ^ (row & 15)
+                const int gm = m0 + row < m_end ? m0 + row : m_end - 1;
+                const char* src = (const char*)p.aux + ((size_t)gm * p.ldaux + n0) * 2 + (swz512(row, c) << 4);
+                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + rp * 1024), 16, 0, 0);
+            }
         }
         wait_vm<0>();
         __syncthreads();
         store_tile_fast<TM, 4, EPI>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end, smem, wm * RW, wn * 8);
-        GEMM_TRACE(2);
-#ifdef REID_GEMM_TRACE
-        wait_vm<0>();
-        GEMM_TRACE(3);
-#endif
-        return;
-    }
-    if constexpr (EPI == EPI_GENERIC) store_tile<TM, 4>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end);
+    } else if constexpr (EPI == EPI_GENERIC) store_tile<TM, 4>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end);
     else store_tile_fast<TM, 4, EPI>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end);
     GEMM_TRACE(2);
 #ifdef REID_GEMM_TRACE
@@ -533,17 +500,11 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pps_kernel(const GemmParams p
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave >> 2, wn = wave & 3;
     const int n_tiles = p.tiles_m * p.tiles_n;
-    auto tile_of = [&](int v, int& m0, int& m_end, int& n0, const bf16_t*& Bw) {
-        const int lin = xcd_linear_block(v, n_tiles);
-        int tm, tn;
-        tile_coords(lin, p.tiles_m, p.tiles_n, tm, tn, p.group_m);
-        tile_rows(p, tm, BM, m0, m_end, Bw);
-        n0 = tn * 256;
+    auto tile = [&](int v, int& m0, int& m_end, int& n0, const bf16_t*& Bw) {
+        const bf16_t* A2;                                    // (no low-rank pair in the persistent form)
+        tile_of<BM, 256>(p, v, n_tiles, m0, m_end, n0, Bw, A2);
     };
-    auto init = [&](f32x4 (&acc)[4][TM], int n0) {
-        if constexpr (EPI == EPI_RES32) init_acc_m<TM, 4, 0>(p, acc, n0 + wn * 64, lane);
-        else init_acc_m<TM, 4, 1>(p, acc, n0 + wn * 64, lane);
-    };
+    auto init = [&](f32x4 (&acc)[4][TM], int n0) { init_acc_e<TM, 4, EPI>(p, acc, n0 + wn * 64, lane); };
     auto epi = [&](f32x4 (&acc)[4][TM], int m0, int m_end, int n0) {
         store_tile_fast<TM, 4, EPI>(p, acc, m0 + wm * RW, n0 + wn * 64, lane, m_end);
     };
@@ -569,130 +530,73 @@ __global__ __launch_bounds__(512, 2) void mer_gemm_pps_kernel(const GemmParams p
 #else
     auto trace = [&](int, int) {};
 #endif
-    stream_pp<BM, 256>(p.A, p.lda, p.ldb, p.N, p.K, n_tiles, smem, p.perm_b != 0, tile_of, init, epi, trace);
+    stream_pp<BM, 256>(p.A, p.lda, p.ldb, p.N, p.K, n_tiles, smem, p.perm_b != 0, tile, init, epi, trace);
 }
 
-template <int EPI, int BM>
-int launch_pps_e(GemmParams& p, hipStream_t s) {
-    using C = PPCfg<BM, 256>;
-    constexpr int LDS = C::LDS_BYTES;
-    REID_MAX_LDS((mer_gemm_pps_kernel<EPI, BM>), LDS);
-    const int tiles = p.tiles_m * p.tiles_n;
-    int grid = reid_num_cus() & ~7;
-    if (grid > tiles) grid = tiles;                              // (then every workgroup has exactly one tile: v + grid >= tiles)
-#ifdef REID_GEMM_TRACE
-    p.trace = g_gemm_trace;
-#endif
-    hipLaunchKernelGGL((mer_gemm_pps_kernel<EPI, BM>), dim3(grid), dim3(C::NT), LDS, s, p);
-    REID_CHECK_LAUNCH("reid_mer_gemm");
-    return REID_OK;
+// ---- host side: the launch plan (plain C++: no HIP call, no knob table, no device query) ----------------------------------------------
+// Every rule of the dispatch lives here and nowhere else; reid_mer_gemm_plan hands the result to the tests.  What was tried and
+// dropped on the way to these rules is in DESIGN.md section 5b, "GEMM dispatch".
+
+// row tiles of height bm, summed over the row groups (a row tile never straddles two groups)
+static int row_tiles(const GemmParams& p, int bm) {
+    if (p.n_groups <= 0) return (p.M + bm - 1) / bm;
+    int t = 0;
+    for (int g = 0; g < p.n_groups; ++g) t += (p.grp_row_end[g] - p.grp_row0[g] + bm - 1) / bm;
+    return t;
 }
 
-
-template <int EPI, int BM>
-int launch_pp_e(GemmParams& p, hipStream_t s) {
-    using C = PPCfg<BM, 256>;
-    REID_MAX_LDS((mer_gemm_pp_kernel<EPI, BM>), C::LDS_BYTES);
-    hipLaunchKernelGGL((mer_gemm_pp_kernel<EPI, BM>), dim3(p.tiles_m * p.tiles_n), dim3(C::NT), C::LDS_BYTES, s, p);
-    REID_CHECK_LAUNCH("reid_mer_gemm");
-    return REID_OK;
-}
-// Tile height of the ping-pong kernel: 224 rows when that needs no more rounds of 256 workgroups than 256 rows do (each round is then 7/8
-// as long: fc2 267 -> 246 us, fc1 backward 223 -> 206 us, q|k|v backward 199 -> 190 us at 50 432 rows, N = 768); with an extra round the
-// per-tile costs (first operands, epilogue) outweigh the shorter tiles (N = 3072: 318 -> 333 us).  REID_GEMM_TILE=12 / 14 force 256 / 224.
-static int pick_pp_bm(const GemmParams& p, int tile_knob) {
-    if (tile_knob == 12) return 256;
-    if (tile_knob == 14) return 224;
-    const long cus = reid_num_cus();
-    const long tn = p.N / 256;
-    GemmParams q = p;
-    const long t256 = (long)row_tiles(q, 256, false) * tn, t224 = (long)row_tiles(q, 224, false) * tn;
-    return (t224 + cus - 1) / cus <= (t256 + cus - 1) / cus ? 224 : 256;
-}
-int launch_pp(GemmParams& p, hipStream_t s, int tile_knob) {
-    p.epi = pick_epilogue(p, 256);
-    const int bm = p.epi == EPI_GENERIC ? 256 : pick_pp_bm(p, tile_knob);     // (the generic epilogue is only built for the 256-row tile)
-    p.tiles_m = row_tiles(p, bm, true);
-    p.tiles_n = (p.N + 255) / 256;
-#ifdef REID_GEMM_TRACE
-    p.trace = g_gemm_trace;
-#endif
-    // persistent stream form for the plain and residual epilogues, the out-projection shapes included.  In-step A/B (r03, bench.py,
-    // one box; the persistent set as a bit mask, 1 = plain / residual, 2 = GELU too, 4 = multiply-by-derivative too, 8 = out-projection
-    // shapes too; the switch is at 13e2fd7): 1: 33.15-33.25 ms/step, 9: 33.02, 13: 32.98-33.00, 5: 33.40 -- inside the step a persistent
-    // GEMM keeps its CUs for its whole duration, so the HBM-bound side-stream kernels cannot take compute units from it (q|k|v backward
-    // 263 -> 194 us in-step)
-    // (r03, tools/bench_gemm_shapes.py, profiles/r03_gemm_pps2.log: q|k|v 195 -> 183 us, q|k|v backward 157 -> 151, fc1 backward 207 -> 202,
-    //  residual shapes unchanged; the GELU shapes are 2 % SLOWER persistent (327 -> 334 us: their 6 + 3.5 us VALU-bound epilogue dominates the
-    //  tile boundary and a static tile sequence cannot rebalance it), so they stay one tile per workgroup)
-    if (p.K2 == 0 && p.K >= 192 && (reid_num_cus() & ~7) >= 8) {
-        switch (p.epi) {
-            case EPI_PLAIN16: return bm == 224 ? launch_pps_e<EPI_PLAIN16, 224>(p, s) : launch_pps_e<EPI_PLAIN16, 256>(p, s);
-#ifndef REID_FLAVOR_F16
-            case EPI_PLAIN16H: return bm == 224 ? launch_pps_e<EPI_PLAIN16H, 224>(p, s) : launch_pps_e<EPI_PLAIN16H, 256>(p, s);
-#endif
-            case EPI_RES32: return bm == 224 ? launch_pps_e<EPI_RES32, 224>(p, s) : launch_pps_e<EPI_RES32, 256>(p, s);
-            default: break;
+static reid_gemm_plan make_plan(const GemmParams& p, int cus, int tile_knob) {
+    reid_gemm_plan pl;
+    auto one_tile_per_workgroup = [&](int kernel, int bm, int bn, int epi) {
+        pl.kernel = kernel; pl.bm = bm; pl.bn = bn; pl.epilogue = epi;
+        pl.tiles_m = row_tiles(p, bm); pl.tiles_n = (p.N + bn - 1) / bn;
+        pl.grid = pl.tiles_m * pl.tiles_n;
+        return pl;
+    };
+    // skinny outputs (LoRA down-projections, N <= 96) use a tall tile so no MFMA work is spent on padding; below 65 536 rows the
+    // 256-row tiles would leave fewer than 256 workgroups, 64-row tiles fill the chip
+    if (p.N <= 32) return one_tile_per_workgroup(REID_GEMM_TILED, p.M >= 65536 ? 256 : 64, 32, EPI_GENERIC);
+    if (p.N <= 64) return one_tile_per_workgroup(REID_GEMM_TILED, p.M >= 65536 ? 256 : 64, 64, EPI_GENERIC);
+    if (p.N <= 96) return one_tile_per_workgroup(REID_GEMM_TILED, 128, 32, EPI_GENERIC);
+    // REID_GEMM_TILE: 3 forces the 128 x 128 tile, 12 / 14 the 256 / 224-row ping-pong tile
+    const int tile = tile_knob > 0 ? tile_knob : 0;
+    // (k2_group_n is a multiple of 128: a column tile must not straddle two LoRA groups of the fused q|k|v projection)
+    const bool pp_ok = (p.k2_group_n == 0 || p.k2_group_n % 256 == 0) && p.N % 256 == 0;
+    if (pp_ok && tile != 3) {
+        // 256 x 256 ping-pong tile (gemm_core.h mainloop_pp) where it wins (r02, sum of the seven ViT shapes: 1.74 ms vs 1.89 ms for the
+        // 128 x 128 tile, both with lean epilogues; with the GENERIC epilogue it loses, 2.16 ms): only when a lean epilogue covers the
+        // launch and there is at least one tile per CU
+        const int epi = pick_epilogue(p, 256);
+        const long tn = p.N / 256, t256 = row_tiles(p, 256) * tn;
+        if (tile == 12 || tile == 14 || (tile == 0 && t256 >= cus && epi != EPI_GENERIC)) {
+            // 224 rows when that needs no more rounds of `cus` workgroups than 256 rows do (each round is then 7/8 as long: fc2 267 ->
+            // 246 us, fc1 backward 223 -> 206 us at 50 432 rows, N = 768); with an extra round the per-tile costs outweigh the shorter
+            // tiles (N = 3072: 318 -> 333 us).  The generic epilogue is only built for the 256-row tile.
+            const long t224 = row_tiles(p, 224) * tn;
+            int bm = (t224 + cus - 1) / cus <= (t256 + cus - 1) / cus ? 224 : 256;
+            if (tile == 12) bm = 256;
+            if (tile == 14) bm = 224;
+            if (epi == EPI_GENERIC) bm = 256;
+            one_tile_per_workgroup(REID_GEMM_PP, bm, 256, epi);
+            // persistent stream form (gemm_core.h stream_pp: merged weights, nk >= 3, a grid that is a multiple of 8) for the plain and
+            // residual epilogues: in-step it keeps its CUs from the side-stream kernels (r03: q|k|v backward 263 -> 194 us in-step;
+            // stand-alone q|k|v 195 -> 183 us).  The GELU shapes are 2 % SLOWER persistent (327 -> 334 us: their VALU-bound epilogue
+            // dominates the tile boundary and a static tile sequence cannot rebalance it), so they stay one tile per workgroup.
+            if (p.K2 == 0 && p.K >= 192 && (cus & ~7) >= 8 && (epi == EPI_PLAIN16 || epi == EPI_PLAIN16H || epi == EPI_RES32)) {
+                pl.kernel = REID_GEMM_PPS;
+                if (pl.grid > (cus & ~7)) pl.grid = cus & ~7;    // (otherwise every workgroup has exactly one tile)
+            }
+            return pl;
         }
     }
-#define REID_PP_CASE(E) case E: return bm == 224 ? launch_pp_e<E, 224>(p, s) : launch_pp_e<E, 256>(p, s);
-    switch (p.epi) {
-        REID_PP_CASE(EPI_PLAIN16)
-#ifndef REID_FLAVOR_F16
-        REID_PP_CASE(EPI_PLAIN16H)
-#endif
-        REID_PP_CASE(EPI_RES32)
-        REID_PP_CASE(EPI_GELU2)
-        REID_PP_CASE(EPI_DGELU)
-        REID_PP_CASE(EPI_GELU2D)
-        REID_PP_CASE(EPI_MULAUX)
-        default: return launch_pp_e<EPI_GENERIC, 256>(p, s);
-    }
-#undef REID_PP_CASE
+    // default: 128 x 128 x 64 tiles, 4 waves, 64 KiB of LDS -> TWO workgroups per CU, one's stores overlap the other's MFMAs (r01, sum
+    // over the seven shapes: 1.90 ms vs 2.04-2.17 ms for plain 256 x 256 / 128 x 256 tiles), with the lean epilogue that covers the launch
+    return one_tile_per_workgroup(REID_GEMM_TILED, 128, 128, pick_epilogue(p, 128));
 }
 
-template <int BM, int BN, int WM, int WN, int EPI>
-int launch_e(GemmParams& p, hipStream_t s) {
-    using C = Cfg<BM, BN, WM, WN>;
-    REID_MAX_LDS((mer_gemm_kernel<BM, BN, WM, WN, EPI>), C::LDS_BYTES);
-    hipLaunchKernelGGL((mer_gemm_kernel<BM, BN, WM, WN, EPI>), dim3(p.tiles_m * p.tiles_n), dim3(C::NT), C::LDS_BYTES, s, p);
-    REID_CHECK_LAUNCH("reid_mer_gemm");
-    return REID_OK;
-}
-// the default 128 x 128 tile with the lean epilogue that covers the launch (GENERIC otherwise)
-int launch_main(GemmParams& p, hipStream_t s) {
-    p.tiles_m = row_tiles(p, 128, true);
-    p.tiles_n = (p.N + 127) / 128;
-    p.epi = pick_epilogue(p, 128);
-    switch (p.epi) {
-        case EPI_PLAIN16: return launch_e<128, 128, 2, 2, EPI_PLAIN16>(p, s);
-#ifndef REID_FLAVOR_F16
-        case EPI_PLAIN16H: return launch_e<128, 128, 2, 2, EPI_PLAIN16H>(p, s);
-#endif
-        case EPI_RES32: return launch_e<128, 128, 2, 2, EPI_RES32>(p, s);
-        case EPI_GELU2: return launch_e<128, 128, 2, 2, EPI_GELU2>(p, s);
-        case EPI_DGELU: return launch_e<128, 128, 2, 2, EPI_DGELU>(p, s);
-        case EPI_GELU2D: return launch_e<128, 128, 2, 2, EPI_GELU2D>(p, s);
-        case EPI_MULAUX: return launch_e<128, 128, 2, 2, EPI_MULAUX>(p, s);
-        default: return launch_e<128, 128, 2, 2, EPI_GENERIC>(p, s);
-    }
-}
-
-template <int BM, int BN, int WM, int WN>
-int launch(GemmParams& p, hipStream_t s) {
-    using C = Cfg<BM, BN, WM, WN>;
-    p.tiles_m = row_tiles(p, BM, true);
-    p.tiles_n = (p.N + BN - 1) / BN;
-    REID_MAX_LDS((mer_gemm_kernel<BM, BN, WM, WN>), C::LDS_BYTES);
-    const int grid = p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((mer_gemm_kernel<BM, BN, WM, WN>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
-    REID_CHECK_LAUNCH("reid_mer_gemm");
-    return REID_OK;
-}
-
-}  // namespace
-
-extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
+// Validates *a (the one copy of the checks, for both entry points), fills the kernel parameters and plans the launch.
+// cus <= 0: the current device's count, asked for only after the checks have passed.
+static int check_and_plan(const reid_gemm_args* a, int cus, int tile_knob, GemmParams& p, reid_gemm_plan& pl) {
     REID_CHECK_ARG(a != nullptr, "reid_mer_gemm: null args");
     REID_CHECK_ARG(a->A && a->B && a->C, "reid_mer_gemm: A, B, C must be non-null");
     REID_CHECK_ARG(a->M > 0 && a->N > 0 && a->K > 0, "reid_mer_gemm: empty problem M=%d N=%d K=%d", a->M, a->N, a->K);
@@ -733,7 +637,6 @@ extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
         REID_CHECK_ARG(a->b_group_stride >= (int64_t)a->N * a->ldb, "reid_mer_gemm: b_group_stride smaller than one [N, ldb] matrix");
         REID_CHECK_ARG(a->c_group == 0 && a->r_period == 0, "reid_mer_gemm: row groups do not combine with c_group / r_period");
     }
-    GemmParams p;
     p.trace = nullptr;
     p.A = (const bf16_t*)a->A; p.B = (const bf16_t*)a->B; p.A2 = (const bf16_t*)a->A2; p.B2 = (const bf16_t*)a->B2;
     p.bias = a->bias; p.R = a->R; p.aux = (const bf16_t*)a->aux; p.C = a->C; p.C2 = a->C2; p.img_mod = a->img_mod; p.row_scale = a->row_scale;
@@ -757,80 +660,107 @@ extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
     if (p.c_dtype == REID_F16 && REID_FLAVOR_ID == 1) p.c_dtype = REID_BF16;          // the f16 flavor's own format (saturating there too)
     REID_CHECK_ARG(!(a->C2 && a->c2_dtype == REID_F16 && REID_FLAVOR_ID == 0) && !(a->R && a->r_dtype == REID_F16 && REID_FLAVOR_ID == 0),
                    "reid_mer_gemm: REID_F16 is supported for C only");
-    // L2 group height of the tile order: 16 row tiles when the weight panel set is wide and K short (q|k|v, fc1: the whole
-    // [N, K] weight no longer fits one XCD's L2 next to 8 activation tiles and was re-streamed per group; r01 sweep 4..64)
-    // r04, 256-row tiles, in-step A/B on one box (tools/exp_ab.sh): 8 for every shape 30.73-30.79 ms per step, 16 for the wide short-K
-    // shapes (the r01 choice, made with 128-row tiles) 30.87-30.89, 4: 30.72-30.84, 16 everywhere 31.3, 32: 32.2
+    // L2 group height of the tile order (gemm_core.h tile_coords).  r04, 256-row tiles, in-step A/B on one box (tools/exp_ab.sh): 8 for
+    // every shape 30.73-30.79 ms per step, 16 for the wide short-K shapes (the r01 choice, made with 128-row tiles) 30.87-30.89,
+    // 4: 30.72-30.84, 16 everywhere 31.3, 32: 32.2
     p.group_m = 8;
     p.perm_b = epilogue_wide16(p) ? 1 : 0;
-    hipStream_t s = (hipStream_t)stream;
-    if (p.c_dtype == REID_F16) {
-        // only the plain lean epilogue stores IEEE half in the bf16 flavor (what the residual-branch GEMMs of the vision blocks use)
-        REID_CHECK_ARG(a->N > 96 && a->N % 128 == 0 && reid_knob(KNOB_GEMM_TILE) <= 0 &&
-                       pick_epilogue(p, 128) == EPI_PLAIN16H,
-                       "reid_mer_gemm: a REID_F16 output needs the plain 16-bit epilogue (N a multiple of 128, no activation / residual / second output / mask / row remap)");
+    pl = make_plan(p, cus > 0 ? cus : reid_num_cus(), tile_knob);
+    // only the plain lean epilogue stores IEEE half in the bf16 flavor (what the residual-branch GEMMs of the vision blocks use); a lean
+    // epilogue implies N a multiple of its tile width, and no forced tile may take the launch elsewhere
+    REID_CHECK_ARG(p.c_dtype != REID_F16 || (tile_knob <= 0 && pl.epilogue == EPI_PLAIN16H),
+                   "reid_mer_gemm: a REID_F16 output needs the plain 16-bit epilogue (N a multiple of 128, no activation / residual / second output / mask / row remap)");
+    return REID_OK;
+}
+
+// ---- host side: the launch table ---------------------------------------------------------------------------------------------------------
+// run-time epilogue -> compile-time one: f(std::integral_constant<int, EPI>).  The ONE place that knows which epilogues a flavor builds
+// (the f16 flavor's own 16-bit format is IEEE half, so it has no PLAIN16H).
+template <typename F>
+int with_epilogue(int epi, F f) {
+#define REID_EPI_CASE(E) case E: return f(std::integral_constant<int, E>{});
+    switch (epi) {
+        REID_EPI_CASE(EPI_PLAIN16)
+#ifndef REID_FLAVOR_F16
+        REID_EPI_CASE(EPI_PLAIN16H)
+#endif
+        REID_EPI_CASE(EPI_RES32)
+        REID_EPI_CASE(EPI_GELU2)
+        REID_EPI_CASE(EPI_DGELU)
+        REID_EPI_CASE(EPI_GELU2D)
+        REID_EPI_CASE(EPI_MULAUX)
+        default: return f(std::integral_constant<int, EPI_GENERIC>{});
     }
-    // skinny outputs (LoRA down-projections, N <= 96) use a tall tile so no MFMA work is spent on padding
-    // (tall 256-row tiles leave a 50k-row problem with < 256 workgroups: 64-row tiles fill the chip; r01: a three-buffer ring
-    //  with counted vmcnt -- twice the bytes in flight per workgroup -- changed the step time by < 0.1 %: not kept)
-    // (r02: a streaming form of these projections -- activation fragments loaded straight into VGPRs, 24 KiB per wave in flight,
-    //  the small weight fragment-linear in LDS -- was built and measured against this tiled form on the three LoRA shapes,
-    //  bit-identical outputs: 26 / 93 / 26 us vs 16 / 58 / 16 us stand-alone.  Fragment-shaped global
-    //  loads (16 rows x 64 bytes per instruction) cost the vector-memory path more than the LDS round trip saves; stand-alone
-    //  the tiled form already streams at 4.9-5.4 TB/s -- the 31 us seen in the train step is interference from the dA/dB
-    //  reductions on the side stream, not this kernel.)
-    if (a->N <= 32) return a->M >= 65536 ? launch<256, 32, 4, 1>(p, s) : launch<64, 32, 4, 1>(p, s);
-    if (a->N <= 64) return a->M >= 65536 ? launch<256, 64, 4, 1>(p, s) : launch<64, 64, 4, 1>(p, s);
-    if (a->N <= 96) return launch<128, 32, 4, 1>(p, s);
-    // REID_GEMM_TILE (cached knob table, common.h): 3 forces the 128 x 128 tile, 12 / 14 the 256 / 224-row ping-pong tile
-    const int tile = reid_knob(KNOB_GEMM_TILE) > 0 ? reid_knob(KNOB_GEMM_TILE) : 0;
-    if (tile == 3) return launch_main(p, s);
-    {
-        // 256 x 256 ping-pong tile (gemm_core.h mainloop_pp) where it wins (r02, same harness, sum of the seven ViT shapes: 1.74 ms vs
-        // 1.89 ms for the 128 x 128 tile, both with the lean epilogues; with the GENERIC epilogue it loses, 2.16 ms): every shape
-        // except the short-K, narrow-N out-projection (591 tiles of 256 x 256 = 2.3 waves of the chip and only 12 K-tiles each),
-        // and only when a lean epilogue covers the launch and there is at least one tile per CU.
-        // (r02, measured and dropped, profiles/r02_gemm_experiments2_persistent_stream.patch: a PERSISTENT form of this kernel whose
-        // half-tile prefetch runs on across output tiles, so a tile's first operands are in LDS when its loop starts -- 1804 us vs
-        // 1667 us per layer.  gfx9 counts loads and stores in one in-order vmcnt: the first counted wait of the next tile has to
-        // drain the previous tile's C stores, whereas a workgroup that simply ENDS leaves its stores draining under the next
-        // workgroup's K loop.  One tile per workgroup already has the store / K-loop overlap the persistent form was after.)
-        // (r02, second attempt, profiles/r02_gemm_experiments3_persistent_queue.patch: persistent workgroups fed from per-XCD atomic
-        // tile counters with one tile of lookahead, the two-phase loop streaming across tile boundaries, register-only epilogues.
-        // Correct (all GEMM tests pass) and 18 % slower over the seven shapes: per-tile traces show K loops of 30.5 us instead of 20.3 us
-        // and 2.8 us between tiles -- hipcc waits vmcnt(0) for the bias loads of the accumulator init and for the queue index, which
-        // drains the prefetch at every tile start, and the loop carries ~40 spilled registers across tile boundaries.)
-        const bool pp_ok = (p.k2_group_n == 0 || p.k2_group_n % 256 == 0) && p.N % 256 == 0;
-        const long tiles256 = (long)row_tiles(p, 256, false) * (p.N / 256);
-        const bool pp_shape = tiles256 >= reid_num_cus();         // the out-projection shapes as well (persistent, see launch_pp)
-        if (pp_ok && (tile == 12 || tile == 14 || (tile == 0 && pp_shape && pick_epilogue(p, 256) != EPI_GENERIC)))
-            return launch_pp(p, s, tile);
+#undef REID_EPI_CASE
+}
+
+template <int BM, int BN, int WM, int WN, int EPI>
+int launch_e(const GemmParams& p, int grid, hipStream_t s) {
+    using C = Cfg<BM, BN, WM, WN>;
+    REID_MAX_LDS((mer_gemm_kernel<BM, BN, WM, WN, EPI>), C::LDS_BYTES);
+    hipLaunchKernelGGL((mer_gemm_kernel<BM, BN, WM, WN, EPI>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
+    REID_CHECK_LAUNCH("reid_mer_gemm");
+    return REID_OK;
+}
+template <int EPI, int BM>
+int launch_pp_e(const GemmParams& p, int grid, hipStream_t s) {
+    using C = PPCfg<BM, 256>;
+    REID_MAX_LDS((mer_gemm_pp_kernel<EPI, BM>), C::LDS_BYTES);
+    hipLaunchKernelGGL((mer_gemm_pp_kernel<EPI, BM>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
+    REID_CHECK_LAUNCH("reid_mer_gemm");
+    return REID_OK;
+}
+template <int EPI, int BM>
+int launch_pps_e(const GemmParams& p, int grid, hipStream_t s) {
+    using C = PPCfg<BM, 256>;
+    REID_MAX_LDS((mer_gemm_pps_kernel<EPI, BM>), C::LDS_BYTES);
+    hipLaunchKernelGGL((mer_gemm_pps_kernel<EPI, BM>), dim3(grid), dim3(C::NT), C::LDS_BYTES, s, p);
+    REID_CHECK_LAUNCH("reid_mer_gemm");
+    return REID_OK;
+}
+
+// Launches what the plan says and decides nothing: the instance of (kernel, tile, epilogue).
+static int launch_plan(GemmParams& p, const reid_gemm_plan& pl, hipStream_t s) {
+    p.tiles_m = pl.tiles_m; p.tiles_n = pl.tiles_n; p.epi = pl.epilogue;
+    for (int g = 0, t = 0; g < p.n_groups; ++g) {                // group g owns row tiles [grp_tile0[g], grp_tile0[g + 1])
+        p.grp_tile0[g] = t;
+        t += (p.grp_row_end[g] - p.grp_row0[g] + pl.bm - 1) / pl.bm;
     }
-    // Default from same-process A/B runs of the seven ViT GEMM variants (tools/bench_gemm_variants.py, r01): 128x128x64
-    // tiles, 4 waves, 64 KiB of LDS -> TWO workgroups per CU.  With the register-direct epilogue its K loop runs as fast
-    // as the 256x256 tile's (~1.0-1.1 PF on these shapes) and, unlike one big workgroup per CU, one workgroup's stores
-    // overlap the other's MFMAs (sum over the seven shapes: 1.90 ms vs 2.04-2.17 ms for 256x256 / 128x256 tiles).
-    // (k2_group_n is a multiple of 128, so a column tile never straddles two LoRA groups of the fused q|k|v projection.)
-    // r02 anatomy of this kernel on the seven ViT shapes (profiles/r02_gemm_variants*.log, sum per layer, 1 MI355X):
-    //   whole kernel 1.93 ms = K loop alone 1.40-1.43 ms + epilogue alone 0.59-0.60 ms (timing modes, at 13e2fd7): they do
-    //   NOT overlap although two workgroups share a CU.  K loop with the MFMAs removed (LDS-DMA + fragment reads only): 1.22 ms =
-    //   22 GB of L2->LDS operand traffic at 71 GB/s per CU, the per-CU LDS-DMA rate of MI355X_MICROARCH.md ("Indexed rows:
-    //   gather into LDS", 66-73 GB/s): the 128x128 K loop is bound by the CU's vector-memory path, not by the matrix pipe
-    //   (MFMAs + fragment reads without any LDS-DMA: 1.10 ms = 1.33 PF); the epilogue streams C / residual / aux at 4.2 TB/s and
-    //   needs the same path.  Tried in r02 and dropped (all measured in that harness, code in git history of this round):
-    //   * persistent two-workgroups-per-CU grid with the partner of each CU (blocks b and b+256, found with tools/hwinfo.hip via
-    //     HW_REG_LDS_ALLOC) started 0.5x..2.5x of a K-loop time late, next tile's first K-step prefetched under the epilogue:
-    //     1.99 ms unstaggered, 2.03-2.22 ms staggered (phasing the pair does not create overlap: they contend for that path);
-    //   * three-slot LDS ring with counted vmcnt + raw s_barrier, one 8-wave workgroup per CU (256x128, 128x256) or 128x128:
-    //     K loops 1.49-1.54 ms / 1.99 ms (eight barrier-coupled waves serialise their read and MFMA phases);
-    //   * epilogue through a wave-private LDS transpose (4 rows x 256 B per access instead of 16 rows x 64 B): epilogue alone
-    //     0.85 ms vs 0.60 ms -- segment length is not what holds the epilogue at 4.2 TB/s.
-    //   What is left is halving the operand traffic per flop (256x256 tiles) TOGETHER with a wave-group ping-pong K loop
-    //   and an epilogue that overlaps the next tile; the plain 256x256 / 128x256 tiles here lose more in the un-hidden
-    //   epilogue (2.27 / 2.15 ms) than their K loop gains (1.35 ms).
-    // Tried and dropped in r01 (same harness): LDS-ring variants with 32-wide K steps and counted vmcnt (128x256 tile with 4
-    // waves of 64x128, 128x128 with 2/3/4 stages at 2/3/4 workgroups per CU): 5-25 % slower than this on every shape;
-    // a DPP lane exchange that makes the epilogue store 128 contiguous bytes per row: slower (the DPP hazards cost more
-    // than the wider segments give).
-    return launch_main(p, s);
+#ifdef REID_GEMM_TRACE
+    p.trace = g_gemm_trace;
+#endif
+    const int grid = pl.grid, tile = pl.bm * 1000 + pl.bn;
+    if (pl.kernel == REID_GEMM_TILED) {
+        switch (tile) {                                          // the skinny tiles exist with the generic epilogue only
+            case 64032: return launch_e<64, 32, 4, 1, EPI_GENERIC>(p, grid, s);
+            case 256032: return launch_e<256, 32, 4, 1, EPI_GENERIC>(p, grid, s);
+            case 64064: return launch_e<64, 64, 4, 1, EPI_GENERIC>(p, grid, s);
+            case 256064: return launch_e<256, 64, 4, 1, EPI_GENERIC>(p, grid, s);
+            case 128032: return launch_e<128, 32, 4, 1, EPI_GENERIC>(p, grid, s);
+            default: return with_epilogue(pl.epilogue, [&](auto e) { return launch_e<128, 128, 2, 2, decltype(e)::value>(p, grid, s); });
+        }
+    }
+    return with_epilogue(pl.epilogue, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (E == EPI_PLAIN16 || E == EPI_PLAIN16H || E == EPI_RES32) {
+            if (pl.kernel == REID_GEMM_PPS) return pl.bm == 224 ? launch_pps_e<E, 224>(p, grid, s) : launch_pps_e<E, 256>(p, grid, s);
+        }
+        if constexpr (E == EPI_GENERIC) return launch_pp_e<E, 256>(p, grid, s);
+        else return pl.bm == 224 ? launch_pp_e<E, 224>(p, grid, s) : launch_pp_e<E, 256>(p, grid, s);
+    });
+}
+
+}  // namespace
+
+extern "C" int reid_mer_gemm_plan(const reid_gemm_args* a, int32_t cus, int32_t tile_knob, reid_gemm_plan* out) {
+    REID_CHECK_ARG(out != nullptr, "reid_mer_gemm_plan: null plan");
+    GemmParams p;
+    return check_and_plan(a, cus, tile_knob, p, *out);
+}
+
+extern "C" int reid_mer_gemm(const reid_gemm_args* a, void* stream) {
+    GemmParams p;
+    reid_gemm_plan pl;
+    const int rc = check_and_plan(a, 0, reid_knob(KNOB_GEMM_TILE), p, pl);
+    return rc != REID_OK ? rc : launch_plan(p, pl, (hipStream_t)stream);
 }

@@ -9,7 +9,7 @@ from typing import Optional
 import torch
 
 from . import _lib as L
-from ._lib import BF16, F32, GemmArgs, check, lib, ptr, stream_ptr
+from ._lib import BF16, F32, GemmArgs, GemmPlan, check, lib, ptr, stream_ptr
 
 ACT = {'none': L.ACT_NONE, 'gelu': L.ACT_GELU, 'quick_gelu': L.ACT_QUICK_GELU, 'relu': L.ACT_RELU,
        'dgelu': L.ACT_DGELU, 'dquick_gelu': L.ACT_DQUICK_GELU, 'drelu': L.ACT_DRELU,
@@ -29,11 +29,10 @@ def gemm_profile_end():
     return p
 
 
-def gemm(A, B, C_out, *, A2=None, B2=None, K2=0, k2_group_n=0, bias=None, R=None, r_period=0, aux=None,
-         C2=None, act='none', img_mod=None, mask_r=0, mask_period=0, rows_per_img=0,
-         c_group=0, c_group_stride=0, c_row_off=0, alpha=1.0, M=None, row_scale=None, row_groups=None):
-    """C_out = epilogue(A @ B.T + A2 @ B2.T + bias); see reid_mer_gemm in include/reid_hip.h.
-    ``row_groups`` = (row_ends, weight_indices): B is then a stack [n_mats, N, K]; rows [row_ends[g-1], row_ends[g]) use B[weight_indices[g]]."""
+def gemm_args(A, B, C_out, *, A2=None, B2=None, K2=0, k2_group_n=0, bias=None, R=None, r_period=0, aux=None,
+              C2=None, act='none', img_mod=None, mask_r=0, mask_period=0, rows_per_img=0,
+              c_group=0, c_group_stride=0, c_row_off=0, alpha=1.0, M=None, row_scale=None, row_groups=None):
+    """The reid_gemm_args of gemm(A, B, C_out, ...).  The tensors supply pointers, shapes and strides only."""
     a = GemmArgs()
     a.A, a.B, a.C = ptr(A), ptr(B), ptr(C_out)
     a.M = A.shape[0] if M is None else M
@@ -70,6 +69,21 @@ def gemm(A, B, C_out, *, A2=None, B2=None, K2=0, k2_group_n=0, bias=None, R=None
     a.alpha = alpha
     if row_scale is not None:
         a.row_scale = ptr(row_scale); a.rows_per_img = rows_per_img
+    return a
+
+
+def gemm_plan(A, B, C_out, *, cus=0, tile=0, **kw):
+    """The launch gemm(A, B, C_out, **kw) would make on a device of ``cus`` compute units (0: the current device's) with the GEMM_TILE
+    knob at ``tile`` (0: not set): a GemmPlan (reid_mer_gemm_plan).  Nothing is launched or dereferenced: CPU tensors will do."""
+    plan = GemmPlan()
+    check(lib().reid_mer_gemm_plan(C.byref(gemm_args(A, B, C_out, **kw)), cus, tile, C.byref(plan)))
+    return plan
+
+
+def gemm(A, B, C_out, *, R=None, r_period=0, aux=None, C2=None, **kw):
+    """C_out = epilogue(A @ B.T + A2 @ B2.T + bias); see reid_mer_gemm in include/reid_hip.h and gemm_args for the keywords.
+    ``row_groups`` = (row_ends, weight_indices): B is then a stack [n_mats, N, K]; rows [row_ends[g-1], row_ends[g]) use B[weight_indices[g]]."""
+    a = gemm_args(A, B, C_out, R=R, r_period=r_period, aux=aux, C2=C2, **kw)
     profiled = _gemm_profile is not None and a.N > 96   # mer_gemm_kernel<128,128,2,2> (dominant); skinny LoRA projections use other tiles
     if profiled:
         e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)

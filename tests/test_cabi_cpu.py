@@ -30,10 +30,11 @@ def header_macro(name):
 
 def ctype_of(c_type):
     """The ctypes type _lib.SIGNATURES uses for a C type of the header."""
-    from prcv2025reid_amd._lib import GemmArgs
+    from prcv2025reid_amd._lib import GemmArgs, GemmPlan
     t = ' '.join(c_type.replace('*', ' * ').replace('const ', ' ').split())
     if t.endswith('*'):
-        return {'char *': ctypes.c_char_p, 'reid_gemm_args *': ctypes.POINTER(GemmArgs)}.get(t, ctypes.c_void_p)
+        return {'char *': ctypes.c_char_p, 'reid_gemm_args *': ctypes.POINTER(GemmArgs),
+                'reid_gemm_plan *': ctypes.POINTER(GemmPlan)}.get(t, ctypes.c_void_p)
     enums = re.findall(r'typedef\s+enum\s*\{[^}]*\}\s*(\w+)\s*;', header_code())
     return {'int': ctypes.c_int32, 'int32_t': ctypes.c_int32, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
             **{e: ctypes.c_int32 for e in enums}}[t]
@@ -77,11 +78,12 @@ def test_header_declares_what_python_binds():
 
 
 def test_structs_match_their_ctypes_mirrors():
-    from prcv2025reid_amd._lib import GemmArgs
+    from prcv2025reid_amd._lib import GemmArgs, GemmPlan
     from prcv2025reid_amd.trainer import _Entry
     gemm = header_struct('reid_gemm_args')
     assert ('row_group_end', ctypes.c_int32 * header_macro('REID_GEMM_MAX_GROUPS')) in gemm
     assert layout(GemmArgs._fields_) == layout(gemm)
+    assert layout(GemmPlan._fields_) == layout(header_struct('reid_gemm_plan'))
     # the optimizer entry's Python field names are shorter than the header's: types and order only
     assert [t for _, t in layout(_Entry._fields_)] == [t for _, t in layout(header_struct('reid_opt_entry'))]
 

@@ -10,13 +10,13 @@ bits.  Scale variants (x 2^9, x 2^-20) move IEEE-half outputs across 65504 (satu
 import pytest
 import torch
 
+from gemm_cases import CASES, S, case_plan, plan_labels
 from helpers import (U, assert_bit_budget, check_bounded, count_ties16, exact_ints, f_dgelu, f_dquick, f_gelu, f_quick, is_sentinel, quantum16,
                      round16, sentinel_buffer)
 
 pytestmark = pytest.mark.gpu
 
 GUARD = 32          # guard rows after the last row of every output buffer
-S = 197             # ViT tokens per image (rows_per_img of the vision tower)
 
 
 @pytest.fixture(scope='module', params=['bf16', 'f16'])
@@ -67,127 +67,15 @@ def padded32(vals, ld):
 # reid_sgemm and reid_eltwise_f32 call the same gauss_cdf_pdf / quick_gelu_f and are held to the same budgets.
 
 
-# ---- dispatch mirror (gemm.hip reid_mer_gemm) ---------------------------------------------------------------------------------
-def _row_tiles(c, bm):
-    if c.get('groups'):
-        return sum((n * S + bm - 1) // bm for n in c['groups'])
-    return (c['M'] + bm - 1) // bm
-
-
-def pick_epilogue(c, BN):
-    N, act, out = c['N'], c.get('act', 'none'), c.get('out', 't16')
-    R, C2, aux, rs = c.get('R', False), c.get('C2', False), act in ('dgelu', 'dquick_gelu', 'drelu', 'mul_aux'), c.get('row_scale', False)
-    if c.get('alpha', 1.0) != 1.0 or c.get('mask_r', 0) or c.get('patch') or N % BN:
-        return 'generic'
-    ldc = c['ldc']
-    if out == 'f32':
-        return 'res32' if R and not C2 and not aux and act == 'none' and ldc % 4 == 0 and c['ldr'] % 4 == 0 else 'generic'
-    wide16 = (N | ldc) & 7 == 0 and (not C2 or c['ldc2'] % 8 == 0) and (not R or c['ldr'] % 8 == 0) and (not aux or c['ldaux'] % 8 == 0)
-    if not wide16 or R or rs:
-        return 'generic'
-    if act == 'none' and not C2:
-        return 'plain16'
-    if act == 'gelu' and C2:
-        return 'gelu2'
-    if act == 'dgelu':
-        return 'dgelu'
-    if act == 'gelu_dsave' and C2:
-        return 'gelu2d'
-    if act == 'mul_aux':
-        return 'mulaux'
-    return 'generic'
-
-
-def route(c, cus):
-    """Labels of the kernel / tile / epilogue reid_mer_gemm launches for case `c` on a device with `cus` compute units."""
-    N, M = c['N'], c['M']
-    if N <= 32:
-        return {'skinny256x32' if M >= 65536 else 'skinny64x32'}
-    if N <= 64:
-        return {'skinny256x64' if M >= 65536 else 'skinny64x64'}
-    if N <= 96:
-        return {'skinny128x32'}
-    tile = c.get('tile', 0)
-    main = {'main128_' + ('generic' if pick_epilogue(c, 128) == 'generic' else 'lean')}
-    if tile == 3:
-        return main
-    k2n = c.get('k2_group_n', 0)
-    pp_ok = (k2n == 0 or k2n % 256 == 0) and N % 256 == 0
-    pp_shape = _row_tiles(c, 256) * (N // 256) >= cus
-    if not (pp_ok and (tile in (12, 14) or (tile == 0 and pp_shape and pick_epilogue(c, 256) != 'generic'))):
-        return main
-    epi = pick_epilogue(c, 256)
-    if epi == 'generic':
-        bm = 256
-    elif tile in (12, 14):
-        bm = 256 if tile == 12 else 224
-    else:
-        t256, t224 = _row_tiles(c, 256) * (N // 256), _row_tiles(c, 224) * (N // 256)
-        bm = 224 if (t224 + cus - 1) // cus <= (t256 + cus - 1) // cus else 256
-    if c.get('K2', 0) == 0 and c['K'] >= 192 and (cus & ~7) >= 8 and epi in ('plain16', 'res32'):
-        labels = {f'pps{bm}'}
-        ragged = any((n * S) % bm for n in c['groups']) if c.get('groups') else M % bm != 0
-        if ragged:
-            labels.add('pps_ragged')
-        if _row_tiles(c, bm) * (N // 256) > (cus & ~7):
-            labels.add('pps_multi')
-        return labels
-    return {f'pp{bm}' + ('_generic' if epi == 'generic' else '')}
-
-
 REQUIRED_LABELS = {'skinny64x32', 'skinny256x32', 'skinny64x64', 'skinny256x64', 'skinny128x32', 'main128_lean', 'main128_generic',
                    'pp256', 'pp224', 'pps_ragged', 'pps_multi'}
 
-BIG = 333 * S       # 65 601 rows: the 256-row skinny tiles (M >= 65536), ragged
-
-# The call forms engine.py makes, plus forced tiles (GEMM_TILE 3 / 12 / 14) where the default would not reach a form.  Ragged M
-# everywhere; lda / ldb / ldc / ldr / ldaux / ldc2 padded (pad 8, or 4 where the 4-aligned store forms are meant).
-CASES = [
-    dict(name='qkv_row_groups', groups=[3, 4, 2, 3], N=2304, K=768, bias=True),
-    dict(name='lora_down_T32', M=9 * S, N=32, K=768, mask_r=8, mask_period=32, alpha=0.5),
-    dict(name='lora_down_T32_big', M=BIG, N=32, K=768, mask_r=8, mask_period=32, alpha=0.5),
-    dict(name='lora_down_T96', M=9 * S, N=96, K=768, mask_r=8, mask_period=32, alpha=0.5),
-    dict(name='lora_down_T64', M=9 * S, N=64, K=768, mask_r=16, mask_period=64, alpha=0.5),
-    dict(name='lora_down_T64_big', M=BIG, N=64, K=768, mask_r=16, mask_period=64, alpha=2.0),
-    dict(name='k_extension', M=1000, N=2304, K=768, K2=32, k2_group_n=768, bias=True),
-    dict(name='k_extension_pp256', M=1000, N=2304, K=768, K2=32, k2_group_n=768, bias=True, tile=12),
-    dict(name='k_extension_pp224', M=1000, N=2304, K=768, K2=32, k2_group_n=768, bias=True, tile=14),
-    dict(name='out_proj_f16', M=1000, N=768, K=768, bias=True, out='f16'),
-    dict(name='out_proj_residual_pps', M=256 * S, N=768, K=768, bias=True, out='f32', R=True, row_scale=True),
-    dict(name='out_proj_residual_groups', groups=[3, 4, 2, 3], N=768, K=768, bias=True, out='f32', R=True, row_scale=True, tile=12),
-    dict(name='fc2_residual', M=1000, N=768, K=3072, bias=True, out='f32', R=True),
-    dict(name='fc2_f16', M=1000, N=768, K=3072, bias=True, out='f16'),
-    dict(name='plain16_pps_multi', M=5700, N=3072, K=256, bias=True, tile=12),
-    dict(name='fc1_gelu_dsave', M=5700, N=3072, K=768, bias=True, act='gelu_dsave', C2=True),
-    dict(name='fc1_gelu_dsave_128', M=1000, N=3072, K=768, bias=True, act='gelu_dsave', C2=True),
-    dict(name='fc1_gelu_pre', M=1000, N=3072, K=768, bias=True, act='gelu', C2=True),
-    dict(name='fc1_gelu_pre_pp256', M=1000, N=3072, K=768, bias=True, act='gelu', C2=True, tile=12),
-    dict(name='fc1_bwd_mul_aux', M=1000, N=3072, K=768, act='mul_aux'),
-    dict(name='fc1_bwd_mul_aux_pp224', M=1000, N=3072, K=768, act='mul_aux', tile=14),
-    dict(name='fc1_bwd_dgelu', M=1000, N=3072, K=768, act='dgelu', tile=3),
-    dict(name='text_fc1_quick_gelu', M=5 * 77, N=2048, K=512, bias=True, act='quick_gelu', C2=True),
-    dict(name='text_fc1_bwd_dquick_gelu', M=5 * 77, N=2048, K=512, act='dquick_gelu'),
-    dict(name='relu_f32', M=5 * 77, N=512, K=512, bias=True, act='relu', out='f32'),
-    dict(name='drelu', M=5 * 77, N=512, K=512, act='drelu'),
-    dict(name='patch_embed', M=6 * (S - 1), N=768, K=768, bias=True, out='f32', R=True, patch=True),
-    dict(name='patch_embed_pp256', M=6 * (S - 1), N=768, K=768, bias=True, out='f32', R=True, patch=True, tile=12),
-    dict(name='alpha_4col_store', M=1000, N=772, K=768, bias=True, alpha=2.0, pad=4),
-    dict(name='plain_f32', M=1000, N=640, K=768, bias=True, out='f32'),
-]
 TRANSCENDENTAL = ('gelu', 'gelu_dsave', 'dgelu', 'quick_gelu', 'dquick_gelu')
 # Operands: A integers in [-a, a], B integers in [-a, a] times 2^-8 (a = 64: outputs of a few hundred with 15-16 significant bits, so
 # that bf16 and half both round, ties included; 32 / 16 where row_scale / aux spend part of the 24-bit budget).  Scale variants
 # (exponent of A, exponent of B on top of its 2^-8): x1, x2^9 (half outputs beyond 65504: saturation), x2^-20 (half outputs in the
 # subnormal range, rounded at 2^-24 from a 2^-28 grid; the operands stay normal: |A| >= 2^-14, |B| >= 2^-14).
 SCALES = {'x1': (0, 0), 'up': (5, 4), 'down': (-14, -6)}
-
-for _c in CASES:
-    if _c.get('groups'):
-        _c['M'] = sum(_c['groups']) * S
-    pad = _c.get('pad', 8)
-    _c['ldc'] = _c['N'] + pad
-    _c['ldr'] = _c['ldaux'] = _c['ldc2'] = _c['N'] + 8
-    _c['lda'] = _c['K'] + 8
 
 PARAMS = [pytest.param(c, s, id=f"{c['name']}-{s}") for c in CASES
           for s in (('x1',) if c.get('act') in TRANSCENDENTAL else ('x1', 'up', 'down'))]
@@ -196,11 +84,12 @@ STATS = {}          # per (flavor, case): ties, clamped, subnormal counts and wo
 
 
 def test_dispatch_table_reaches_every_path():
-    """The case table, run through the mirror of reid_mer_gemm's dispatch for THIS device's CU count, reaches every kernel / tile."""
+    """The case table, planned by the library itself (reid_mer_gemm_plan) for THIS device's CU count, reaches every kernel / tile."""
+    from prcv2025reid_amd import ops
     cus = torch.cuda.get_device_properties(0).multi_processor_count
     reached = set()
     for c in CASES:
-        labels = route(c, cus)
+        labels = plan_labels(c, case_plan(ops, c, 0))
         print(f"{c['name']:28s} -> {sorted(labels)}")
         reached |= labels
     missing = REQUIRED_LABELS - reached
@@ -317,8 +206,8 @@ def test_mer_gemm_exact(ops, case, scale):
     c = case
     fmt = flavor()
     gen = torch.Generator(device='cuda').manual_seed(sum(map(ord, c['name'] + scale)))
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    labels = route(c, cus)
+    plan = case_plan(ops, c, 0)
+    labels = plan_labels(c, plan)
     A, B, kw, pre, aux64, keep = _build(c, scale, fmt, gen)
     M, N = c['M'], c['N']
     act = c.get('act', 'none')
@@ -327,7 +216,7 @@ def test_mer_gemm_exact(ops, case, scale):
     cfmt = 'f32' if out == 'f32' else ('f16' if out == 'f16' else fmt)
     crow, crows = _crow(c, M)
     # the lean GELU epilogues evaluate Phi with gelu_both_x2, the generic one and every dgelu with gauss_cdf_pdf
-    x2 = act in ('gelu', 'gelu_dsave') and not any(l.endswith('generic') for l in labels)
+    x2 = act in ('gelu', 'gelu_dsave') and plan.epilogue != 0          # (0 = REID_EPI_GENERIC)
 
     def run():
         C = sentinel_buffer(crows + GUARD, c['ldc'], cdt, cfmt)
