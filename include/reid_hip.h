@@ -555,6 +555,58 @@ int reid_center_bwd(int32_t S, int32_t N, int32_t D, const float* ws, const floa
                     int32_t lddx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cluster-contrast memory loss, "ClusterNCE" (the cluster-level memory of SpCL, Ge et al., NeurIPS 2020; Cluster-Contrast, Dai et
+ * al., 2021; the reference has no such loss; csrc/cluster_nce.hip): a non-parametric classifier over one unit centroid per cluster
+ * of a pseudo-labelled set, kept in a table on the device and moved by momentum.  All fp32.
+ *   x [S*N, D] (ldx): S sides stacked, row r = s*N + i = instance i of side s; labels [N] int64, shared by the sides; valid [S*N] uint8
+ *   or NULL (all valid); table [K, D] f32, contiguous, unit rows.  A row is USED when it is valid and 0 <= labels[i] < K (a DBSCAN
+ *   noise label of -1 is simply unused).  With x^ = x / max(|x|, 1e-12):
+ *     l_rc = (x^_r . C_c) / tau,   loss = mean over the used rows of (lse_c(l_rc) - l_r,y),  0 when no row is used.
+ *   reid_cluster_nce_plan(R, K, D, plan): plan[0] = row tile, plan[1] = class tile, plan[2] = the number of splits of the class range
+ *   over workgroups, plan[3] = class tiles per split (split s takes class tiles [s * plan[3], (s + 1) * plan[3])).  It depends on the
+ *   shape only: splits = min(class tiles, 64, max(1, 512 / row tiles)), then made free of empty splits.
+ *   ws: reid_cluster_nce_ws_floats(S, N, D, K) floats kept from fwd to update and bwd (a negative count = bad shape).
+ *   reid_cluster_nce_fwd: the [S*N, K] logits are never stored -- a tile of x^ C^T lives in v_mfma_f32_32x32x2_f32 accumulators (exact
+ *   fp32 products); every row carries a running maximum and sum of exp over the class tiles, the splits' partials are merged in
+ *   split order by a second kernel, which also writes row_loss[r] = lse_r - l_r,y and target_cos[r] = x^_r . C_y (unused rows: 0) and
+ *   result[0] = sum over the used rows of row_loss / max(1, n_used), added in ascending row order in fp64 and rounded once,
+ *   result[1] = n_used as a float.  Neither is read back.  with_grad = 0 stops there: the table is streamed ONCE.  with_grad = 1
+ *   streams it a second time for sum_c p_rc C_c (p = exp(l - lse), per-split partials added in split order) and leaves
+ *     G_r = (sum_c p_rc C_c - C_y) / tau,   H_r = (G_r - x^_r (x^_r . G_r)) / max(|x_r|, 1e-12)      (unused rows: zeros)
+ *   in ws.  The table is a constant of the loss.
+ *   reid_cluster_nce_update (with the labels / valid the forward had, after the forward): a row CONTRIBUTES when it is used and its
+ *   row_loss is finite.  For every label with a contributing row, mode REID_CLUSTER_NCE_MEAN applies, for its contributing rows in
+ *   ascending row order,  c = momentum * c + (1 - momentum) * x^_r;  c = c / max(|c|, 1e-12)  (Cluster-Contrast's sequential loop);
+ *   REID_CLUSTER_NCE_HARD applies the same blend once, with the contributing row of the smallest target_cos (ties: the lowest row).
+ *   Gather form: the wave of the lowest contributing row of a label does its centroid, every other wave leaves; centroids of labels
+ *   not in the batch keep their bits.
+ *   reid_cluster_nce_bwd: dx[r, c] = (dloss[0] / max(1.0f, result[1])) * H[r, c]; dx [S*N, D] (lddx) is OVERWRITTEN (unused rows with
+ *   zeros, padding columns untouched).  It reads ws and result only, never the table: an update or a second forward into another ws
+ *   between the forward and the backward does not change the gradient.
+ *   reid_cluster_centroids: table[k] = the normalised fp32 mean of the rows order[offsets[k]] .. order[offsets[k + 1] - 1] of feats
+ *   [rows, D] (ldf), summed in that order (the caller groups the row indices by label, ascending inside a label: offsets [K + 1]);
+ *   one wave per cluster; an empty cluster gets zeros.
+ *   No atomics: two runs give the same bits in every output and in the table.  Nothing is allocated, synchronised or read back.
+ * Requirements: 1 <= S <= 9, 1 <= N <= 8192, K >= 1, D % 32 == 0, 32 <= D <= 1024, K*D < 2^31, ldx / lddx / ldf multiples of 4 and
+ * >= D, rows * ld < 2^31, x, feats, table, ws and dx 16-byte aligned, tau > 0 and finite, 0 <= momentum <= 1, with_grad 0 or 1.
+ * Anything else: REID_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define REID_CLUSTER_NCE_MEAN 0
+#define REID_CLUSTER_NCE_HARD 1
+int64_t reid_cluster_nce_ws_floats(int32_t S, int32_t N, int32_t D, int32_t K);
+int reid_cluster_nce_plan(int32_t R, int32_t K, int32_t D, int32_t* plan);
+int reid_cluster_nce_fwd(const float* x, int32_t ldx, const int64_t* labels, const uint8_t* valid, int32_t S, int32_t N, int32_t D,
+                         const float* table, int32_t K, float tau, int32_t with_grad, float* ws, float* row_loss, float* target_cos,
+                         float* result, void* stream);
+int reid_cluster_nce_update(const int64_t* labels, const uint8_t* valid, int32_t S, int32_t N, int32_t D, const float* row_loss,
+                            const float* target_cos, const float* ws, float* table, int32_t K, float momentum, int32_t mode,
+                            void* stream);
+int reid_cluster_nce_bwd(int32_t S, int32_t N, int32_t D, const float* ws, const float* result, const float* dloss, float* dx,
+                         int32_t lddx, void* stream);
+int reid_cluster_centroids(const float* feats, int32_t ldf, int64_t rows, const int64_t* order, const int64_t* offsets, int32_t K,
+                           int32_t D, float* table, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Retrieval (train.py:499 + :463; tools/eval_mm_protocol.py:50-53,401-423,622-625):
  *   sim = Q . G^T on L2-normalised rows, per-query top-k in (score desc, index asc) order.
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;

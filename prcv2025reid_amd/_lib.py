@@ -34,6 +34,7 @@ ABI_VERSION = 201                 # REID_ABI_VERSION of include/reid_hip.h: a li
 BF16, F32, F16 = 0, 1, 2          # reid_dtype: BF16 = the flavor's 16-bit format, F16 = IEEE half whatever the flavor
 ACT_NONE, ACT_GELU, ACT_QUICK_GELU, ACT_RELU, ACT_DGELU, ACT_DQUICK_GELU, ACT_DRELU, ACT_MUL_AUX, ACT_GELU_DSAVE = range(9)
 MARGIN_KINDS = {'cosine': 0, 'cosface': 1, 'arcface': 2, 'circle': 3}      # REID_MARGIN_*
+CLUSTER_NCE_MODES = {'mean': 0, 'hard': 1}                                  # REID_CLUSTER_NCE_*
 
 
 class GemmArgs(C.Structure):
@@ -116,6 +117,12 @@ SIGNATURES = {
     'reid_center_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
     'reid_center_update': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _F, _P]),
     'reid_center_bwd': (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    'reid_cluster_nce_ws_floats': (_I64, [_I, _I, _I, _I]),
+    'reid_cluster_nce_plan': (_I, [_I, _I, _I, _P]),
+    'reid_cluster_nce_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _I, _F, _I, _P, _P, _P, _P, _P]),
+    'reid_cluster_nce_update': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _I, _P]),
+    'reid_cluster_nce_bwd': (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    'reid_cluster_centroids': (_I, [_P, _I, _I64, _P, _P, _I, _I, _P, _P]),
     'reid_topk_ws_bytes': (_I64, [_I, _I, _I]),
     'reid_topk_scan_ok': (_I, [_I, _I, _I, _I]),
     'reid_cosine_topk': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

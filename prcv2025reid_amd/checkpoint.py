@@ -120,7 +120,9 @@ def save_checkpoint(model, optimizer, scheduler_state, epoch: int, best_map: flo
     either way.
 
     A model that holds class centres of the center loss (``model.centers``) adds ``center_state_dict`` = the table on the CPU plus the
-    ``center_source`` it was trained on; ``load_checkpoint`` restores it, creating the table when the model has none yet."""
+    ``center_source`` it was trained on; ``load_checkpoint`` restores it, creating the table when the model has none yet.  A model
+    that holds a cluster memory of the cluster-contrast loss (``model.cluster_memory``) adds ``cluster_memory_state_dict`` in the same
+    way; a model without one writes exactly the keys it wrote before."""
     if use_ema and not _has_ema(optimizer):
         raise ValueError('use_ema=True needs an optimizer that keeps an EMA (FusedAdamW(ema_decay=...))')
     os.makedirs(os.path.dirname(os.path.abspath(filename)), exist_ok=True)
@@ -150,6 +152,8 @@ def save_checkpoint(model, optimizer, scheduler_state, epoch: int, best_map: flo
         ckpt['ema_state_dict'] = optimizer.ema_state()
     if getattr(model, 'centers', None) is not None:
         ckpt['center_state_dict'] = dict(model.centers.state(), center_source=getattr(model, 'center_source', 'fused'))
+    if getattr(model, 'cluster_memory', None) is not None:
+        ckpt['cluster_memory_state_dict'] = dict(model.cluster_memory.state(), cluster_nce_source=getattr(model, 'cluster_nce_source', 'bn'))
     torch.save(ckpt, filename)
     return ckpt
 
@@ -183,7 +187,15 @@ def load_checkpoint(filename: str, model, optimizer=None, strict: bool = True) -
             C, D = st['centers'].shape
             model.centers = ClassCenters(C, D, getattr(model, 'device', 'cpu'))
         model.centers.load_state(st)
-    return ({k: v for k, v in ckpt.items() if k not in ('model_state_dict', 'optimizer_state_dict', 'ema_state_dict', 'center_state_dict')}
+    if isinstance(ckpt, dict) and ckpt.get('cluster_memory_state_dict'):
+        st = ckpt['cluster_memory_state_dict']
+        if getattr(model, 'cluster_memory', None) is None:
+            from .losses import ClusterMemory
+            K, D = st['centroids'].shape
+            model.cluster_memory = ClusterMemory(K, D, getattr(model, 'device', 'cpu'))
+        model.cluster_memory.load_state(st)
+    return ({k: v for k, v in ckpt.items() if k not in ('model_state_dict', 'optimizer_state_dict', 'ema_state_dict', 'center_state_dict',
+                                                        'cluster_memory_state_dict')}
             if isinstance(ckpt, dict) else {})
 
 

@@ -109,6 +109,13 @@ class TrainingConfig:
     id_head: str = 'linear'
     id_scale: Optional[float] = None                 # None: the kind's default (30; circle 64)
     id_margin: Optional[float] = None                # None: the kind's default (cosine 0, cosface 0.35, arcface 0.5, circle 0.35)
+    # nor these: cluster-contrast memory loss (ClusterNCE: SpCL, Ge et al. 2020; Cluster-Contrast, Dai et al. 2021) over the pseudo-labels
+    # of cluster.jaccard_dbscan; the labels of a step are then cluster numbers and model.set_cluster_memory() installs the memory
+    cluster_nce_weight: float = 0.0
+    cluster_nce_temperature: float = 0.05            # Cluster-Contrast's
+    cluster_nce_momentum: float = 0.1                # c <- m c + (1 - m) x^, Cluster-Contrast's m
+    cluster_nce_mode: str = 'mean'                   # 'mean': every row of a cluster, in row order; 'hard': its row of the smallest cosine
+    cluster_nce_source: str = 'bn'                   # 'bn': the retrieval feature behind the BN-neck; 'modalities': every modality's raw feature
     sdm_semantic_dim: int = 512
     sdm_num_heads: int = 8
     sdm_dropout: float = 0.1   # not a reference config field: hard-coded in SemanticDisentanglementModule (models/model.py:35,43)

@@ -564,4 +564,85 @@ __device__ __forceinline__ void stream_pp(const bf16_t* __restrict__ A, int lda,
 }
 
 
+// ---- fp32 score tile on v_mfma_f32_32x32x2_f32 (sdm.hip, cluster_nce.hip): exact fp32 products, bit for bit an fmaf chain.
+typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+__device__ __forceinline__ f32x16_t mfma_f32(float a, float b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+
+// TS x TS tile by 4 waves as 2 x 2, each wave (TS/2) x (TS/2) = NT32 x NT32 MFMA tiles; one K-step = 32 floats of both operands.
+template <int TS>
+struct F32Tile {
+    static constexpr int WT = TS / 2, NT32 = WT / 32;
+    static constexpr int STAGE = 2 * TS * 128;
+    static constexpr int LDS_STAGE = 2 * STAGE;                      // double buffered
+};
+
+// acc[ai][bi][reg] = a[m] . b[n] over D (a multiple of 32),  m = wm*WT + 32 ai + (reg&3) + 8 (reg>>2) + 4 (lane>>5),
+// n = wn*WT + 32 bi + (lane&31): `a` and `b` point at the tile's first row of two row-major fp32 matrices with D floats per row; rows
+// past a_max / b_max (tile-relative) are read as that row.  Operands staged by LDS-DMA in swizzled 128-byte rows, double buffered in
+// smem (F32Tile<TS>::LDS_STAGE bytes); the lane offsets are tile-relative, so a matrix may be larger than 4 GiB.  Ends with a barrier:
+// the staging buffers are free for the caller.
+template <int TS>
+__device__ __forceinline__ void f32_tile(const float* __restrict__ a, int a_max, const float* __restrict__ b, int b_max, int D, char* smem,
+                                         f32x16_t (&acc)[F32Tile<TS>::NT32][F32Tile<TS>::NT32]) {
+    using G = F32Tile<TS>;
+    constexpr int NW = 4, INSTR = TS / 8 / NW;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    const int steps = D >> 5;
+    uint32_t offA[INSTR], offB[INSTR];
+    // rows are D fp32 = 2D 16-bit units wide for the byte arithmetic of the staging helpers
+    stage_offsets<TS, NW, false>(2 * D, 0, a_max, wave, lane, offA);
+    stage_offsets<TS, NW, false>(2 * D, 0, b_max, wave, lane, offB);
+    auto issue = [&](int t, int buf) {
+        char* la = smem + buf * G::STAGE;
+        char* lb = la + TS * 128;
+        stage_from<TS, NW>((const char*)a + (size_t)t * 128, offA, la, wave);
+        stage_from<TS, NW>((const char*)b + (size_t)t * 128, offB, lb, wave);
+    };
+    const int i = lane & 31, h = lane >> 5;
+#pragma unroll
+    for (int ai = 0; ai < G::NT32; ++ai)
+#pragma unroll
+        for (int bi = 0; bi < G::NT32; ++bi)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ai][bi][r] = 0.f;
+    auto compute = [&](int buf) {
+        const char* la = smem + buf * G::STAGE;
+        const char* lb = la + TS * 128;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            // lane (i, h) takes the 16-byte chunk 2t+h of its row: element u of it is k = 4(2t+h)+u for BOTH operands
+            f32x4 af[G::NT32], bf[G::NT32];
+#pragma unroll
+            for (int ai = 0; ai < G::NT32; ++ai) {
+                const int row = wm * G::WT + 32 * ai + i;
+                af[ai] = *(const f32x4*)(la + row * 128 + (swz(row, 2 * t + h) << 4));
+            }
+#pragma unroll
+            for (int bi = 0; bi < G::NT32; ++bi) {
+                const int row = wn * G::WT + 32 * bi + i;
+                bf[bi] = *(const f32x4*)(lb + row * 128 + (swz(row, 2 * t + h) << 4));
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+#pragma unroll
+                for (int ai = 0; ai < G::NT32; ++ai)
+#pragma unroll
+                    for (int bi = 0; bi < G::NT32; ++bi) acc[ai][bi] = mfma_f32(af[ai][u], bf[bi][u], acc[ai][bi]);
+        }
+    };
+    issue(0, 0);
+    __syncthreads();
+    int cur = 0;
+    for (int t = 0; t < steps - 1; ++t) {
+        issue(t + 1, cur ^ 1);
+        compute(cur);
+        __syncthreads();
+        cur ^= 1;
+    }
+    compute(cur);
+    __syncthreads();                                   // the staging buffers are free for the caller
+}
+
 }  // namespace gemmcore

@@ -33,9 +33,6 @@ struct SdmParams {
     float* dqn; float* dgn;                            // bwd: [P*N, D], [M, D] accumulators (zeroed by the caller)
 };
 
-typedef __attribute__((ext_vector_type(16))) float f32x16_t;
-__device__ __forceinline__ f32x16_t mfma_f32(float a, float b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
 // sum over the 32 lanes of this lane's half-wave (lanes 0-31 / 32-63): the MFMA column index lives on lane & 31
 __device__ __forceinline__ float half_sum(float v) {
 #pragma unroll
@@ -56,69 +53,11 @@ struct Geo {
     static constexpr int LDS_BWD = (DS_BYTES > LDS_STAGE ? DS_BYTES : LDS_STAGE) + 32 * TS;
 };
 
-// S tile: acc[a][b][reg] = q^[m] . g^[n],  m = wm*WT + 32a + (reg&3) + 8(reg>>2) + 4(lane>>5),  n = wn*WT + 32b + (lane&31)
+// S tile: acc[a][b][reg] = q^[m] . g^[n],  m = wm*WT + 32a + (reg&3) + 8(reg>>2) + 4(lane>>5),  n = wn*WT + 32b + (lane&31): gemm_core.h's
+// f32_tile on the rows m0.. of pair `row_lo`'s query side and the rows n0.. of the gallery side
 template <int TS>
-__device__ __forceinline__ void s_tile(const SdmParams& p, int row_lo, int row_hi, int m0, int n0, char* smem,
-                                       f32x16_t (&acc)[Geo<TS>::NT32][Geo<TS>::NT32]) {
-    using G = Geo<TS>;
-    constexpr int NW = 4, INSTR = TS / 8 / NW;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    const int steps = p.D >> 5;
-    uint32_t offA[INSTR], offB[INSTR];
-    // rows are D fp32 = 2D 16-bit units wide for the byte arithmetic of gemm_core's staging
-    stage_offsets<TS, NW, false>(2 * p.D, row_lo + m0, row_hi, wave, lane, offA);
-    stage_offsets<TS, NW, false>(2 * p.D, n0, p.M - 1, wave, lane, offB);
-    auto issue = [&](int t, int buf) {
-        char* la = smem + buf * G::STAGE;
-        char* lb = la + TS * 128;
-        stage_from<TS, NW>((const char*)p.qn + (size_t)t * 128, offA, la, wave);
-        stage_from<TS, NW>((const char*)p.gn + (size_t)t * 128, offB, lb, wave);
-    };
-    const int i = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int a = 0; a < G::NT32; ++a)
-#pragma unroll
-        for (int b = 0; b < G::NT32; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
-    auto compute = [&](int buf) {
-        const char* la = smem + buf * G::STAGE;
-        const char* lb = la + TS * 128;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            // lane (i, h) takes the 16-byte chunk 2t+h of its row: element u of it is k = 4(2t+h)+u for BOTH operands
-            f32x4 af[G::NT32], bf[G::NT32];
-#pragma unroll
-            for (int a = 0; a < G::NT32; ++a) {
-                const int row = wm * G::WT + 32 * a + i;
-                af[a] = *(const f32x4*)(la + row * 128 + (swz(row, 2 * t + h) << 4));
-            }
-#pragma unroll
-            for (int b = 0; b < G::NT32; ++b) {
-                const int row = wn * G::WT + 32 * b + i;
-                bf[b] = *(const f32x4*)(lb + row * 128 + (swz(row, 2 * t + h) << 4));
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int a = 0; a < G::NT32; ++a)
-#pragma unroll
-                    for (int b = 0; b < G::NT32; ++b) acc[a][b] = mfma_f32(af[a][u], bf[b][u], acc[a][b]);
-        }
-    };
-    issue(0, 0);
-    __syncthreads();
-    int cur = 0;
-    for (int t = 0; t < steps - 1; ++t) {
-        issue(t + 1, cur ^ 1);
-        compute(cur);
-        __syncthreads();
-        cur ^= 1;
-    }
-    compute(cur);
-    __syncthreads();                                   // the staging buffers are free for the epilogue's scratch
+__device__ __forceinline__ void s_tile(const SdmParams& p, int row_lo, int m0, int n0, char* smem, f32x16_t (&acc)[Geo<TS>::NT32][Geo<TS>::NT32]) {
+    f32_tile<TS>(p.qn + (size_t)(row_lo + m0) * p.D, p.N - 1 - m0, p.gn + (size_t)n0 * p.D, p.M - 1 - n0, p.D, smem, acc);
 }
 
 // tile -> (pair, row tile, column tile)
@@ -140,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void sdm_fwd_tile_kernel(const SdmParams p)
     tile_of(p, pair, tm, tn);
     const int row_lo = pair * p.N, m0 = tm * TS, n0 = tn * TS;
     f32x16_t acc[G::NT32][G::NT32];
-    s_tile<TS>(p, row_lo, row_lo + p.N - 1, m0, n0, smem, acc);
+    s_tile<TS>(p, row_lo, m0, n0, smem, acc);
 
     // scratch in the (now idle) staging area: labels / validity of the tile's rows and columns, then the cross-wave sums
     int64_t* l_ql = (int64_t*)smem; int64_t* l_gl = l_ql + TS;
@@ -338,7 +277,7 @@ __global__ __launch_bounds__(256, TS == 128 ? 1 : 2) void sdm_bwd_tile_kernel(co
     if (!(cnt_r > 0.f)) return;                          // the pair contributes nothing (uniform over the workgroup)
     const int row_lo = pair * p.N, m0 = tm * TS, n0 = tn * TS;
     f32x16_t acc[G::NT32][G::NT32];
-    s_tile<TS>(p, row_lo, row_lo + p.N - 1, m0, n0, smem, acc);
+    s_tile<TS>(p, row_lo, m0, n0, smem, acc);
 
     float* ds = (float*)smem;                           // [TS][TS + 1], over the (idle) staging buffers
     int64_t* l_ql = (int64_t*)(smem + G::LDS_BWD - 32 * TS); int64_t* l_gl = l_ql + TS;

@@ -473,6 +473,151 @@ def center_loss(x, labels, centers, valid=None, alpha=0.5, update=True):
 
 
 # ----------------------------------------------------------------------------------------------------------------
+CLUSTER_NCE_MODES = ('mean', 'hard')
+
+
+def cluster_nce_args(who, temperature, momentum, mode):
+    """The checked (temperature, momentum, mode) of the cluster-contrast loss."""
+    if mode not in CLUSTER_NCE_MODES:
+        raise ValueError(f"{who}: mode must be 'mean' or 'hard', not {mode!r}")
+    temperature, momentum = float(temperature), float(momentum)
+    if not (temperature > 0 and math.isfinite(temperature)):
+        raise ValueError(f'{who}: temperature must be > 0 and finite, not {temperature}')
+    if not 0 <= momentum <= 1:
+        raise ValueError(f'{who}: momentum must be in [0, 1], not {momentum}')
+    return temperature, momentum, mode
+
+
+class ClusterMemory:
+    """The memory of cluster_nce (SpCL's cluster-level memory, Ge et al. 2020; Cluster-Contrast, Dai et al. 2021; csrc/cluster_nce.hip):
+    one unit centroid per cluster of a pseudo-labelled set, ``centroids`` f32 [num_clusters, dim], moved by the momentum update only --
+    not by the optimizer.  A plain tensor, not a parameter or buffer: ``state()`` / ``load_state()`` carry it through a checkpoint
+    (``cluster_memory_state_dict``).  Cluster numbers change at every re-clustering: build a new memory from the features with
+    ``from_labels`` / ``from_clustering``.  It may be constructed on the CPU to carry a state; the kernels need the device."""
+
+    def __init__(self, num_clusters, dim, device='cuda'):
+        if not (num_clusters >= 1 and dim % 32 == 0 and 32 <= dim <= 1024 and num_clusters * dim < 2 ** 31):
+            raise ValueError('ClusterMemory: num_clusters >= 1, dim a multiple of 32 in 32..1024, num_clusters * dim < 2^31')
+        self.num_clusters, self.dim = int(num_clusters), int(dim)
+        self.centroids = torch.zeros(self.num_clusters, self.dim, dtype=torch.float32, device=torch.device(device))
+
+    @classmethod
+    def from_labels(cls, feats, labels):
+        """The memory of the pseudo-labelled rows ``feats`` [n, D] (device, fp32): K = max label + 1, centroid k = the normalised fp32
+        mean of the rows with label k, summed in ascending row index (grouped by a stable sort here, one wave per cluster on the
+        device).  Labels of -1 (DBSCAN noise) are skipped; a cluster number without a row raises."""
+        _need_device('ClusterMemory.from_labels', feats, labels)
+        if feats.dim() != 2 or labels.shape != feats.shape[:1]:
+            raise ValueError('ClusterMemory.from_labels: feats [n, D], labels [n]')
+        labels = labels.long()
+        if labels.numel() == 0 or int(labels.max()) < 0:
+            raise ValueError('ClusterMemory.from_labels: no row has a cluster')
+        if int(labels.min()) < -1:
+            raise ValueError('ClusterMemory.from_labels: labels are cluster numbers >= 0, or -1 for a row without one')
+        K = int(labels.max()) + 1
+        counts = torch.bincount(labels[labels >= 0], minlength=K)
+        if bool((counts == 0).any()):
+            raise ValueError(f'ClusterMemory.from_labels: cluster {int((counts == 0).nonzero()[0])} has no row (cluster numbers must be 0..K-1 without gaps)')
+        mem = cls(K, feats.shape[1], feats.device)
+        order = torch.sort(labels, stable=True).indices[int((labels < 0).sum()):].contiguous()
+        offsets = torch.cat([counts.new_zeros(1), counts.cumsum(0)]).contiguous()
+        feats = feats.float()
+        if feats.stride(1) != 1 or feats.stride(0) % 4 or feats.data_ptr() % 16:
+            feats = feats.contiguous()
+        ops.cluster_centroids(feats, order, offsets, mem.centroids)
+        return mem
+
+    @classmethod
+    def from_clustering(cls, feats, clustering):
+        """The memory of a ``cluster.Clustering`` of the rows ``feats`` (jaccard_dbscan's result): its noise rows are skipped."""
+        return cls.from_labels(feats, clustering.labels.to(feats.device))
+
+    def reset(self):
+        """Zeroes the table in place (a device fill: a captured graph that holds it stays valid)."""
+        self.centroids.zero_()
+
+    def state(self):
+        return {'centroids': self.centroids.detach().cpu().clone()}
+
+    def load_state(self, state):
+        """Copies ``state['centroids']`` into the table in place; a table of another shape is refused."""
+        c = state['centroids']
+        if tuple(c.shape) != (self.num_clusters, self.dim):
+            raise ValueError(f'ClusterMemory: the state holds centroids {tuple(c.shape)}, this memory is [{self.num_clusters}, {self.dim}]')
+        self.centroids.copy_(c.to(torch.float32))
+
+
+class ClusterNCEFn(torch.autograd.Function):
+    """(loss, n_used) of the cluster-contrast loss of x [S, N, D] (S sides stacked, ``labels`` [N] shared) against ``memory``
+    (csrc/cluster_nce.hip; the reference has no such loss): the mean over the used rows of lse_c(x^ . C_c / tau) - x^ . C_y / tau, a row
+    used when it is valid and its label lies in the memory.  With ``update`` the centroids the forward used are then moved by momentum
+    (``mode`` 'mean' | 'hard').  The centroids are constants of the loss: the gradient reaches x only, from what the forward left in
+    its workspace (the memory may have moved before the backward runs).  Without gradients the table is streamed once and nothing is
+    kept.  n_used is a float tensor; nothing is read back to the host.  ``rows_out``: an optional trailing dict that receives COPIES of
+    ``row_loss`` and ``target_cos`` (cluster_nce); the call the model makes is ``apply(x, labels, valid, memory, tau, momentum, mode,
+    update)``."""
+    @staticmethod
+    def forward(ctx, x, labels, valid, memory, tau: float, momentum: float, mode: str, update: bool, rows_out=None):
+        (S, N, D), dev = x.shape, x.device
+        if D != memory.dim:
+            raise _lib.ReidHipError(f'ClusterNCEFn: the memory holds centroids of D={memory.dim}, the batch has D={D}')
+        with_grad = bool(ctx.needs_input_grad[0])
+        x2 = x.reshape(S * N, D).contiguous().float()
+        labels = labels.contiguous()
+        vv = None if valid is None else valid.reshape(S * N).contiguous()
+        ws = torch.empty(ops.cluster_nce_ws_floats(S, N, D, memory.num_clusters), device=dev)
+        row_loss = torch.empty(S * N, device=dev); tcos = torch.empty(S * N, device=dev); res = torch.empty(2, device=dev)
+        ops.cluster_nce_fwd(x2, labels, vv, memory.centroids, tau, with_grad, ws, row_loss, tcos, res, S=S)
+        if update:
+            ops.cluster_nce_update(labels, vv, row_loss, tcos, ws, memory.centroids, momentum, mode, S=S)
+        ctx.save_for_backward(ws, res)
+        ctx.shape, ctx.with_grad = (S, N, D), with_grad
+        loss, n_used = res[0], res[1]
+        ctx.mark_non_differentiable(n_used)
+        if rows_out is not None:
+            rows_out.update(row_loss=row_loss.view(S, N).clone(), target_cos=tcos.view(S, N).clone())
+        return loss, n_used
+
+    @staticmethod
+    def backward(ctx, dloss, _dn):
+        ws, res = ctx.saved_tensors
+        S, N, D = ctx.shape
+        dx = torch.empty(S * N, D, device=ws.device)
+        ops.cluster_nce_bwd(ws, res, dloss.reshape(1).float().contiguous(), dx, S=S)
+        return dx.view(S, N, D), None, None, None, None, None, None, None, None
+
+
+def cluster_nce(x, labels, memory, valid=None, temperature=0.05, momentum=0.1, mode='mean', update=True):
+    """Cluster-contrast loss (ClusterNCE) for users with their own loop: ``x`` [S, N, D] (S sides stacked; [N, D] = one side) of the N
+    instances with pseudo-labels ``labels`` [N], ``memory`` a ClusterMemory(K, D).  A row is used when it is valid (``valid`` [S, N] or
+    [N] for one side: optional bool / uint8) and its label lies in 0..K-1 -- a DBSCAN noise label of -1 is simply unused;
+    loss = mean over the used rows of lse_c(x^ . C_c / temperature) - x^ . C_y / temperature, 0 when no row is used.  With ``update``
+    (and gradients enabled) the centroids of the labels in the batch then move: 'mean' blends c <- m c + (1 - m) x^, renormalised, over
+    the label's rows in ascending row order; 'hard' blends once with the row of the smallest x^ . C_y; rows with a non-finite loss
+    are left out; ``update=False`` leaves the memory as it is.  Returns (loss, LazyCount(n_used), rows) with rows = {'row_loss',
+    'target_cos'} [S, N] (copies); the loss carries the gradient to ``x``."""
+    _need_device('cluster_nce', x, labels, valid)
+    if not isinstance(memory, ClusterMemory):
+        raise TypeError('cluster_nce: memory must be a ClusterMemory')
+    if not memory.centroids.is_cuda:
+        raise _lib.ReidHipError('cluster_nce needs the memory on the device (there is no CPU path)')
+    flat = x.dim() == 2
+    if flat:
+        x = x.unsqueeze(0)
+    if x.dim() != 3 or labels.shape != x.shape[1:2]:
+        raise ValueError('cluster_nce: x [S, N, D] or [N, D], labels [N]')
+    if valid is not None:
+        valid = valid.to(torch.uint8).reshape(x.shape[0], x.shape[1]).contiguous()
+    temperature, momentum, mode = cluster_nce_args('cluster_nce', temperature, momentum, mode)
+    rows = {}
+    loss, n_used = ClusterNCEFn.apply(x, labels.long(), valid, memory, temperature, momentum, mode,
+                                      bool(update and torch.is_grad_enabled()), rows)
+    if flat:
+        rows = {k: v[0] for k, v in rows.items()}
+    return loss, LazyCount(n_used), rows
+
+
+# ----------------------------------------------------------------------------------------------------------------
 MARGIN_KINDS = ('cosine', 'cosface', 'arcface', 'circle')
 # (scale, margin) a kind takes when the caller leaves them open (TrainingConfig.id_scale / id_margin = None)
 MARGIN_DEFAULTS = {'cosine': (30.0, 0.0), 'cosface': (30.0, 0.35), 'arcface': (30.0, 0.5), 'circle': (64.0, 0.35)}

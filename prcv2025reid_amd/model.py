@@ -38,8 +38,8 @@ from .config import TrainingConfig, arch_of
 from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CosineLinearFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn, NanToNumFn,
                    SmallAttnFn)
-from .losses import (CenterLossFn, ClassCenters, CrossBatchMemory, CrossEntropyLSFn, CrossTripletFn, HcTripletFn, LazyCount, MarginCEFn,
-                     SDMFn, TripletHardFn, XbmTripletFn, margin_args)
+from .losses import (CenterLossFn, ClassCenters, ClusterMemory, ClusterNCEFn, CrossBatchMemory, CrossEntropyLSFn, CrossTripletFn, HcTripletFn,
+                     LazyCount, MarginCEFn, SDMFn, TripletHardFn, XbmTripletFn, cluster_nce_args, margin_args)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -91,6 +91,7 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self.xbm_memory = None               # a CrossBatchMemory made on first use; a plain attribute: not in state_dict()
         self._xbm_sides = None               # the modality names of its sides 1 .. P
         self.centers = None                  # the ClassCenters of the center loss, made on first use; a plain attribute: not in state_dict()
+        self.cluster_memory = None           # the ClusterMemory of the cluster-contrast loss (set_cluster_memory); not in state_dict() either
         self.num_classes = None
         self.bn_neck = None
         self._ref: "OrderedDict[str, nn.Parameter]" = OrderedDict()
@@ -161,6 +162,13 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
                 raise ValueError(f"TrainingConfig.id_head must be 'linear', 'cosine', 'cosface', 'arcface' or 'circle', not {self.id_head!r}")
             self.id_head, self.id_scale, self.id_margin = margin_args('TrainingConfig.id_head', self.id_head, getattr(config, 'id_scale', None),
                                                                       getattr(config, 'id_margin', None))
+        # cluster-contrast memory loss (not in the reference; csrc/cluster_nce.hip): read beside id_head, LOSS_FIELDS stays what it was
+        for name in ('cluster_nce_weight', 'cluster_nce_temperature', 'cluster_nce_momentum', 'cluster_nce_mode', 'cluster_nce_source'):
+            setattr(self, name, getattr(config, name, getattr(defaults, name)))
+        self.cluster_nce_temperature, self.cluster_nce_momentum, self.cluster_nce_mode = cluster_nce_args(
+            'TrainingConfig.cluster_nce', self.cluster_nce_temperature, self.cluster_nce_momentum, self.cluster_nce_mode)
+        if self.cluster_nce_source not in ('bn', 'modalities'):
+            raise ValueError(f"TrainingConfig.cluster_nce_source must be 'bn' or 'modalities', not {self.cluster_nce_source!r}")
 
     # ------------------------------------------------------------------ parameter plumbing
     def _add_param(self, ref_name: str, value: torch.Tensor, buffer: bool = False):
@@ -632,6 +640,11 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
                 out['total_loss'] = out['total_loss'] + weight * term[0]
                 out[name + '_loss'] = term[0]
                 out[count_key] = LazyCount(term[1])
+        if self.cluster_nce_weight > 0:      # behind the AUX_TERMS (whose five names are pinned): the same shape, its own two keys last
+            term = self._cluster_nce_term(outputs, labels, cent)
+            out['total_loss'] = out['total_loss'] + self.cluster_nce_weight * term[0]
+            out['cluster_nce_loss'] = term[0]
+            out['cluster_nce_valid_cnt'] = LazyCount(term[1])
         return out
 
     # The auxiliary terms (AUX_TERMS; none is in the reference): (loss, count) of one term from compute_loss's outputs, labels, cached
@@ -692,6 +705,41 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         if self.centers is None:
             self.centers = ClassCenters(self.num_classes, x.shape[2], x.device)
         return CenterLossFn.apply(x, labels, xv, self.centers, float(self.center_alpha), bool(self.training and torch.is_grad_enabled()))
+
+    def _cluster_nce_term(self, outputs, labels, cent):
+        """Cluster-contrast memory loss (csrc/cluster_nce.hip) of the step's pseudo-labels (cluster numbers; -1 = no cluster: unused)
+        against model.cluster_memory: 'bn' = the retrieval feature behind the BN-neck with the CE branch's validity; 'modalities' = the
+        raw feature of every modality that has a mask (vis first), stacked as _center_term stacks them, against the ONE memory.  The
+        centroids move once per forward in training with gradients; eval() and no_grad() leave them alone."""
+        if self.cluster_memory is None:
+            raise ValueError('cluster_nce_weight > 0 needs a cluster memory: build one with ClusterMemory.from_clustering(features, '
+                             'clustering) or ClusterMemory.from_labels and install it with model.set_cluster_memory(memory)')
+        if self.cluster_nce_source == 'bn':
+            if 'bn_features' not in outputs:
+                raise ValueError("cluster_nce_source='bn' needs bn_features: call set_num_classes first")
+            x, xv = outputs['bn_features'].unsqueeze(0), cent['valid']
+        else:
+            raw, fm = outputs.get('raw_modality_features', {}), outputs.get('feature_masks', {})
+            cm = [m for m in raw if m in fm]
+            cm = [m for m in cm if m == 'vis'] + [m for m in cm if m != 'vis']
+            if not cm:
+                raise ValueError("cluster_nce_source='modalities' needs raw_modality_features with feature_masks")
+            x = torch.stack([raw[m] for m in cm], dim=0)                                     # [S, B, D]
+            xv = cent.get(('cv', tuple(cm)))
+            if xv is None:
+                xv = cent[('cv', tuple(cm))] = torch.stack([(fm[m].to(x.device) > 0) for m in cm], dim=0).to(torch.uint8).contiguous()
+        return ClusterNCEFn.apply(x, labels, xv, self.cluster_memory, float(self.cluster_nce_temperature), float(self.cluster_nce_momentum),
+                                  self.cluster_nce_mode, bool(self.training and torch.is_grad_enabled()))
+
+    def set_cluster_memory(self, memory):
+        """Installs the ClusterMemory the cluster-contrast term runs against (None removes it): after every re-clustering, a new one
+        from the features.  A captured graph holds the old table: capture again after this."""
+        if memory is not None:
+            if not isinstance(memory, ClusterMemory):
+                raise TypeError('set_cluster_memory: a ClusterMemory, or None')
+            if not memory.centroids.is_cuda:
+                raise _lib.ReidHipError('set_cluster_memory needs the memory on the device (there is no CPU path)')
+        self.cluster_memory = memory
 
     def reset_centers(self):
         """Zeroes the class centres of the center loss in place (a device fill: a captured graph that holds the table stays valid)."""

@@ -593,6 +593,80 @@ def center_bwd(ws, result, dloss, dx, S=1):
     check(lib().reid_center_bwd(S, N, D, ptr(ws), ptr(result), ptr(dloss), ptr(dx), dx.stride(0), stream_ptr()))
 
 
+def cluster_nce_ws_floats(S, N, D, K):
+    return _ws_floats(lib().reid_cluster_nce_ws_floats, S, N, D, K)
+
+
+def cluster_nce_plan(R, K, D):
+    """(row tile, class tile, splits, class tiles per split) of the forward of R rows against K centroids of D columns: the rule
+    depends on the shape only.  Nothing is launched."""
+    plan = (C.c_int32 * 4)()
+    check(lib().reid_cluster_nce_plan(R, K, D, C.cast(plan, C.c_void_p)))
+    return tuple(plan)
+
+
+def _cluster_table(who, table, D=None):
+    """table f32 [K, D], contiguous; a table of another D than the batch's is refused.  Returns its D."""
+    text = 'table [K, D], contiguous'
+    _f32_matrices(who, text, ('table', table, (None, None)))
+    _vectors(who, text, ('table', table, f32, 0))
+    if D is not None and table.shape[1] != D:
+        raise L.ReidHipError(f'{who}: the memory holds centroids of D={table.shape[1]}, the batch has D={D}')
+    return table.shape[1]
+
+
+def cluster_nce_fwd(x, labels, valid, table, tau, with_grad, ws, row_loss, target_cos, result, S=1):
+    """ClusterNCE of x [S*N, D] (S sides stacked, labels [N] shared) against the unit centroids table [K, D]: row_loss / target_cos
+    [S*N] = lse - l_y and x^ . C_y of the used rows (others 0), result f32 [2] = (mean row loss over the used rows, n_used).
+    ``with_grad``: the table is streamed a second time and ws keeps what cluster_nce_bwd needs; ws also holds x^ for cluster_nce_update."""
+    N, D = _stacked_rows('cluster_nce_fwd', 'x [S*N, D]', 'x', x, S)
+    _center_batch('cluster_nce_fwd', labels, valid, S, N)
+    _cluster_table('cluster_nce_fwd', table, D)
+    K = table.shape[0]
+    _vectors('cluster_nce_fwd', 'ws [cluster_nce_ws_floats(S, N, D, K)], row_loss / target_cos [S*N], result [2], all contiguous',
+             ('ws', ws, f32, cluster_nce_ws_floats(S, N, D, K)), ('row_loss', row_loss, f32, S * N), ('target_cos', target_cos, f32, S * N),
+             ('result', result, f32, 2))
+    check(lib().reid_cluster_nce_fwd(ptr(x), x.stride(0), ptr(labels), ptr(valid), S, N, D, ptr(table), K, float(tau), int(bool(with_grad)),
+                                     ptr(ws), ptr(row_loss), ptr(target_cos), ptr(result), stream_ptr()))
+
+
+def cluster_nce_update(labels, valid, row_loss, target_cos, ws, table, momentum, mode='mean', S=1):
+    """The momentum update of the centroids cluster_nce_fwd has just used, in place (one launch, no atomics): mode 'mean' blends a
+    label's contributing rows in ascending row order, 'hard' its row of the smallest target cosine; absent labels keep their bits."""
+    if mode not in L.CLUSTER_NCE_MODES:
+        raise ValueError(f"cluster_nce_update: mode must be 'mean' or 'hard', not {mode!r}")
+    N = labels.numel()
+    _center_batch('cluster_nce_update', labels, valid, S, N)
+    D = _cluster_table('cluster_nce_update', table)
+    _vectors('cluster_nce_update', 'ws [cluster_nce_ws_floats(S, N, D, K)], row_loss / target_cos [S*N], all contiguous',
+             ('ws', ws, f32, cluster_nce_ws_floats(S, N, D, table.shape[0])), ('row_loss', row_loss, f32, S * N),
+             ('target_cos', target_cos, f32, S * N))
+    check(lib().reid_cluster_nce_update(ptr(labels), ptr(valid), S, N, D, ptr(row_loss), ptr(target_cos), ptr(ws), ptr(table), table.shape[0],
+                                        float(momentum), L.CLUSTER_NCE_MODES[mode], stream_ptr()))
+
+
+def cluster_nce_bwd(ws, result, dloss, dx, S=1):
+    """dx [S*N, D] = dloss / max(1, n_used) * H from what cluster_nce_fwd(with_grad=True) saved (overwritten, one launch) -- the table
+    itself is not read; dloss a device scalar."""
+    N, D = _stacked_rows('cluster_nce_bwd', 'dx [S*N, D]', 'dx', dx, S)
+    _vectors('cluster_nce_bwd', 'ws [cluster_nce_ws_floats(S, N, D, K)], result [2], dloss [1], all contiguous',
+             ('ws', ws, f32, cluster_nce_ws_floats(S, N, D, 1)), ('result', result, f32, 2), ('dloss', dloss, f32, 1))
+    check(lib().reid_cluster_nce_bwd(S, N, D, ptr(ws), ptr(result), ptr(dloss), ptr(dx), dx.stride(0), stream_ptr()))
+
+
+def cluster_centroids(feats, order, offsets, table):
+    """table [K, D] = the normalised fp32 mean of the rows order[offsets[k] : offsets[k + 1]] of feats [rows, D], summed in that order
+    (order i64: row indices grouped by label, offsets i64 [K + 1]); one launch, one wave per cluster."""
+    text = 'feats [rows, D], table [K, D] fp32; order [n], offsets [K + 1] int64'
+    _f32_matrices('cluster_centroids', text, ('feats', feats, (None, None)))
+    D = _cluster_table('cluster_centroids', table, feats.shape[1])
+    K = table.shape[0]
+    _vectors('cluster_centroids', text, ('order', order, i64, 0), ('offsets', offsets, i64, K + 1))
+    if offsets.numel() != K + 1:
+        raise ValueError(f'cluster_centroids: {text}')
+    check(lib().reid_cluster_centroids(ptr(feats), feats.stride(0), feats.shape[0], ptr(order), ptr(offsets), K, D, ptr(table), stream_ptr()))
+
+
 def cos_logits_fwd(x, W, scale, eps, rx, rw, logits):
     """logits [B, C] = scale * cos(x_b, W_c) of x [B, D], W [C, D] (fp32, any leading dimension); rx f64 [B], rw f64 [C] receive the
     inverse norms 1 / max(|row|, eps) and are kept for the backward.  Two launches."""
