@@ -607,6 +607,52 @@ int reid_cluster_centroids(const float* feats, int32_t ldf, int64_t rows, const 
                            int32_t D, float* table, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Cross-modal Smooth-AP ranking loss (Brown et al., "Smooth-AP: Smoothing the Path Towards Large-Scale Image Retrieval", ECCV 2020;
+ * the reference has no such loss; csrc/smooth_ap.hip): the differentiable form of the AP the evaluator
+ * reports, in the batch or against the slots of a cross-batch memory.  All fp32 in and out.
+ *   q [P*N, D] (ldq), g [Mg, D] (ldg), q_label [N], g_label [Mg] int64, q_valid [P*N] / g_valid [Mg] uint8 or NULL (all valid): as
+ *   for reid_cross_triplet_fwd.  Every direction of every pair p is one set of ranking problems against a GALLERY given as (rows, ld,
+ *   labels, validity bytes or NULL, count):
+ *     q->g: the valid rows of q[p] are the anchors, gallery A = (ga, ldga, ga_label [Ga], ga_valid [Ga], Ga), shared by the pairs;
+ *     g->q: the valid rows of g are the anchors, gallery B of pair p = rows [p*Gb, (p+1)*Gb) of gb (ldgb), gb_label [Gb] shared,
+ *           gb_valid [P*Gb].
+ *   gallery_grad = 1, the batch form: the galleries ARE the batch (ga = g, gb = q, with their labels, validity and counts: anything
+ *   else is refused) and receive a gradient.  gallery_grad = 0, the ring form: gallery A = side 0 of a memory filed by
+ *   reid_xbm_enqueue, gallery B = its sides 1 .. P; their rows are constants, taken as they are.
+ *   Score of anchor a and gallery row j: s_j = x^_a . g^_j with x^ = x / max(|x|, eps) (normalize = 0: the rows as they are; ring rows
+ *   are always taken as they are) -- the dot product and the norms in fp64 from the fp32 inputs, rounded to fp32 ONCE.  No
+ *   self-exclusion.  P_a = the valid gallery rows with the anchor's label; a is ACTIVE when it is valid, P_a is not empty and a
+ *   valid gallery row lies outside it.  With sigma_ij = sigma((s_j - s_i) / tau) over the valid gallery rows:
+ *     R_i = 1 + sum_{j != i} sigma_ij,  R+_i = 1 + sum_{j in P_a, j != i} sigma_ij,  AP_a = (1 / |P_a|) sum_{i in P_a} R+_i / R_i,
+ *     L_dir = mean over the active anchors of (1 - AP_a) (0 when there is none),  L_p = 0.5 * (L_qg + L_gq).
+ *   sigma is evaluated in fp32 as e = exp(-|d|): d >= 0 ? 1 / (1 + e) : e / (1 + e).  Every sum has a fixed order (over j: per-lane
+ *   ascending, then a butterfly across the lanes; over i, anchors and pairs: ascending); no atomics; two runs give the same bits.
+ *   Outputs: q_ap [P*N], g_ap [P*Mg] = AP_a (-1: not active), q_npos / g_npos int32 = |P_a| (0 for an invalid anchor), result
+ *   [P, 4] = (L_p, flag_p, n_qg, n_gq) with flag_p = 1 when either direction has an active anchor; the means are fp64 sums in
+ *   ascending row order, rounded once.  None is read back.
+ *   ws: reid_smooth_ap_ws_floats(P, N, Mg, D, Ga, Gb, with_grad) floats (a negative count = bad shape).  with_grad = 0 stops after
+ *   result.  with_grad = 1 also forms d(1 - AP_a)/ds in closed form, gathers it into the unit-space gradients of the anchors (and, in
+ *   the batch form, of the gallery rows), projects them through the normalisation as reid_cross_triplet_bwd does (G / eps where
+ *   |x| < eps) and leaves Hq [P*N, D], Hg [P, Mg, D] at the head of ws: everything the backward needs, so an enqueue or a second
+ *   forward into another ws between the forward and the backward does not change the gradient.
+ *   reid_smooth_ap_bwd: dq[p*N + i] = gscale[p] * Hq[p*N + i], dg[j] = sum over p ascending of gscale[p] * Hg[p, j]; dq [P*N, D]
+ *   (lddq) and dg [Mg, D] (lddg) are OVERWRITTEN (invalid rows with zeros, padding columns untouched); ws must come from a forward
+ *   with with_grad = 1.
+ * Requirements: those of reid_cross_triplet_fwd / _bwd for P, N, Mg, D, the leading dimensions and eps; 1 <= Ga, Gb <= 8192, ldga /
+ * ldgb multiples of 4 and >= D, tau finite and > 0, normalize / gallery_grad / with_grad 0 or 1, q, g, ga, gb, ws, dq, dg 16-byte
+ * aligned.  Anything else: REID_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int64_t reid_smooth_ap_ws_floats(int32_t P, int32_t N, int32_t Mg, int32_t D, int32_t Ga, int32_t Gb, int32_t with_grad);
+int reid_smooth_ap_fwd(const float* q, int32_t ldq, const float* g, int32_t ldg, const int64_t* q_label, const int64_t* g_label,
+                       const uint8_t* q_valid, const uint8_t* g_valid, int32_t P, int32_t N, int32_t Mg, int32_t D, float tau,
+                       int32_t normalize, float eps, const float* ga, int32_t ldga, const int64_t* ga_label, const uint8_t* ga_valid,
+                       int32_t Ga, const float* gb, int32_t ldgb, const int64_t* gb_label, const uint8_t* gb_valid, int32_t Gb,
+                       int32_t gallery_grad, int32_t with_grad, float* q_ap, int32_t* q_npos, float* g_ap, int32_t* g_npos, float* ws,
+                       float* result, void* stream);
+int reid_smooth_ap_bwd(const uint8_t* q_valid, const uint8_t* g_valid, int32_t P, int32_t N, int32_t Mg, int32_t D, const float* ws,
+                       const float* gscale, float* dq, int32_t lddq, float* dg, int32_t lddg, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Retrieval (train.py:499 + :463; tools/eval_mm_protocol.py:50-53,401-423,622-625):
  *   sim = Q . G^T on L2-normalised rows, per-query top-k in (score desc, index asc) order.
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;

@@ -123,6 +123,10 @@ SIGNATURES = {
     'reid_cluster_nce_update': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _F, _I, _P]),
     'reid_cluster_nce_bwd': (_I, [_I, _I, _I, _P, _P, _P, _P, _I, _P]),
     'reid_cluster_centroids': (_I, [_P, _I, _I64, _P, _P, _I, _I, _P, _P]),
+    'reid_smooth_ap_ws_floats': (_I64, [_I, _I, _I, _I, _I, _I, _I]),
+    'reid_smooth_ap_fwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I,
+                                _P, _P, _P, _P, _P, _P, _P]),
+    'reid_smooth_ap_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P]),
     'reid_topk_ws_bytes': (_I64, [_I, _I, _I]),
     'reid_topk_scan_ok': (_I, [_I, _I, _I, _I]),
     'reid_cosine_topk': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

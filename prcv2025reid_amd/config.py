@@ -116,6 +116,13 @@ class TrainingConfig:
     cluster_nce_momentum: float = 0.1                # c <- m c + (1 - m) x^, Cluster-Contrast's m
     cluster_nce_mode: str = 'mean'                   # 'mean': every row of a cluster, in row order; 'hard': its row of the smallest cosine
     cluster_nce_source: str = 'bn'                   # 'bn': the retrieval feature behind the BN-neck; 'modalities': every modality's raw feature
+    # nor these: cross-modal Smooth-AP ranking loss (Brown et al., ECCV 2020) of every non-vis modality against vis, both directions, on
+    # the stack the SDM branch uses; smooth_ap_size > 0 ranks a ring of that many vis / modality rows per side instead of the batch
+    smooth_ap_weight: float = 0.0
+    smooth_ap_temperature: float = 0.01              # the paper's
+    smooth_ap_size: int = 0                          # 0: in-batch; otherwise ring slots per side, batch size .. 8192
+    smooth_ap_normalize: bool = True
+    smooth_ap_start_epoch: int = 0
     sdm_semantic_dim: int = 512
     sdm_num_heads: int = 8
     sdm_dropout: float = 0.1   # not a reference config field: hard-coded in SemanticDisentanglementModule (models/model.py:35,43)

@@ -1,5 +1,6 @@
 """Autograd boundaries and public functions of the loss kernels: label-smoothed CE, SDM loss, batch-hard triplet loss, cross-modal
-batch-hard triplet loss, hetero-center triplet loss, cross-batch memory (XBM), center loss, margin CE of the cosine-margin heads.
+batch-hard triplet loss, hetero-center triplet loss, cross-batch memory (XBM), cross-modal Smooth-AP (in the batch or over a ring), center
+loss, cluster-contrast memory loss, margin CE of the cosine-margin heads.
 
 Reference: compute_loss models/model.py:512-659; sdm_loss_stable models/sdm_loss.py:13-149 (the reference has CE and SDM only).  All
 arithmetic is in libreid_hip.so (fp32); torch only carries the tensors.  The two-sided losses (one stack of query modalities against
@@ -376,6 +377,104 @@ def xbm_cross_triplet(q, g, labels, memory, q_valid=None, g_valid=None, margin=0
     'g_idx_p', 'g_idx_n'} [P, N] (indices are slot numbers, -1 = inactive) plus 'n_active' [P, 2]; the losses carry the gradient to
     ``q`` and ``g``."""
     return _two_sided_loss('xbm_cross_triplet', XbmTripletFn, q, g, (labels,), q_valid, g_valid, memory, margin, bool(normalize), bool(enqueue))
+
+
+def smooth_ap_temperature(who, temperature):
+    """The checked temperature of the Smooth-AP loss."""
+    temperature = float(temperature)
+    if not (temperature > 0 and math.isfinite(temperature)):
+        raise ValueError(f'{who}: temperature must be > 0 and finite, not {temperature}')
+    return temperature
+
+
+def _check_ring(who, memory, P, N, Mg, D, enqueue):
+    """A CrossBatchMemory against the batch q [P, N, D], g [Mg, D] of the ring forms."""
+    if Mg != N or P + 1 != memory.sides:
+        raise ValueError(f'{who}: q [P, N, D] and g [N, D] with P + 1 = {memory.sides} sides of the memory')
+    if enqueue and N > memory.capacity:
+        raise ValueError(f'{who}: a batch of N={N} rows does not fit a memory of {memory.capacity} slots')
+    if D != memory.dim:
+        raise _lib.ReidHipError(f'{who}: the memory holds rows of D={memory.dim}, the batch has D={D}')
+
+
+class SmoothAPFn(torch.autograd.Function):
+    """(loss [P], flag [P], n_active [P, 2]) of the cross-modal Smooth-AP ranking loss between P stacked modality feature sets
+    q [P, N, D] and the vis features g [Mg, D] (csrc/smooth_ap.hip; the reference has no such loss): every valid
+    q row of pair p ranks a gallery by cosine and so does every valid g row; L_p = 0.5 * (mean of 1 - AP over the active q anchors +
+    the same over the active g anchors), AP in Brown et al.'s sigmoid form at temperature ``tau``.  ``memory`` None: the galleries are
+    g and pair p's q rows and receive a gradient.  ``memory`` a CrossBatchMemory: with ``enqueue`` the batch is first filed into it
+    (reid_xbm_enqueue, unchanged), then the q rows rank the valid slots of side 0 and the g rows those of side p + 1; the slots are
+    constants, and the forward leaves the finished gradients in its workspace, so later enqueues cannot change a pending backward.
+    ``with_grad`` False (or no input that requires a gradient): the gradient part of the forward is skipped.  n_active = (q->g, g->q)
+    active anchors as floats; nothing is read back to the host.  ``rows_out``: an optional trailing dict that receives COPIES of
+    ``q_ap``, ``g_ap`` (-1 = inactive), ``q_npos``, ``g_npos``; the call the model makes is
+    ``apply(q, g, q_label, g_label, q_valid, g_valid, memory, tau, normalize, enqueue, with_grad)``."""
+    @staticmethod
+    def forward(ctx, q, g, q_label, g_label, q_valid, g_valid, memory, tau: float, normalize: bool, enqueue: bool, with_grad: bool, rows_out=None):
+        (P, N, D), Mg, dev = q.shape, g.shape[0], q.device
+        _, q2, g, qv, res = _two_sided_prepare(SmoothAPFn, q, g, q_valid, 0.0)
+        with_grad = bool(with_grad and any(ctx.needs_input_grad[:2]))
+        q_label, g_label = q_label.contiguous(), g_label.contiguous()
+        ring = None
+        if memory is not None:
+            _check_ring('SmoothAPFn', memory, P, N, Mg, D, enqueue)
+            ring = (memory.rows, memory.labels, memory.valid)
+            if enqueue:
+                ops.xbm_enqueue(q2, g, g_label, qv, g_valid, normalize, EPS, *ring, memory.cursor, P=P)
+        G = (Mg, N) if memory is None else (memory.capacity, memory.capacity)
+        ws = torch.empty(ops.smooth_ap_ws_floats(P, N, Mg, D, *G, with_grad), device=dev)
+        ap = torch.empty(P * (N + Mg), device=dev); npos = torch.empty(P * (N + Mg), dtype=torch.int32, device=dev)      # q anchors | g anchors
+        ops.smooth_ap_fwd(q2, g, q_label, g_label, qv, g_valid, tau, normalize, EPS, with_grad, ap[:P * N], npos[:P * N], ap[P * N:],
+                          npos[P * N:], ws, res, P=P, ring=ring)
+        if rows_out is not None:
+            rows_out.update(q_ap=ap[:P * N].view(P, N).clone(), g_ap=ap[P * N:].view(P, Mg).clone(),
+                            q_npos=npos[:P * N].view(P, N).clone(), g_npos=npos[P * N:].view(P, Mg).clone())
+        ctx.with_grad = with_grad
+        return _two_sided_finish(ctx, (q2, g, qv, g_valid, ws, res), 0.0, normalize, res)
+
+    @staticmethod
+    def backward(ctx, dloss, _dflag, _dn):            # saved: q2, g (their shapes only), qv, gv | ws, res
+        if not ctx.with_grad:
+            raise _lib.ReidHipError('SmoothAPFn: this forward ran without its gradient part (with_grad=False)')
+        return _two_sided_backward(ctx, dloss, 12, lambda s, consts, outs: ops.smooth_ap_bwd(s[2], s[3], s[4], *outs, P=ctx.P))
+
+
+def _smooth_ap_with_grad(q, g):
+    return bool(torch.is_grad_enabled() and (q.requires_grad or g.requires_grad))
+
+
+def smooth_ap(q, g, q_labels, g_labels, q_valid=None, g_valid=None, temperature=0.01, normalize=True):
+    """Cross-modal Smooth-AP ranking loss (Brown et al., ECCV 2020) for users with their own loop: ``q`` [P, N, D] (P query modalities
+    stacked; [N, D] = one) against the vis features ``g`` [Mg, D].  Per pair, every valid q row ranks the valid g rows by cosine and
+    every valid g row the pair's valid q rows (no self-exclusion); with sigma_ij = sigmoid((s_j - s_i) / temperature), R_i = 1 +
+    sum_{j != i} sigma_ij over the gallery and R+_i the same over the anchor's positives, AP = mean over the positives of R+_i / R_i;
+    an anchor is active when it has a positive and a negative; L_p = 0.5 * (mean of 1 - AP over the active q anchors + the same over
+    the active g anchors).  As temperature -> 0 this is 1 - the AP evaluate.rank_and_metrics reports.  Cosines are formed in fp64 and
+    rounded once, the rest is fp32 in a fixed order: two runs give the same bits.  ``q_valid`` [P, N] / ``g_valid`` [Mg]: optional
+    bool / uint8, rows that take part; ``normalize`` False: the rows are used as they are.  At most 8192 rows per side.  Returns
+    (losses [P], flags [P], rows): flag 1 where the pair has an active anchor, rows = {'q_ap', 'q_npos'} [P, N], {'g_ap', 'g_npos'}
+    [P, Mg] (copies; AP -1 = inactive) plus 'n_active' [P, 2]; the losses carry the gradient to ``q`` and ``g``.  Without gradients
+    (no_grad, or neither input requires one) the gradient part of the forward is skipped."""
+    tau = smooth_ap_temperature('smooth_ap', temperature)
+    _need_device('smooth_ap', q, g)
+    return _two_sided_loss('smooth_ap', SmoothAPFn, q, g, (q_labels, g_labels), q_valid, g_valid, None, tau, bool(normalize), False,
+                           _smooth_ap_with_grad(q, g))
+
+
+def smooth_ap_xbm(q, g, labels, memory, q_valid=None, g_valid=None, temperature=0.01, normalize=True, enqueue=True):
+    """Smooth-AP over a ring, for users with their own loop: ``q`` [P, N, D] and the vis features ``g`` [N, D] of the SAME N instances,
+    ``labels`` [N], ``memory`` a CrossBatchMemory(capacity, P + 1, D) of this loss alone.  With ``enqueue`` the batch is first filed
+    into the memory at its cursor (capacity >= N), so it is part of what is ranked; ``enqueue=False`` ranks the memory as it stands and
+    leaves it untouched.  Per pair, every valid q row ranks the valid slots of memory side 0 (vis) and every valid g row those of side
+    p + 1, by the rules of ``smooth_ap``; a list of thousands of rows is what the soft rank wants.  The memory's rows are constants:
+    the gradient reaches ``q`` and ``g`` only, and it is finished inside the forward, so later enqueues cannot change a pending
+    backward.  Returns (losses [P], flags [P], rows) as ``smooth_ap`` with every array [P, N]."""
+    tau = smooth_ap_temperature('smooth_ap_xbm', temperature)
+    _need_device('smooth_ap_xbm', q, g)
+    if not isinstance(memory, CrossBatchMemory):
+        raise TypeError('smooth_ap_xbm: memory must be a CrossBatchMemory')
+    return _two_sided_loss('smooth_ap_xbm', SmoothAPFn, q, g, (labels, labels), q_valid, g_valid, memory, tau, bool(normalize), bool(enqueue),
+                           _smooth_ap_with_grad(q, g))
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -39,7 +39,8 @@ from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CosineLinearFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn, NanToNumFn,
                    SmallAttnFn)
 from .losses import (CenterLossFn, ClassCenters, ClusterMemory, ClusterNCEFn, CrossBatchMemory, CrossEntropyLSFn, CrossTripletFn, HcTripletFn,
-                     LazyCount, MarginCEFn, SDMFn, TripletHardFn, XbmTripletFn, cluster_nce_args, margin_args)
+                     LazyCount, MarginCEFn, SDMFn, SmoothAPFn, TripletHardFn, XbmTripletFn, cluster_nce_args, margin_args,
+                     smooth_ap_temperature)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
 
@@ -92,6 +93,8 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self._xbm_sides = None               # the modality names of its sides 1 .. P
         self.centers = None                  # the ClassCenters of the center loss, made on first use; a plain attribute: not in state_dict()
         self.cluster_memory = None           # the ClusterMemory of the cluster-contrast loss (set_cluster_memory); not in state_dict() either
+        self.smooth_ap_memory = None         # the Smooth-AP term's own CrossBatchMemory (smooth_ap_size > 0), made on first use; not in state_dict()
+        self._smooth_ap_sides = None         # the modality names of its sides 1 .. P
         self.num_classes = None
         self.bn_neck = None
         self._ref: "OrderedDict[str, nn.Parameter]" = OrderedDict()
@@ -169,6 +172,13 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             'TrainingConfig.cluster_nce', self.cluster_nce_temperature, self.cluster_nce_momentum, self.cluster_nce_mode)
         if self.cluster_nce_source not in ('bn', 'modalities'):
             raise ValueError(f"TrainingConfig.cluster_nce_source must be 'bn' or 'modalities', not {self.cluster_nce_source!r}")
+        # cross-modal Smooth-AP (not in the reference; csrc/smooth_ap.hip): read here for the same reason
+        for name in ('smooth_ap_weight', 'smooth_ap_temperature', 'smooth_ap_size', 'smooth_ap_normalize', 'smooth_ap_start_epoch'):
+            setattr(self, name, getattr(config, name, getattr(defaults, name)))
+        self.smooth_ap_temperature = smooth_ap_temperature('TrainingConfig.smooth_ap', self.smooth_ap_temperature)
+        if int(self.smooth_ap_size) != self.smooth_ap_size or not 0 <= self.smooth_ap_size <= 8192:
+            raise ValueError(f'TrainingConfig.smooth_ap_size must be 0 (in-batch) or the ring slots per side, up to 8192, not {self.smooth_ap_size!r}')
+        self.smooth_ap_size = int(self.smooth_ap_size)
 
     # ------------------------------------------------------------------ parameter plumbing
     def _add_param(self, ref_name: str, value: torch.Tensor, buffer: bool = False):
@@ -619,8 +629,9 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         use_sdm = (self.current_epoch >= self.config.sdm_weight_warmup_epochs) and (self.contrastive_weight > 0)
         raw = outputs.get('raw_modality_features', {})
         use_xbm = self.xbm_weight > 0 and self.current_epoch >= self.xbm_start_epoch
+        use_smooth_ap = self.smooth_ap_weight > 0 and self.current_epoch >= self.smooth_ap_start_epoch
         pairs = None
-        if (use_sdm or self.cross_triplet_weight > 0 or self.hc_triplet_weight > 0 or use_xbm) and 'vis' in raw and 'vis' in fm:
+        if (use_sdm or self.cross_triplet_weight > 0 or self.hc_triplet_weight > 0 or use_xbm or use_smooth_ap) and 'vis' in raw and 'vis' in fm:
             mods = [m for m in raw if m != 'vis' and m in fm]
             if mods:
                 # every non-vis modality against vis in ONE fused launch per loss: the query sides are stacked (built once for all)
@@ -645,6 +656,11 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             out['total_loss'] = out['total_loss'] + self.cluster_nce_weight * term[0]
             out['cluster_nce_loss'] = term[0]
             out['cluster_nce_valid_cnt'] = LazyCount(term[1])
+        if use_smooth_ap and pairs is not None:      # behind it, for the same reason: its own two keys last
+            term = self._smooth_ap_term(labels, pairs)
+            out['total_loss'] = out['total_loss'] + self.smooth_ap_weight * term[0]
+            out['smooth_ap_loss'] = term[0]
+            out['smooth_ap_active_cnt'] = LazyCount(term[1])
         return out
 
     # The auxiliary terms (AUX_TERMS; none is in the reference): (loss, count) of one term from compute_loss's outputs, labels, cached
@@ -731,6 +747,25 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         return ClusterNCEFn.apply(x, labels, xv, self.cluster_memory, float(self.cluster_nce_temperature), float(self.cluster_nce_momentum),
                                   self.cluster_nce_mode, bool(self.training and torch.is_grad_enabled()))
 
+    def _smooth_ap_term(self, labels, pairs):
+        """Cross-modal Smooth-AP (csrc/smooth_ap.hip) on the stack the SDM branch uses, from epoch smooth_ap_start_epoch and not tied to the
+        SDM warm-up: the mean over the pairs with an active anchor.  smooth_ap_size = 0 ranks the batch; otherwise the batch is filed into
+        the term's OWN ring (training with gradients only; separate from xbm_memory, so each ring is enqueued once per step) and every
+        anchor ranks the ring, whose rows are constants."""
+        q, g, qv, gv, mods = pairs
+        memory = None
+        if self.smooth_ap_size > 0:
+            if self.smooth_ap_memory is None:
+                self.smooth_ap_memory = CrossBatchMemory(self.smooth_ap_size, len(mods) + 1, q.shape[2], q.device)
+                self._smooth_ap_sides = mods
+            elif self._smooth_ap_sides != mods:
+                raise ValueError(f'the Smooth-AP memory was made for the modalities {self._smooth_ap_sides}, this batch brings {mods}: '
+                                 'set model.smooth_ap_memory = None to start a new one')
+            memory = self.smooth_ap_memory
+        L, flag, n_act = SmoothAPFn.apply(q, g, labels, labels, qv, gv, memory, float(self.smooth_ap_temperature), bool(self.smooth_ap_normalize),
+                                          bool(self.training and torch.is_grad_enabled()), torch.is_grad_enabled())
+        return _pair_mean(L, flag), n_act.sum()
+
     def set_cluster_memory(self, memory):
         """Installs the ClusterMemory the cluster-contrast term runs against (None removes it): after every re-clustering, a new one
         from the features.  A captured graph holds the old table: capture again after this."""
@@ -750,6 +785,11 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         """Empties the cross-batch memory in place (device fills: a captured graph that holds it stays valid)."""
         if self.xbm_memory is not None:
             self.xbm_memory.reset()
+
+    def reset_smooth_ap(self):
+        """Empties the Smooth-AP term's ring in place (device fills: a captured graph that holds it stays valid)."""
+        if self.smooth_ap_memory is not None:
+            self.smooth_ap_memory.reset()
 
     # ------------------------------------------------------------------ optimiser groups
     def get_learnable_params(self) -> List[Dict[str, Any]]:

@@ -667,6 +667,49 @@ def cluster_centroids(feats, order, offsets, table):
     check(lib().reid_cluster_centroids(ptr(feats), feats.stride(0), feats.shape[0], ptr(order), ptr(offsets), K, D, ptr(table), stream_ptr()))
 
 
+def smooth_ap_ws_floats(P, N, Mg, D, Ga, Gb, with_grad):
+    return _ws_floats(lib().reid_smooth_ap_ws_floats, P, N, Mg, D, Ga, Gb, int(bool(with_grad)))
+
+
+def smooth_ap_fwd(q, g, q_label, g_label, q_valid, g_valid, tau, normalize, eps, with_grad, q_ap, q_npos, g_ap, g_npos, ws, result, P=1,
+                  ring=None):
+    """Cross-modal Smooth-AP: q [P*N, D] (P query sides stacked) against g [Mg, D], ranked in both directions.  ``ring`` None: inside the
+    batch (the galleries are g and pair p's q rows, and get a gradient); ``ring`` = (rows [P+1, M, D], mem_labels [M], mem_valid
+    [P+1, M]) of a cross-batch memory: the q rows rank the slots of side 0, the g rows those of side p + 1, as constants (then Mg = N).
+    q_ap / q_npos [P*N], g_ap / g_npos [P*Mg] = AP_a (-1: inactive), |P_a|; result f32 [P, 4] = (L_p, flag_p, n_qg, n_gq).  With
+    ``with_grad`` ws keeps the projected gradients for smooth_ap_bwd."""
+    who = 'smooth_ap_fwd'
+    N, Mg, D = _pair_batch(who, q, g, q_valid, g_valid, P)
+    _vectors(who, 'q_label [N], g_label [Mg]', ('q_label', q_label, i64, N), ('g_label', g_label, i64, Mg), exact=True)
+    if ring is None:
+        ga, gb = (g, g.stride(0), g_label, g_valid, Mg), (q, q.stride(0), q_label, q_valid, N)
+    else:
+        if N != Mg:
+            raise ValueError(f'{who}: q [P*N, D], g [N, D] against a memory')
+        rows, mem_labels, mem_valid = ring
+        M = _xbm_memory(who, rows, mem_labels, mem_valid, P, 1, D)
+        ga, gb = (rows[0], D, mem_labels, mem_valid[0], M), (rows[1:], D, mem_labels, mem_valid[1:], M)
+    n_ws = smooth_ap_ws_floats(P, N, Mg, D, ga[4], gb[4], with_grad)
+    _vectors(who, 'q_ap / q_npos [P*N], g_ap / g_npos [P*Mg], result [P, 4], all contiguous', ('q_ap', q_ap, f32, P * N),
+             ('q_npos', q_npos, i32, P * N), ('g_ap', g_ap, f32, P * Mg), ('g_npos', g_npos, i32, P * Mg), ('result', result, f32, 4 * P))
+    _vectors(who, f'ws holds fewer than the {n_ws} floats of smooth_ap_ws_floats', ('ws', ws, f32, n_ws))
+    check(lib().reid_smooth_ap_fwd(ptr(q), q.stride(0), ptr(g), g.stride(0), ptr(q_label), ptr(g_label), ptr(q_valid), ptr(g_valid), P, N, Mg, D,
+                                   float(tau), int(normalize), eps, ptr(ga[0]), ga[1], ptr(ga[2]), ptr(ga[3]), ga[4],
+                                   ptr(gb[0]), gb[1], ptr(gb[2]), ptr(gb[3]), gb[4], int(ring is None), int(bool(with_grad)),
+                                   ptr(q_ap), ptr(q_npos), ptr(g_ap), ptr(g_npos), ptr(ws), ptr(result), stream_ptr()))
+
+
+def smooth_ap_bwd(q_valid, g_valid, ws, gscale, dq, dg, P=1):
+    """dq [P*N, D] = gscale[p] * Hq, dg [Mg, D] = sum_p gscale[p] * Hg[p] (both overwritten, one launch) from the projected gradients
+    smooth_ap_fwd(with_grad=True) left at the head of ws -- neither the batch nor a memory is read; gscale f32 [P] on the device."""
+    who = 'smooth_ap_bwd'
+    N, Mg, D = _pair_batch(who, dq, dg, q_valid, g_valid, P)
+    _vectors(who, 'gscale [P]', ('gscale', gscale, f32, P))
+    _vectors(who, 'ws holds fewer floats than the projected gradients of smooth_ap_fwd(with_grad=True)', ('ws', ws, f32, (P * N + P * Mg) * D))
+    check(lib().reid_smooth_ap_bwd(ptr(q_valid), ptr(g_valid), P, N, Mg, D, ptr(ws), ptr(gscale), ptr(dq), dq.stride(0), ptr(dg), dg.stride(0),
+                                   stream_ptr()))
+
+
 def cos_logits_fwd(x, W, scale, eps, rx, rw, logits):
     """logits [B, C] = scale * cos(x_b, W_c) of x [B, D], W [C, D] (fp32, any leading dimension); rx f64 [B], rw f64 [C] receive the
     inverse norms 1 / max(|row|, eps) and are kept for the backward.  Two launches."""
