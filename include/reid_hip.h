@@ -653,6 +653,46 @@ int reid_smooth_ap_bwd(const uint8_t* q_valid, const uint8_t* g_valid, int32_t P
                        const float* gscale, float* dq, int32_t lddq, float* dg, int32_t lddg, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Hybrid memory loss (SpCL: Ge et al., "Self-paced Contrastive Learning with Hybrid Memory", NeurIPS 2020, sections 3.1-3.2; the
+ * reference has no such loss; csrc/hybrid_nce.hip): the memory behind the cluster-NCE block's forward and
+ * backward when EVERY instance trains -- a cluster is a class, an un-clustered instance is a class of its own.  All fp32.
+ *   State: V [M, D] (ldv) holds one unit entry per training instance and persists across re-clusterings; cls [M] (host side) the
+ *   class of every instance in 0..C-1, every class with at least one member; the members of class c are order[offsets[c]] ..
+ *   order[offsets[c + 1] - 1] in ASCENDING instance index (order [M], offsets [C + 1] int64); n_c = their number.
+ *   Table T [C, D], contiguous: per column d
+ *     T_c[d] = fl( fl(sum of V_i[d] over the members i of c, added one by one in ascending i, fp32, not fused) / float(n_c) ),
+ *   the sum starting from the first member; the rows are NOT renormalised (SpCL's mean; |T_c| <= 1 up to rounding); a singleton
+ *   class is its entry, bit for bit.
+ *   Loss: x [S*N, D] with S sides stacked (row r = s*N + n), index [N] int64 shared by the sides (the dataset row of each
+ *   instance), valid [S*N] or NULL.  A row is USED when it is valid and 0 <= index < M; its label is y_r = cls[index_n];
+ *   loss = mean over the used rows of lse_c(x^_r . T_c / tau) - x^_r . T_y / tau, 0 when no row is used.  The mean of dot products
+ *   is the dot product with the mean, so forward and backward ARE reid_cluster_nce_fwd / reid_cluster_nce_bwd with table = T,
+ *   K = C and labels[n] = cls[index[n]] (-1 for an index outside 0..M-1).
+ *   reid_class_means: T from (V, order, offsets) by the formula above, one workgroup per class; an empty class gets zeros.
+ *   Update, after the forward, with what the forward had (row_loss, its ws): a row CONTRIBUTES when it is used and its row_loss is
+ *   finite.
+ *   reid_hybrid_update_instances: for every instance with a contributing row, over its contributing rows in ascending r (the
+ *   sides of an instance in side order, an index that appears twice in a side in row order), with x^_r from ws:
+ *     v = momentum * v + (1 - momentum) * x^_r;  v = v / max(|v|, 1e-12).
+ *   The wave of the instance's lowest contributing row is the only reader and writer of that entry; other entries keep their bits.
+ *   reid_hybrid_refresh_classes (labels = the gathered labels the forward had; after reid_hybrid_update_instances in stream order):
+ *   every class with a contributing row has its row of T re-formed from the UPDATED V by the table formula, by the workgroup of the
+ *   class's lowest contributing row, the only writer of that row; untouched classes keep their bits.  After any number of steps T
+ *   equals reid_class_means of V bit for bit.
+ *   No atomics: two runs give the same bits in V and T.  Nothing is allocated, synchronised or read back.
+ * Requirements: 1 <= S <= 9, 1 <= N <= 8192, D % 32 == 0, 32 <= D <= 1024, C >= 1, C*D < 2^31, M >= 1 (rows of V are addressed in
+ * 64 bits), ldv a multiple of 4 and >= D, V, T and ws 16-byte aligned, 0 <= momentum <= 1; every order[t] in 0..M-1 and offsets
+ * ascending from 0 (the caller's: they are not read on the host).  Anything else: REID_ERR_ARG before any launch.
+ * ------------------------------------------------------------------------------------------ */
+int reid_class_means(const float* V, int32_t ldv, int64_t M, const int64_t* order, const int64_t* offsets, int32_t C, int32_t D,
+                     float* T, void* stream);
+int reid_hybrid_update_instances(const int64_t* index, const uint8_t* valid, int32_t S, int32_t N, int32_t D, const float* row_loss,
+                                 const float* ws, float* V, int32_t ldv, int64_t M, float momentum, void* stream);
+int reid_hybrid_refresh_classes(const int64_t* labels, const uint8_t* valid, int32_t S, int32_t N, int32_t D, const float* row_loss,
+                                const float* V, int32_t ldv, int64_t M, const int64_t* order, const int64_t* offsets, float* T,
+                                int32_t C, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Retrieval (train.py:499 + :463; tools/eval_mm_protocol.py:50-53,401-423,622-625):
  *   sim = Q . G^T on L2-normalised rows, per-query top-k in (score desc, index asc) order.
  *   Q [Nq, D], G [Ng, D] bf16 copies drive a tiled MFMA GEMM with an on-chip candidate filter;

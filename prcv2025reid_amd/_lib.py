@@ -127,6 +127,9 @@ SIGNATURES = {
     'reid_smooth_ap_fwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _F, _P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _I, _I,
                                 _P, _P, _P, _P, _P, _P, _P]),
     'reid_smooth_ap_bwd': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P]),
+    'reid_class_means': (_I, [_P, _I, _I64, _P, _P, _I, _I, _P, _P]),
+    'reid_hybrid_update_instances': (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I64, _F, _P]),
+    'reid_hybrid_refresh_classes': (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I64, _P, _P, _P, _I, _P]),
     'reid_topk_ws_bytes': (_I64, [_I, _I, _I]),
     'reid_topk_scan_ok': (_I, [_I, _I, _I, _I]),
     'reid_cosine_topk': (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),

@@ -154,6 +154,8 @@ def save_checkpoint(model, optimizer, scheduler_state, epoch: int, best_map: flo
         ckpt['center_state_dict'] = dict(model.centers.state(), center_source=getattr(model, 'center_source', 'fused'))
     if getattr(model, 'cluster_memory', None) is not None:
         ckpt['cluster_memory_state_dict'] = dict(model.cluster_memory.state(), cluster_nce_source=getattr(model, 'cluster_nce_source', 'bn'))
+    if getattr(model, 'hybrid_memory', None) is not None:
+        ckpt['hybrid_memory_state_dict'] = dict(model.hybrid_memory.state(), hybrid_nce_source=getattr(model, 'hybrid_nce_source', 'bn'))
     torch.save(ckpt, filename)
     return ckpt
 
@@ -194,8 +196,15 @@ def load_checkpoint(filename: str, model, optimizer=None, strict: bool = True) -
             K, D = st['centroids'].shape
             model.cluster_memory = ClusterMemory(K, D, getattr(model, 'device', 'cpu'))
         model.cluster_memory.load_state(st)
+    if isinstance(ckpt, dict) and ckpt.get('hybrid_memory_state_dict'):
+        st = ckpt['hybrid_memory_state_dict']
+        if getattr(model, 'hybrid_memory', None) is None:
+            from .losses import HybridMemory
+            M, D = st['instances'].shape
+            model.hybrid_memory = HybridMemory(M, D, getattr(model, 'device', 'cpu'))
+        model.hybrid_memory.load_state(st)
     return ({k: v for k, v in ckpt.items() if k not in ('model_state_dict', 'optimizer_state_dict', 'ema_state_dict', 'center_state_dict',
-                                                        'cluster_memory_state_dict')}
+                                                        'cluster_memory_state_dict', 'hybrid_memory_state_dict')}
             if isinstance(ckpt, dict) else {})
 
 

@@ -66,6 +66,13 @@ class Clustering:
         index = torch.nonzero(self.labels >= 0).flatten()
         return index, self.labels[index]
 
+    def hybrid_labels(self) -> Tuple[torch.Tensor, int]:
+        """(labels i64 [N], num_classes) for a hybrid memory (losses.HybridMemory, SpCL): the cluster numbers as they are, and every
+        noise row a class of its own -- ``n_clusters`` + its rank among the noise rows in ascending row order."""
+        noise = self.labels < 0
+        rank = torch.cumsum(noise.to(torch.int64), 0) - 1
+        return torch.where(noise, self.n_clusters + rank, self.labels), self.n_clusters + int(noise.sum())
+
 
 def round_cap(N: int) -> int:
     """Hook passes allowed before ``dbscan_rows`` gives up: 4 ceil(log2(N + 1)) + 8 (a permuted chain of 65 536 rows needs 12)."""

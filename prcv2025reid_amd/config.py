@@ -123,6 +123,13 @@ class TrainingConfig:
     smooth_ap_size: int = 0                          # 0: in-batch; otherwise ring slots per side, batch size .. 8192
     smooth_ap_normalize: bool = True
     smooth_ap_start_epoch: int = 0
+    # nor these: hybrid memory loss (SpCL, Ge et al. 2020) -- one entry per training instance, a cluster of cluster.jaccard_dbscan trains
+    # against the mean of its members' entries, an un-clustered instance against its own; the labels of a step are then DATASET INSTANCE
+    # INDICES (every other term sees memory.labels[index]) and model.set_hybrid_memory() installs the memory
+    hybrid_nce_weight: float = 0.0
+    hybrid_nce_temperature: float = 0.05             # SpCL's
+    hybrid_nce_momentum: float = 0.2                 # v <- m v + (1 - m) x^, SpCL's m
+    hybrid_nce_source: str = 'bn'                    # 'bn': the retrieval feature behind the BN-neck; 'modalities': every modality's raw feature
     sdm_semantic_dim: int = 512
     sdm_num_heads: int = 8
     sdm_dropout: float = 0.1   # not a reference config field: hard-coded in SemanticDisentanglementModule (models/model.py:35,43)

@@ -25,7 +25,7 @@
 // Centroid initialisation (cnce_centroids_kernel): one wave per cluster over the rows the host has grouped by label.
 // No atomics anywhere; nothing is allocated, synchronised or read back.
 #include "gemm_core.h"
-#include "triplet_mine.h"
+#include "cluster_nce_ws.h"      // the workspace layout and the shape checks, shared with hybrid_nce.hip
 
 // A logit is the ROUNDED product cos * (1 / tau) wherever it is formed (the running maximum, the exponent of p, l_y of the row loss):
 // with K = 1 lse equals l_y bit for bit and loss and gradient are exactly 0.  A fused multiply-add would keep the product unrounded in
@@ -38,14 +38,18 @@ using triplet::NV;
 using triplet::load_row;
 using triplet::store_row;
 using triplet::zero_acc;
+using cnce::MAX_SIDES;
+using cnce::EPS;
+using cnce::Ws;
+using cnce::check_d;
+using cnce::check_shape;
+using cnce::check_table;
 
-constexpr int MAX_SIDES = 9;
 constexpr int TS = 64;                   // row tile = class tile: 4 waves as 2 x 2, one 32 x 32 MFMA tile each
 constexpr int TARGET_WGS = 512;          // the class range is split until the grid has about this many workgroups (a constant: the
                                          // rule depends on the shape only, so two devices form the same sums)
 constexpr int MAX_SPLITS = 64;
 constexpr int SLICE = 256;               // columns of D one grad workgroup accumulates: 2 chunks of 32 per wave
-constexpr float EPS = 1e-12f;
 constexpr float M_NONE = -3.0e38f;       // running maximum of "nothing yet": finite, so exp(m - m') never sees inf - inf
 constexpr int LDS_BYTES = F32Tile<TS>::LDS_STAGE;      // f32_tile's staging buffers; the p tile (TS x (TS + 1) floats) takes them over after the K loop
 constexpr int P_LD = TS + 1;
@@ -64,18 +68,6 @@ Plan plan_of(int R, int K, int D) {
     p.slices = (D + SLICE - 1) / SLICE;
     return p;
 }
-
-// ws (floats): H R D | x^ R D | used R | inv R | target cosine R | lse R | (max, sum) splits R 2 | sum_c p C splits R D
-struct Ws {
-    int64_t h, xhat, used, inv, tgt, lse, part, gpart, total;
-    Ws(int64_t R, int64_t D, int64_t splits) {
-        int64_t o = 0;
-        auto take = [&](int64_t n) { const int64_t at = o; o += (n + 3) & ~(int64_t)3; return at; };
-        h = take(R * D); xhat = take(R * D); used = take(R); inv = take(R); tgt = take(R); lse = take(R);
-        part = take(2 * splits * R); gpart = take(splits * R * D);
-        total = o;
-    }
-};
 
 __device__ __forceinline__ bool row_used(const int64_t* __restrict__ labels, const uint8_t* __restrict__ valid, int r, int N, int K) {
     const int64_t y = labels[r % N];
@@ -390,23 +382,6 @@ __global__ __launch_bounds__(256) void cnce_centroids_kernel(const float* __rest
         for (int v = 0; v < NV; ++v) acc[v] = acc[v] / den;
     }
     store_row(table + (size_t)k * D, acc, lane, D);
-}
-
-int check_d(const char* who, int32_t D) {
-    REID_CHECK_ARG(D % 32 == 0 && D >= 32 && D <= 1024, "%s: D=%d (a multiple of 32, 32..1024)", who, D);
-    return REID_OK;
-}
-
-int check_shape(const char* who, int32_t S, int32_t N, int32_t D) {
-    REID_CHECK_ARG(S >= 1 && S <= MAX_SIDES, "%s: S=%d (1..9)", who, S);
-    REID_CHECK_ARG(N >= 1 && N <= triplet::MAX_ROWS, "%s: N=%d (1..8192)", who, N);
-    return check_d(who, D);                                          // (S N D <= 9 * 8192 * 1024 < 2^31: x^ and H [S N, D] fit)
-}
-
-int check_table(const char* who, int32_t K, int32_t D) {
-    REID_CHECK_ARG(K >= 1, "%s: K=%d (>= 1)", who, K);
-    REID_CHECK_ARG((int64_t)K * D < (1ll << 31), "%s: K * D beyond 2^31 elements", who);
-    return REID_OK;
 }
 
 }  // namespace

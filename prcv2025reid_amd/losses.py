@@ -1,6 +1,6 @@
 """Autograd boundaries and public functions of the loss kernels: label-smoothed CE, SDM loss, batch-hard triplet loss, cross-modal
 batch-hard triplet loss, hetero-center triplet loss, cross-batch memory (XBM), cross-modal Smooth-AP (in the batch or over a ring), center
-loss, cluster-contrast memory loss, margin CE of the cosine-margin heads.
+loss, cluster-contrast memory loss, hybrid (instance + cluster) memory loss, margin CE of the cosine-margin heads.
 
 Reference: compute_loss models/model.py:512-659; sdm_loss_stable models/sdm_loss.py:13-149 (the reference has CE and SDM only).  All
 arithmetic is in libreid_hip.so (fp32); torch only carries the tensors.  The two-sided losses (one stack of query modalities against
@@ -713,6 +713,162 @@ def cluster_nce(x, labels, memory, valid=None, temperature=0.05, momentum=0.1, m
                                       bool(update and torch.is_grad_enabled()), rows)
     if flat:
         rows = {k: v[0] for k, v in rows.items()}
+    return loss, LazyCount(n_used), rows
+
+
+# ----------------------------------------------------------------------------------------------------------------
+def hybrid_nce_args(who, temperature, momentum):
+    """The checked (temperature, momentum) of the hybrid memory loss."""
+    return cluster_nce_args(who, temperature, momentum, 'mean')[:2]
+
+
+class HybridMemory:
+    """The hybrid memory of hybrid_nce (SpCL, Ge et al. 2020, sections 3.1-3.2; csrc/hybrid_nce.hip): one unit
+    entry per training INSTANCE, ``instances`` f32 [num_instances, dim], which persists across re-clusterings and is only re-labelled
+    (``set_labels``); ``labels`` i64 [num_instances] the class of every instance in 0..num_classes-1 -- a cluster, or a class of its
+    own for an un-clustered instance (``Clustering.hybrid_labels()``); ``table`` f32 [num_classes, dim] the class vectors = the fp32
+    mean of the members' entries added in ascending instance index, NOT renormalised, kept exact after every update; ``counts`` i64
+    [num_classes].  Plain tensors moved by the momentum update only, not by the optimizer; ``state()`` / ``load_state()`` carry entries
+    and labels through a checkpoint (``hybrid_memory_state_dict``).  A new memory holds zero entries, all in class 0.  It may be
+    constructed on the CPU to carry a state (its table then stays zero); the kernels need the device."""
+
+    def __init__(self, num_instances, dim, device='cuda'):
+        if not (num_instances >= 1 and dim % 32 == 0 and 32 <= dim <= 1024):
+            raise ValueError('HybridMemory: num_instances >= 1, dim a multiple of 32 in 32..1024')
+        self.num_instances, self.dim = int(num_instances), int(dim)
+        self.instances = torch.zeros(self.num_instances, self.dim, dtype=torch.float32, device=torch.device(device))
+        self._relabel(torch.zeros(self.num_instances, dtype=torch.int64, device=self.instances.device), 1)
+
+    def _relabel(self, labels, C):
+        """Installs checked labels: members grouped by class (a stable sort: ascending instance index inside a class), counts, and
+        the table from the entries as they stand."""
+        if C * self.dim >= 2 ** 31:
+            raise ValueError(f'HybridMemory: num_classes * dim = {C} * {self.dim} must stay below 2^31')
+        self.labels, self.num_classes = labels.contiguous(), int(C)
+        self.counts = torch.bincount(self.labels, minlength=self.num_classes)
+        self.order = torch.sort(self.labels, stable=True).indices.contiguous()
+        self.offsets = torch.cat([self.counts.new_zeros(1), self.counts.cumsum(0)]).contiguous()
+        self.table = torch.zeros(self.num_classes, self.dim, dtype=torch.float32, device=self.instances.device)
+        if self.instances.is_cuda:
+            ops.class_means(self.instances, self.order, self.offsets, self.table)
+
+    def set_labels(self, labels):
+        """Re-labels the memory after a re-clustering: the entries stay as they are; the members, the counts and the table (the number
+        of classes may change) are rebuilt.  ``labels`` [num_instances]: classes 0..C-1 without gaps (Clustering.hybrid_labels()).
+        A captured graph holds the old table: capture again."""
+        if labels.shape != (self.num_instances,):
+            raise ValueError(f'HybridMemory.set_labels: labels [{self.num_instances}], one per instance')
+        labels = labels.to(self.instances.device).long()
+        if int(labels.min()) < 0:
+            raise ValueError('HybridMemory.set_labels: every instance needs a class >= 0; a -1 (DBSCAN noise) becomes a class of its '
+                             'own with Clustering.hybrid_labels()')
+        C = int(labels.max()) + 1
+        counts = torch.bincount(labels, minlength=C)
+        if bool((counts == 0).any()):
+            raise ValueError(f'HybridMemory.set_labels: class {int((counts == 0).nonzero()[0])} has no instance (classes must be 0..C-1 without gaps)')
+        self._relabel(labels.clone(), C)
+
+    @classmethod
+    def from_labels(cls, feats, labels):
+        """The memory of the rows ``feats`` [M, D] (device): entries = l2_normalize(feats), classes ``labels`` [M] >= 0 without gaps."""
+        _need_device('HybridMemory.from_labels', feats, labels)
+        if feats.dim() != 2 or labels.shape != feats.shape[:1]:
+            raise ValueError('HybridMemory.from_labels: feats [M, D], labels [M]')
+        mem = cls(feats.shape[0], feats.shape[1], feats.device)
+        ops.l2norm_rows(feats.float().contiguous(), y=mem.instances, eps=EPS)
+        mem.set_labels(labels)
+        return mem
+
+    @classmethod
+    def from_clustering(cls, feats, clustering):
+        """The memory of a ``cluster.Clustering`` of the rows ``feats`` (jaccard_dbscan's result): every noise row is a class of its own."""
+        return cls.from_labels(feats, clustering.hybrid_labels()[0].to(feats.device))
+
+    def classes_of(self, index):
+        """The classes of the dataset rows ``index`` (i64, on the memory's device), -1 for an index outside the memory; no host read."""
+        ok = (index >= 0) & (index < self.num_instances)
+        return torch.where(ok, self.labels[index.clamp(0, self.num_instances - 1)], torch.full_like(index, -1))
+
+    def state(self):
+        return {'instances': self.instances.detach().cpu().clone(), 'labels': self.labels.detach().cpu().clone()}
+
+    def load_state(self, state):
+        """Copies ``state['instances']`` into the entries in place and re-labels with ``state['labels']``; another shape is refused."""
+        v = state['instances']
+        if tuple(v.shape) != (self.num_instances, self.dim):
+            raise ValueError(f'HybridMemory: the state holds instances {tuple(v.shape)}, this memory is [{self.num_instances}, {self.dim}]')
+        self.instances.copy_(v.to(torch.float32))
+        self.set_labels(state['labels'])
+
+
+class HybridNCEFn(torch.autograd.Function):
+    """(loss, n_used) of the hybrid memory loss of x [S, N, D] (S sides stacked, ``index`` [N] shared: the dataset row of each instance)
+    against ``memory`` (csrc/hybrid_nce.hip): ClusterNCEFn's forward against the memory's table of class means with the labels
+    memory.labels[index] -- a row is used when it is valid and its index lies in the memory.  With ``update`` the entries of the
+    contributing instances are then moved by momentum and the class means of their classes re-formed from the moved entries, two
+    kernels in stream order.  Entries and table are constants of the loss: the gradient reaches x only, from what the forward left in
+    its workspace.  n_used is a float tensor; nothing is read back to the host.  ``rows_out``: an optional trailing dict that receives
+    COPIES of ``row_loss``, ``target_cos`` and ``labels``; the call the model makes is ``apply(x, index, valid, memory, tau, momentum,
+    update)``."""
+    @staticmethod
+    def forward(ctx, x, index, valid, memory, tau: float, momentum: float, update: bool, rows_out=None):
+        (S, N, D), dev = x.shape, x.device
+        if D != memory.dim:
+            raise _lib.ReidHipError(f'HybridNCEFn: the memory holds entries of D={memory.dim}, the batch has D={D}')
+        with_grad = bool(ctx.needs_input_grad[0])
+        x2 = x.reshape(S * N, D).contiguous().float()
+        index = index.contiguous()
+        labels = memory.classes_of(index).contiguous()
+        vv = None if valid is None else valid.reshape(S * N).contiguous()
+        ws = torch.empty(ops.cluster_nce_ws_floats(S, N, D, memory.num_classes), device=dev)
+        row_loss = torch.empty(S * N, device=dev); tcos = torch.empty(S * N, device=dev); res = torch.empty(2, device=dev)
+        ops.cluster_nce_fwd(x2, labels, vv, memory.table, tau, with_grad, ws, row_loss, tcos, res, S=S)
+        if update:
+            ops.hybrid_update_instances(index, vv, row_loss, ws, memory.instances, momentum, S=S)
+            ops.hybrid_refresh_classes(labels, vv, row_loss, memory.instances, memory.order, memory.offsets, memory.table, S=S)
+        ctx.save_for_backward(ws, res)
+        ctx.shape = (S, N, D)
+        loss, n_used = res[0], res[1]
+        ctx.mark_non_differentiable(n_used)
+        if rows_out is not None:
+            rows_out.update(row_loss=row_loss.view(S, N).clone(), target_cos=tcos.view(S, N).clone(), labels=labels.clone())
+        return loss, n_used
+
+    @staticmethod
+    def backward(ctx, dloss, _dn):
+        ws, res = ctx.saved_tensors
+        S, N, D = ctx.shape
+        dx = torch.empty(S * N, D, device=ws.device)
+        ops.cluster_nce_bwd(ws, res, dloss.reshape(1).float().contiguous(), dx, S=S)
+        return dx.view(S, N, D), None, None, None, None, None, None, None
+
+
+def hybrid_nce(x, index, memory, valid=None, temperature=0.05, momentum=0.2, update=True):
+    """Hybrid memory loss (SpCL) for users with their own loop: ``x`` [S, N, D] (S sides stacked; [N, D] = one side) of the N instances
+    whose dataset rows are ``index`` [N], ``memory`` a HybridMemory(M, D).  A row is used when it is valid (``valid`` [S, N] or [N] for
+    one side: optional bool / uint8) and 0 <= index < M; its label is memory.labels[index];
+    loss = mean over the used rows of lse_c(x^ . T_c / temperature) - x^ . T_y / temperature against the class means T, 0 when no row
+    is used.  With ``update`` (and gradients enabled) the entries of the batch's instances then move, v <- m v + (1 - m) x^,
+    renormalised, over an instance's rows in ascending row order, and the means of their classes are re-formed; rows with a
+    non-finite loss are left out; ``update=False`` leaves the memory as it is.  Returns (loss, LazyCount(n_used), rows) with rows =
+    {'row_loss', 'target_cos'} [S, N] and 'labels' [N] (copies); the loss carries the gradient to ``x``."""
+    _need_device('hybrid_nce', x, index, valid)
+    if not isinstance(memory, HybridMemory):
+        raise TypeError('hybrid_nce: memory must be a HybridMemory')
+    if not memory.instances.is_cuda:
+        raise _lib.ReidHipError('hybrid_nce needs the memory on the device (there is no CPU path)')
+    flat = x.dim() == 2
+    if flat:
+        x = x.unsqueeze(0)
+    if x.dim() != 3 or index.shape != x.shape[1:2]:
+        raise ValueError('hybrid_nce: x [S, N, D] or [N, D], index [N]')
+    if valid is not None:
+        valid = valid.to(torch.uint8).reshape(x.shape[0], x.shape[1]).contiguous()
+    temperature, momentum = hybrid_nce_args('hybrid_nce', temperature, momentum)
+    rows = {}
+    loss, n_used = HybridNCEFn.apply(x, index.long(), valid, memory, temperature, momentum, bool(update and torch.is_grad_enabled()), rows)
+    if flat:
+        rows = {k: (v if k == 'labels' else v[0]) for k, v in rows.items()}
     return loss, LazyCount(n_used), rows
 
 

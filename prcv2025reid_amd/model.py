@@ -39,7 +39,7 @@ from .engine import TextEncodeFn, Engine, LoraLayout, VisionEncodeFn
 from .head import (MulFn, ActFn, AddFn, BNNeckFn, CosineLinearFn, LayerNormF32Fn, LinearF32Fn, LinearNdF32Fn, MaskedMeanFn, NanToNumFn,
                    SmallAttnFn)
 from .losses import (CenterLossFn, ClassCenters, ClusterMemory, ClusterNCEFn, CrossBatchMemory, CrossEntropyLSFn, CrossTripletFn, HcTripletFn,
-                     LazyCount, MarginCEFn, SDMFn, SmoothAPFn, TripletHardFn, XbmTripletFn, cluster_nce_args, margin_args,
+                     HybridMemory, HybridNCEFn, LazyCount, MarginCEFn, SDMFn, SmoothAPFn, TripletHardFn, XbmTripletFn, cluster_nce_args, hybrid_nce_args, margin_args,
                      smooth_ap_temperature)
 from .tokenizer import load_tokenizer
 from .weights import param_spec, reference_init_state, seeded_tensor, is_dead_key
@@ -93,6 +93,7 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         self._xbm_sides = None               # the modality names of its sides 1 .. P
         self.centers = None                  # the ClassCenters of the center loss, made on first use; a plain attribute: not in state_dict()
         self.cluster_memory = None           # the ClusterMemory of the cluster-contrast loss (set_cluster_memory); not in state_dict() either
+        self.hybrid_memory = None            # the HybridMemory of the hybrid memory loss (set_hybrid_memory); not in state_dict() either
         self.smooth_ap_memory = None         # the Smooth-AP term's own CrossBatchMemory (smooth_ap_size > 0), made on first use; not in state_dict()
         self._smooth_ap_sides = None         # the modality names of its sides 1 .. P
         self.num_classes = None
@@ -179,6 +180,13 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         if int(self.smooth_ap_size) != self.smooth_ap_size or not 0 <= self.smooth_ap_size <= 8192:
             raise ValueError(f'TrainingConfig.smooth_ap_size must be 0 (in-batch) or the ring slots per side, up to 8192, not {self.smooth_ap_size!r}')
         self.smooth_ap_size = int(self.smooth_ap_size)
+        # hybrid memory loss (SpCL; not in the reference; csrc/hybrid_nce.hip): read here for the same reason
+        for name in ('hybrid_nce_weight', 'hybrid_nce_temperature', 'hybrid_nce_momentum', 'hybrid_nce_source'):
+            setattr(self, name, getattr(config, name, getattr(defaults, name)))
+        self.hybrid_nce_temperature, self.hybrid_nce_momentum = hybrid_nce_args('TrainingConfig.hybrid_nce', self.hybrid_nce_temperature,
+                                                                               self.hybrid_nce_momentum)
+        if self.hybrid_nce_source not in ('bn', 'modalities'):
+            raise ValueError(f"TrainingConfig.hybrid_nce_source must be 'bn' or 'modalities', not {self.hybrid_nce_source!r}")
 
     # ------------------------------------------------------------------ parameter plumbing
     def _add_param(self, ref_name: str, value: torch.Tensor, buffer: bool = False):
@@ -604,6 +612,14 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         logits = outputs['logits']
         dev = logits.device
         labels = labels.to(dev).long()
+        index = None
+        if self.hybrid_nce_weight > 0:
+            # the hybrid memory term: ``labels`` holds dataset instance indices; the class labels every term below (the CE included) sees
+            # are the memory's, gathered on the device
+            if self.hybrid_memory is None:
+                raise ValueError('hybrid_nce_weight > 0 needs a hybrid memory: build one with HybridMemory.from_clustering(features, '
+                                 'clustering) or HybridMemory.from_labels and install it with model.set_hybrid_memory(memory)')
+            index, labels = labels, self.hybrid_memory.classes_of(labels)
         fm = outputs.get('feature_masks', {})
         Bn = labels.shape[0]
         # validity vectors depend on the masks alone: derived once per mask set (see _fusion)
@@ -661,6 +677,11 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             out['total_loss'] = out['total_loss'] + self.smooth_ap_weight * term[0]
             out['smooth_ap_loss'] = term[0]
             out['smooth_ap_active_cnt'] = LazyCount(term[1])
+        if index is not None:                # behind it, for the same reason: its own two keys last
+            term = self._hybrid_nce_term(outputs, index, cent)
+            out['total_loss'] = out['total_loss'] + self.hybrid_nce_weight * term[0]
+            out['hybrid_nce_loss'] = term[0]
+            out['hybrid_nce_valid_cnt'] = LazyCount(term[1])
         return out
 
     # The auxiliary terms (AUX_TERMS; none is in the reference): (loss, count) of one term from compute_loss's outputs, labels, cached
@@ -709,18 +730,33 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         if self.center_source == 'fused':
             x, xv = outputs['features'].unsqueeze(0), cent['valid']
         else:
-            raw, fm = outputs.get('raw_modality_features', {}), outputs.get('feature_masks', {})
-            cm = [m for m in raw if m in fm]
-            cm = [m for m in cm if m == 'vis'] + [m for m in cm if m != 'vis']
-            if not cm:
-                raise ValueError("center_source='modalities' needs raw_modality_features with feature_masks")
-            x = torch.stack([raw[m] for m in cm], dim=0)                                     # [S, B, D]
-            xv = cent.get(('cv', tuple(cm)))
-            if xv is None:
-                xv = cent[('cv', tuple(cm))] = torch.stack([(fm[m].to(x.device) > 0) for m in cm], dim=0).to(torch.uint8).contiguous()
+            x, xv = self._modality_stack('center_source', outputs, cent)
         if self.centers is None:
             self.centers = ClassCenters(self.num_classes, x.shape[2], x.device)
         return CenterLossFn.apply(x, labels, xv, self.centers, float(self.center_alpha), bool(self.training and torch.is_grad_enabled()))
+
+    def _modality_stack(self, setting, outputs, cent):
+        """(x [S, B, D], valid [S, B]) of the source 'modalities' of the term whose setting is ``setting``: the raw feature of every modality
+        that has a mask (vis first), stacked; the validity bytes are cached beside the step's other validity vectors."""
+        raw, fm = outputs.get('raw_modality_features', {}), outputs.get('feature_masks', {})
+        cm = [m for m in raw if m in fm]
+        cm = [m for m in cm if m == 'vis'] + [m for m in cm if m != 'vis']
+        if not cm:
+            raise ValueError(f"{setting}='modalities' needs raw_modality_features with feature_masks")
+        x = torch.stack([raw[m] for m in cm], dim=0)                                     # [S, B, D]
+        xv = cent.get(('cv', tuple(cm)))
+        if xv is None:
+            xv = cent[('cv', tuple(cm))] = torch.stack([(fm[m].to(x.device) > 0) for m in cm], dim=0).to(torch.uint8).contiguous()
+        return x, xv
+
+    def _memory_source(self, setting, outputs, cent):
+        """(x [S, B, D], valid) of a memory loss whose source setting is ``setting``: 'bn' = the retrieval feature behind the BN-neck with
+        the CE branch's validity; 'modalities' = _modality_stack."""
+        if getattr(self, setting) == 'bn':
+            if 'bn_features' not in outputs:
+                raise ValueError(f"{setting}='bn' needs bn_features: call set_num_classes first")
+            return outputs['bn_features'].unsqueeze(0), cent['valid']
+        return self._modality_stack(setting, outputs, cent)
 
     def _cluster_nce_term(self, outputs, labels, cent):
         """Cluster-contrast memory loss (csrc/cluster_nce.hip) of the step's pseudo-labels (cluster numbers; -1 = no cluster: unused)
@@ -730,22 +766,18 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
         if self.cluster_memory is None:
             raise ValueError('cluster_nce_weight > 0 needs a cluster memory: build one with ClusterMemory.from_clustering(features, '
                              'clustering) or ClusterMemory.from_labels and install it with model.set_cluster_memory(memory)')
-        if self.cluster_nce_source == 'bn':
-            if 'bn_features' not in outputs:
-                raise ValueError("cluster_nce_source='bn' needs bn_features: call set_num_classes first")
-            x, xv = outputs['bn_features'].unsqueeze(0), cent['valid']
-        else:
-            raw, fm = outputs.get('raw_modality_features', {}), outputs.get('feature_masks', {})
-            cm = [m for m in raw if m in fm]
-            cm = [m for m in cm if m == 'vis'] + [m for m in cm if m != 'vis']
-            if not cm:
-                raise ValueError("cluster_nce_source='modalities' needs raw_modality_features with feature_masks")
-            x = torch.stack([raw[m] for m in cm], dim=0)                                     # [S, B, D]
-            xv = cent.get(('cv', tuple(cm)))
-            if xv is None:
-                xv = cent[('cv', tuple(cm))] = torch.stack([(fm[m].to(x.device) > 0) for m in cm], dim=0).to(torch.uint8).contiguous()
+        x, xv = self._memory_source('cluster_nce_source', outputs, cent)
         return ClusterNCEFn.apply(x, labels, xv, self.cluster_memory, float(self.cluster_nce_temperature), float(self.cluster_nce_momentum),
                                   self.cluster_nce_mode, bool(self.training and torch.is_grad_enabled()))
+
+    def _hybrid_nce_term(self, outputs, index, cent):
+        """Hybrid memory loss (SpCL; csrc/hybrid_nce.hip) of the step's dataset instance indices against model.hybrid_memory: every
+        instance trains, a cluster against its class mean, an un-clustered one against its own entry; the sources are
+        _cluster_nce_term's.  Entries and class means move once per forward in training with gradients; eval() and no_grad() leave
+        them alone."""
+        x, xv = self._memory_source('hybrid_nce_source', outputs, cent)
+        return HybridNCEFn.apply(x, index, xv, self.hybrid_memory, float(self.hybrid_nce_temperature), float(self.hybrid_nce_momentum),
+                                 bool(self.training and torch.is_grad_enabled()))
 
     def _smooth_ap_term(self, labels, pairs):
         """Cross-modal Smooth-AP (csrc/smooth_ap.hip) on the stack the SDM branch uses, from epoch smooth_ap_start_epoch and not tied to the
@@ -775,6 +807,17 @@ class CLIPBasedMultiModalReIDModel(nn.Module):
             if not memory.centroids.is_cuda:
                 raise _lib.ReidHipError('set_cluster_memory needs the memory on the device (there is no CPU path)')
         self.cluster_memory = memory
+
+    def set_hybrid_memory(self, memory):
+        """Installs the HybridMemory the hybrid memory term runs against (None removes it).  It persists across re-clusterings:
+        memory.set_labels(new_labels) re-labels it in place of a new one.  A captured graph holds the old table: capture again after
+        either."""
+        if memory is not None:
+            if not isinstance(memory, HybridMemory):
+                raise TypeError('set_hybrid_memory: a HybridMemory, or None')
+            if not memory.instances.is_cuda:
+                raise _lib.ReidHipError('set_hybrid_memory needs the memory on the device (there is no CPU path)')
+        self.hybrid_memory = memory
 
     def reset_centers(self):
         """Zeroes the class centres of the center loss in place (a device fill: a captured graph that holds the table stays valid)."""

@@ -667,6 +667,49 @@ def cluster_centroids(feats, order, offsets, table):
     check(lib().reid_cluster_centroids(ptr(feats), feats.stride(0), feats.shape[0], ptr(order), ptr(offsets), K, D, ptr(table), stream_ptr()))
 
 
+def _hybrid_memory(who, entries, order, offsets, table):
+    """The hybrid memory as the kernels see it: entries f32 [M, D] (unit column stride), order i64 [M] and offsets i64 [C + 1]
+    contiguous (the members of every class, ascending), table f32 [C, D] contiguous.  Returns (M, C, D)."""
+    text = 'entries [M, D], table [C, D] fp32; order [M], offsets [C + 1] int64, contiguous'
+    _f32_matrices(who, text, ('entries', entries, (None, None)))
+    D = _cluster_table(who, table, entries.shape[1])
+    M, C_ = entries.shape[0], table.shape[0]
+    _vectors(who, text, ('order', order, i64, M), ('offsets', offsets, i64, C_ + 1), exact=True)
+    return M, C_, D
+
+
+def class_means(entries, order, offsets, table):
+    """table [C, D] = the fp32 mean of the rows order[offsets[c] : offsets[c + 1]] of entries [M, D], added one by one in that order
+    and divided by their count -- not renormalised (the hybrid memory's class vectors); one launch, one workgroup per class."""
+    M, C_, D = _hybrid_memory('class_means', entries, order, offsets, table)
+    check(lib().reid_class_means(ptr(entries), entries.stride(0), M, ptr(order), ptr(offsets), C_, D, ptr(table), stream_ptr()))
+
+
+def hybrid_update_instances(index, valid, row_loss, ws, entries, momentum, S=1):
+    """The momentum update of the instance entries [M, D] of the rows cluster_nce_fwd has just used (``index`` [N]: the dataset row
+    of each instance), in place: v <- m v + (1 - m) x^_r, renormalised, over an instance's contributing rows in ascending row order
+    (one launch, no atomics); other entries keep their bits."""
+    N = index.numel()
+    _center_batch('hybrid_update_instances', index, valid, S, N)
+    _f32_matrices('hybrid_update_instances', 'entries [M, D]', ('entries', entries, (None, None)))
+    M, D = entries.shape
+    _vectors('hybrid_update_instances', 'ws [cluster_nce_ws_floats(S, N, D, C)], row_loss [S*N], all contiguous',
+             ('ws', ws, f32, cluster_nce_ws_floats(S, N, D, 1)), ('row_loss', row_loss, f32, S * N))
+    check(lib().reid_hybrid_update_instances(ptr(index), ptr(valid), S, N, D, ptr(row_loss), ptr(ws), ptr(entries), entries.stride(0), M,
+                                             float(momentum), stream_ptr()))
+
+
+def hybrid_refresh_classes(labels, valid, row_loss, entries, order, offsets, table, S=1):
+    """Re-forms, from the entries as they stand, the class means of the classes with a contributing row (``labels`` [N]: the gathered
+    class labels cluster_nce_fwd had), in place (one launch, no atomics); the other rows of the table keep their bits."""
+    N = labels.numel()
+    _center_batch('hybrid_refresh_classes', labels, valid, S, N)
+    M, C_, D = _hybrid_memory('hybrid_refresh_classes', entries, order, offsets, table)
+    _vectors('hybrid_refresh_classes', 'row_loss [S*N], contiguous', ('row_loss', row_loss, f32, S * N))
+    check(lib().reid_hybrid_refresh_classes(ptr(labels), ptr(valid), S, N, D, ptr(row_loss), ptr(entries), entries.stride(0), M, ptr(order),
+                                            ptr(offsets), ptr(table), C_, stream_ptr()))
+
+
 def smooth_ap_ws_floats(P, N, Mg, D, Ga, Gb, with_grad):
     return _ws_floats(lib().reid_smooth_ap_ws_floats, P, N, Mg, D, Ga, Gb, int(bool(with_grad)))
 
