@@ -157,6 +157,11 @@ class LoraLayout:
 class Engine:
     """Owns packed bf16 weights and runs the encoders.  ``P`` maps reference names -> fp32 tensors."""
 
+    # Test hook of vision_backward: a callable ``probe(name, layer, tensor)`` is handed every intermediate of the backward pass right
+    # after the launch that produces it, on the stream that produced it (scratch is reused from layer to layer, so a probe that wants
+    # to keep a tensor clones it there).  None (the default): one attribute test per site, nothing else changes.
+    probe = None
+
     def __init__(self, arch: dict, P: Dict[str, torch.Tensor], lora_arena: torch.Tensor, device, layout: Optional[LoraLayout] = None):
         self.arch = arch
         self.P = P
@@ -516,6 +521,8 @@ class Engine:
         ce = 'clip_encoder.'
         f32, b16 = self._kw()
         grad = torch.zeros(lay.size, **f32)               # the dA/dB GEMMs accumulate (beta=1): no per-call fill
+        probe = self.probe
+        L = a['vision_layers']
         pk = lambda l, nm, w: lay.pk(self._lora_pack, l, nm, w)
         scale_t = None
         if self.loss_scaling or self.dx_half:
@@ -523,6 +530,8 @@ class Engine:
             scale_t = grad_scale(amax)
             dfeat = dfeat * scale_t
         dfb = ops.to_bf16(dfeat)
+        if probe is not None:
+            probe('scale', L, scale_t); probe('dfb', L, dfb)
         gx = dict(dtype=torch.float16 if self.dx_half else torch.float32, device=dev)      # the residual-stream gradient
         ovf = None
         if self.dx_half:
@@ -530,6 +539,8 @@ class Engine:
             ovf.zero_()
         dcls = torch.empty(n_img, d, **b16)
         ops.gemm(dfb, W['vprojT'], dcls)
+        if probe is not None:
+            probe('dcls', L, dcls)
         idxl = st['idxl']
         # class rows only until the last block's attention (see vision_forward)
         dx = torch.empty(M, d, **gx); dxb = torch.empty(M, d, **b16)            # first written (all rows) by the last block's LN1 backward
@@ -543,6 +554,8 @@ class Engine:
         # dxb always holds the gradient ENTERING the next residual branch: dx times that branch's DropPath factor
         ops.layernorm_bwd(dcls, st['x_final'], P[ce + 'vision_ln_final.weight'], st['mf'], st['rf'], dx_c, dx_bf16=dxb_c,
                           bf16_row_scale=st['layers'][-1]['sm'], rows_per_img=1, dgamma=dgf, dbeta=dbf, overflow=ovf)
+        if probe is not None:                               # (layer L: the gradient of x_final, the class rows leaving the last block)
+            probe('dx', L, dx_c); probe('dxb', L, dxb_c)
         # Scratch.  Everything the SIDE stream reads (the dY of the four linears: dxb, du, dxmb, dqkv) exists twice, used by alternate
         # layers: the main stream may then run a whole layer ahead of the adapter-gradient kernels without overwriting their inputs.
         # U* (= dY . Bcat, the rank-r cotangents) are written and read on the side stream only.
@@ -559,7 +572,6 @@ class Engine:
         main = torch.cuda.current_stream(dev)
         side = self._side_stream() if self.overlap_tn else None
         side_done = {}
-        L = a['vision_layers']
         # the gradient ENTERING layer l (dx times that layer's MLP DropPath factor, 16-bit) lives in dxb2[l & 1]
         u_part = torch.empty(M, Rp, **f32)                  # fp32 partial U of fc1's four column blocks (side stream only)
         # The scratch of a block's MLP / out-projection, on all rows and on the class rows: a row set of the forward (_rows) plus the
@@ -599,6 +611,8 @@ class Engine:
                     else:
                         ops.gemm(dYg, BTg, Ug, **rows.mask)
                         ops.gemm_tn(dYg, Tg, dBg, beta=1.0)
+                if probe is not None:
+                    probe('U_' + nm, l, U)
                 if ops.lora_da_fused_ok(X.shape[1], Rp, rows.rpi, r, G):
                     ops.lora_da_fused(X, U, lay.view_A(grad, l, nm), rows.img_mod, rows.rpi, r, n_groups=G)
                 else:
@@ -615,12 +629,16 @@ class Engine:
             # ---- fc2:  x_next = xm + g W2_eff^T + b2
             adapter_grads(l, 'fc2', gyb, s['g'], s['T2'], sc.U2, sc)
             ops.gemm(gyb, weT(l, 'fc2'), du, act='mul_aux', aux=s['u'], row_groups=rg)
+            if probe is not None:
+                probe('du', l, du)
             if want_dense:
                 dense[lp + 'mlp.fc2.shared_linear.weight'] = dg.wgrad(gyb, s['g'])
                 dense[lp + 'mlp.fc2.shared_linear.bias'] = dg.colsum(gyb)
             # ---- fc1:  u = h2 W1_eff^T + b1
             adapter_grads(l, 'fc1', du, s['h2'], s['T1'], sc.U1, sc)
             ops.gemm(du, weT(l, 'fc1'), sc.dh, row_groups=rg)
+            if probe is not None:
+                probe('dh2', l, sc.dh)
             if want_dense:
                 dense[lp + 'mlp.fc1.shared_linear.weight'] = dg.wgrad(du, s['h2'])
                 dense[lp + 'mlp.fc1.shared_linear.bias'] = dg.colsum(du)
@@ -628,17 +646,25 @@ class Engine:
             dg2, db2 = ln_pair(lp + 'ln2', d)
             ops.layernorm_bwd(sc.dh, s['xm'], P[lp + 'ln2.weight'], s['mean2'], s['rstd2'], sc.dxm, dx_bf16=dxmb, dres=gy,
                               bf16_row_scale=s['sa'], rows_per_img=sc.rpi, dgamma=dg2, dbeta=db2, overflow=ovf)
+            if probe is not None:
+                probe('dxm', l, sc.dxm); probe('dxmb', l, dxmb)
             # ---- out proj:  xm = x + o Wo_eff^T + bo
             adapter_grads(l, 'out', dxmb, s['o_rows'], s['To'], sc.Uo, sc)
             ops.gemm(dxmb, weT(l, 'out'), sc.do, row_groups=rg)
+            if probe is not None:
+                probe('do', l, sc.do)
             if want_dense:
                 dense[lp + 'attn.out_proj.shared_linear.weight'] = dg.wgrad(dxmb, s['o_rows'])
                 dense[lp + 'attn.out_proj.shared_linear.bias'] = dg.colsum(dxmb)
             if c:                                           # back to all rows: zero everywhere but the class rows
                 do.zero_(); do.index_copy_(0, idxl, sc.do)
                 dxm.zero_(); dxm.index_copy_(0, idxl, sc.dxm)
+                if probe is not None:
+                    probe('do_rows', l, do); probe('dxm_rows', l, dxm)
             # ---- attention
             ops.attn_bwd(s['qkv'], s['o'], do, s['lse'], dqkv, delta, n_img, S, heads, q_tiles=1 if c else 0)
+            if probe is not None:
+                probe('dqkv', l, dqkv); probe('delta', l, delta)
             # ---- qkv:  qkv = h Wqkv_eff^T + b (one adapter set per projection)
             adapter_grads(l, 'qkv', dqkv, s['h'], s['T'], Uq, full)
             if side is not None:
@@ -648,6 +674,8 @@ class Engine:
                 # q|k|v projection and the LN1 backward) would be computed only to be thrown away
                 break
             ops.gemm(dqkv, weT(l, 'qkv'), dh, row_groups=full.rg)
+            if probe is not None:
+                probe('dh', l, dh)
             if want_dense:
                 gw = dg.wgrad(dqkv, s['h']); gb_ = dg.colsum(dqkv)
                 for gi, nm in enumerate('qkv'):
@@ -661,6 +689,8 @@ class Engine:
             ops.layernorm_bwd(dh, s['x'], P[lp + 'ln1.weight'], s['mean1'], s['rstd1'], dx, dx_bf16=dxb2[(l - 1) & 1], dres=dxm,
                               bf16_row_scale=st['layers'][l - 1]['sm'] if l > 0 else None, rows_per_img=S, dgamma=dg1, dbeta=db1,
                               overflow=ovf)
+            if probe is not None:                           # (dxb: the copy that carries the MLP DropPath factor of layer l - 1)
+                probe('dx', l, dx); probe('dxb', l, dxb2[(l - 1) & 1])
         if side is not None:                                # the gradient arena is complete only when the side stream is
             wait_for(main, side)
         if want_dense:
